@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: MPC QP builds+solves per second (batched).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in
 HBM when the timed region starts. ``--config`` picks the BASELINE.json configuration that is
@@ -73,6 +73,8 @@ def parse_args(argv=None):
     ap.add_argument("--spinup", type=float, default=0.25, help="seconds of untimed launches before the warm-up (clock ramp)")
     ap.add_argument("--no-extras", action="store_true", help="skip the short runs of the other configurations")
     ap.add_argument("--no-overlap", action="store_true", help="skip the extra two-streams-in-flight measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args(argv)
     defaults = {2: (2000, 200), 3: (100, 20), 4: (200, 20), 5: (20, 3)}
     if args.steps is None:
@@ -255,6 +257,8 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
     elapsed, kernel_s = clock.time(run.launch, args.steps, getattr(run, "launch_steps", None))
     barrier()
     kernel_ms = kernel_s / args.steps * 1e3  # average duration of one step's launches, HIP events
+    # taken right after the timed region: the extra measurements below launch the solver again
+    dumped = _dump_outputs(args.dump_outputs, _last_step_outputs(run), rank, world) if args.dump_outputs else None
 
     # whole-job reductions: MAX of the elapsed time, SUMs of the counts
     t = allreduce(torch.tensor([elapsed], dtype=torch.float64, device=dev), "MAX")
@@ -325,6 +329,8 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
         out["all_gather_note"] = "U [B, n] + status [B] to every rank (padded all_gather, qpmpc_amd.distributed.gather_batch); outside the timed region"
     if overlap is not None:
         out["overlap_2_streams"] = overlap
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if device == "cuda":
         out["roofline"] = _roofline(args, w, local_per_step, kernel_ms, out["mean_iters"])
         if args.config == 5:
@@ -349,6 +355,47 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
             out["speedup_vs_cpu_port"] = out["value"] / out["cpu_baseline"]["value"]
             out["speedup_vs_cpu_all_cores"] = out["value"] / out["cpu_baseline"]["all_cores_value"]
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def _last_step_outputs(run):
+    """What a caller of the timed path holds after its last step, as host float arrays: the plans U [B, n], the
+    statuses and iteration counts [B] and, for the closed loops of config 3, the loops' states [B, 4] after the
+    last period (the plans are that period's)."""
+    import numpy as np
+
+    out = {"U": run.U.cpu().numpy()}
+    out["U"] = out["U"].astype(np.float32 if out["U"].dtype == np.float32 else np.float64)
+    out["status"] = run.status.cpu().numpy().astype(np.float64)
+    out["iters"] = run.iters.cpu().numpy().astype(np.float64)
+    if hasattr(run, "loop"):
+        out["states"] = run.loop.states.cpu().numpy().astype(np.float64)
+    return out
+
+
+def _dump_outputs(directory: str, arrays, rank: int, world: int):
+    """Write ``arrays`` (all with the batch as first axis) as DIR/<name>.npy (DIR/<name>.rank<r>.npy with several ranks).
+    Above DUMP_LIMIT_BYTES a fixed, seeded sample of the problems is written for all of them, with its row indices
+    (``rows.npy``), so that two builds given the same arguments write the same problems."""
+    import numpy as np
+
+    batch = int(next(iter(arrays.values())).shape[0])
+    row_bytes = sum(a.nbytes // max(batch, 1) for a in arrays.values()) + 8  # + the row index, if sampled
+    budget = DUMP_LIMIT_BYTES // max(world, 1) - 4096  # (room for the .npy headers)
+    rows = None
+    if row_bytes * batch > budget:
+        keep = max(1, budget // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(batch, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()} | {"rows": rows.astype(np.float64)}
+    os.makedirs(directory, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+    return {"dir": directory, "files": sorted(f"{k}{suffix}.npy" for k in arrays), "problems": batch,
+            "sampled_problems": None if rows is None else int(rows.size),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def predicted_strong_scaling():

@@ -204,3 +204,47 @@ def test_bench_config5_slices_are_one_global_problem_set():
     b = W.synthetic_ltv_batch_slice(2, 4, N=8)
     for key in ("A", "B", "x0"):
         assert np.array_equal(a[key][2:], b[key])
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs DIR: after exactly --steps timed steps the last step's plans, statuses and iteration counts land in
+    DIR/<name>.npy as float arrays, identical from run to run; above the size limit a fixed, seeded sample is written."""
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    runs = []
+
+    def make_runner(config, w, device):
+        runs.append(_OracleRunner(config, w, device))
+        return runs[-1]
+
+    for k, steps in enumerate((3, 5)):
+        out_dir = tmp_path / f"run{k}"
+        args = bench.parse_args(["--config", "2", "--steps", str(steps), "--warmup", "1", "--batch", "12", "--spinup", "0",
+                                 "--no-cpu-baseline", "--dump-outputs", str(out_dir)])
+        rec = bench.run_bench(args, 0, 1, None, make_runner=make_runner, device="cpu")
+        assert runs[-1].launches == 1 + 1 + steps  # construction, warm-up, timed steps
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        assert rec["dump_outputs"]["files"] == ["U.npy", "iters.npy", "status.npy"]
+        assert rec["dump_outputs"]["sampled_problems"] is None
+        U = np.load(out_dir / "U.npy")
+        assert U.dtype == np.float64 and U.shape == (12, 16)
+        assert np.array_equal(U, runs[-1].U.numpy())
+        for name in ("status", "iters"):
+            a = np.load(out_dir / f"{name}.npy")
+            assert a.dtype == np.float64 and np.array_equal(a, getattr(runs[-1], name).numpy())
+    for name in ("U", "status", "iters"):
+        assert np.array_equal(np.load(tmp_path / "run0" / f"{name}.npy"), np.load(tmp_path / "run1" / f"{name}.npy"))
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 40 * (8 * 16 + 8 + 8))
+    big = {"U": np.arange(100 * 16, dtype=np.float64).reshape(100, 16), "status": np.zeros(100)}
+    for k in range(2):
+        info = bench._dump_outputs(str(tmp_path / f"big{k}"), big, 0, 1)
+        assert info["sampled_problems"] == 40 and info["files"] == ["U.npy", "rows.npy", "status.npy"]
+    rows = np.load(tmp_path / "big0" / "rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "big1" / "rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "big0" / "U.npy"), big["U"][rows.astype(int)])
