@@ -329,8 +329,12 @@ int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P,
  * status[b] is what an exact backend of the reference would report (found / not found, plan.py:35-40): problems of 17 .. 128
  * variables with nx <= 4, nu <= 2 -- the narrow stage-wise kernel, whose active-set operator is an explicit inverse -- that this
  * kernel leaves MPCQP_MAX_ITER or MPCQP_INFEASIBLE are solved once more by the wide stage-wise kernel (thin QR factor of the
- * active rows) in a second launch on the same stream and in the same workspace, before the call returns (ABI 11; not when the
- * launch keeps state for a later one: MPCQP_OPT_KEEP_FACTOR / _REUSE_FACTOR / _PIPELINE_FACTOR, a warm state). */
+ * active rows) in a second launch on the same stream, before the call returns (ABI 11). Stateful launches -- MPCQP_OPT_KEEP_FACTOR /
+ * _REUSE_FACTOR / _PIPELINE_FACTOR, a warm state -- take it too: the wide kernel works in a region of the workspace after the narrow
+ * kernel's (mpcqp_workspace_bytes prices the sum), so the factor images and the rows a warm record points at survive it, and it
+ * leaves the warm record as the narrow kernel wrote it (the next warm start re-checks it). For an item the wide kernel re-solved,
+ * U, lam, status and iters are the wide kernel's: iters counts its iterations only, the narrow kernel's are not added. The
+ * multi-period launches (mpcqp_wip_periods_batch) have no second opinion. */
 int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem,
                             int64_t batch, const MpcqpSolveOpts *opts, void *U,
                             void *lam, int32_t *status, int32_t *iters,
@@ -350,7 +354,8 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem,
  * nx <= 32, nu <= 8: thin-QR active-set operator, like the wide kernel's since ABI 11) whatever
  * the width; its workspace is sized by the query with max_active = -1 (default slots) or -k (k slots). As in
  * mpcqp_build_solve_batch, what the narrow kernel leaves MPCQP_MAX_ITER / MPCQP_INFEASIBLE is solved once more by the wide kernel
- * (same slots, same workspace, same stream) before the call returns. */
+ * (same slots, same stream, its own region after the narrow kernel's workspace: the query reports the sum) before the call
+ * returns, stateful launches included; iters of such an item is the wide kernel's count. */
 int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes);
 int mpcqp_stagewise_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
                                 const MpcqpSolveOpts *opts, int32_t max_active, void *U, void *lam,

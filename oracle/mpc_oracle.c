@@ -178,6 +178,23 @@ void oracle_rollout_one(int nx, int nu, int N, const double *A, int64_t sA,
  */
 static double hyp(double a, double b) { return hypot(a, b); }
 
+/* The clamp of the active rows' multipliers u[0 .. iq) after refinement: a multiplier below zero by at most -1e-12 (1 + max u)
+ * is a weakly active row's, at rounding level, and becomes 0; a clearly negative one is LEFT as it is, so the acceptance check
+ * refuses the point (zeroing every negative multiplier here, as this file once did, would accept a non-optimal active set).
+ * Returns the number of clearly negative multipliers. Exported for tests/test_oracle_certificate.py. */
+int oracle_clamp_multipliers(int iq, double *u)
+{
+    double umax = 0.0;
+    int neg = 0;
+    for (int i = 0; i < iq; ++i)
+        if (u[i] > umax) umax = u[i];
+    for (int i = 0; i < iq; ++i) {
+        if (u[i] < 0.0 && u[i] >= -1e-12 * (1.0 + umax)) u[i] = 0.0;
+        if (!(u[i] >= 0.0)) ++neg;
+    }
+    return neg;
+}
+
 /* Iterative refinement of the final active set's KKT system at (x, u): see the comment at the end of oracle_gi_solve.
  * r: scratch of iq + 1 doubles. */
 static void refine_active(int n, int iq, const int *act, const double *P, const double *qv, const double *G, const double *h,
@@ -308,8 +325,7 @@ int oracle_gi_solve(int n, int m, const double *P, const double *qv,
                again -- a row that was feasible by less than the refinement moved the point is taken up like any other */
             if (iq > 0 && !refined) {
                 refine_active(n, iq, act, P, qv, G, h, J, R, x, u, r);
-                for (int i = 0; i < iq; ++i)
-                    if (u[i] < 0.0) u[i] = 0.0; /* (rounding level: a weakly active row) */
+                oracle_clamp_multipliers(iq, u); /* (rounding level: a weakly active row; a clearly negative one fails below) */
                 refined = 1;
                 continue;
             }
@@ -434,10 +450,7 @@ int oracle_gi_solve(int n, int m, const double *P, const double *qv,
        of an inconsistent problem slipped through the pivot test above: no feasible point was found -> status 2, what qpsolvers
        reports as found=False (plan.py:35-40). */
     if (status == 0) {
-        int bad = 0;
-        double umax = 0.0;
-        for (int i = 0; i < iq; ++i)
-            if (u[i] > umax) umax = u[i];
+        int bad = oracle_clamp_multipliers(iq, u) > 0;
         for (int k = 0; k < n; ++k)
             if (!isfinite(x[k])) bad = 1;
         for (int i = 0; i < iq && !bad; ++i) {
@@ -445,8 +458,6 @@ int oracle_gi_solve(int n, int m, const double *P, const double *qv,
             long double s = (long double)h[a];
             for (int k = 0; k < n; ++k) s -= (long double)G[(size_t)a * n + k] * (long double)x[k];
             if (!(fabsl(s) <= 1e-9L * (1.0L + fabsl((long double)h[a])))) bad = 1;
-            if (u[i] < 0.0 && u[i] >= -1e-12 * (1.0 + umax)) u[i] = 0.0;  /* a weakly active row's multiplier, at rounding level */
-            if (!(u[i] >= 0.0)) bad = 1;
         }
         if (bad) status = 2;
     }

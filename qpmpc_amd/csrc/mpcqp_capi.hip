@@ -163,13 +163,31 @@ bool use_stage_long(const KernelArgs &ka, int dtype)
     (void)dtype;
     return false;
 }
-// the narrow stage-wise kernel's unsolved verdicts get a second opinion from the wide one (kOptSecondOpinion) in one-shot launches of
-// mpcqp_build_solve_batch: not when the launch keeps state in its workspace or its warm-state record for a later one
+// the narrow stage-wise kernel's unsolved verdicts get a second opinion from the wide one (kOptSecondOpinion) in every launch of
+// mpcqp_build_solve_batch / mpcqp_stagewise_solve_batch that it serves, the stateful ones included (KEEP / REUSE / PIPELINE_FACTOR,
+// a warm state): the wide kernel runs in a region of its own after the narrow kernel's workspace (second_opinion_offset), so the
+// factor images and the vectors a warm record points at survive it, and it neither reads nor writes the warm record
 bool second_opinion_applies(const KernelArgs &ka, int dtype, bool size_query = false)
 {
     // (a size query carries neither outputs nor options: it prices the launch that takes the second opinion)
-    return stagew_supported(ka, dtype) && (size_query || ka.status) && !ka.warm_state &&
-           !(ka.opt_flags & (MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR));
+    return stagew_supported(ka, dtype) && (size_query || ka.status);
+}
+int64_t al256(int64_t bytes);
+// byte offset of the second opinion's region in the workspace: the narrow kernel's workspace for the batch, rounded up to 256 bytes
+size_t second_opinion_offset(const KernelArgs &ka, int maxq, int64_t batch)
+{
+    return (size_t)al256((int64_t)(stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch));
+}
+// the wide kernel's arguments behind the narrow one: only what the narrow kernel left unsolved, nothing kept, no warm record
+KernelArgs second_opinion_args(const KernelArgs &ka)
+{
+    KernelArgs kb = ka;
+    kb.opt_flags = (ka.opt_flags | kOptSecondOpinion) & ~(MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR);
+    kb.warm_state = nullptr;
+    kb.warm_state_bytes = 0;
+    kb.warm_start = 0;
+    kb.probe = nullptr;
+    return kb;
 }
 int stagew_auto_maxq(const KernelArgs &ka)
 {
@@ -474,8 +492,9 @@ int mpcqp_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t for_solv
         if (for_solve && use_stage_auto(ka, dims->dtype)) {
             const size_t sw = stage_ws_doubles(ka, stage_default_maxq(ka)) * sizeof(double) * (size_t)batch;
             if (sw > v) v = sw;
-            if (second_opinion_applies(ka, dims->dtype, true)) {  // (the wide kernel behind the narrow one, in the same buffer)
-                const size_t s2 = stagew_ws_elems(ka, stagew_auto_maxq(ka), dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
+            if (second_opinion_applies(ka, dims->dtype, true)) {  // (the wide kernel behind the narrow one, in a region of its own)
+                const size_t s2 = second_opinion_offset(ka, stage_default_maxq(ka), batch) +
+                                  stagew_ws_elems(ka, stagew_auto_maxq(ka), dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
                 if (s2 > v) v = s2;
             }
         }
@@ -767,17 +786,12 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
         size_t need = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
         const bool second = second_opinion_applies(ka, dims->dtype);
         const int maxq2 = stagew_auto_maxq(ka);
-        if (second) {
-            const size_t need2 = stagew_ws_elems(ka, maxq2, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-            need = need2 > need ? need2 : need;
-        }
+        const size_t off2 = second_opinion_offset(ka, maxq, batch);
+        if (second) need = off2 + stagew_ws_elems(ka, maxq2, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
         if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
         if ((rc = launch_stage(ka, maxq, batch, workspace, st)) || !second) return rc;
-        // the second opinion (mpcqp_internal.h, kOptSecondOpinion): same stream, same workspace (the first launch is done with it)
-        KernelArgs kb = ka;
-        kb.opt_flags |= kOptSecondOpinion;
-        kb.probe = nullptr;
-        rc = launch_stagew(kb, dims->dtype, maxq2, batch, workspace, st);
+        // the second opinion (mpcqp_internal.h, kOptSecondOpinion): same stream, its own region after the narrow kernel's workspace
+        rc = launch_stagew(second_opinion_args(ka), dims->dtype, maxq2, batch, (char *)workspace + off2, st);
         return rc == MPCQP_ETOOLARGE ? 0 : rc;  // (a horizon beyond the wide kernel's 32-bit offsets: the narrow kernel's verdicts stand)
     }
     if (use_stage_long(ka, dims->dtype)) {
@@ -856,6 +870,7 @@ int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_
     size_t a = 0, b = 0;
     if (stage_supported(ka, dims->dtype)) a = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
     if (stagew_supported(ka, dims->dtype)) b = stagew_ws_elems(ka, maxq, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
+    if (a && b) a = second_opinion_offset(ka, maxq, batch) + b;  // (the narrow kernel, then the second opinion's region after it)
     if (!stage_supported(ka, dims->dtype) && !stagew_supported(ka, dims->dtype)) {
         if (!stageg_supported(ka, dims->dtype)) return MPCQP_EUNSUPPORTED;
         *bytes = stageg_ws_doubles(ka, max_active > 0 ? max_active : stageg_default_maxq(ka)) * sizeof(double) * (size_t)batch;
@@ -901,17 +916,15 @@ int mpcqp_stagewise_solve_batch(const MpcqpDims *dims, const MpcqpProblem *probl
     const int maxq = max_active > 0 ? max_active : stage_default_maxq(ka);
     const size_t need_w = stagew_supported(ka, dims->dtype) ? stagew_ws_elems(ka, maxq, dims->dtype) * elem_size(dims->dtype) * (size_t)batch : 0;
     // (as in mpcqp_build_solve_batch: what the narrow kernel leaves MPCQP_MAX_ITER / MPCQP_INFEASIBLE goes through the wide one, with
-    // the same slots, in the same workspace -- mpcqp_stagewise_workspace_bytes reports the larger of the two)
+    // the same slots, in a region of its own after the narrow kernel's workspace -- mpcqp_stagewise_workspace_bytes reports the sum)
     const bool second = narrow && second_opinion_applies(ka, dims->dtype);
+    const size_t off2 = narrow ? second_opinion_offset(ka, maxq, batch) : 0;
     size_t need = narrow ? stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch : need_w;
-    if (second && need_w > need) need = need_w;
+    if (second) need = off2 + need_w;
     if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
     if (!narrow) return launch_stagew(ka, dims->dtype, maxq, batch, workspace, (hipStream_t)stream);
     if ((rc = launch_stage(ka, maxq, batch, workspace, (hipStream_t)stream)) || !second) return rc;
-    KernelArgs kb = ka;
-    kb.opt_flags |= kOptSecondOpinion;
-    kb.probe = nullptr;
-    rc = launch_stagew(kb, dims->dtype, maxq, batch, workspace, (hipStream_t)stream);
+    rc = launch_stagew(second_opinion_args(ka), dims->dtype, maxq, batch, (char *)workspace + off2, (hipStream_t)stream);
     return rc == MPCQP_ETOOLARGE ? 0 : rc;  // (a horizon beyond the wide kernel's 32-bit offsets: the narrow kernel's verdicts stand)
 }
 

@@ -25,28 +25,36 @@ def row_residuals(w, b, U):
     return np.concatenate(out)
 
 
+def draw(kind, rng, batch, tight):
+    """One round's workload of family ``kind`` at tightness ``tight`` (STRESS_TIGHT): the dimensions, then random_ltv's problems
+    (shared by run() and the tests that replay these families through other launch modes; the draws stay in this order)."""
+    if kind == "narrow":
+        nx, nu = int(rng.integers(2, 5)), int(rng.integers(1, 3))
+    elif kind in ("wide", "widef"):
+        nx, nu = int(rng.integers(5, 17)), int(rng.integers(1, 5))
+    else:
+        nx, nu = int(rng.integers(17, 33)), int(rng.integers(1, 9))
+    N = int(rng.integers(20, 41)); mk = int(rng.integers(4, 7))
+    if kind == "widef":  # constraint matrices FIXED along the horizon, 4 / 8 / 12 / 16 rows per step: the wide kernel's layout in
+        mk = 4 * int(rng.integers(1, 5))  # which the forward sweep forms the rows itself (config 5's)
+    w = random_ltv(rng, batch, nx, nu, N, mk, tight)  # (smaller: tighter rows, more of them active)
+    w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
+    if kind == "widef":
+        w["C"], w["D"] = w["C"][:, :1].copy(), w["D"][:, :1].copy()
+        for b in range(batch):  # bounds around the free response, as random_ltv makes them (with the fixed C)
+            x = w["x0"][b].copy()
+            for k in range(N):
+                w["e"][b, k] = w["C"][b, 0] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
+                x = w["A"][b, k] @ x
+    return w
+
+
 def run(kind, rounds, batch, seed, verbose=True):
     rng = np.random.default_rng(seed)
     worst, bad = 0.0, 0
     for it in range(rounds):
-        if kind == "narrow":
-            nx, nu = int(rng.integers(2, 5)), int(rng.integers(1, 3))
-        elif kind in ("wide", "widef"):
-            nx, nu = int(rng.integers(5, 17)), int(rng.integers(1, 5))
-        else:
-            nx, nu = int(rng.integers(17, 33)), int(rng.integers(1, 9))
-        N = int(rng.integers(20, 41)); mk = int(rng.integers(4, 7))
-        if kind == "widef":  # constraint matrices FIXED along the horizon, 4 / 8 / 12 / 16 rows per step: the wide kernel's layout in
-            mk = 4 * int(rng.integers(1, 5))  # which the forward sweep forms the rows itself (config 5's)
-        w = random_ltv(rng, batch, nx, nu, N, mk, float(os.environ.get("STRESS_TIGHT", "0.5")))  # (smaller: tighter rows, more of them active)
-        w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
-        if kind == "widef":
-            w["C"], w["D"] = w["C"][:, :1].copy(), w["D"][:, :1].copy()
-            for b in range(batch):  # bounds around the free response, as random_ltv makes them (with the fixed C)
-                x = w["x0"][b].copy()
-                for k in range(N):
-                    w["e"][b, k] = w["C"][b, 0] @ x + float(os.environ.get("STRESS_TIGHT", "0.5")) * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
-                    x = w["A"][b, k] @ x
+        w = draw(kind, rng, batch, float(os.environ.get("STRESS_TIGHT", "0.5")))
+        nx, nu, N, mk = w["A"].shape[-1], w["B"].shape[-1], int(w["N"]), w["e"].shape[-1]
         kw = {}
         if os.environ.get("STRESS_FORMULATION") == "stagewise":  # (mpcqp_stagewise_solve_batch instead of the default entry point)
             kw = dict(formulation="stagewise", max_active=min(N * nu, N * mk))
