@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define MPCQP_ABI_VERSION 11
+#define MPCQP_ABI_VERSION 12
 
 /* element type of every floating-point buffer of a call. It is the STORAGE type: mpcqp_build_solve_batch computes
  * MPCQP_F32 problems of at most 160 variables (and every float32 problem only the general stage-wise kernel serves) in
@@ -410,6 +410,25 @@ int mpcqp_solve_model_bounds_batch(const MpcqpDims *dims, const void *model, con
 int mpcqp_rollout_batch(const MpcqpDims *dims, const MpcqpOperand *A,
                         const MpcqpOperand *B, const MpcqpOperand *x0,
                         const void *U, int64_t batch, void *X, void *stream);
+
+/* Vector-Jacobian product of solved plans (ABI 12). The reference has no gradients; this is an extension for callers who
+ * learn through the controller. Given the forward solve's multipliers lam [batch*m] and status [batch]
+ * (mpcqp_build_solve_batch / mpcqp_stagewise_solve_batch with lam != NULL), gU = dL/dU [batch*n] and gX = dL/dX
+ * [batch*(N+1)*nx] (nullable; X = the rollout of mpcqp_rollout_batch), writes per problem, packed:
+ *     g_x0 [nx], g_goal [nx], g_targets [N*nx], g_e [N*mk]   (all but g_x0 nullable)
+ * with respect to that problem's own x0, goal, targets and e; a reduction over operands the batch shares is the caller's.
+ * The active set is {i : lam_i > 0}: a row that is tight with lam_i = 0 counts as inactive, so at weakly active points
+ * the result is one element of the generalized Jacobian. Terms follow dims->flags (MPCQP_Q_TERMINAL / MPCQP_Q_STAGE): a
+ * goal or targets that do not enter q get zero gradients.
+ * Per problem: status[b] != 0 gives all-zero gradients and vjp_status[b] = status[b]; more active rows than variables or
+ * a Gram matrix of the active rows that is not positive definite gives zeros and MPCQP_NOT_PD; else vjp_status[b] = 0.
+ * Envelope: float64 (MPCQP_EDTYPE otherwise), n <= 128 and whatever mpcqp_condense_batch condenses (MPCQP_EUNSUPPORTED
+ * otherwise). The call runs mpcqp_condense_batch (Phi, Psi kept) into the workspace, then one adjoint launch. */
+int mpcqp_plan_vjp_workspace_bytes(const MpcqpDims *dims, int64_t batch, size_t *bytes);
+int mpcqp_plan_vjp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                         const void *lam, const int32_t *status, const void *gU, const void *gX,
+                         void *g_x0, void *g_goal, void *g_targets, void *g_e, int32_t *vjp_status,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of

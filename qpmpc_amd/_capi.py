@@ -13,8 +13,8 @@ from .exceptions import BackendError
 F64, F32 = 0, 1
 P_TERMINAL, P_STAGE, Q_TERMINAL, Q_STAGE = 1, 2, 4, 8
 SOLVED, MAX_ITER, INFEASIBLE, NOT_PD, SLOTS_FULL = 0, 1, 2, 3, 4
-EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -5, -6
-ABI_VERSION = 11
+EINVAL, EDTYPE, EWORKSPACE, EUNSUPPORTED = -1, -3, -5, -6
+ABI_VERSION = 12
 OPT_FORCE_LDS, OPT_FORCE_GWS, OPT_FORCE_DENSE_G, OPT_ONE_PER_WAVE, OPT_FORCE_CONDENSED, OPT_STAGE_WIDE = 1, 2, 4, 8, 16, 32
 OPT_KEEP_FACTOR, OPT_REUSE_FACTOR, OPT_PIPELINE_FACTOR, OPT_SEED_VIOLATED, OPT_EXACT_SELECTION = 64, 128, 256, 512, 1024
 OPT_TWO_PER_WAVE, OPT_FOUR_PER_WAVE = 2048, 4096
@@ -53,6 +53,8 @@ EXPORTS = (
     "mpcqp_wip_periods_batch",
     "mpcqp_lipm_advance_batch",
     "mpcqp_lipm_advance_stats_batch",
+    "mpcqp_plan_vjp_workspace_bytes",
+    "mpcqp_plan_vjp_batch",
 )
 
 
@@ -173,6 +175,11 @@ def load():
     lib.mpcqp_rollout_batch.restype = C.c_int
     lib.mpcqp_rollout_batch.argtypes = [C.POINTER(Dims), C.POINTER(Operand), C.POINTER(Operand),
                                         C.POINTER(Operand), vp, i64, vp, vp]
+    lib.mpcqp_plan_vjp_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_vjp_workspace_bytes.argtypes = [C.POINTER(Dims), i64, C.POINTER(C.c_size_t)]
+    lib.mpcqp_plan_vjp_batch.restype = C.c_int
+    lib.mpcqp_plan_vjp_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -1,0 +1,348 @@
+// mpcqp_adjoint.hip -- vector-Jacobian product of a batch of solved MPC plans (mpcqp_plan_vjp_batch).
+//
+// One problem per workgroup, float64. The condensed matrices P, G, Phi, Psi come from mpcqp_condense_batch (the C ABI
+// runs it into the workspace first); the active set comes from the forward solve's multipliers (lam_i > 0). Per problem:
+//   1. gU += Psi' gX                                  (state gradients folded into the input gradient)
+//   2. P = L L' (Cholesky), t = L^-1 gU
+//   3. A = {i : lam_i > 0}, compacted with a ballot and prefix count (k = |A| <= n, else MPCQP_NOT_PD)
+//   4. M_A' = L^-1 G_A'                              (the k active rows solved together with t: one forward sweep)
+//   5. S = M_A M_A' = R R', nu = S^-1 M_A t, w = L^-T (t - M_A' nu)
+//   6. dL/dq = -w, dL/dh_A = nu; then back through the condensing:
+//      y = Psi dL/dq;  g_goal = -w_t y_N;  g_targets_k = -w_x y_k;  g_e = dL/dh;
+//      g_x0 = sum_k Phi_k' v_k,  v_k = gX_k + w_x y_k [k < N] + w_t y_N [k = N] - C_k' dL/dh_k
+// The carve (L, the k + 1 right-hand sides, the k x k Gram, the vectors) is sized from the actual n, rows at an odd
+// stride (as in mpcqp_lds.hip); it lives in LDS when it fits a CU (about n <= 78: 8.3 KB at n = 16, 19 workgroups per CU), else in the workspace.
+#include <hip/hip_runtime.h>
+
+#include "mpcqp.h"
+#include "mpcqp_internal.h"
+
+namespace mpcqp {
+namespace {
+
+struct AdjArgs {
+    int nx, nu, N, mk, n, m, flags;
+    double wt, wx;
+    const double *P, *G, *Phi, *Psi;  // condensed (packed per problem, mpcqp_condense_batch)
+    MpcqpOperand C;                   // ineq_state_matrix of the problem (nullable)
+    const double *lam, *gU, *gX;      // gX nullable
+    const int32_t *status;
+    double *g_x0, *g_goal, *g_targets, *g_e;  // all but g_x0 nullable
+    int32_t *vjp_status;                       // nullable
+    double *carve_ws;                          // per-problem carves when they do not fit LDS (else null)
+    int64_t carve;                             // doubles per problem
+};
+
+struct Carve {
+    int ld;  // odd row stride of the n-wide matrices
+    int64_t L, Z, S, nu, s, y, v, red, idx, total;
+};
+
+__host__ __device__ inline Carve make_carve(int n, int N, int nx, int threads)
+{
+    Carve c;
+    c.ld = n | 1;
+    const int64_t mat = (int64_t)n * c.ld;
+    c.L = 0;
+    c.Z = c.L + mat;                      // row 0: t; rows 1 .. k: the active rows of M_A (n + 1 rows)
+    c.S = c.Z + mat + c.ld;               // k x k Gram, stride ld
+    c.nu = c.S + mat;                     // n
+    c.s = c.nu + n;                       // n: t - M_A' nu, then w in place
+    c.y = c.s + n;                        // (N + 1) nx: Psi dL/dq
+    c.v = c.y + (int64_t)(N + 1) * nx;    // (N + 1) nx
+    c.red = c.v + (int64_t)(N + 1) * nx;  // threads: partial sums of g_x0
+    c.idx = c.red + threads;              // n + 1 int32 (active row ids)
+    c.total = c.idx + (n + 2) / 2;
+    return c;
+}
+
+// In-place lower Cholesky of the nn x nn matrix a (stride ld; only the lower triangle is read or written).
+// Uniform result: every thread reads the same pivot after a barrier.
+template <int BS>
+__device__ bool chol_lower(double *a, int nn, int ld, int tid)
+{
+    for (int j = 0; j < nn; ++j) {
+        __syncthreads();
+        const double d = a[j * ld + j];
+        if (!(d > 0.0)) return false;
+        const double sd = sqrt(d), inv = 1.0 / sd;
+        __syncthreads();
+        if (tid == 0) a[j * ld + j] = sd;
+        for (int i = j + 1 + tid; i < nn; i += BS) a[i * ld + j] *= inv;
+        __syncthreads();
+        const int w = nn - j - 1;
+        for (int e = tid; e < w * w; e += BS) {
+            const int i = j + 1 + e / w, c = j + 1 + e % w;
+            if (c <= i) a[i * ld + c] -= a[i * ld + j] * a[c * ld + j];
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// x <- R^-1 x, then (transposed) x <- R^-T x for one vector and the lower factor R (stride ld)
+template <int BS>
+__device__ void solve_lower(const double *R, int nn, int ld, double *x, int tid)
+{
+    for (int j = 0; j < nn; ++j) {
+        if (tid == 0) x[j] /= R[j * ld + j];
+        __syncthreads();
+        for (int i = j + 1 + tid; i < nn; i += BS) x[i] -= R[i * ld + j] * x[j];
+        __syncthreads();
+    }
+}
+template <int BS>
+__device__ void solve_lower_t(const double *R, int nn, int ld, double *x, int tid)
+{
+    for (int j = nn - 1; j >= 0; --j) {
+        if (tid == 0) x[j] /= R[j * ld + j];
+        __syncthreads();
+        for (int i = tid; i < j; i += BS) x[i] -= R[j * ld + i] * x[j];
+        __syncthreads();
+    }
+}
+
+template <int BS, bool kLds>
+__global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
+{
+    extern __shared__ double lds_carve[];
+    __shared__ int s_k;
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int n = a.n, m = a.m, nx = a.nx, N = a.N, mk = a.mk;
+    const int R = (N + 1) * nx;  // rows of Phi / Psi (blocks 0 .. N)
+    const Carve cv = make_carve(n, N, nx, BS);
+    const int ld = cv.ld;
+    double *base = kLds ? lds_carve : a.carve_ws + b * a.carve;
+    double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *nu = base + cv.nu, *s = base + cv.s;
+    double *y = base + cv.y, *v = base + cv.v, *red = base + cv.red;
+    int *idx = (int *)(base + cv.idx);
+
+    double *gx0 = a.g_x0 + b * nx;
+    double *ggoal = a.g_goal ? a.g_goal + b * nx : nullptr;
+    double *gtgt = a.g_targets ? a.g_targets + b * (int64_t)N * nx : nullptr;
+    double *ge = a.g_e ? a.g_e + b * (int64_t)m : nullptr;
+    const double *P = a.P + b * (int64_t)n * n;
+    const double *G = a.G ? a.G + b * (int64_t)m * n : nullptr;
+    const double *Phi = a.Phi + b * (int64_t)R * nx;
+    const double *Psi = a.Psi + b * (int64_t)R * n;
+    const double *lam = a.lam + b * (int64_t)m;
+    const double *gU = a.gU + b * (int64_t)n;
+    const double *gX = a.gX ? a.gX + b * (int64_t)R : nullptr;
+
+    int verdict = a.status[b];
+    if (verdict == 0) {
+        // 1. lower triangle of P; Z row 0 = gU + Psi' gX; 3. active rows (wave 0: ballot + prefix count, ids ascending)
+        for (int e = tid; e < n * n; e += BS) {
+            const int i = e / n, j = e % n;
+            if (j <= i) L[i * ld + j] = P[e];
+        }
+        for (int i = tid; i < n; i += BS) {
+            double acc = gU[i];
+            if (gX)
+                for (int r = 0; r < R; ++r) acc += Psi[(int64_t)r * n + i] * gX[r];
+            Z[i] = acc;
+        }
+        if (tid < 64) {
+            int count = 0;
+            for (int i0 = 0; i0 < m; i0 += 64) {
+                const int i = i0 + tid;
+                const bool act = i < m && lam[i] > 0.0;
+                const unsigned long long mask = __ballot(act);
+                const int pre = __popcll(mask & ((1ull << tid) - 1ull));
+                if (act && count + pre < n) idx[count + pre] = i;
+                count += __popcll(mask);
+            }
+            if (tid == 0) s_k = count;
+        }
+        __syncthreads();
+        const int k = s_k;
+        if (k > n) {
+            verdict = MPCQP_NOT_PD;  // more active rows than variables: the forward's multipliers are not a vertex's
+        } else {
+            // 4. G_A rows into Z rows 1 .. k, then one forward sweep L^-1 over all k + 1 right-hand sides
+            for (int e = tid; e < k * n; e += BS) {
+                const int r = e / n, j = e % n;
+                Z[(r + 1) * ld + j] = G[(int64_t)idx[r] * n + j];
+            }
+            if (!chol_lower<BS>(L, n, ld, tid)) {
+                verdict = MPCQP_NOT_PD;
+            } else {
+                const int nr = k + 1;
+                for (int j = 0; j < n; ++j) {
+                    const double inv = 1.0 / L[j * ld + j];
+                    for (int r = tid; r < nr; r += BS) Z[r * ld + j] *= inv;
+                    __syncthreads();
+                    const int w = n - j - 1;
+                    for (int e = tid; e < nr * w; e += BS) {
+                        const int r = e / w, i = j + 1 + e % w;
+                        Z[r * ld + i] -= L[i * ld + j] * Z[r * ld + j];
+                    }
+                    __syncthreads();
+                }
+                // 5. Gram S = M_A M_A' (lower) and nu = M_A t
+                for (int e = tid; e < k * k; e += BS) {
+                    const int i = e / k, j = e % k;
+                    if (j <= i) {
+                        const double *zi = Z + (i + 1) * ld, *zj = Z + (j + 1) * ld;
+                        double acc = 0.0;
+                        for (int c = 0; c < n; ++c) acc += zi[c] * zj[c];
+                        S[i * ld + j] = acc;
+                    }
+                }
+                for (int i = tid; i < k; i += BS) {
+                    const double *zi = Z + (i + 1) * ld;
+                    double acc = 0.0;
+                    for (int c = 0; c < n; ++c) acc += zi[c] * Z[c];
+                    nu[i] = acc;
+                }
+                if (!chol_lower<BS>(S, k, ld, tid)) {
+                    verdict = MPCQP_NOT_PD;
+                } else {
+                    solve_lower<BS>(S, k, ld, nu, tid);
+                    solve_lower_t<BS>(S, k, ld, nu, tid);
+                    // w = L^-T (t - M_A' nu)
+                    for (int j = tid; j < n; j += BS) {
+                        double acc = Z[j];
+                        for (int r = 0; r < k; ++r) acc -= Z[(r + 1) * ld + j] * nu[r];
+                        s[j] = acc;
+                    }
+                    __syncthreads();
+                    solve_lower_t<BS>(L, n, ld, s, tid);
+                    // 6. y = Psi dL/dq = -Psi w
+                    for (int r = tid; r < R; r += BS) {
+                        const double *pr = Psi + (int64_t)r * n;
+                        double acc = 0.0;
+                        for (int c = 0; c < n; ++c) acc += pr[c] * s[c];
+                        y[r] = -acc;
+                    }
+                    __syncthreads();
+                    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+                    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
+                    for (int e = tid; e < R; e += BS) {
+                        const int kk = e / nx, j = e % nx;
+                        double acc = gX ? gX[e] : 0.0;
+                        if (qs && kk < N) acc += a.wx * y[e];
+                        if (qt && kk == N) acc += a.wt * y[e];
+                        if (Cb && kk < N) {
+                            const double *Ck = Cb + kk * a.C.step_stride;
+                            for (int r = 0; r < k; ++r) {
+                                const int row = idx[r];
+                                if (row / mk == kk) acc -= Ck[(row % mk) * nx + j] * nu[r];
+                            }
+                        }
+                        v[e] = acc;
+                        if (ggoal && kk == N) ggoal[j] = qt ? -a.wt * y[e] : 0.0;
+                        if (gtgt && kk < N) gtgt[e] = qs ? -a.wx * y[e] : 0.0;
+                    }
+                    if (ge) {
+                        for (int i = tid; i < m; i += BS) {
+                            // idx is ascending: binary search for row i among the k active ones
+                            int lo = 0, hi = k;
+                            while (lo < hi) {
+                                const int mid = (lo + hi) >> 1;
+                                if (idx[mid] < i) lo = mid + 1; else hi = mid;
+                            }
+                            ge[i] = (lo < k && idx[lo] == i) ? nu[lo] : 0.0;
+                        }
+                    }
+                    __syncthreads();
+                    // g_x0 = sum_k Phi_k' v_k: lanes split the (N + 1) nx rows, one partial per lane, then a column sum
+                    if (nx <= BS) {
+                        const int nsl = BS / nx;
+                        if (tid < nsl * nx) {
+                            const int c = tid % nx, sl = tid / nx;
+                            double acc = 0.0;
+                            for (int r = sl; r < R; r += nsl) acc += Phi[(int64_t)r * nx + c] * v[r];
+                            red[tid] = acc;
+                        }
+                        __syncthreads();
+                        if (tid < nx) {
+                            double acc = 0.0;
+                            for (int sl = 0; sl < nsl; ++sl) acc += red[sl * nx + tid];
+                            gx0[tid] = acc;
+                        }
+                    } else {
+                        for (int c = tid; c < nx; c += BS) {
+                            double acc = 0.0;
+                            for (int r = 0; r < R; ++r) acc += Phi[(int64_t)r * nx + c] * v[r];
+                            gx0[c] = acc;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (verdict != 0) {  // (uniform: every thread took the same branches) unsolved or degenerate: all-zero gradients
+        for (int j = tid; j < nx; j += BS) gx0[j] = 0.0;
+        if (ggoal)
+            for (int j = tid; j < nx; j += BS) ggoal[j] = 0.0;
+        if (gtgt)
+            for (int j = tid; j < N * nx; j += BS) gtgt[j] = 0.0;
+        if (ge)
+            for (int j = tid; j < m; j += BS) ge[j] = 0.0;
+    }
+    if (a.vjp_status && tid == 0) a.vjp_status[b] = verdict;
+}
+
+// 64 lanes for n <= 32 (config 2: n = 16, several workgroups per CU); 256 above
+inline int adjoint_threads(int n) { return n <= 32 ? 64 : 256; }
+
+template <int BS>
+int launch_bs(const AdjArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
+{
+    if (lds) {
+        auto kern = mpcqp_adjoint_kernel<BS, true>;
+        if (lds_bytes > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (e != hipSuccess) return (int)e;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(BS), lds_bytes, st, a);
+    } else {
+        hipLaunchKernelGGL((mpcqp_adjoint_kernel<BS, false>), dim3((unsigned)batch), dim3(BS), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
+}  // namespace
+
+size_t adjoint_carve_bytes(int n, int N, int nx) { return (size_t)make_carve(n, N, nx, adjoint_threads(n)).total * sizeof(double); }
+
+// (the 64 bytes spare leave room for the kernel's static s_k)
+bool adjoint_carve_in_lds(int n, int N, int nx) { return adjoint_carve_bytes(n, N, nx) + 64 <= kLdsBytesPerCU; }
+
+int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
+{
+    AdjArgs a;
+    a.nx = l.nx;
+    a.nu = l.nu;
+    a.N = l.N;
+    a.mk = l.mk;
+    a.n = l.N * l.nu;
+    a.m = l.N * l.mk;
+    a.flags = l.flags;
+    a.wt = l.wt;
+    a.wx = l.wx;
+    a.P = (const double *)l.P;
+    a.G = (const double *)l.G;
+    a.Phi = (const double *)l.Phi;
+    a.Psi = (const double *)l.Psi;
+    a.C = l.C;
+    a.lam = (const double *)l.lam;
+    a.gU = (const double *)l.gU;
+    a.gX = (const double *)l.gX;
+    a.status = l.status;
+    a.g_x0 = (double *)l.g_x0;
+    a.g_goal = (double *)l.g_goal;
+    a.g_targets = (double *)l.g_targets;
+    a.g_e = (double *)l.g_e;
+    a.vjp_status = l.vjp_status;
+    const bool lds = adjoint_carve_in_lds(a.n, a.N, a.nx);
+    const size_t bytes = adjoint_carve_bytes(a.n, a.N, a.nx);
+    a.carve_ws = lds ? nullptr : (double *)l.carve_ws;
+    a.carve = (int64_t)(bytes / sizeof(double));
+    if (!lds && !a.carve_ws) return MPCQP_EWORKSPACE;
+    return adjoint_threads(a.n) == 64 ? launch_bs<64>(a, lds, bytes, batch, st) : launch_bs<256>(a, lds, bytes, batch, st);
+}
+
+}  // namespace mpcqp

@@ -1024,6 +1024,93 @@ int mpcqp_rollout_batch(const MpcqpDims *dims, const MpcqpOperand *A, const Mpcq
     return launch_rollout(ka, dims->dtype, batch, (hipStream_t)stream);
 }
 
+namespace {
+// mpcqp_plan_vjp_batch's workspace, per launch: the condensed P, q, G, h, Phi, Psi of every problem (256-byte aligned
+// segments), mpcqp_condense_batch's own scratch, then the adjoint carves when they do not fit LDS
+struct VjpPlan {
+    int64_t P, q, G, h, Phi, Psi, cws, carve, total;
+    size_t cws_bytes;
+};
+
+static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v)
+{
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    if (batch < 0) return MPCQP_EINVAL;
+    if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
+    const int64_t nx = dims->nx, N = dims->N, n = N * dims->nu, m = N * dims->mk;
+    if (n > 128) return MPCQP_EUNSUPPORTED;
+    size_t cws = 0;
+    if ((rc = mpcqp_workspace_bytes(dims, batch, 0, &cws))) return rc == MPCQP_ETOOLARGE ? MPCQP_EUNSUPPORTED : rc;
+    const int64_t d = 8 * batch;
+    v.P = 0;
+    v.q = v.P + al256(d * n * n);
+    v.G = v.q + al256(d * n);
+    v.h = v.G + al256(d * m * n);
+    v.Phi = v.h + al256(d * m);
+    v.Psi = v.Phi + al256(d * (N + 1) * nx * nx);
+    v.cws = v.Psi + al256(d * (N + 1) * nx * n);
+    v.cws_bytes = cws;
+    v.carve = v.cws + al256((int64_t)cws);
+    const bool lds = adjoint_carve_in_lds((int)n, (int)N, (int)nx);
+    v.total = v.carve + (lds ? 0 : al256((int64_t)adjoint_carve_bytes((int)n, (int)N, (int)nx) * batch));
+    return 0;
+}
+}  // namespace
+
+int mpcqp_plan_vjp_workspace_bytes(const MpcqpDims *dims, int64_t batch, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    VjpPlan v;
+    const int rc = vjp_plan(dims, batch, v);
+    if (rc) return rc;
+    *bytes = (size_t)v.total;
+    return 0;
+}
+
+int mpcqp_plan_vjp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const void *lam,
+                         const int32_t *status, const void *gU, const void *gX, void *g_x0, void *g_goal, void *g_targets,
+                         void *g_e, int32_t *vjp_status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    VjpPlan v;
+    int rc = vjp_plan(dims, batch, v);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    if (!status || !gU || !g_x0 || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
+    char *w = (char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    // the existing condensing, Phi and Psi kept
+    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
+                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
+    if (rc) return rc;
+    AdjointLaunch l;
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.flags = dims->flags;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.P = w + v.P;
+    l.G = dims->mk > 0 ? w + v.G : nullptr;
+    l.Phi = w + v.Phi;
+    l.Psi = w + v.Psi;
+    l.C = problem->C;
+    l.lam = lam;
+    l.gU = gU;
+    l.gX = gX;
+    l.status = status;
+    l.g_x0 = g_x0;
+    l.g_goal = g_goal;
+    l.g_targets = g_targets;
+    l.g_e = g_e;
+    l.vjp_status = vjp_status;
+    l.carve_ws = (v.total > v.carve) ? w + v.carve : nullptr;
+    return launch_adjoint(l, batch, st);
+}
+
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const MpcqpSolveOpts *opts,
                            void *U, void *lam, int32_t *status, int32_t *iters, void *workspace, size_t workspace_bytes,
                            void *states, int64_t *loop_stats, double sampling_period, double target_vel, double length,

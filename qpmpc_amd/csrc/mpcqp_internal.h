@@ -272,6 +272,21 @@ int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStre
 int launch_phi(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);
 int launch_update(const KernelArgs &ka, int dtype, int64_t phi_bs, int64_t psi_bs, int64_t batch, hipStream_t st);
 int launch_rollout(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);
+// vector-Jacobian product of solved plans (mpcqp_adjoint.hip; float64): one problem per workgroup on the condensed matrices
+struct AdjointLaunch {
+    int nx, nu, N, mk, flags;
+    double wt, wx;
+    const void *P, *G, *Phi, *Psi;  // mpcqp_condense_batch's outputs, packed per problem
+    MpcqpOperand C;
+    const void *lam, *gU, *gX;
+    const int32_t *status;
+    void *g_x0, *g_goal, *g_targets, *g_e;
+    int32_t *vjp_status;
+    void *carve_ws;  // batch * adjoint_carve_bytes when the carve does not fit LDS
+};
+size_t adjoint_carve_bytes(int n, int N, int nx);
+bool adjoint_carve_in_lds(int n, int N, int nx);
+int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st);
 
 }  // namespace mpcqp
 #endif
