@@ -123,7 +123,7 @@ typedef struct MpcqpProblem {
 #define MPCQP_OPT_FORCE_DENSE_G 4  /* large fused path: form G (and its transpose) instead of applying it */
 #define MPCQP_OPT_ONE_PER_WAVE 8   /* small problems: one problem per wavefront instead of two            */
 #define MPCQP_OPT_FORCE_CONDENSED 16 /* keep the condensed kernels (mpcqp_build_solve_batch otherwise hands 16 < n <= 128,
-                                        nx <= 4, nu <= 2, float64 -- and every other problem of more than 24 variables with
+                                        nx <= 4, nu <= 2, float64 -- and every other problem of more than 20 variables with
                                         nx <= 16 (float32: 12), nu <= 4 -- to the stage-wise kernels, which are faster
                                         there and return the same minimiser)                                      */
 

@@ -102,9 +102,16 @@ int layout_for(const KernelArgs &ka, bool stepA, bool stepB, int mode, int dtype
 bool force_lds(int fl) { return fl & MPCQP_OPT_FORCE_LDS; }
 bool force_gws(int fl) { return fl & MPCQP_OPT_FORCE_GWS; }
 bool force_dense_g(int fl) { return fl & MPCQP_OPT_FORCE_DENSE_G; }
+// the overrides that take a launch off the automatic choice of kernel (the cross-check tests of the kernels)
+constexpr int kOverrideFlags =
+    MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED | MPCQP_OPT_ONE_PER_WAVE;
 // every combination of overrides a launch may carry: the workspace queries, which see no opts, report the
 // largest amount any of them needs
 const int kFlagVariants[] = {0, MPCQP_OPT_FORCE_LDS, MPCQP_OPT_FORCE_GWS, MPCQP_OPT_FORCE_DENSE_G, MPCQP_OPT_FORCE_CONDENSED};
+
+// A size query carries the dimensions only, no operands (a launch always carries A: check_problem). It is priced for the
+// bulkiest operand layout (per-step A and B on chip, both layouts of the wide kernel) and for the second opinion.
+bool size_query(const KernelArgs &ka) { return !ka.A.ptr; }
 
 // float64 problems that would take the dense HBM-resident path (nx <= 16, nu > 4, n <= 256: condense + one QP per workgroup)
 // go to the general stage-wise kernel instead, unless an override flag asks for the dense solvers: since its second version
@@ -112,19 +119,17 @@ const int kFlagVariants[] = {0, MPCQP_OPT_FORCE_LDS, MPCQP_OPT_FORCE_GWS, MPCQP_
 // path (MFMA Gram, float32 solver), which is what makes that size affordable in float32.
 static bool prefer_general(const KernelArgs &ka, int dtype)
 {
-    const int override_bits = MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED |
-                              MPCQP_OPT_ONE_PER_WAVE;
-    return dtype == MPCQP_F64 && !(ka.opt_flags & override_bits) && !ka.warm_state && stageg_supported(ka, MPCQP_F64);
+    return dtype == MPCQP_F64 && !(ka.opt_flags & kOverrideFlags) && !ka.warm_state && stageg_supported(ka, MPCQP_F64);
 }
 
 // Fused build+solve of mid-size problems of small systems goes to the stage-wise kernel (mpcqp_stage.hip): same
 // minimiser (tests), 1.5-1.9x the mid-size condensed kernel on config 3. Its slots hold min(n, m) <= 128 active rows, i.e.
 // every row that can be active at once, so nothing is lost against the condensed kernels.
+// Beyond n = 128 (round 3) the wide kernel is 1.3-2x faster where many rows become active and ties where few do
+// (tools/probe_long_narrow.py, tools/probe_narrow_vs_wide.py); the narrow one stays reachable through mpcqp_stagewise_solve_batch.
 bool use_stage_auto(const KernelArgs &ka, int dtype)
 {
-    const int override_bits = MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED |
-                              MPCQP_OPT_ONE_PER_WAVE;
-    return !(ka.opt_flags & override_bits) && stage_supported(ka, dtype) && ka.n > 16 && ka.n <= 128 && ka.m >= 1;
+    return !(ka.opt_flags & kOverrideFlags) && stage_supported(ka, dtype) && ka.n > 16 && ka.n <= 128 && ka.m >= 1;
 }
 
 // Fused build+solve of problems that do NOT fit the on-chip condensed kernels goes to the wide stage-wise kernel
@@ -134,50 +139,27 @@ bool use_stage_auto(const KernelArgs &ka, int dtype)
 bool fits_on_chip(const KernelArgs &ka, bool stepA, bool stepB, int mode, int dtype);
 bool use_stagew_auto(const KernelArgs &ka, int dtype)
 {
-    const int override_bits = MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED |
-                              MPCQP_OPT_ONE_PER_WAVE;
-    // Round 3: ... and what DOES fit on chip but is no small problem (n > 24): measured on batches of 512 random LTV problems
+    // Round 3: ... and what DOES fit on chip but is no small problem (n > 24, n > 20 since round 6): measured on batches of 512 random LTV problems
     // (tools/probe_f32_dispatch.py), the stage-wise kernel is 2-2.5x the mid-size / LDS condensed kernels in float64 (nx = 6 .. 12,
     // n = 37 .. 64: 590-980 us against 1180-2170 us) and 2-3x in float32, where it is also 5-30x closer to the float64 oracle
     // (the condensed float32 path squares the conditioning into P: 1e-3 at n ~ 130). Small problems stay on chip: up to n = 20 since
     // round 6 (4096 problems, float64, default / wide stage-wise, us: (nx, nu, N) = (8, 2, 10) n = 20: 824 / 843; (8, 2, 12) n = 24:
     // 1471 / 1087; (12, 4, 6): 860 / 490; (7, 1, 24): 2332 / 1123; (6, 2, 12): 683 / 535; n <= 16: the on-chip kernels by 1.2-2.3x).
-    return !(ka.opt_flags & override_bits) && !(ka.warm_state && ka.warm_start == MPCQP_WARM_OPERATOR) && stagew_supported(ka, dtype) && ka.m >= 1 &&
+    return !(ka.opt_flags & kOverrideFlags) && !(ka.warm_state && ka.warm_start == MPCQP_WARM_OPERATOR) && stagew_supported(ka, dtype) && ka.m >= 1 &&
            ((ka.n > 20 && (dtype == MPCQP_F64 || ka.nx <= 12)) || !fits_on_chip(ka, true, true, MODE_FUSED, dtype));
     // (float32 with nx > 12 -- the LDS-tiled Riccati recursion -- stays on chip while it fits: on borderline problems of that size
     // the condensed float32 kernel was the closer one, 1e-3 against 3e-3)
 }
-// ... and the narrow stage-wise kernel (float64, nx <= 4, nu <= 2: chunked scans, depth ~2 N / 64 per sweep instead of N
-// serial steps) takes what does not fit on chip among the systems it serves: horizons of any length (n > 256 included)
-bool use_stage_long(const KernelArgs &ka, int dtype)
-{
-    const int override_bits = MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED |
-                              MPCQP_OPT_ONE_PER_WAVE;
-    // Round 3, late: no longer taken by the automatic dispatch. On long horizons the two stage-wise kernels tie when few rows become
-    // active (triple integrator, N = 256 / 1024 / 4096, 3.5-12 iterations: 4.97 / 52.2 / 399 ms narrow against 6.03 / 54.2 / 387 ms
-    // wide) and the wide one -- active-set state in LDS, eight right-hand sides per sweep pair, 256 slots -- is 1.3-2x faster when
-    // many do (random LTV, n = 160 .. 256, 50-140 iterations: 7.5 / 40.3 / 13.4 / 42.9 ms against 5.0 / 26.8 / 6.9 / 32.7 ms;
-    // tools/probe_long_narrow.py, tools/probe_narrow_vs_wide.py): n > 128 goes to the wide kernel (use_stagew_auto). The narrow
-    // kernel stays reachable through mpcqp_stagewise_solve_batch.
-    (void)override_bits;
-    (void)dtype;
-    return false;
-}
 // the narrow stage-wise kernel's unsolved verdicts get a second opinion from the wide one (kOptSecondOpinion) in every launch of
 // mpcqp_build_solve_batch / mpcqp_stagewise_solve_batch that it serves, the stateful ones included (KEEP / REUSE / PIPELINE_FACTOR,
-// a warm state): the wide kernel runs in a region of its own after the narrow kernel's workspace (second_opinion_offset), so the
+// a warm state): the wide kernel runs in a region of its own after the narrow kernel's workspace (Route::off2), so the
 // factor images and the vectors a warm record points at survive it, and it neither reads nor writes the warm record
-bool second_opinion_applies(const KernelArgs &ka, int dtype, bool size_query = false)
+bool second_opinion_applies(const KernelArgs &ka, int dtype)
 {
     // (a size query carries neither outputs nor options: it prices the launch that takes the second opinion)
-    return stagew_supported(ka, dtype) && (size_query || ka.status);
+    return stagew_supported(ka, dtype) && (size_query(ka) || ka.status);
 }
-int64_t al256(int64_t bytes);
-// byte offset of the second opinion's region in the workspace: the narrow kernel's workspace for the batch, rounded up to 256 bytes
-size_t second_opinion_offset(const KernelArgs &ka, int maxq, int64_t batch)
-{
-    return (size_t)al256((int64_t)(stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch));
-}
+int64_t al256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 // the wide kernel's arguments behind the narrow one: only what the narrow kernel left unsolved, nothing kept, no warm record
 KernelArgs second_opinion_args(const KernelArgs &ka)
 {
@@ -193,31 +175,6 @@ int stagew_auto_maxq(const KernelArgs &ka)
 {
     const int q = ka.n < ka.m ? ka.n : ka.m;
     return q < 256 ? q : 256;
-}
-
-// warm start: the small-problem pair kernel (operator + slot ids) and the narrow stage-wise kernel (row ids; the rows'
-// vectors stay in its workspace); 0 = not offered for these dimensions
-bool promote_f32(const KernelArgs &ka, int dtype);
-// (kind: MPCQP_WARM_KIND_* -- whose record it is; the host side reads it instead of re-deriving the dispatch)
-size_t warm_bytes_per_problem(KernelArgs ka, int dtype, int *kind = nullptr)
-{
-    ka.opt_flags = 0;
-    ka.warm_state = nullptr;
-    int k = MPCQP_WARM_KIND_NONE;
-    size_t bytes = 0;
-    if (dtype == MPCQP_F32 && promote_f32(ka, dtype)) dtype = MPCQP_F64;  // (the launch that is solved in float64: its kernel's record)
-    if (pair_eligible(ka, MODE_FUSED, dtype)) {
-        k = MPCQP_WARM_KIND_OPERATOR;
-        bytes = kPairWarmDoubles * sizeof(double);
-    } else if (use_stage_auto(ka, dtype)) {
-        k = MPCQP_WARM_KIND_STAGE;
-        bytes = stage_warm_bytes(stage_default_maxq(ka));
-    } else if (use_stagew_auto(ka, dtype)) {
-        k = MPCQP_WARM_KIND_ROWS;
-        bytes = stagew_warm_bytes(stagew_auto_maxq(ka));  // row ids only (MPCQP_WARM_ACTIVE_SET)
-    }
-    if (kind) *kind = k;
-    return bytes;
 }
 
 bool use_bigsolve(int n, int m, int dtype, int fl) { return !force_gws(fl) && m > 0 && bigsolve_supported(n, m, dtype); }
@@ -267,16 +224,6 @@ BigPlan big_plan(const KernelArgs &ka, int dtype, bool condense, bool solve)
 bool use_mid(const KernelArgs &ka, int dtype)
 {
     return !force_lds(ka.opt_flags) && !w64_eligible(ka, MODE_FUSED, dtype) && mid_supported(ka, dtype);
-}
-
-// mpcqp_workspace_bytes sees the dimensions only, not the operand strides: it reports the mid-size
-// kernel's workspace whenever the most compact operand layout (LTI, no C/D) would be taken. A launch with
-// bulkier operands may still fall back to the all-in-LDS kernel, which simply ignores the workspace.
-bool problem_strides_unknown_mid(KernelArgs ka, int dtype)
-{
-    ka.A.step_stride = ka.B.step_stride = ka.C.step_stride = ka.D.step_stride = 0;
-    ka.C.ptr = ka.D.ptr = nullptr;
-    return use_mid(ka, dtype);
 }
 
 bool fits_on_chip(const KernelArgs &ka, bool stepA, bool stepB, int mode, int dtype)
@@ -386,13 +333,38 @@ int64_t operand_elems(const MpcqpOperand &op, int64_t block, int N, int64_t batc
     const int64_t per_problem = (per_step && op.step_stride) ? (int64_t)N * block : block;
     return op.batch_stride ? (batch - 1) * op.batch_stride + per_problem : per_problem;
 }
-int64_t al256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+
+// ---- The dispatch table. route() decides, for one launch, which path runs, with how many slots, and the workspace that
+// path needs, laid out. The launch entry points follow it, and the size queries report the largest route over what they
+// cannot see (the override flags, the operands' bulk). A new path is one entry here. The choice among the on-chip kernels (quad4 / quad / pair / w64 / LDS) needs no
+// workspace and depends on the batch size and the device: it stays in run_solver.
+// Paths: Refused (Route::rc), OnChip (the condensed on-chip kernels, run_solver), Narrow (narrow stage-wise kernel, then the wide
+// one as its second opinion where that applies), Wide, Mid (mid-size condensed kernel), General (general stage-wise kernel), the
+// dense HBM-resident path with G applied through the roll-out (DenseStruct) or formed (DenseGws), and Promote (promote_f32).
+enum class Path { Refused, OnChip, Narrow, Wide, Mid, General, DenseStruct, DenseGws, Promote };
+
+struct Entry {
+    enum Kind { BUILD_SOLVE, STAGEWISE, WIP_PERIODS } kind = BUILD_SOLVE;
+    int max_active = 0;                  // STAGEWISE: slots asked for (<= 0: the kernel's default)
+    bool general = false, wide = false;  // STAGEWISE: MPCQP_OPT_STAGE_GENERAL / MPCQP_OPT_STAGE_WIDE
+    bool bulky = false;                  // BUILD_SOLVE size queries: operands too bulky for the mid-size kernel's LDS
+};
+
+struct Route {
+    Path path = Path::Refused;
+    int rc = 0;         // Refused: the launch's return code; Promote: that of the float64 size query
+    int maxq = 0;       // slots of the stage-wise kernel
+    int maxq2 = 0;      // Narrow: slots of the second opinion (0: no second opinion)
+    size_t off2 = 0;    // Narrow: byte offset of the second opinion's region
+    size_t bytes = 0;   // workspace (Promote: the operand copies at their largest -- the launch packs the ones it makes)
+    size_t inner = 0;   // Promote: workspace of the float64 launch, after the copies
+};
+
+Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e);
 
 bool promote_f32(const KernelArgs &ka, int dtype)
 {
-    const int override_bits = MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED |
-                              MPCQP_OPT_ONE_PER_WAVE;
-    if (dtype != MPCQP_F32 || (ka.opt_flags & override_bits) || ka.m < 1) return false;
+    if (dtype != MPCQP_F32 || (ka.opt_flags & kOverrideFlags) || ka.m < 1) return false;
     // The wide stage-wise kernel squares nothing, and BASELINE config 5 (n = 256) comes out 1e-6 from the float64 plan in
     // float32 -- but on adversarial mid-size families (bounds at the edge of consistency, 60-270 iterations) one plan in
     // ~1500 came back SOLVED 1.4e-3 .. 3.6e-3 away with every active row on its bound to rounding noise: the error sits in the
@@ -407,9 +379,170 @@ bool promote_f32(const KernelArgs &ka, int dtype)
         // problems/s where the general kernel, in float64, is an order of magnitude faster (tools/probe_dense_vs_general.py). The
         // dense solvers are left with nu > 8, MPCQP_OPT_FORCE_CONDENSED / _GWS / _DENSE_G and mpcqp_condense_batch + mpcqp_solve_batch.
         return stageg_supported(ka, MPCQP_F64);
-    // ... and the float64 dispatch must have an on-chip / stage-wise kernel for it
-    return pair_eligible(ka, MODE_FUSED, MPCQP_F64) || use_stage_auto(ka, MPCQP_F64) || use_stagew_auto(ka, MPCQP_F64) ||
-           use_mid(ka, MPCQP_F64) || fits_on_chip(ka, true, true, MODE_FUSED, MPCQP_F64);
+    // ... and the float64 dispatch must have a stage-wise / mid-size kernel for it, or an on-chip one for the bulkiest operand layout
+    const Path p = route(ka, MPCQP_F64, 1, Entry{}).path;
+    return p == Path::Narrow || p == Path::Wide || p == Path::Mid || fits_on_chip(ka, true, true, MODE_FUSED, MPCQP_F64);
+}
+
+Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
+{
+    Route r;
+    const size_t nb = (size_t)batch, esz = elem_size(dtype);
+    auto refuse = [&](int rc) {  // (r.path is still Path::Refused)
+        r.rc = rc;
+        return r;
+    };
+    auto take = [&](Path p, int maxq, size_t bytes_per_problem) {
+        r.path = p;
+        r.maxq = maxq;
+        r.bytes = bytes_per_problem * nb;
+        return r;
+    };
+    auto wide = [&](int maxq) { return take(Path::Wide, maxq, stagew_ws_elems(ka, maxq, dtype) * esz); };
+    auto general = [&](int maxq) { return take(Path::General, maxq, stageg_ws_doubles(ka, maxq) * sizeof(double)); };
+    // the narrow kernel's workspace, then -- where the second opinion applies -- the wide kernel's in a region of its own
+    auto narrow = [&](int maxq, int maxq2) {
+        take(Path::Narrow, maxq, stage_ws_doubles(ka, maxq) * sizeof(double));
+        if (maxq2 && second_opinion_applies(ka, dtype)) {
+            r.maxq2 = maxq2;
+            r.off2 = (size_t)al256((int64_t)r.bytes);
+            r.bytes = r.off2 + stagew_ws_elems(ka, maxq2, dtype) * esz * nb;
+        }
+        return r;
+    };
+    switch (e.kind) {
+    case Entry::WIP_PERIODS:  // (the closed-loop epilogue is compiled into the narrow kernel; no second opinion)
+        return use_stage_auto(ka, dtype) ? narrow(stage_default_maxq(ka), 0) : refuse(MPCQP_EUNSUPPORTED);
+    case Entry::STAGEWISE: {
+        // (float32 problems the general kernel would take: through mpcqp_build_solve_batch, which converts)
+        const bool narrow_ok = stage_supported(ka, dtype), wide_ok = stagew_supported(ka, dtype);
+        if (e.general || (!narrow_ok && !wide_ok))
+            return stageg_supported(ka, dtype) ? general(e.max_active > 0 ? e.max_active : stageg_default_maxq(ka)) : refuse(MPCQP_EUNSUPPORTED);
+        const int maxq = e.max_active > 0 ? e.max_active : stage_default_maxq(ka);
+        return (!narrow_ok || (e.wide && wide_ok)) ? wide(maxq) : narrow(maxq, maxq);
+    }
+    case Entry::BUILD_SOLVE: break;
+    }
+    if (promote_f32(ka, dtype)) {
+        // the copies at their largest (nothing shared, every segment 256-byte aligned), the float64 plan and multipliers, then
+        // the float64 launch's own workspace
+        r.path = Path::Promote;
+        const MpcqpDims d64{ka.nx, ka.nu, ka.N, ka.mk, MPCQP_F64, ka.flags, ka.wt, ka.wx, ka.wu};
+        r.rc = mpcqp_workspace_bytes(&d64, batch, 1, &r.inner);
+        const int64_t N = ka.N, nx = ka.nx, nu = ka.nu, mk = ka.mk;
+        const int64_t per = N * (nx * nx + nx * nu + mk * nx + mk * nu + mk) + 2 * nx + N * nx + ka.n + ka.m;
+        r.bytes = (size_t)(per * 8 * batch + 10 * 256) + r.inner;
+        return r;
+    }
+    if (use_stage_auto(ka, dtype)) return narrow(stage_default_maxq(ka), stagew_auto_maxq(ka));
+    if (use_stagew_auto(ka, dtype)) return wide(stagew_auto_maxq(ka));
+    if (!e.bulky && use_mid(ka, dtype)) return take(Path::Mid, 0, bigsolve_ws_elems(ka.n) * esz);
+    const bool q = size_query(ka);
+    if (fits_on_chip(ka, q || ka.A.step_stride, q || ka.B.step_stride, MODE_FUSED, dtype)) return take(Path::OnChip, 0, 0);
+    // wide systems on horizons the dense path cannot hold -- and every float64 problem it could hold (prefer_general): the
+    // general stage-wise kernel (float64; float32 launches of these dimensions arrive here converted, promote_f32)
+    if (!big_supported(ka) || ka.n > 256 || prefer_general(ka, dtype))
+        return (stageg_supported(ka, dtype) && !ka.warm_state) ? general(stageg_default_maxq(ka)) : refuse(MPCQP_ETOOLARGE);
+    const BigPlan b = big_plan(ka, dtype, true, true);
+    return take(b.matrix_free ? Path::DenseStruct : Path::DenseGws, 0, b.total(true) * esz);
+}
+
+// whose warm-state record a launch on this route reads and writes (MPCQP_WARM_KIND_*): the small-problem pair kernel's
+// (operator + slot ids), the narrow stage-wise kernel's (row ids; the rows' vectors stay in its workspace) or the wide one's
+// (row ids only, MPCQP_WARM_ACTIVE_SET)
+int warm_kind(const Route &r, const KernelArgs &ka, int dtype)
+{
+    switch (r.path) {
+    case Path::Narrow: return MPCQP_WARM_KIND_STAGE;
+    case Path::Wide: return MPCQP_WARM_KIND_ROWS;
+    case Path::OnChip: return pair_eligible(ka, MODE_FUSED, dtype) ? MPCQP_WARM_KIND_OPERATOR : MPCQP_WARM_KIND_NONE;
+    default: return MPCQP_WARM_KIND_NONE;
+    }
+}
+
+// the warm-state record of the automatic dispatch, per problem; 0 = not offered for these dimensions
+// (kind: MPCQP_WARM_KIND_* -- whose record it is; the host side reads it instead of re-deriving the dispatch)
+size_t warm_bytes_per_problem(KernelArgs ka, int dtype, int *kind = nullptr)
+{
+    ka.opt_flags = 0;
+    ka.warm_state = nullptr;
+    if (dtype == MPCQP_F32 && promote_f32(ka, dtype)) dtype = MPCQP_F64;  // (the launch that is solved in float64: its kernel's record)
+    const Route r = route(ka, dtype, 1, Entry{});
+    const int k = warm_kind(r, ka, dtype);
+    if (kind) *kind = k;
+    switch (k) {
+    case MPCQP_WARM_KIND_OPERATOR: return kPairWarmDoubles * sizeof(double);
+    case MPCQP_WARM_KIND_STAGE: return stage_warm_bytes(r.maxq);
+    case MPCQP_WARM_KIND_ROWS: return stagew_warm_bytes(r.maxq);
+    default: return 0;
+    }
+}
+
+// mpcqp_workspace_bytes of a fused build+solve. The query sees dimensions, not operand strides or MpcqpSolveOpts.flags, while
+// the launch picks its kernel with both: it reports the largest workspace of the routes over the override flags and over the
+// operands' bulk -- the mid-size kernel's LDS holds the most compact operands (LTI, no C / D) where bulkier ones may not fit,
+// and such a launch takes the path behind it. Only the automatic dispatch with compact operands refuses: an override
+// combination that has no kernel for these dimensions is refused by the launch that carries it, not by the size query.
+int workspace_query(const KernelArgs &ka, int dtype, int64_t batch, size_t *bytes)
+{
+    size_t need = 0;
+    for (int fl : kFlagVariants) {
+        KernelArgs kv = ka;
+        kv.opt_flags = fl;
+        for (const bool bulky : {false, true}) {
+            const Route r = route(kv, dtype, batch, {Entry::BUILD_SOLVE, 0, false, false, bulky});
+            if (r.path == Path::Refused || r.rc) {
+                if (fl == 0 && !bulky) return r.rc;
+                continue;
+            }
+            if (r.bytes > need) need = r.bytes;
+        }
+    }
+    *bytes = need;
+    return 0;
+}
+
+// the narrow stage-wise kernel, then its second opinion (mpcqp_internal.h, kOptSecondOpinion) on the same stream, in the
+// region the route set aside after the narrow kernel's workspace
+int run_narrow(const KernelArgs &ka, int dtype, const Route &r, int64_t batch, void *ws, hipStream_t st)
+{
+    int rc = launch_stage(ka, r.maxq, batch, ws, st);
+    if (rc || !r.maxq2) return rc;
+    rc = launch_stagew(second_opinion_args(ka), dtype, r.maxq2, batch, (char *)ws + r.off2, st);
+    return rc == MPCQP_ETOOLARGE ? 0 : rc;  // (a horizon beyond the wide kernel's 32-bit offsets: the narrow kernel's verdicts stand)
+}
+
+// HBM-resident path: propagate + Gram (MFMA for f32) into the workspace, then the general solver with its arrays in the
+// workspace as well
+int run_dense(KernelArgs ka, int dtype, int64_t batch, void *workspace, hipStream_t st)
+{
+    const size_t esz = elem_size(dtype), nb = (size_t)batch;
+    const BigPlan b = big_plan(ka, dtype, true, true);
+    char *w = (char *)workspace;
+    void *psi_ws = w;
+    void *res_ws = w + (size_t)(ka.N + 1) * ka.nx * ka.n * nb * esz;
+    w += b.psi * nb * esz;
+    void *Pw = w;
+    w += b.P * nb * esz;
+    void *qw = w;
+    w += b.q * nb * esz;
+    void *Gw = w;
+    w += b.G * nb * esz;
+    void *hw = w;
+    w += b.h * nb * esz;
+    int rc;
+    if (b.matrix_free) {
+        void *nw = w;
+        w += b.nrm * nb * esz;
+        if ((rc = launch_big_condense(ka, dtype, batch, psi_ws, res_ws, Pw, qw, nullptr, hw, nw, st))) return rc;
+        return launch_bigsolve_struct(ka, dtype, batch, Pw, qw, psi_ws, hw, nw, w, st);
+    }
+    if ((rc = launch_big_condense(ka, dtype, batch, psi_ws, res_ws, Pw, qw, Gw, hw, nullptr, st))) return rc;
+    ka.P = Pw;
+    ka.q = qw;
+    ka.G = Gw;
+    ka.h = hw;
+    return run_gws_solve(ka, dtype, batch, w, b.solver * nb * esz, st);
 }
 
 }  // namespace
@@ -478,78 +611,11 @@ int mpcqp_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t for_solv
     KernelArgs ka;
     fill_args(ka, dims, nullptr);
     *bytes = 0;
-    const int mode = for_solve ? MODE_FUSED : MODE_CONDENSE;
-    // The query sees dimensions, not operand strides or MpcqpSolveOpts.flags, while the launch picks its kernel
-    // with both (bulkier operands need more LDS): report the LARGEST workspace any path the launch may take needs.
-    size_t need = 0;
-    bool served = false;  // the automatic dispatch (fl == 0, first) has a kernel for these dimensions
-    bool toolarge = false;
-    for (int fl : kFlagVariants) {
-        ka.opt_flags = fl;
-        const bool maybe_mid = for_solve && problem_strides_unknown_mid(ka, dims->dtype);
-        size_t v = 0;
-        if (maybe_mid) v = bigsolve_ws_elems(ka.n) * elem_size(dims->dtype) * (size_t)batch;  // N* and M_A rows
-        if (for_solve && use_stage_auto(ka, dims->dtype)) {
-            const size_t sw = stage_ws_doubles(ka, stage_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-            if (sw > v) v = sw;
-            if (second_opinion_applies(ka, dims->dtype, true)) {  // (the wide kernel behind the narrow one, in a region of its own)
-                const size_t s2 = second_opinion_offset(ka, stage_default_maxq(ka), batch) +
-                                  stagew_ws_elems(ka, stagew_auto_maxq(ka), dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-                if (s2 > v) v = s2;
-            }
-        }
-        if (for_solve && use_stage_long(ka, dims->dtype)) {
-            const size_t sw = stage_ws_doubles(ka, stage_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-            if (sw > v) v = sw;
-            served = true;
-        }
-        if (for_solve && use_stagew_auto(ka, dims->dtype)) {
-            const size_t sw = stagew_ws_elems(ka, stagew_auto_maxq(ka), dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-            if (sw > v) v = sw;
-            served = true;
-        } else if (!fits_on_chip(ka, true, true, mode, dims->dtype)) {
-            if (big_supported(ka) && ka.n <= 256) {
-                const BigPlan b = big_plan(ka, dims->dtype, true, for_solve != 0);
-                const size_t big = b.total(for_solve != 0) * elem_size(dims->dtype) * (size_t)batch;
-                if (big > v) v = big;
-                if (for_solve && prefer_general(ka, dims->dtype)) {  // (the launch takes the general kernel: the larger of the two)
-                    const size_t sg = stageg_ws_doubles(ka, stageg_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-                    if (sg > v) v = sg;
-                }
-                served = true;
-            } else if (for_solve && stageg_supported(ka, dims->dtype)) {
-                const size_t sg = stageg_ws_doubles(ka, stageg_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-                if (sg > v) v = sg;
-                served = true;
-            } else if (!maybe_mid && fl == 0 && !served) {
-                // (only the automatic dispatch decides: an override combination that has no kernel for these
-                // dimensions is refused by the launch that carries it, not by the size query)
-                if (!(for_solve && dims->dtype == MPCQP_F32)) return MPCQP_ETOOLARGE;
-                toolarge = true;  // (float32: unless the launch is one that is solved in float64, below)
-            }
-        }
-        if (v > need) need = v;
-    }
-    if (for_solve && dims->dtype == MPCQP_F32) {
-        // a float32 launch of an on-chip condensed kernel's size is solved in float64 on copies of its operands (promote_f32):
-        // the copies at their largest (nothing shared), the float64 plan and multipliers, and the float64 launch's own scratch
-        ka.opt_flags = 0;
-        if (promote_f32(ka, MPCQP_F32)) {
-            MpcqpDims d64 = *dims;
-            d64.dtype = MPCQP_F64;
-            size_t inner = 0;
-            const int rc64 = mpcqp_workspace_bytes(&d64, batch, 1, &inner);
-            if (rc64 == 0) {
-                const int64_t N = ka.N, nx = ka.nx, nu = ka.nu, mk = ka.mk;
-                const int64_t per = N * (nx * nx + nx * nu + mk * nx + mk * nu + mk) + 2 * nx + N * nx + ka.n + ka.m;
-                const size_t v = (size_t)(per * 8 * batch + 10 * 256) + inner;  // (every segment starts 256-byte aligned)
-                if (v > need) need = v;
-                toolarge = false;
-            }
-        }
-    }
-    if (toolarge) return MPCQP_ETOOLARGE;
-    *bytes = need;
+    if (for_solve) return workspace_query(ka, dims->dtype, batch, bytes);
+    // mpcqp_condense_batch: on chip, or the HBM-resident propagation
+    if (fits_on_chip(ka, true, true, MODE_CONDENSE, dims->dtype)) return 0;
+    if (!big_supported(ka)) return MPCQP_ETOOLARGE;
+    *bytes = big_condense_ws_elems(ka) * elem_size(dims->dtype) * (size_t)batch;
     return 0;
 }
 
@@ -717,7 +783,8 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
         return MPCQP_EUNSUPPORTED;
     const bool stepA = problem->A.step_stride != 0, stepB = problem->B.step_stride != 0;
     hipStream_t st = (hipStream_t)stream;
-    if (promote_f32(ka, dims->dtype)) {
+    const Route r = route(ka, dims->dtype, batch, Entry{});
+    if (r.path == Path::Promote) {
         // float32 at an on-chip condensed kernel's size: solved in float64 on converted copies (see promote_f32)
         const int64_t N = ka.N, nx = ka.nx, nu = ka.nu, mk = ka.mk;
         const MpcqpOperand *src[8] = {&problem->A, &problem->B, &problem->C, &problem->D, &problem->e, &problem->x0, &problem->goal, &problem->targets};
@@ -754,8 +821,8 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
         if (lam) off += al256(batch * ka.m * 8);
         MpcqpDims d64 = *dims;
         d64.dtype = MPCQP_F64;
-        size_t inner = 0;
-        if ((rc = mpcqp_workspace_bytes(&d64, batch, 1, &inner))) return rc;
+        const size_t inner = r.inner;
+        if (r.rc) return r.rc;
         if (!workspace || workspace_bytes < (size_t)off + inner) return MPCQP_EWORKSPACE;
         if ((rc = launch_convert(in, st))) return rc;
         MpcqpSolveOpts o64{};
@@ -770,87 +837,27 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
         if (lam) out.seg[out.nseg++] = ConvSeg{w + offL, lam, batch * ka.m};
         return launch_convert(out, st);
     }
-    if (ka.warm_state && !pair_eligible(ka, MODE_FUSED, dims->dtype) && !use_stage_auto(ka, dims->dtype) && !use_stagew_auto(ka, dims->dtype))
-        return MPCQP_EUNSUPPORTED;
+    const int kind = ka.warm_state ? warm_kind(r, ka, dims->dtype) : MPCQP_WARM_KIND_NONE;  // (warm_start is 0 without a state)
+    if (ka.warm_state && kind == MPCQP_WARM_KIND_NONE) return MPCQP_EUNSUPPORTED;
     // (row-id warm starts: the pair kernel and the wide stage-wise kernel; the narrow stage-wise kernel, which the dispatch
     // prefers for small systems with 16 < n <= 128, has its own kind of record)
-    if (ka.warm_start == MPCQP_WARM_ACTIVE_SET && !pair_eligible(ka, MODE_FUSED, dims->dtype) &&
-        (use_stage_auto(ka, dims->dtype) || !use_stagew_auto(ka, dims->dtype)))
-        return MPCQP_EUNSUPPORTED;
-    if ((ka.opt_flags & MPCQP_OPT_PIPELINE_FACTOR) && !(use_stage_auto(ka, dims->dtype) && stage_pipeline_supported(ka, dims->dtype)))
+    if (ka.warm_start == MPCQP_WARM_ACTIVE_SET && kind != MPCQP_WARM_KIND_OPERATOR && kind != MPCQP_WARM_KIND_ROWS) return MPCQP_EUNSUPPORTED;
+    if ((ka.opt_flags & MPCQP_OPT_PIPELINE_FACTOR) && !(r.path == Path::Narrow && stage_pipeline_supported(ka, dims->dtype)))
         return MPCQP_EUNSUPPORTED;
     // the state is indexed by problem: a buffer made for a smaller batch would be read and written out of bounds
     if (ka.warm_state && ka.warm_state_bytes < (size_t)batch * warm_bytes_per_problem(ka, dims->dtype)) return MPCQP_EWORKSPACE;
-    if (use_stage_auto(ka, dims->dtype)) {
-        const int maxq = stage_default_maxq(ka);
-        size_t need = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
-        const bool second = second_opinion_applies(ka, dims->dtype);
-        const int maxq2 = stagew_auto_maxq(ka);
-        const size_t off2 = second_opinion_offset(ka, maxq, batch);
-        if (second) need = off2 + stagew_ws_elems(ka, maxq2, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-        if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-        if ((rc = launch_stage(ka, maxq, batch, workspace, st)) || !second) return rc;
-        // the second opinion (mpcqp_internal.h, kOptSecondOpinion): same stream, its own region after the narrow kernel's workspace
-        rc = launch_stagew(second_opinion_args(ka), dims->dtype, maxq2, batch, (char *)workspace + off2, st);
-        return rc == MPCQP_ETOOLARGE ? 0 : rc;  // (a horizon beyond the wide kernel's 32-bit offsets: the narrow kernel's verdicts stand)
+    if (r.path == Path::Refused) return r.rc;
+    if (r.path != Path::OnChip && (!workspace || workspace_bytes < r.bytes)) return MPCQP_EWORKSPACE;
+    switch (r.path) {
+    case Path::Narrow: return run_narrow(ka, dims->dtype, r, batch, workspace, st);
+    case Path::Wide: return launch_stagew(ka, dims->dtype, r.maxq, batch, workspace, st);
+    case Path::Mid: return launch_mid(ka, dims->dtype, batch, workspace, st);
+    case Path::OnChip: return run_solver<MODE_FUSED>(ka, stepA, stepB, dims->dtype, batch, st);
+    case Path::General: return launch_stageg(ka, r.maxq, batch, workspace, st);
+    case Path::DenseStruct:
+    case Path::DenseGws: return run_dense(ka, dims->dtype, batch, workspace, st);
+    default: return MPCQP_ETOOLARGE;  // (Refused and Promote returned above)
     }
-    if (use_stage_long(ka, dims->dtype)) {
-        const int maxq = stage_default_maxq(ka);
-        const size_t need = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
-        if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-        return launch_stage(ka, maxq, batch, workspace, st);
-    }
-    if (use_stagew_auto(ka, dims->dtype)) {
-        const int maxq = stagew_auto_maxq(ka);
-        const size_t need = stagew_ws_elems(ka, maxq, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-        if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-        return launch_stagew(ka, dims->dtype, maxq, batch, workspace, st);
-    }
-    if (use_mid(ka, dims->dtype)) {
-        const size_t need = bigsolve_ws_elems(ka.n) * elem_size(dims->dtype) * (size_t)batch;
-        if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-        return launch_mid(ka, dims->dtype, batch, workspace, st);
-    }
-    if (fits_on_chip(ka, stepA, stepB, MODE_FUSED, dims->dtype))
-        return run_solver<MODE_FUSED>(ka, stepA, stepB, dims->dtype, batch, st);
-    // HBM-resident path: propagate + Gram (MFMA for f32) into the workspace, then the
-    // general solver with its arrays in the workspace as well
-    if (!big_supported(ka) || ka.n > 256 || prefer_general(ka, dims->dtype)) {
-        // wide systems on horizons the dense path cannot hold -- and every float64 problem it could hold (prefer_general): the
-        // general stage-wise kernel (float64; float32 launches of these dimensions arrive here converted, promote_f32)
-        if (!stageg_supported(ka, dims->dtype) || ka.warm_state) return MPCQP_ETOOLARGE;
-        const int maxq = stageg_default_maxq(ka);
-        const size_t need = stageg_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
-        if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-        return launch_stageg(ka, maxq, batch, workspace, st);
-    }
-    const size_t esz = elem_size(dims->dtype), nb = (size_t)batch;
-    const BigPlan b = big_plan(ka, dims->dtype, true, true);
-    if (!workspace || workspace_bytes < b.total(true) * esz * nb) return MPCQP_EWORKSPACE;
-    char *w = (char *)workspace;
-    void *psi_ws = w;
-    void *res_ws = w + (size_t)(ka.N + 1) * ka.nx * ka.n * nb * esz;
-    w += b.psi * nb * esz;
-    void *Pw = w;
-    w += b.P * nb * esz;
-    void *qw = w;
-    w += b.q * nb * esz;
-    void *Gw = w;
-    w += b.G * nb * esz;
-    void *hw = w;
-    w += b.h * nb * esz;
-    if (b.matrix_free) {
-        void *nw = w;
-        w += b.nrm * nb * esz;
-        if ((rc = launch_big_condense(ka, dims->dtype, batch, psi_ws, res_ws, Pw, qw, nullptr, hw, nw, st))) return rc;
-        return launch_bigsolve_struct(ka, dims->dtype, batch, Pw, qw, psi_ws, hw, nw, w, st);
-    }
-    if ((rc = launch_big_condense(ka, dims->dtype, batch, psi_ws, res_ws, Pw, qw, Gw, hw, nullptr, st))) return rc;
-    ka.P = Pw;
-    ka.q = qw;
-    ka.G = Gw;
-    ka.h = hw;
-    return run_gws_solve(ka, dims->dtype, batch, w, b.solver * nb * esz, st);
 }
 
 int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes)
@@ -860,24 +867,14 @@ int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_
     if (!bytes || batch < 0) return MPCQP_EINVAL;
     KernelArgs ka;
     fill_args(ka, dims, nullptr);
-    if (max_active < 0) {  // the general kernel's workspace (MPCQP_OPT_STAGE_GENERAL): -1 default slots, -k: k slots
-        if (!stageg_supported(ka, dims->dtype)) return MPCQP_EUNSUPPORTED;
-        *bytes = stageg_ws_doubles(ka, max_active < -1 ? -max_active : stageg_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-        return 0;
-    }
-    const int maxq = max_active > 0 ? max_active : stage_default_maxq(ka);
+    // (max_active < 0: the general kernel's workspace, MPCQP_OPT_STAGE_GENERAL: -1 default slots, -k: k slots)
+    Entry e{Entry::STAGEWISE, max_active < -1 ? -max_active : max_active, max_active < 0};
+    const Route r = route(ka, dims->dtype, batch, e);
+    if (r.path == Path::Refused) return r.rc;
     // (the query does not see MpcqpSolveOpts.flags: where both kernels apply it reports the larger workspace)
-    size_t a = 0, b = 0;
-    if (stage_supported(ka, dims->dtype)) a = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
-    if (stagew_supported(ka, dims->dtype)) b = stagew_ws_elems(ka, maxq, dims->dtype) * elem_size(dims->dtype) * (size_t)batch;
-    if (a && b) a = second_opinion_offset(ka, maxq, batch) + b;  // (the narrow kernel, then the second opinion's region after it)
-    if (!stage_supported(ka, dims->dtype) && !stagew_supported(ka, dims->dtype)) {
-        if (!stageg_supported(ka, dims->dtype)) return MPCQP_EUNSUPPORTED;
-        *bytes = stageg_ws_doubles(ka, max_active > 0 ? max_active : stageg_default_maxq(ka)) * sizeof(double) * (size_t)batch;
-        return 0;
-    }
-    if (!a && !b && batch > 0) return MPCQP_EUNSUPPORTED;
-    *bytes = a > b ? a : b;
+    e.wide = true;
+    const Route w = route(ka, dims->dtype, batch, e);
+    *bytes = r.bytes > w.bytes ? r.bytes : w.bytes;
     return 0;
 }
 
@@ -892,40 +889,24 @@ int mpcqp_stagewise_solve_batch(const MpcqpDims *dims, const MpcqpProblem *probl
     if (batch == 0) return 0;
     KernelArgs ka;
     fill_args(ka, dims, problem);
-    bool narrow = stage_supported(ka, dims->dtype);
-    const bool general = opts && (opts->flags & MPCQP_OPT_STAGE_GENERAL);
-    if (general || (!narrow && !stagew_supported(ka, dims->dtype))) {
-        if (!stageg_supported(ka, dims->dtype)) return MPCQP_EUNSUPPORTED;  // (float32: through mpcqp_build_solve_batch, which converts)
-        ka.U = U;
-        ka.lam = lam;
-        ka.status = status;
-        ka.iters = iters;
-        if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
-        if (ka.warm_state) return MPCQP_EUNSUPPORTED;
-        const int mq = max_active > 0 ? max_active : stageg_default_maxq(ka);
-        if (!workspace || workspace_bytes < stageg_ws_doubles(ka, mq) * sizeof(double) * (size_t)batch) return MPCQP_EWORKSPACE;
-        return launch_stageg(ka, mq, batch, workspace, (hipStream_t)stream);
-    }
-    if (opts && (opts->flags & MPCQP_OPT_STAGE_WIDE) && stagew_supported(ka, dims->dtype)) narrow = false;
     ka.U = U;
     ka.lam = lam;
     ka.status = status;
     ka.iters = iters;
-    if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
-    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
-    const int maxq = max_active > 0 ? max_active : stage_default_maxq(ka);
-    const size_t need_w = stagew_supported(ka, dims->dtype) ? stagew_ws_elems(ka, maxq, dims->dtype) * elem_size(dims->dtype) * (size_t)batch : 0;
+    const bool general = opts && (opts->flags & MPCQP_OPT_STAGE_GENERAL), wide = opts && (opts->flags & MPCQP_OPT_STAGE_WIDE);
     // (as in mpcqp_build_solve_batch: what the narrow kernel leaves MPCQP_MAX_ITER / MPCQP_INFEASIBLE goes through the wide one, with
     // the same slots, in a region of its own after the narrow kernel's workspace -- mpcqp_stagewise_workspace_bytes reports the sum)
-    const bool second = narrow && second_opinion_applies(ka, dims->dtype);
-    const size_t off2 = narrow ? second_opinion_offset(ka, maxq, batch) : 0;
-    size_t need = narrow ? stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch : need_w;
-    if (second) need = off2 + need_w;
-    if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
-    if (!narrow) return launch_stagew(ka, dims->dtype, maxq, batch, workspace, (hipStream_t)stream);
-    if ((rc = launch_stage(ka, maxq, batch, workspace, (hipStream_t)stream)) || !second) return rc;
-    rc = launch_stagew(second_opinion_args(ka), dims->dtype, maxq, batch, (char *)workspace + off2, (hipStream_t)stream);
-    return rc == MPCQP_ETOOLARGE ? 0 : rc;  // (a horizon beyond the wide kernel's 32-bit offsets: the narrow kernel's verdicts stand)
+    const Route r = route(ka, dims->dtype, batch, {Entry::STAGEWISE, max_active, general, wide});
+    if (r.path == Path::Refused) return r.rc;
+    if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
+    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
+    if (!workspace || workspace_bytes < r.bytes) return MPCQP_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    switch (r.path) {
+    case Path::General: return launch_stageg(ka, r.maxq, batch, workspace, st);
+    case Path::Wide: return launch_stagew(ka, dims->dtype, r.maxq, batch, workspace, st);
+    default: return run_narrow(ka, dims->dtype, r, batch, workspace, st);
+    }
 }
 
 int mpcqp_model_bytes(const MpcqpDims *dims, size_t *bytes)
@@ -1140,13 +1121,12 @@ int mpcqp_wip_periods_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
     // the plant is the 4-state, 1-input pendulum, every loop with its own x0, goal and targets; only the stage-wise
     // kernel carries the epilogue
+    const Route r = route(ka, dims->dtype, batch, {Entry::WIP_PERIODS});
     if (ka.nx != 4 || ka.nu != 1 || !problem->x0.ptr || !problem->goal.ptr || !problem->targets.ptr ||
         problem->x0.batch_stride != 4 || problem->goal.batch_stride != 4 || problem->targets.batch_stride != (int64_t)ka.N * 4 ||
-        !use_stage_auto(ka, dims->dtype))
+        r.path == Path::Refused)
         return MPCQP_EUNSUPPORTED;
-    const int maxq = stage_default_maxq(ka);
-    const size_t need = stage_ws_doubles(ka, maxq) * sizeof(double) * (size_t)batch;
-    if (!workspace || workspace_bytes < need) return MPCQP_EWORKSPACE;
+    if (!workspace || workspace_bytes < r.bytes) return MPCQP_EWORKSPACE;
     // (as in mpcqp_build_solve_batch: the warm-state record is indexed by problem and written by the kernel, so a buffer
     // that is too small -- or an old caller that leaves warm_state_bytes at zero -- is refused before anything is launched)
     if (ka.warm_state && ka.warm_state_bytes < (size_t)batch * warm_bytes_per_problem(ka, dims->dtype)) return MPCQP_EWORKSPACE;
@@ -1163,7 +1143,7 @@ int mpcqp_wip_periods_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     ka.ep_g = gravity;
     ka.ep_states = states;
     ka.ep_loopstats = (long long *)loop_stats;
-    return launch_stage(ka, maxq, batch, workspace, (hipStream_t)stream);
+    return run_narrow(ka, dims->dtype, r, batch, workspace, (hipStream_t)stream);
 }
 
 int mpcqp_wip_advance_stats_batch(int32_t dtype, void *states, const void *U, int64_t u_stride, const int32_t *status,
