@@ -430,6 +430,27 @@ int mpcqp_plan_vjp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
                          void *g_x0, void *g_goal, void *g_targets, void *g_e, int32_t *vjp_status,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* Outputs of mpcqp_plan_vjp_model_batch, every pointer nullable; per problem, packed per step whatever the operand
+ * strides: the four of mpcqp_plan_vjp_batch, then
+ *     g_A [N*nx*nx], g_B [N*nx*nu], g_C [N*mk*nx], g_D [N*mk*nu], g_w [3] (terminal, stage, input weight). */
+typedef struct MpcqpVjpModelOut {
+    void *g_x0, *g_goal, *g_targets, *g_e;
+    void *g_A, *g_B, *g_C, *g_D, *g_w;
+} MpcqpVjpModelOut;
+
+/* As mpcqp_plan_vjp_batch, with gradients also with respect to that problem's A_k, B_k, C_k, D_k (an absent C or D: the
+ * gradient at zero) and the three cost weights; an additive part of ABI 12 (MPCQP_ABI_VERSION is unchanged). U is the
+ * forward plan [batch*n]. The four outputs shared with mpcqp_plan_vjp_batch are bitwise those it writes; envelope,
+ * status and vjp_status rules are its own, and unsolved problems get zeros in every output. A cost term follows
+ * dims->flags: a P term without its q term (weight set, goal or targets not) weighs the forced response Psi U, a weight
+ * whose P term is not flagged gets 0. Reductions over operands the batch or the steps share are the caller's. The
+ * workspace holds mpcqp_plan_vjp_batch's and the longer carve of this launch (its own size query). */
+int mpcqp_plan_vjp_model_workspace_bytes(const MpcqpDims *dims, int64_t batch, size_t *bytes);
+int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                               const void *lam, const int32_t *status, const void *U, const void *gU,
+                               const void *gX, const MpcqpVjpModelOut *out, int32_t *vjp_status,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of
  * sampling_period/nsub (WheeledInvertedPendulum.integrate,

@@ -55,6 +55,8 @@ EXPORTS = (
     "mpcqp_lipm_advance_stats_batch",
     "mpcqp_plan_vjp_workspace_bytes",
     "mpcqp_plan_vjp_batch",
+    "mpcqp_plan_vjp_model_workspace_bytes",
+    "mpcqp_plan_vjp_model_batch",
 )
 
 
@@ -72,6 +74,10 @@ class Operand(C.Structure):
 
 class Problem(C.Structure):
     _fields_ = [(name, Operand) for name in ("A", "B", "C", "D", "e", "x0", "goal", "targets")]
+
+
+class VjpModelOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("g_x0", "g_goal", "g_targets", "g_e", "g_A", "g_B", "g_C", "g_D", "g_w")]
 
 
 class SolveOpts(C.Structure):
@@ -180,6 +186,11 @@ def load():
     lib.mpcqp_plan_vjp_batch.restype = C.c_int
     lib.mpcqp_plan_vjp_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                          vp, C.c_size_t, vp]
+    lib.mpcqp_plan_vjp_model_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_vjp_model_workspace_bytes.argtypes = [C.POINTER(Dims), i64, C.POINTER(C.c_size_t)]
+    lib.mpcqp_plan_vjp_model_batch.restype = C.c_int
+    lib.mpcqp_plan_vjp_model_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, vp, vp, vp, vp, vp,
+                                               C.POINTER(VjpModelOut), vp, vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -3,7 +3,8 @@
 The forward is ``solve_mpc_batch`` with multipliers; the backward is one call of ``mpcqp_plan_vjp_batch``
 (include/mpcqp.h): the condensing of the batch into scratch, then one KKT adjoint solve per problem in HIP
 (qpmpc_amd/csrc/mpcqp_adjoint.hip). Gradients reach the initial state, the goal, the stage targets and the inequality
-vector ``e``; the model matrices and the cost weights are constants.
+vector ``e``; when one of the model matrices A, B, C, D or the cost weights passed requires grad, the backward is
+``mpcqp_plan_vjp_model_batch`` instead, the same adjoint followed by its costate pass.
 
 The reference has no counterpart: its plans are NumPy arrays.
 """
@@ -29,8 +30,22 @@ def _detached(x):
     return x.detach() if isinstance(x, torch.Tensor) else x
 
 
-def _replaced(problem: BatchMPCProblem, x0, goal, targets, e) -> BatchMPCProblem:
-    """A shallow copy of ``problem`` whose operands are replaced by the (detached) tensors passed, validated and
+MODEL_OPERANDS = ("transition_state_matrix", "transition_input_matrix", "ineq_state_matrix", "ineq_input_matrix")
+WEIGHTS = ("terminal_cost_weight", "stage_state_cost_weight", "stage_input_cost_weight")  # the order of g_w
+
+
+def _weight(value, name: str) -> float:
+    torch = _torch()
+    if isinstance(value, torch.Tensor):
+        if value.dim() != 0:
+            raise ProblemDefinitionError(f"{name}: expected a float or a 0-dim tensor, got shape {tuple(value.shape)}")
+        return float(value.detach().item())
+    return float(value)
+
+
+def _replaced(problem: BatchMPCProblem, x0, goal, targets, e, A=None, B=None, C=None, D=None,
+              wt=None, wx=None, wu=None) -> BatchMPCProblem:
+    """A shallow copy of ``problem`` whose operands are replaced by the (detached) tensors or values passed, validated and
     canonicalised exactly as ``BatchMPCProblem`` does."""
     work = BatchMPCProblem.__new__(BatchMPCProblem)
     work.__dict__.update(problem.__dict__)
@@ -45,6 +60,23 @@ def _replaced(problem: BatchMPCProblem, x0, goal, targets, e) -> BatchMPCProblem
         if ev.shape[1] not in (1, work.nb_timesteps) or ev.shape[0] not in (1, work.batch_size):
             raise ProblemDefinitionError(f"ineq_vector: shape {tuple(ev.shape)} is not [B|1, N|1, {work.ineq_dim}]")
         work.e = ev
+    nx, nu, mk = work.state_dim, work.input_dim, work.ineq_dim
+    for attr, name, value, tail in (("A", MODEL_OPERANDS[0], A, (nx, nx)), ("B", MODEL_OPERANDS[1], B, (nx, nu)),
+                                    ("C", MODEL_OPERANDS[2], C, (mk, nx)), ("D", MODEL_OPERANDS[3], D, (mk, nu))):
+        if value is None:
+            continue
+        t = _canon(_as_tensor(_detached(value), work.dtype, work.device), tail, name)
+        if t.shape[1] not in (1, work.nb_timesteps) or t.shape[0] not in (1, work.batch_size):
+            raise ProblemDefinitionError(f"{name}: shape {tuple(t.shape)} is not [B|1, N|1, {tail[0]}, {tail[1]}]")
+        setattr(work, attr, t)
+    if wt is not None:
+        work.terminal_cost_weight = _weight(wt, WEIGHTS[0])
+    if wx is not None:
+        work.stage_state_cost_weight = _weight(wx, WEIGHTS[1])
+    if wu is not None:
+        work.stage_input_cost_weight = _weight(wu, WEIGHTS[2])
+        if work.stage_input_cost_weight <= 0.0:
+            raise ProblemDefinitionError("stage non-negative control weight needed for regularization")
     return work
 
 
@@ -92,28 +124,45 @@ def _reduce(g, like, canon_shape):
     return g.reshape(shape).to(dtype=dtype, device=device)
 
 
+def _vjp_inputs(work: BatchMPCProblem, plan, gU, gX):
+    torch = _torch()
+    p64 = _as_float64(work)
+    Bn, N, nx, mk, n = work.batch_size, work.nb_timesteps, work.state_dim, work.ineq_dim, work.nb_variables
+    f64 = dict(dtype=torch.float64, device=work.device)
+    gU = torch.zeros((Bn, n), **f64) if gU is None else gU.reshape(Bn, n).to(torch.float64).contiguous()
+    gX = None if gX is None else gX.reshape(Bn, (N + 1) * nx).to(torch.float64).contiguous()
+    lam = plan.multipliers.to(torch.float64).contiguous() if mk > 0 else None
+    return p64, gU, gX, lam
+
+
+def _workspace_for(query, dims, Bn, device):
+    torch = _torch()
+    nbytes = C.c_size_t(0)
+    _capi.check(query(C.byref(dims), Bn, C.byref(nbytes)), query.__name__)
+    return torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=device)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _plan_vjp(work: BatchMPCProblem, plan, gU, gX, want):
     """(g_x0 [B,nx], g_goal [B,nx], g_targets [B,N*nx], g_e [B,N,mk]) in float64 through mpcqp_plan_vjp_batch; entries not
     in ``want`` are None. Sets ``plan.vjp_status``."""
     torch = _torch()
     lib = _capi.load()
-    p64 = _as_float64(work)
-    Bn, N, nx, mk, n = work.batch_size, work.nb_timesteps, work.state_dim, work.ineq_dim, work.nb_variables
+    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
+    Bn, N, nx, mk = work.batch_size, work.nb_timesteps, work.state_dim, work.ineq_dim
     dev = work.device
     f64 = dict(dtype=torch.float64, device=dev)
-    gU = torch.zeros((Bn, n), **f64) if gU is None else gU.reshape(Bn, n).to(torch.float64).contiguous()
-    gX = None if gX is None else gX.reshape(Bn, (N + 1) * nx).to(torch.float64).contiguous()
-    lam = plan.multipliers.to(torch.float64).contiguous() if mk > 0 else None
     g_x0 = torch.empty((Bn, nx), **f64)
     g_goal = torch.empty((Bn, nx), **f64) if "goal" in want else None
     g_tgt = torch.empty((Bn, N * nx), **f64) if "targets" in want else None
     g_e = torch.empty((Bn, N, mk), **f64) if "e" in want and mk > 0 else None
     vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
     dims, cp = _vjp_dims(p64), p64.c_problem()
-    nbytes = C.c_size_t(0)
-    _capi.check(lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), Bn, C.byref(nbytes)), "mpcqp_plan_vjp_workspace_bytes")
-    ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    ws = _workspace_for(lib.mpcqp_plan_vjp_workspace_bytes, dims, Bn, dev)
+    ptr = _ptr
     rc = lib.mpcqp_plan_vjp_batch(
         C.byref(dims), C.byref(cp), Bn, ptr(lam), plan.status.data_ptr(), gU.data_ptr(), ptr(gX), g_x0.data_ptr(),
         ptr(g_goal), ptr(g_tgt), ptr(g_e), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
@@ -125,28 +174,66 @@ def _plan_vjp(work: BatchMPCProblem, plan, gU, gX, want):
     return g_x0, g_goal, g_tgt, g_e
 
 
+GRAD_KEYS = ("x0", "goal", "targets", "e", "A", "B", "C", "D", "wt", "wx", "wu")
+
+
+def _plan_vjp_model(work: BatchMPCProblem, plan, gU, gX, want):
+    """The gradients of ``GRAD_KEYS`` in float64 through mpcqp_plan_vjp_model_batch, per problem: x0 [B,nx], goal [B,nx],
+    targets [B,N*nx], e [B,N,mk], A [B,N,nx,nx], B [B,N,nx,nu], C [B,N,mk,nx], D [B,N,mk,nu] and the three weights [B];
+    entries not in ``want`` are None. Sets ``plan.vjp_status``."""
+    torch = _torch()
+    lib = _capi.load()
+    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
+    Bn, N, nx, nu, mk = work.batch_size, work.nb_timesteps, work.state_dim, work.input_dim, work.ineq_dim
+    dev = work.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    shapes = dict(x0=(nx,), goal=(nx,), targets=(N * nx,), e=(N, mk), A=(N, nx, nx), B=(N, nx, nu), C=(N, mk, nx),
+                  D=(N, mk, nu))
+    out = {k: (torch.empty((Bn,) + shp, **f64) if k in want else None) for k, shp in shapes.items()}
+    g_w = torch.empty((Bn, 3), **f64) if want & {"wt", "wx", "wu"} else None
+    U = plan.U.reshape(Bn, -1).to(torch.float64).contiguous()
+    vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    dims, cp = _vjp_dims(p64), p64.c_problem()
+    ws = _workspace_for(lib.mpcqp_plan_vjp_model_workspace_bytes, dims, Bn, dev)
+    res = _capi.VjpModelOut(*[_ptr(out[k]) for k in ("x0", "goal", "targets", "e", "A", "B", "C", "D")], _ptr(g_w))
+    rc = lib.mpcqp_plan_vjp_model_batch(
+        C.byref(dims), C.byref(cp), Bn, _ptr(lam), plan.status.data_ptr(), U.data_ptr(), gU.data_ptr(), _ptr(gX),
+        C.byref(res), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+    _capi.check(rc, "mpcqp_plan_vjp_model_batch")
+    plan.vjp_status = vjp_status
+    plan._vjp_keep = (ws, p64, lam, U, gU, gX)  # alive until the stream has consumed them
+    for i, k in enumerate(("wt", "wx", "wu")):
+        out[k] = g_w[:, i] if k in want else None
+    return tuple(out[k] for k in GRAD_KEYS)
+
+
 def _make_function():
     torch = _torch()
     from torch.autograd.function import once_differentiable
 
     class _PlanFunction(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, work, states, solve_kw, box, x0, goal, targets, e):
+        def forward(ctx, work, states, solve_kw, box, *operands):
             plan = solve_mpc_batch(work, return_multipliers=True, **solve_kw)
             U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
             box["plan"] = plan
             ctx.work, ctx.plan, ctx.states = work, plan, states
-            ctx.inputs = tuple(None if t is None else (t.shape, t.dtype, t.device) for t in (x0, goal, targets, e))
-            ctx.canon = (work.initial_state.shape, work.goal_state.shape if goal is not None else None,
-                         work.target_states.shape if targets is not None else None, work.e.shape if e is not None else None)
+            ctx.inputs = tuple(None if t is None else (t.shape, t.dtype, t.device) for t in operands)
+            canon = (work.initial_state, work.goal_state, work.target_states, work.e, work.A, work.B, work.C, work.D)
+            # a weight is one value for the batch: shape (1,) sums its per-problem gradients
+            ctx.canon = (tuple(None if t is None else c.shape for t, c in zip(operands, canon))
+                         + tuple(None if t is None else (1,) for t in operands[8:]))
             return (U, plan.states) if states else U
 
         @staticmethod
         @once_differentiable
         def backward(ctx, gU, gX=None):
             need = ctx.needs_input_grad[4:]
-            want = {nm for nm, nd in zip(("x0", "goal", "targets", "e"), need) if nd}
-            grads = _plan_vjp(ctx.work, ctx.plan, gU, gX, want)
+            want = {nm for nm, nd in zip(GRAD_KEYS, need) if nd}
+            if any(need[4:]):
+                grads = _plan_vjp_model(ctx.work, ctx.plan, gU, gX, want)
+            else:
+                grads = _plan_vjp(ctx.work, ctx.plan, gU, gX, want) + (None,) * 7
             out = [_reduce(g, like, canon) if nd else None
                    for nd, g, like, canon in zip(need, grads, ctx.inputs, ctx.canon)]
             return (None, None, None, None, *out)
@@ -158,29 +245,41 @@ _FUNCTION = None
 
 
 def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_state=None, target_states=None,
-                         ineq_vector=None, states: bool = False, **solve_kw):
+                         ineq_vector=None, states: bool = False, *, transition_state_matrix=None,
+                         transition_input_matrix=None, ineq_state_matrix=None, ineq_input_matrix=None,
+                         terminal_cost_weight=None, stage_state_cost_weight=None, stage_input_cost_weight=None,
+                         **solve_kw):
     """Solve a batch like ``solve_mpc_batch`` and return ``(U, X, plan)`` whose ``U`` [B, N, nu] and, with ``states=True``,
     ``X`` [B, N+1, nx] carry a ``grad_fn`` (``X`` is None otherwise).
 
     ``initial_state``, ``goal_state``, ``target_states`` and ``ineq_vector`` replace the problem's own values when given
     and take the shapes ``BatchMPCProblem`` accepts (``[B, nx]``; ``[B|1, nx]`` or ``[nx]``; ``[B|1, N*nx]``;
-    ``[B|1, N|1, mk]``, ``[N|1, mk]`` or ``[mk]``); the others are constants taken from ``problem``. A gradient reaching an
-    operand shared by the batch (or by the steps) is the sum of the per-problem (per-step) gradients.
+    ``[B|1, N|1, mk]``, ``[N|1, mk]`` or ``[mk]``). So do the keyword-only ``transition_state_matrix``,
+    ``transition_input_matrix``, ``ineq_state_matrix`` and ``ineq_input_matrix`` (``[B|1, N|1, r, c]``, ``[N|1, r, c]``
+    or ``[r, c]``) and the cost weights ``terminal_cost_weight``, ``stage_state_cost_weight`` and
+    ``stage_input_cost_weight`` (a float or a 0-dim tensor; the forward reads its value, and which cost terms exist follows
+    from the weights and states as in ``BatchMPCProblem``). The others are constants taken from ``problem``. A gradient
+    reaching an operand shared by the batch (or by the steps), or a weight, is the sum of the per-problem (per-step)
+    gradients. The gradient with respect to ``ineq_state_matrix`` or ``ineq_input_matrix`` passed where the problem has
+    none is the one at zero.
 
     The forward is ``solve_mpc_batch(..., return_multipliers=True, **solve_kw)`` on detached copies (every dispatch path
     of it returns multipliers, with exact zeros on inactive rows), then the rollout for ``X``. The backward is one
-    ``mpcqp_plan_vjp_batch`` call (float64: a float32 problem's operands are converted, its gradients cast back). The
-    active set is ``{i : lam_i > 0}``: at weakly active points (a tight row with a zero multiplier) the gradient is one
-    element of the generalized Jacobian, as in OptNet. Problems that were not solved (``plan.status != 0``) get zero
-    gradients; after the backward ``plan.vjp_status`` holds their status (and ``MPCQP_NOT_PD`` where the active rows'
-    Gram matrix is singular). Envelope: n = N * nu <= 128; beyond it a request for gradients raises ``BackendError``
-    before anything is launched. Only first derivatives (``once_differentiable``).
+    ``mpcqp_plan_vjp_batch`` call, or ``mpcqp_plan_vjp_model_batch`` when one of the model matrices or weights passed
+    requires grad (float64: a float32 problem's operands are converted, its gradients cast back). The active set is
+    ``{i : lam_i > 0}``: at weakly active points (a tight row with a zero multiplier) the gradient is one element of the
+    generalized Jacobian, as in OptNet. Problems that were not solved (``plan.status != 0``) get zero gradients; after the
+    backward ``plan.vjp_status`` holds their status (and ``MPCQP_NOT_PD`` where the active rows' Gram matrix is singular).
+    Envelope: n = N * nu <= 128; beyond it a request for gradients raises ``BackendError`` before anything is launched.
+    Only first derivatives (``once_differentiable``).
 
     When no operand passed requires grad (or grad mode is off), this is ``solve_mpc_batch(problem', **solve_kw)`` on the
     problem with the replaced operands, and its plan is returned as is."""
     global _FUNCTION
     torch = _torch()
-    passed = (initial_state, goal_state, target_states, ineq_vector)
+    passed = (initial_state, goal_state, target_states, ineq_vector, transition_state_matrix, transition_input_matrix,
+              ineq_state_matrix, ineq_input_matrix, terminal_cost_weight, stage_state_cost_weight,
+              stage_input_cost_weight)
     work = _replaced(problem, *passed)
     need = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in passed)
     if not need:

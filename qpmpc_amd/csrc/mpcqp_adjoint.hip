@@ -12,6 +12,16 @@
 //      g_x0 = sum_k Phi_k' v_k,  v_k = gX_k + w_x y_k [k < N] + w_t y_N [k = N] - C_k' dL/dh_k
 // The carve (L, the k + 1 right-hand sides, the k x k Gram, the vectors) is sized from the actual n, rows at an odd
 // stride (as in mpcqp_lds.hip); it lives in LDS when it fits a CU (about n <= 78: 8.3 KB at n = 16, 19 workgroups per CU), else in the workspace.
+//
+// kModel (mpcqp_plan_vjp_model_batch) appends, after phase 6, the gradients with respect to A, B, C, D and the three cost
+// weights ("model and cost gradients"; Y = -y, w, nu and the plan U are held fixed):
+//   7. Z = Psi U (forced response), X = Phi x0 + Z; E = X - r_k / X_N - goal where the q term is flagged, else Z
+//   8. costates, serial over k and parallel over nx lanes: p from a = v (phase 6's v), pz from the P-only weighted Y
+//      terms, s from b = -(w_x E_k + w_t E_N + C_k' lam_k); x_k = a_k + A_k' x_{k+1}
+//   9. g_A_k = p_{k+1} X_k' + pz_{k+1} Z_k' + s_{k+1} Y_k',  g_B_k = (p + pz)_{k+1} u_k' + s_{k+1} w_k',
+//      g_C_k = -(lam_k Y_k' + nu_k X_k'),  g_D_k = -(lam_k w_k' + nu_k u_k')     (coalesced over (k, i, j))
+//  10. g_w = (-Y_N'E_N, -sum_{k<N} Y_k'E_k, -w'U), one block reduction
+// The carve grows by X, Z, pz, s ((N + 1) nx each), nu scattered over all m rows and the reduction's 3 x threads.
 #include <hip/hip_runtime.h>
 
 #include "mpcqp.h"
@@ -31,14 +41,19 @@ struct AdjArgs {
     int32_t *vjp_status;                       // nullable
     double *carve_ws;                          // per-problem carves when they do not fit LDS (else null)
     int64_t carve;                             // doubles per problem
+    // kModel only
+    MpcqpOperand A, x0, goal, targets;
+    const double *U;                           // the forward plan [batch * n]
+    double *g_A, *g_B, *g_C, *g_D, *g_w;       // nullable, packed per problem
 };
 
 struct Carve {
     int ld;  // odd row stride of the n-wide matrices
     int64_t L, Z, S, nu, s, y, v, red, idx, total;
+    int64_t X, Zf, pz, sc, nuf, wred;  // model: appended after idx (total includes them only when model)
 };
 
-__host__ __device__ inline Carve make_carve(int n, int N, int nx, int threads)
+__host__ __device__ inline Carve make_carve(int n, int N, int nx, int threads, int m = 0, bool model = false)
 {
     Carve c;
     c.ld = n | 1;
@@ -53,6 +68,14 @@ __host__ __device__ inline Carve make_carve(int n, int N, int nx, int threads)
     c.red = c.v + (int64_t)(N + 1) * nx;  // threads: partial sums of g_x0
     c.idx = c.red + threads;              // n + 1 int32 (active row ids)
     c.total = c.idx + (n + 2) / 2;
+    const int64_t R = (int64_t)(N + 1) * nx;
+    c.X = c.total;           // (N + 1) nx: Phi x0 + Psi U
+    c.Zf = c.X + R;          // (N + 1) nx: Psi U
+    c.pz = c.Zf + R;         // (N + 1) nx: costate of Z (p lives in v)
+    c.sc = c.pz + R;         // (N + 1) nx: costate of Y
+    c.nuf = c.sc + R;        // m: dL/dh over every row
+    c.wred = c.nuf + m;      // 3 x threads: partial sums of g_w
+    if (model) c.total = c.wred + 3 * threads;
     return c;
 }
 
@@ -102,7 +125,132 @@ __device__ void solve_lower_t(const double *R, int nn, int ld, double *x, int ti
     }
 }
 
-template <int BS, bool kLds>
+// 7 .. 10 of the header, after phase 6 of a solved problem (uniform: every thread of the block gets here). On entry the
+// carve holds w (s), the k active entries of dL/dh (nu, rows idx), y = -Y and v = a; g_x0 is written.
+template <int BS>
+__device__ void model_phase(const AdjArgs &a, const Carve &cv, double *base, const double *Phi, const double *Psi,
+                            const double *lam, int k, int64_t b)
+{
+    const int tid = threadIdx.x;
+    const int n = a.n, m = a.m, nx = a.nx, nu = a.nu, N = a.N, mk = a.mk;
+    const int R = (N + 1) * nx;
+    const double *w = base + cv.s, *nu_a = base + cv.nu, *y = base + cv.y;
+    const int *idx = (const int *)(base + cv.idx);
+    double *p = base + cv.v, *X = base + cv.X, *Zf = base + cv.Zf, *pz = base + cv.pz, *sc = base + cv.sc;
+    double *nuf = base + cv.nuf, *wred = base + cv.wred;
+    const double *U = a.U + b * (int64_t)n;
+    const bool pt = (a.flags & MPCQP_P_TERMINAL) != 0, ps = (a.flags & MPCQP_P_STAGE) != 0;
+    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+    const double *x0 = (const double *)a.x0.ptr + b * a.x0.batch_stride;
+    const double *goal = qt ? (const double *)a.goal.ptr + b * a.goal.batch_stride : nullptr;
+    const double *tgt = qs ? (const double *)a.targets.ptr + b * a.targets.batch_stride : nullptr;
+    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
+    const double *Ab = (const double *)a.A.ptr + b * a.A.batch_stride;
+
+    // 7. Z = Psi U, X = Phi x0 + Z; nu over every row (zero off the active set)
+    for (int r = tid; r < R; r += BS) {
+        const double *pr = Psi + (int64_t)r * n, *fr = Phi + (int64_t)r * nx;
+        double z = 0.0, f = 0.0;
+        for (int c = 0; c < n; ++c) z += pr[c] * U[c];
+        for (int c = 0; c < nx; ++c) f += fr[c] * x0[c];
+        Zf[r] = z;
+        X[r] = f + z;
+    }
+    for (int i = tid; i < m; i += BS) nuf[i] = 0.0;
+    __syncthreads();
+    for (int r = tid; r < k; r += BS) nuf[idx[r]] = nu_a[r];
+    // 8. right-hand sides of pz and s (p starts as v), with the partial sums of Y'E for g_w
+    double tw = 0.0, sw = 0.0;
+    for (int e = tid; e < R; e += BS) {
+        const int kk = e / nx, i = e % nx;
+        double az = 0.0, bb = 0.0;
+        if (kk < N) {
+            if (ps) {
+                const double E = qs ? X[e] - tgt[e] : Zf[e];
+                bb -= a.wx * E;
+                sw += y[e] * E;
+                if (!qs) az += a.wx * y[e];
+            }
+            if (Cb) {
+                const double *Ck = Cb + kk * a.C.step_stride;
+                for (int r = 0; r < mk; ++r) bb -= Ck[r * nx + i] * lam[kk * mk + r];
+            }
+        } else if (pt) {
+            const double E = qt ? X[e] - goal[i] : Zf[e];
+            bb -= a.wt * E;
+            tw += y[e] * E;
+            if (!qt) az += a.wt * y[e];
+        }
+        pz[e] = az;
+        sc[e] = bb;
+    }
+    __syncthreads();
+    // ... then x_k += A_k' x_{k+1} for k = N - 1 .. 0, the three costates side by side
+    for (int kk = N - 1; kk >= 0; --kk) {
+        const double *Ak = Ab + kk * a.A.step_stride;
+        for (int e = tid; e < 3 * nx; e += BS) {
+            const int which = e / nx, i = e % nx;
+            double *x = which == 0 ? p : (which == 1 ? pz : sc);
+            const double *xn = x + (kk + 1) * nx;
+            double acc = 0.0;
+            for (int j = 0; j < nx; ++j) acc += Ak[j * nx + i] * xn[j];
+            x[kk * nx + i] += acc;
+        }
+        __syncthreads();
+    }
+    // 9. outer products, packed per problem
+    if (a.g_A) {
+        const int64_t NA = (int64_t)N * nx * nx;
+        double *gA = a.g_A + b * NA;
+        for (int64_t e = tid; e < NA; e += BS) {
+            const int kk = (int)(e / (nx * nx)), r = (int)(e % (nx * nx)), i = r / nx, j = r % nx;
+            const int o = (kk + 1) * nx + i, c = kk * nx + j;
+            gA[e] = p[o] * X[c] + pz[o] * Zf[c] - sc[o] * y[c];
+        }
+    }
+    if (a.g_B) {
+        const int64_t NB = (int64_t)N * nx * nu;
+        double *gB = a.g_B + b * NB;
+        for (int64_t e = tid; e < NB; e += BS) {
+            const int kk = (int)(e / (nx * nu)), r = (int)(e % (nx * nu)), i = r / nu, j = r % nu;
+            const int o = (kk + 1) * nx + i, c = kk * nu + j;
+            gB[e] = (p[o] + pz[o]) * U[c] + sc[o] * w[c];
+        }
+    }
+    if (a.g_C) {
+        const int64_t NC = (int64_t)m * nx;
+        double *gC = a.g_C + b * NC;
+        for (int64_t e = tid; e < NC; e += BS) {
+            const int row = (int)(e / nx), i = (int)(e % nx), c = (row / mk) * nx + i;
+            gC[e] = lam[row] * y[c] - nuf[row] * X[c];
+        }
+    }
+    if (a.g_D) {
+        const int64_t ND = (int64_t)m * nu;
+        double *gD = a.g_D + b * ND;
+        for (int64_t e = tid; e < ND; e += BS) {
+            const int row = (int)(e / nu), j = (int)(e % nu), c = (row / mk) * nu + j;
+            gD[e] = -(lam[row] * w[c] + nuf[row] * U[c]);
+        }
+    }
+    // 10. g_w = (-Y_N'E_N, -sum Y_k'E_k, -w'U) with Y = -y: one tree reduction of the three partial sums
+    if (a.g_w) {
+        double uw = 0.0;
+        for (int c = tid; c < n; c += BS) uw += w[c] * U[c];
+        wred[tid] = tw;
+        wred[BS + tid] = sw;
+        wred[2 * BS + tid] = uw;
+        __syncthreads();
+        for (int st = BS / 2; st > 0; st >>= 1) {
+            if (tid < st)
+                for (int q = 0; q < 3; ++q) wred[q * BS + tid] += wred[q * BS + tid + st];
+            __syncthreads();
+        }
+        if (tid < 3) a.g_w[b * 3 + tid] = tid < 2 ? wred[tid * BS] : -wred[2 * BS];
+    }
+}
+
+template <int BS, bool kLds, bool kModel>
 __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
 {
     extern __shared__ double lds_carve[];
@@ -111,7 +259,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
     const int64_t b = blockIdx.x;
     const int n = a.n, m = a.m, nx = a.nx, N = a.N, mk = a.mk;
     const int R = (N + 1) * nx;  // rows of Phi / Psi (blocks 0 .. N)
-    const Carve cv = make_carve(n, N, nx, BS);
+    const Carve cv = make_carve(n, N, nx, BS, m, kModel);
     const int ld = cv.ld;
     double *base = kLds ? lds_carve : a.carve_ws + b * a.carve;
     double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *nu = base + cv.nu, *s = base + cv.s;
@@ -269,6 +417,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
                             gx0[c] = acc;
                         }
                     }
+                    if constexpr (kModel) model_phase<BS>(a, cv, base, Phi, Psi, lam, k, b);
                 }
             }
         }
@@ -281,6 +430,19 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
             for (int j = tid; j < N * nx; j += BS) gtgt[j] = 0.0;
         if (ge)
             for (int j = tid; j < m; j += BS) ge[j] = 0.0;
+        if constexpr (kModel) {
+            const int64_t NA = (int64_t)N * nx * nx, NB = (int64_t)N * nx * a.nu, NC = (int64_t)m * nx,
+                          ND = (int64_t)m * a.nu;
+            if (a.g_A)
+                for (int64_t j = tid; j < NA; j += BS) a.g_A[b * NA + j] = 0.0;
+            if (a.g_B)
+                for (int64_t j = tid; j < NB; j += BS) a.g_B[b * NB + j] = 0.0;
+            if (a.g_C)
+                for (int64_t j = tid; j < NC; j += BS) a.g_C[b * NC + j] = 0.0;
+            if (a.g_D)
+                for (int64_t j = tid; j < ND; j += BS) a.g_D[b * ND + j] = 0.0;
+            if (a.g_w && tid < 3) a.g_w[b * 3 + tid] = 0.0;
+        }
     }
     if (a.vjp_status && tid == 0) a.vjp_status[b] = verdict;
 }
@@ -288,28 +450,34 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
 // 64 lanes for n <= 32 (config 2: n = 16, several workgroups per CU); 256 above
 inline int adjoint_threads(int n) { return n <= 32 ? 64 : 256; }
 
-template <int BS>
+template <int BS, bool kModel>
 int launch_bs(const AdjArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
 {
     if (lds) {
-        auto kern = mpcqp_adjoint_kernel<BS, true>;
+        auto kern = mpcqp_adjoint_kernel<BS, true, kModel>;
         if (lds_bytes > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
             if (e != hipSuccess) return (int)e;
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(BS), lds_bytes, st, a);
     } else {
-        hipLaunchKernelGGL((mpcqp_adjoint_kernel<BS, false>), dim3((unsigned)batch), dim3(BS), 0, st, a);
+        hipLaunchKernelGGL((mpcqp_adjoint_kernel<BS, false, kModel>), dim3((unsigned)batch), dim3(BS), 0, st, a);
     }
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-size_t adjoint_carve_bytes(int n, int N, int nx) { return (size_t)make_carve(n, N, nx, adjoint_threads(n)).total * sizeof(double); }
+size_t adjoint_carve_bytes(int n, int N, int nx, int m, bool model)
+{
+    return (size_t)make_carve(n, N, nx, adjoint_threads(n), m, model).total * sizeof(double);
+}
 
 // (the 64 bytes spare leave room for the kernel's static s_k)
-bool adjoint_carve_in_lds(int n, int N, int nx) { return adjoint_carve_bytes(n, N, nx) + 64 <= kLdsBytesPerCU; }
+bool adjoint_carve_in_lds(int n, int N, int nx, int m, bool model)
+{
+    return adjoint_carve_bytes(n, N, nx, m, model) + 64 <= kLdsBytesPerCU;
+}
 
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
 {
@@ -337,12 +505,25 @@ int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
     a.g_targets = (double *)l.g_targets;
     a.g_e = (double *)l.g_e;
     a.vjp_status = l.vjp_status;
-    const bool lds = adjoint_carve_in_lds(a.n, a.N, a.nx);
-    const size_t bytes = adjoint_carve_bytes(a.n, a.N, a.nx);
+    a.A = l.A;
+    a.x0 = l.x0;
+    a.goal = l.goal;
+    a.targets = l.targets;
+    a.U = (const double *)l.U;
+    a.g_A = (double *)l.g_A;
+    a.g_B = (double *)l.g_B;
+    a.g_C = (double *)l.g_C;
+    a.g_D = (double *)l.g_D;
+    a.g_w = (double *)l.g_w;
+    const bool lds = adjoint_carve_in_lds(a.n, a.N, a.nx, a.m, l.model);
+    const size_t bytes = adjoint_carve_bytes(a.n, a.N, a.nx, a.m, l.model);
     a.carve_ws = lds ? nullptr : (double *)l.carve_ws;
     a.carve = (int64_t)(bytes / sizeof(double));
     if (!lds && !a.carve_ws) return MPCQP_EWORKSPACE;
-    return adjoint_threads(a.n) == 64 ? launch_bs<64>(a, lds, bytes, batch, st) : launch_bs<256>(a, lds, bytes, batch, st);
+    if (l.model && (!a.U || !a.A.ptr || !a.x0.ptr)) return MPCQP_EINVAL;
+    if (adjoint_threads(a.n) == 64)
+        return l.model ? launch_bs<64, true>(a, lds, bytes, batch, st) : launch_bs<64, false>(a, lds, bytes, batch, st);
+    return l.model ? launch_bs<256, true>(a, lds, bytes, batch, st) : launch_bs<256, false>(a, lds, bytes, batch, st);
 }
 
 }  // namespace mpcqp

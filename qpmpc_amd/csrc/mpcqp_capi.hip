@@ -1007,13 +1007,14 @@ int mpcqp_rollout_batch(const MpcqpDims *dims, const MpcqpOperand *A, const Mpcq
 
 namespace {
 // mpcqp_plan_vjp_batch's workspace, per launch: the condensed P, q, G, h, Phi, Psi of every problem (256-byte aligned
-// segments), mpcqp_condense_batch's own scratch, then the adjoint carves when they do not fit LDS
+// segments), mpcqp_condense_batch's own scratch, then the adjoint carves when they do not fit LDS. The model export's
+// carve is the longer one of the kModel kernel, and a g_x0 the caller did not ask for goes to a scratch segment after it.
 struct VjpPlan {
-    int64_t P, q, G, h, Phi, Psi, cws, carve, total;
+    int64_t P, q, G, h, Phi, Psi, cws, carve, gx0, total;
     size_t cws_bytes;
 };
 
-static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v)
+static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v, bool model = false)
 {
     int rc = check_dims(dims);
     if (rc) return rc;
@@ -1033,9 +1034,56 @@ static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v)
     v.cws = v.Psi + al256(d * (N + 1) * nx * n);
     v.cws_bytes = cws;
     v.carve = v.cws + al256((int64_t)cws);
-    const bool lds = adjoint_carve_in_lds((int)n, (int)N, (int)nx);
-    v.total = v.carve + (lds ? 0 : al256((int64_t)adjoint_carve_bytes((int)n, (int)N, (int)nx) * batch));
+    const bool lds = adjoint_carve_in_lds((int)n, (int)N, (int)nx, (int)m, model);
+    v.gx0 = v.carve + (lds ? 0 : al256((int64_t)adjoint_carve_bytes((int)n, (int)N, (int)nx, (int)m, model) * batch));
+    v.total = v.gx0 + (model ? al256(d * nx) : 0);
     return 0;
+}
+
+// Both exports: checks in the order of mpcqp_plan_vjp_batch, the condensing, then one adjoint launch. `l` carries the
+// outputs (and, for the model export, model = true and its operands); the rest is filled here.
+static int plan_vjp(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const void *lam,
+                    const int32_t *status, const void *gU, const void *gX, AdjointLaunch &l, void *workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    VjpPlan v;
+    int rc = vjp_plan(dims, batch, v, l.model);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    if (!status || !gU || (!l.model && !l.g_x0) || (l.model && !l.U) || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
+    char *w = (char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    // the existing condensing, Phi and Psi kept
+    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
+                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
+    if (rc) return rc;
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.flags = dims->flags;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.P = w + v.P;
+    l.G = dims->mk > 0 ? w + v.G : nullptr;
+    l.Phi = w + v.Phi;
+    l.Psi = w + v.Psi;
+    l.C = problem->C;
+    l.lam = lam;
+    l.gU = gU;
+    l.gX = gX;
+    l.status = status;
+    if (!l.g_x0) l.g_x0 = w + v.gx0;
+    l.carve_ws = (v.gx0 > v.carve) ? w + v.carve : nullptr;
+    if (l.model) {
+        l.A = problem->A;
+        l.x0 = problem->x0;
+        l.goal = problem->goal;
+        l.targets = problem->targets;
+    }
+    return launch_adjoint(l, batch, st);
 }
 }  // namespace
 
@@ -1053,43 +1101,45 @@ int mpcqp_plan_vjp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
                          const int32_t *status, const void *gU, const void *gX, void *g_x0, void *g_goal, void *g_targets,
                          void *g_e, int32_t *vjp_status, void *workspace, size_t workspace_bytes, void *stream)
 {
-    VjpPlan v;
-    int rc = vjp_plan(dims, batch, v);
-    if (rc) return rc;
-    if ((rc = check_problem(dims, problem))) return rc;
-    if (!status || !gU || !g_x0 || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
-    if (batch == 0) return 0;
-    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
-    char *w = (char *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    // the existing condensing, Phi and Psi kept
-    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
-                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
-    if (rc) return rc;
     AdjointLaunch l;
-    l.nx = dims->nx;
-    l.nu = dims->nu;
-    l.N = dims->N;
-    l.mk = dims->mk;
-    l.flags = dims->flags;
-    l.wt = dims->w_terminal;
-    l.wx = dims->w_stage;
-    l.P = w + v.P;
-    l.G = dims->mk > 0 ? w + v.G : nullptr;
-    l.Phi = w + v.Phi;
-    l.Psi = w + v.Psi;
-    l.C = problem->C;
-    l.lam = lam;
-    l.gU = gU;
-    l.gX = gX;
-    l.status = status;
     l.g_x0 = g_x0;
     l.g_goal = g_goal;
     l.g_targets = g_targets;
     l.g_e = g_e;
     l.vjp_status = vjp_status;
-    l.carve_ws = (v.total > v.carve) ? w + v.carve : nullptr;
-    return launch_adjoint(l, batch, st);
+    return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
+}
+
+int mpcqp_plan_vjp_model_workspace_bytes(const MpcqpDims *dims, int64_t batch, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    VjpPlan v;
+    const int rc = vjp_plan(dims, batch, v, true);
+    if (rc) return rc;
+    *bytes = (size_t)v.total;
+    return 0;
+}
+
+int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const void *lam,
+                               const int32_t *status, const void *U, const void *gU, const void *gX,
+                               const MpcqpVjpModelOut *out, int32_t *vjp_status, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (!out) return MPCQP_EINVAL;
+    AdjointLaunch l;
+    l.g_x0 = out->g_x0;
+    l.g_goal = out->g_goal;
+    l.g_targets = out->g_targets;
+    l.g_e = out->g_e;
+    l.vjp_status = vjp_status;
+    l.model = true;
+    l.U = U;
+    l.g_A = out->g_A;
+    l.g_B = out->g_B;
+    l.g_C = out->g_C;
+    l.g_D = out->g_D;
+    l.g_w = out->g_w;
+    return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
 }
 
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const MpcqpSolveOpts *opts,

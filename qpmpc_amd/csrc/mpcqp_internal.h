@@ -283,9 +283,15 @@ struct AdjointLaunch {
     void *g_x0, *g_goal, *g_targets, *g_e;
     int32_t *vjp_status;
     void *carve_ws;  // batch * adjoint_carve_bytes when the carve does not fit LDS
+    // model and cost gradients (mpcqp_plan_vjp_model_batch): the kModel kernel, which also reads A, x0, goal, targets
+    // and the plan U, and writes the nullable g_A, g_B, g_C, g_D, g_w
+    bool model = false;
+    MpcqpOperand A{}, x0{}, goal{}, targets{};
+    const void *U = nullptr;
+    void *g_A = nullptr, *g_B = nullptr, *g_C = nullptr, *g_D = nullptr, *g_w = nullptr;
 };
-size_t adjoint_carve_bytes(int n, int N, int nx);
-bool adjoint_carve_in_lds(int n, int N, int nx);
+size_t adjoint_carve_bytes(int n, int N, int nx, int m = 0, bool model = false);
+bool adjoint_carve_in_lds(int n, int N, int nx, int m = 0, bool model = false);
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st);
 
 }  // namespace mpcqp
