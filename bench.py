@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: MPC QP builds+solves per second (batched).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in
 HBM when the timed region starts. ``--config`` picks the BASELINE.json configuration that is
@@ -21,6 +21,13 @@ timed (configs[1..4]; configs[0] is the reference's single CPU problem):
 N > 1 runs one rank per GPU over RCCL: either launched by ``torch.distributed.run`` (the driver's way) or,
 when started as a plain ``python bench.py --gpus N``, by re-executing itself through it. Problems never
 interact, so the data path has no collective. Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: it sets up, spins up, warms up, times the K steps, writes
+``--dump-outputs`` and prints the line (``value``, ``ms_per_step``, ``solved_frac`` / ``mean_iters`` of the timed steps and
+the ``roofline`` of their launches). ``--full`` adds everything that takes runs or checks of its own: the all_gather of the
+strong configurations, two streams in flight (config 2), the comparison with the CPU oracle (``accuracy``), config 5's Gram
+kernel and sweep counts, config 4's paired order, the other configurations and the predicted strong scaling (config 2), and
+the CPU baseline. All of it comes after the timed steps, so it never changes ``value`` or the dumped outputs.
 
 Without a GPU (build container) the same command runs the RANK LOGIC ONLY over gloo with a runner that
 computes nothing: the record then carries ``"value": null`` and ``"dry_run"`` -- it is not a measurement.
@@ -68,11 +75,13 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None, help="override the configuration's batch (per GPU if weak, total if strong)")
     ap.add_argument("--shared-lti", action="store_true", help="config 2 with stride-0 operands (not the headline mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--spinup", type=float, default=0.25, help="seconds of untimed launches before the warm-up (clock ramp)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short runs of the other configurations")
-    ap.add_argument("--no-overlap", action="store_true", help="skip the extra two-streams-in-flight measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the short runs of the other configurations")
+    ap.add_argument("--no-overlap", action="store_true", help="with --full: skip the extra two-streams-in-flight measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args(argv)
@@ -273,7 +282,7 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
 
     # strong-scaling configurations hand the whole batch to every rank afterwards: all_gather, timed apart
     gather_ms = None
-    if spec["scaling"] == "strong":
+    if args.full and spec["scaling"] == "strong":
         from qpmpc_amd.distributed import gather_batch
 
         for _ in range(2):
@@ -292,7 +301,7 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
 
     # Extra (config 2, not `value`): two independent batches in flight on two streams
     overlap = None
-    if args.config == 2 and not args.no_overlap and device == "cuda":
+    if args.full and args.config == 2 and not args.no_overlap and device == "cuda":
         overlap = _overlap_two_streams(args, run, rank, world, barrier, allreduce, dev)
 
     if rank != 0:
@@ -333,6 +342,7 @@ def run_bench(args, rank: int, world: int, dist=None, make_runner=_Runner, devic
         out["dump_outputs"] = dumped
     if device == "cuda":
         out["roofline"] = _roofline(args, w, local_per_step, kernel_ms, out["mean_iters"])
+    if args.full and device == "cuda":
         if args.config == 5:
             # north_star's "fraction of the dense-GEMM roofline": the benched path forms no Gram, so the MFMA Gram kernel of
             # the dense path (qpmpc/mpc_qp.py:99-105) is timed by itself, in this run, on this workload's problems

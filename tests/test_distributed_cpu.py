@@ -106,7 +106,7 @@ def _bench_worker(rank, world, port, config, batch, out_dir):
         dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         args = bench.parse_args(["--gpus", str(world), "--config", str(config), "--steps", "2", "--warmup", "1",
-                                 "--batch", str(batch), "--spinup", "0", "--no-cpu-baseline"])
+                                 "--batch", str(batch), "--spinup", "0", "--no-cpu-baseline", "--full"])
         out = bench.run_bench(args, rank, world, dist if world > 1 else None, make_runner=_OracleRunner, device="cpu")
         assert (out is not None) == (rank == 0)
         if rank == 0:
@@ -143,6 +143,34 @@ def test_bench_rank_logic_two_ranks_gloo(tmp_path, config, batch):
         assert abs(one["solved_frac"] - two["solved_frac"]) < 1e-12 and abs(one["mean_iters"] - two["mean_iters"]) < 1e-12
 
 
+def test_bench_plain_run_is_only_the_headline():
+    """Without --full, run_bench launches the solver only for construction, warm-up and the timed steps, and the record
+    carries none of the measurements --full adds (on CPU the strong configurations' all_gather is the one that shows)."""
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    runs = []
+
+    def make_runner(config, w, device):
+        runs.append(_OracleRunner(config, w, device))
+        return runs[-1]
+
+    common = ["--config", "4", "--steps", "3", "--warmup", "1", "--batch", "9", "--spinup", "0"]
+    assert bench.parse_args(common).full is False
+    plain = bench.run_bench(bench.parse_args(common), 0, 1, None, make_runner=make_runner, device="cpu")
+    assert runs[-1].launches == 1 + 1 + 3
+    assert set(plain) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "spinup_s", "rewarm_after_barrier",
+                          "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                          "solved_frac", "mean_iters"}
+    full = bench.run_bench(bench.parse_args(common + ["--full"]), 0, 1, None, make_runner=make_runner, device="cpu")
+    assert full["all_gather_ms"] >= 0.0 and set(full) - set(plain) == {"all_gather_ms", "all_gather_note"}
+    assert full["solved_frac"] == plain["solved_frac"] and full["mean_iters"] == plain["mean_iters"]
+
+
 @pytest.mark.parametrize("config,batch", [(2, 16), (5, 6)])
 def test_bench_main_spawns_its_own_ranks(config, batch):
     """``python bench.py --gpus 2`` started WITHOUT torch.distributed.run (how a user, or a driver that only knows
@@ -155,7 +183,7 @@ def test_bench_main_spawns_its_own_ranks(config, batch):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", str(config), "--steps", "2",
-           "--warmup", "1", "--batch", str(batch)]
+           "--warmup", "1", "--batch", str(batch)] + (["--full"] if config == 5 else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -168,6 +196,7 @@ def test_bench_main_spawns_its_own_ranks(config, batch):
         assert rec["value"] is None and "dry_run" in rec
     if config == 2:
         assert rec["scaling"] == "weak" and rec["config"]["problems_per_step"] == 2 * batch
+        assert not {"overlap_2_streams", "accuracy"} & rec.keys()  # a plain run
     else:
         assert rec["scaling"] == "strong" and rec["config"]["problems_per_step"] == batch and "all_gather_ms" in rec
 

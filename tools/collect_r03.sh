@@ -14,11 +14,11 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc $?" >> $OUT/pytest_gpu.log
   tail -3 $OUT/pytest_gpu.log
 fi
-timeout 300 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 300 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 for c in 2 3 4 5; do
-  timeout 300 python bench.py --config $c --no-extras > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
+  timeout 300 python bench.py --full --config $c --no-extras > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
 done
-timeout 300 python bench.py --config 5 --batch 1024 --no-extras --no-cpu-baseline > $OUT/bench_config5_b1024.json 2> $OUT/bench_config5_b1024.err
+timeout 300 python bench.py --full --config 5 --batch 1024 --no-extras --no-cpu-baseline > $OUT/bench_config5_b1024.json 2> $OUT/bench_config5_b1024.err
 cat $OUT/bench_config*.json
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   timeout 900 bash $R/tools/collect_profiles.sh pair_$TAG

@@ -14,16 +14,16 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc $?" >> $OUT/pytest_gpu.log
   tail -3 $OUT/pytest_gpu.log
 fi
-timeout 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 for c in 2 3 4 5; do
-  timeout 300 python bench.py --config $c --no-extras > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
+  timeout 300 python bench.py --full --config $c --no-extras > $OUT/bench_config$c.json 2> $OUT/bench_config$c.err
 done
-timeout 300 python bench.py --config 5 --batch 1024 --no-extras --no-cpu-baseline > $OUT/bench_config5_b1024.json 2> $OUT/bench_config5_b1024.err
-timeout 300 python bench.py --steps 2000 --warmup 200 --no-extras --no-cpu-baseline > $OUT/bench_config2_2000steps.json 2> /dev/null
+timeout 300 python bench.py --full --config 5 --batch 1024 --no-extras --no-cpu-baseline > $OUT/bench_config5_b1024.json 2> $OUT/bench_config5_b1024.err
+timeout 300 python bench.py --full --steps 2000 --warmup 200 --no-extras --no-cpu-baseline > $OUT/bench_config2_2000steps.json 2> /dev/null
 # one rank over RCCL (backend nccl): the init / barrier / all_gather / all_reduce path of bench.py on real hardware
 for c in 2 4 5; do
   HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2950$c \
-    bench.py --gpus 1 --config $c --no-extras --no-cpu-baseline > $OUT/bench_rccl_single_rank_config$c.json 2> $OUT/bench_rccl_single_rank_config$c.err
+    bench.py --full --gpus 1 --config $c --no-extras --no-cpu-baseline > $OUT/bench_rccl_single_rank_config$c.json 2> $OUT/bench_rccl_single_rank_config$c.err
 done
 cat $OUT/bench_config*.json $OUT/bench_rccl_*.json | cut -c1-400
 if [ "${SKIP_PROF:-0}" != "1" ]; then
