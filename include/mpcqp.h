@@ -451,6 +451,24 @@ int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *proble
                                const void *gX, const MpcqpVjpModelOut *out, int32_t *vjp_status,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* The stage-wise adjoint: mpcqp_plan_vjp_model_batch's products at any horizon, without condensing; an additive part of
+ * ABI 12 (MPCQP_ABI_VERSION is unchanged). The same KKT adjoint on A = {i : lam_i > 0} is solved on the Riccati
+ * recursion of each problem in whitened coordinates (P = L L' block-wise, DESIGN.md section 9 "Stage-wise adjoint"): one
+ * backward sweep for L^-1 (gU + Psi' gX), one per active row for its whitened vector, the active rows' Gram matrix and its
+ * Cholesky factor, then one forward sweep for L^-T; the gradients follow from costate recursions over A_k (section 9's
+ * formulas for v, g_x0, g_goal, g_targets, g_e and, for the model and cost gradients, the rollouts X, Z and the costates
+ * p, pz, s). Outputs are those of mpcqp_plan_vjp_model_batch, every pointer of `out` nullable; when g_A .. g_w are all
+ * NULL the model phase is skipped and U may be NULL. `max_active` (>= 0) bounds |A| per problem and sizes the workspace:
+ * a problem with more active rows gets zeros and vjp_status MPCQP_SLOTS_FULL. Otherwise the status and vjp_status rules
+ * are mpcqp_plan_vjp_batch's (unsolved: zeros and its status; more active rows than variables, a stage Hessian or a Gram
+ * matrix that is not positive definite: zeros and MPCQP_NOT_PD). Envelope: float64 (MPCQP_EDTYPE otherwise), nx <= 32,
+ * nu <= 8 (MPCQP_EUNSUPPORTED otherwise), any N. The workspace is batch regions of the size the query reports. */
+int mpcqp_plan_vjp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes);
+int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                                   int32_t max_active, const void *lam, const int32_t *status, const void *U,
+                                   const void *gU, const void *gX, const MpcqpVjpModelOut *out,
+                                   int32_t *vjp_status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of
  * sampling_period/nsub (WheeledInvertedPendulum.integrate,

@@ -57,6 +57,8 @@ EXPORTS = (
     "mpcqp_plan_vjp_batch",
     "mpcqp_plan_vjp_model_workspace_bytes",
     "mpcqp_plan_vjp_model_batch",
+    "mpcqp_plan_vjp_stagewise_workspace_bytes",
+    "mpcqp_plan_vjp_stagewise_batch",
 )
 
 
@@ -191,6 +193,11 @@ def load():
     lib.mpcqp_plan_vjp_model_batch.restype = C.c_int
     lib.mpcqp_plan_vjp_model_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, vp, vp, vp, vp, vp,
                                                C.POINTER(VjpModelOut), vp, vp, C.c_size_t, vp]
+    lib.mpcqp_plan_vjp_stagewise_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_vjp_stagewise_workspace_bytes.argtypes = [C.POINTER(Dims), i64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.mpcqp_plan_vjp_stagewise_batch.restype = C.c_int
+    lib.mpcqp_plan_vjp_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, vp, vp, vp, vp,
+                                                   vp, C.POINTER(VjpModelOut), vp, vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -4,7 +4,9 @@ The forward is ``solve_mpc_batch`` with multipliers; the backward is one call of
 (include/mpcqp.h): the condensing of the batch into scratch, then one KKT adjoint solve per problem in HIP
 (qpmpc_amd/csrc/mpcqp_adjoint.hip). Gradients reach the initial state, the goal, the stage targets and the inequality
 vector ``e``; when one of the model matrices A, B, C, D or the cost weights passed requires grad, the backward is
-``mpcqp_plan_vjp_model_batch`` instead, the same adjoint followed by its costate pass.
+``mpcqp_plan_vjp_model_batch`` instead, the same adjoint followed by its costate pass. With
+``adjoint="stagewise"`` the backward is ``mpcqp_plan_vjp_stagewise_batch`` (qpmpc_amd/csrc/mpcqp_adjoint_stagewise.hip):
+the same adjoint on each problem's Riccati recursion, at any horizon ("Stage-wise adjoint").
 
 The reference has no counterpart: its plans are NumPy arrays.
 """
@@ -17,6 +19,10 @@ from .batch import BatchMPCProblem, _canon, _as_tensor, _stream_ptr, solve_mpc_b
 from .exceptions import BackendError, ProblemDefinitionError
 
 MAX_VARIABLES = 128  # envelope of mpcqp_plan_vjp_batch: n = N * nu <= 128 (and what mpcqp_condense_batch condenses)
+STAGEWISE_MAX_NX, STAGEWISE_MAX_NU = 32, 8  # envelope of mpcqp_plan_vjp_stagewise_batch (any N)
+# the stage-wise backward splits its batch so that one launch's workspace stays below this many bytes
+STAGEWISE_WORKSPACE_CAP = 2 << 30
+ADJOINTS = ("condensed", "stagewise")
 
 
 def _torch():
@@ -105,13 +111,28 @@ def check_envelope(problem: BatchMPCProblem) -> None:
     lib = _capi.load()
     n = problem.nb_variables
     if n > MAX_VARIABLES:
-        raise BackendError(f"gradients through plans are served for n = N * nu <= {MAX_VARIABLES} variables, not {n} "
-                           "(a stage-wise adjoint for longer horizons is not built)")
+        raise BackendError(f"gradients through plans are served for n = N * nu <= {MAX_VARIABLES} variables, not {n}, by "
+                           "the condensed adjoint (adjoint=\"stagewise\" serves any horizon for nx <= 32, nu <= 8)")
     nbytes = C.c_size_t(0)
     dims = _vjp_dims(problem)
     rc = lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), problem.batch_size, C.byref(nbytes))
     if rc != 0:
         _capi.check(rc, "mpcqp_plan_vjp_workspace_bytes")
+
+
+def check_envelope_stagewise(problem: BatchMPCProblem) -> None:
+    """Raise ``BackendError`` unless ``mpcqp_plan_vjp_stagewise_batch`` serves this problem's dimensions (nothing is
+    launched): nx <= 32, nu <= 8, any horizon."""
+    lib = _capi.load()
+    nx, nu = problem.state_dim, problem.input_dim
+    if nx > STAGEWISE_MAX_NX or nu > STAGEWISE_MAX_NU:
+        raise BackendError(f"the stage-wise adjoint serves nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU}, "
+                           f"not nx = {nx}, nu = {nu}")
+    nbytes = C.c_size_t(0)
+    dims = _vjp_dims(problem)
+    rc = lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), problem.batch_size, 0, C.byref(nbytes))
+    if rc != 0:
+        _capi.check(rc, "mpcqp_plan_vjp_stagewise_workspace_bytes")
 
 
 def _reduce(g, like, canon_shape):
@@ -207,6 +228,75 @@ def _plan_vjp_model(work: BatchMPCProblem, plan, gU, gX, want):
     return tuple(out[k] for k in GRAD_KEYS)
 
 
+def _shifted(cp, b0: int):
+    """A copy of the C problem ``cp`` whose per-problem operands start at problem ``b0`` (float64 elements)."""
+    out = _capi.Problem()
+    for name, _ in _capi.Problem._fields_:
+        op = getattr(cp, name)
+        ptr = None if not op.ptr else op.ptr + 8 * b0 * op.batch_stride
+        setattr(out, name, _capi.Operand(ptr, op.batch_stride, op.step_stride))
+    return out
+
+
+def _plan_vjp_stagewise(work: BatchMPCProblem, plan, gU, gX, want):
+    """The gradients of ``GRAD_KEYS`` in float64 through mpcqp_plan_vjp_stagewise_batch, shaped as ``_plan_vjp_model``'s;
+    entries not in ``want`` are None. Sets ``plan.vjp_status``.
+
+    ``max_active`` is the largest number of active rows (lam > 0) of a solved problem, capped at n: the one host sync of
+    the backward. The batch is split into launches whose workspace stays below ``STAGEWISE_WORKSPACE_CAP``."""
+    torch = _torch()
+    lib = _capi.load()
+    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
+    Bn, N, nx, nu, mk, n = (work.batch_size, work.nb_timesteps, work.state_dim, work.input_dim, work.ineq_dim,
+                            work.nb_variables)
+    dev = work.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    shapes = dict(x0=(nx,), goal=(nx,), targets=(N * nx,), e=(N, mk), A=(N, nx, nx), B=(N, nx, nu), C=(N, mk, nx),
+                  D=(N, mk, nu))
+    out = {k: (torch.empty((Bn,) + shp, **f64) if k in want else None) for k, shp in shapes.items()}
+    g_w = torch.empty((Bn, 3), **f64) if want & {"wt", "wx", "wu"} else None
+    model = g_w is not None or any(out[k] is not None for k in ("A", "B", "C", "D"))
+    U = plan.U.reshape(Bn, -1).to(torch.float64).contiguous() if model else None
+    status = plan.status
+    if lam is not None and Bn > 0:
+        act = ((lam > 0) & (status == 0)[:, None]).sum(dim=1)
+        max_active = min(int(act.max().item()), n)  # the host sync
+    else:
+        max_active = 0
+    vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    dims, cp = _vjp_dims(p64), p64.c_problem()
+    one = C.c_size_t(0)
+    _capi.check(lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), 1, max_active, C.byref(one)),
+                "mpcqp_plan_vjp_stagewise_workspace_bytes")
+    chunk = max(1, min(Bn, STAGEWISE_WORKSPACE_CAP // max(one.value, 1)))
+    nbytes = C.c_size_t(0)
+    _capi.check(lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), chunk, max_active, C.byref(nbytes)),
+                "mpcqp_plan_vjp_stagewise_workspace_bytes")
+    ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=dev)
+
+    def at(t, b0):
+        return None if t is None else t[b0:].data_ptr()
+
+    keep = []
+    for b0 in range(0, Bn, chunk):
+        nb = min(chunk, Bn - b0)
+        cpb = _shifted(cp, b0)
+        res = _capi.VjpModelOut(*[at(out[k], b0) for k in ("x0", "goal", "targets", "e", "A", "B", "C", "D")],
+                                at(g_w, b0))
+        rc = lib.mpcqp_plan_vjp_stagewise_batch(
+            C.byref(dims), C.byref(cpb), nb, max_active, at(lam, b0), at(status, b0), at(U, b0), at(gU, b0), at(gX, b0),
+            C.byref(res), at(vjp_status, b0), ws.data_ptr(), ws.numel(), _stream_ptr())
+        _capi.check(rc, "mpcqp_plan_vjp_stagewise_batch")
+        keep.append(cpb)
+    plan.vjp_status = vjp_status
+    plan._vjp_keep = (ws, p64, lam, U, gU, gX, keep)  # alive until the stream has consumed them
+    if out["e"] is not None and mk == 0:
+        out["e"] = torch.zeros((Bn, N, mk), **f64)
+    for i, k in enumerate(("wt", "wx", "wu")):
+        out[k] = g_w[:, i] if k in want else None
+    return tuple(out[k] for k in GRAD_KEYS)
+
+
 def _make_function():
     torch = _torch()
     from torch.autograd.function import once_differentiable
@@ -217,7 +307,7 @@ def _make_function():
             plan = solve_mpc_batch(work, return_multipliers=True, **solve_kw)
             U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
             box["plan"] = plan
-            ctx.work, ctx.plan, ctx.states = work, plan, states
+            ctx.work, ctx.plan, ctx.states, ctx.adjoint = work, plan, states, box["adjoint"]
             ctx.inputs = tuple(None if t is None else (t.shape, t.dtype, t.device) for t in operands)
             canon = (work.initial_state, work.goal_state, work.target_states, work.e, work.A, work.B, work.C, work.D)
             # a weight is one value for the batch: shape (1,) sums its per-problem gradients
@@ -230,7 +320,9 @@ def _make_function():
         def backward(ctx, gU, gX=None):
             need = ctx.needs_input_grad[4:]
             want = {nm for nm, nd in zip(GRAD_KEYS, need) if nd}
-            if any(need[4:]):
+            if ctx.adjoint == "stagewise":
+                grads = _plan_vjp_stagewise(ctx.work, ctx.plan, gU, gX, want)
+            elif any(need[4:]):
                 grads = _plan_vjp_model(ctx.work, ctx.plan, gU, gX, want)
             else:
                 grads = _plan_vjp(ctx.work, ctx.plan, gU, gX, want) + (None,) * 7
@@ -248,7 +340,7 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
                          ineq_vector=None, states: bool = False, *, transition_state_matrix=None,
                          transition_input_matrix=None, ineq_state_matrix=None, ineq_input_matrix=None,
                          terminal_cost_weight=None, stage_state_cost_weight=None, stage_input_cost_weight=None,
-                         **solve_kw):
+                         adjoint: str = "condensed", **solve_kw):
     """Solve a batch like ``solve_mpc_batch`` and return ``(U, X, plan)`` whose ``U`` [B, N, nu] and, with ``states=True``,
     ``X`` [B, N+1, nx] carry a ``grad_fn`` (``X`` is None otherwise).
 
@@ -273,10 +365,18 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
     Envelope: n = N * nu <= 128; beyond it a request for gradients raises ``BackendError`` before anything is launched.
     Only first derivatives (``once_differentiable``).
 
+    ``adjoint`` picks the backward: ``"condensed"`` (the default, as above) or ``"stagewise"``, which solves the same
+    adjoint on each problem's Riccati recursion without condensing (``mpcqp_plan_vjp_stagewise_batch``) and serves every
+    horizon and every n for nx <= 32, nu <= 8 (``BackendError`` outside, before anything is launched). Its backward sizes
+    the workspace from the largest number of active rows in the batch, which costs one host sync. Any other value raises
+    ``ProblemDefinitionError``.
+
     When no operand passed requires grad (or grad mode is off), this is ``solve_mpc_batch(problem', **solve_kw)`` on the
     problem with the replaced operands, and its plan is returned as is."""
     global _FUNCTION
     torch = _torch()
+    if adjoint not in ADJOINTS:
+        raise ProblemDefinitionError(f"adjoint: expected one of {ADJOINTS}, got {adjoint!r}")
     passed = (initial_state, goal_state, target_states, ineq_vector, transition_state_matrix, transition_input_matrix,
               ineq_state_matrix, ineq_input_matrix, terminal_cost_weight, stage_state_cost_weight,
               stage_input_cost_weight)
@@ -286,10 +386,13 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
         plan = solve_mpc_batch(work, **solve_kw)
         U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
         return U, (plan.states if states else None), plan
-    check_envelope(work)
+    if adjoint == "stagewise":
+        check_envelope_stagewise(work)
+    else:
+        check_envelope(work)
     if _FUNCTION is None:
         _FUNCTION = _make_function()
-    box = {}
+    box = {"adjoint": adjoint}
     tens = [t if isinstance(t, torch.Tensor) else None for t in passed]
     out = _FUNCTION.apply(work, bool(states), dict(solve_kw), box, *tens)
     U, X = out if states else (out, None)

@@ -1142,6 +1142,66 @@ int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *proble
     return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
 }
 
+namespace {
+// mpcqp_plan_vjp_stagewise_batch's workspace: one region per problem (mpcqp_adjoint_stagewise.hip's carve, phase 6 included)
+static int vjp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t &total)
+{
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    if (batch < 0 || max_active < 0) return MPCQP_EINVAL;
+    if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
+    if (!stagewise_adjoint_applies(dims->nx, dims->nu)) return MPCQP_EUNSUPPORTED;
+    total = (size_t)al256((int64_t)stagewise_adjoint_bytes(dims->nx, dims->nu, dims->N, dims->mk, max_active) * batch);
+    return 0;
+}
+}  // namespace
+
+int mpcqp_plan_vjp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    size_t total = 0;
+    const int rc = vjp_stagewise_plan(dims, batch, max_active, total);
+    if (rc) return rc;
+    *bytes = total;
+    return 0;
+}
+
+int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t max_active,
+                                   const void *lam, const int32_t *status, const void *U, const void *gU, const void *gX,
+                                   const MpcqpVjpModelOut *out, int32_t *vjp_status, void *workspace,
+                                   size_t workspace_bytes, void *stream)
+{
+    size_t total = 0;
+    int rc = vjp_stagewise_plan(dims, batch, max_active, total);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    if (!out || !status || !gU || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    const bool model = out->g_A || out->g_B || out->g_C || out->g_D || out->g_w;
+    if (model && !U) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < total) return MPCQP_EWORKSPACE;
+    StagewiseAdjointLaunch l;
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.flags = dims->flags;
+    l.max_active = max_active;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.wu = dims->w_input;
+    l.problem = *problem;
+    l.lam = lam;
+    l.gU = gU;
+    l.gX = gX;
+    l.U = U;
+    l.status = status;
+    l.out = *out;
+    l.vjp_status = vjp_status;
+    l.workspace = workspace;
+    return launch_adjoint_stagewise(l, batch, (hipStream_t)stream);
+}
+
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const MpcqpSolveOpts *opts,
                            void *U, void *lam, int32_t *status, int32_t *iters, void *workspace, size_t workspace_bytes,
                            void *states, int64_t *loop_stats, double sampling_period, double target_vel, double length,

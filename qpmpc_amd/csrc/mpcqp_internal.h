@@ -293,6 +293,21 @@ struct AdjointLaunch {
 size_t adjoint_carve_bytes(int n, int N, int nx, int m = 0, bool model = false);
 bool adjoint_carve_in_lds(int n, int N, int nx, int m = 0, bool model = false);
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st);
+// the stage-wise adjoint (mpcqp_adjoint_stagewise.hip; float64, nx <= 32, nu <= 8, any N): one problem per workgroup on its
+// Riccati recursion, the records and the active rows' whitened vectors in a per-problem region of the workspace
+struct StagewiseAdjointLaunch {
+    int nx, nu, N, mk, flags, max_active;
+    double wt, wx, wu;
+    MpcqpProblem problem;
+    const void *lam, *gU, *gX, *U;  // lam nullable when mk = 0, gX nullable, U needed when a model output is requested
+    const int32_t *status;
+    MpcqpVjpModelOut out;          // every pointer nullable
+    int32_t *vjp_status;
+    void *workspace;               // batch * stagewise_adjoint_bytes
+};
+bool stagewise_adjoint_applies(int nx, int nu);
+size_t stagewise_adjoint_bytes(int nx, int nu, int N, int mk, int max_active);  // per problem
+int launch_adjoint_stagewise(const StagewiseAdjointLaunch &l, int64_t batch, hipStream_t st);
 
 }  // namespace mpcqp
 #endif
