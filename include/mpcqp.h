@@ -469,6 +469,34 @@ int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
                                    const void *gU, const void *gX, const MpcqpVjpModelOut *out,
                                    int32_t *vjp_status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Jacobian-vector products of solved plans, the forward-mode counterpart of mpcqp_plan_vjp_batch; an additive part of
+ * ABI 12 (MPCQP_ABI_VERSION is unchanged). Tangents of x0, goal, targets and e, ntan of them per problem (1 .. 256), each
+ * pointer nullable (a NULL tangent is zero). Within one problem tangent t sits at offset t*nx (dx0, dgoal), t*N*nx
+ * (dtargets) or t*N*mk (de); a stride is the number of elements between two problems' tangents, 0 = one set shared by
+ * the batch (one identity gives the Jacobian of every problem). */
+typedef struct MpcqpTangents {
+    const void *dx0, *dgoal, *dtargets, *de;
+    int64_t dx0_stride, dgoal_stride, dtargets_stride, de_stride;
+} MpcqpTangents;
+
+/* On the active set A = {i : lam_i > 0} of the forward solve (lam, status as for mpcqp_plan_vjp_batch), the plan is affine
+ * in its data; this writes, packed, dU [batch][ntan][n] and dX [batch][ntan][(N+1)*nx] (nullable) for every tangent:
+ *     dq = w_t psi_N'(phi_N dx0 - dgoal) + w_x Psi'(Phi dx0 - dtargets)    (terms as dims->flags has them)
+ *     dh = de - C Phi dx0,   [P G_A'; G_A 0] [dU; dlam_A] = [-dq; dh_A],   dX = Phi dx0 + Psi dU
+ * ("Forward sensitivities"). With dx0 the identity, dU is the feedback Jacobian dU/dx0 whose first
+ * block is the local gain of the controller. At weakly active points the result is one element of the generalized
+ * Jacobian, as for the VJP. Per problem: status[b] != 0 gives zeros and jvp_status[b] = status[b]; more active rows than
+ * variables or a Gram matrix of the active rows that is not positive definite gives zeros and MPCQP_NOT_PD; else
+ * jvp_status[b] = 0 (jvp_status nullable). Checks: MPCQP_EDTYPE unless float64; MPCQP_EUNSUPPORTED for n > 128 (or what
+ * mpcqp_condense_batch does not condense); MPCQP_EINVAL for ntan outside 1 .. 256, a NULL tan, status or dU, a negative
+ * stride, or a NULL lam when mk > 0; MPCQP_EWORKSPACE for a missing or short workspace. The call runs
+ * mpcqp_condense_batch into the workspace, then one tangent launch (one workgroup per problem). */
+int mpcqp_plan_jvp_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t ntan, size_t *bytes);
+int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t ntan,
+                         const void *lam, const int32_t *status, const MpcqpTangents *tan,
+                         void *dU, void *dX, int32_t *jvp_status,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of
  * sampling_period/nsub (WheeledInvertedPendulum.integrate,

@@ -4,7 +4,8 @@ Same public names as the reference (qpmpc/__init__.py:9-21) -- ``MPCProblem``,
 ``MPCQP``, ``Plan``, ``solve_mpc`` -- plus the batched entry points that are the
 reason this package exists: ``BatchMPCProblem``, ``solve_mpc_batch``,
 ``BatchMPCQP``, ``solve_qp_batch``, ``rollout_batch`` -- and ``solve_mpc_batch_diff``, whose plans
-carry gradients to x0, goal, targets and e (an extension: the reference has no gradients).
+carry gradients to x0, goal, targets and e, and ``plan_jvp`` / ``plan_jacobian``, their forward sensitivities (extensions:
+the reference has no gradients).
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of
 ``include/mpcqp.h``; without the compiled library or without a GPU every
@@ -23,7 +24,7 @@ from .batch import (  # noqa: F401
     solve_mpc_batch,
     solve_qp_batch,
 )
-from .autodiff import solve_mpc_batch_diff  # noqa: F401
+from .autodiff import plan_jacobian, plan_jvp, solve_mpc_batch_diff  # noqa: F401
 from .exceptions import (  # noqa: F401
     BackendError,
     PlanError,
@@ -53,6 +54,8 @@ __all__ = [
     "solve_qp_batch",
     "rollout_batch",
     "solve_mpc_batch_diff",
+    "plan_jvp",
+    "plan_jacobian",
 ]
 
 __version__ = "0.1.0"

@@ -59,6 +59,8 @@ EXPORTS = (
     "mpcqp_plan_vjp_model_batch",
     "mpcqp_plan_vjp_stagewise_workspace_bytes",
     "mpcqp_plan_vjp_stagewise_batch",
+    "mpcqp_plan_jvp_workspace_bytes",
+    "mpcqp_plan_jvp_batch",
 )
 
 
@@ -80,6 +82,11 @@ class Problem(C.Structure):
 
 class VjpModelOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("g_x0", "g_goal", "g_targets", "g_e", "g_A", "g_B", "g_C", "g_D", "g_w")]
+
+
+class Tangents(C.Structure):
+    _fields_ = ([(name, C.c_void_p) for name in ("dx0", "dgoal", "dtargets", "de")]
+                + [(name + "_stride", C.c_int64) for name in ("dx0", "dgoal", "dtargets", "de")])
 
 
 class SolveOpts(C.Structure):
@@ -198,6 +205,11 @@ def load():
     lib.mpcqp_plan_vjp_stagewise_batch.restype = C.c_int
     lib.mpcqp_plan_vjp_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, vp, vp, vp, vp,
                                                    vp, C.POINTER(VjpModelOut), vp, vp, C.c_size_t, vp]
+    lib.mpcqp_plan_jvp_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_jvp_workspace_bytes.argtypes = [C.POINTER(Dims), i64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.mpcqp_plan_jvp_batch.restype = C.c_int
+    lib.mpcqp_plan_jvp_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, vp, vp,
+                                         C.POINTER(Tangents), vp, vp, vp, vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

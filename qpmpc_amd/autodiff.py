@@ -8,6 +8,12 @@ vector ``e``; when one of the model matrices A, B, C, D or the cost weights pass
 ``adjoint="stagewise"`` the backward is ``mpcqp_plan_vjp_stagewise_batch`` (qpmpc_amd/csrc/mpcqp_adjoint_stagewise.hip):
 the same adjoint on each problem's Riccati recursion, at any horizon ("Stage-wise adjoint").
 
+Forward mode: ``plan_jvp`` pushes tangents of the initial state, the goal, the targets and ``e`` through a solved plan
+with one call of ``mpcqp_plan_jvp_batch`` (the same KKT system on the same active set, the tangents as right-hand sides:
+``mpcqp_tangent_kernel`` in mpcqp_adjoint.hip); ``plan_jacobian`` is its feedback Jacobian ``dU/dx0`` (or ``dU/dgoal``),
+and ``solve_mpc_batch_diff`` serves ``torch.autograd.forward_ad`` dual tensors through it ("Forward
+sensitivities").
+
 The reference has no counterpart: its plans are NumPy arrays.
 """
 from __future__ import annotations
@@ -23,6 +29,7 @@ STAGEWISE_MAX_NX, STAGEWISE_MAX_NU = 32, 8  # envelope of mpcqp_plan_vjp_stagewi
 # the stage-wise backward splits its batch so that one launch's workspace stays below this many bytes
 STAGEWISE_WORKSPACE_CAP = 2 << 30
 ADJOINTS = ("condensed", "stagewise")
+MAX_TANGENTS = 256  # tangents per problem of one mpcqp_plan_jvp_batch call
 
 
 def _torch():
@@ -133,6 +140,20 @@ def check_envelope_stagewise(problem: BatchMPCProblem) -> None:
     rc = lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), problem.batch_size, 0, C.byref(nbytes))
     if rc != 0:
         _capi.check(rc, "mpcqp_plan_vjp_stagewise_workspace_bytes")
+
+
+def check_envelope_jvp(problem: BatchMPCProblem) -> None:
+    """Raise ``BackendError`` unless ``mpcqp_plan_jvp_batch`` serves this problem's dimensions (nothing is launched)."""
+    lib = _capi.load()
+    n = problem.nb_variables
+    if n > MAX_VARIABLES:
+        raise BackendError(f"forward sensitivities of plans are served for n = N * nu <= {MAX_VARIABLES} variables, not "
+                           f"{n}, by the condensed tangent solve (there is no stage-wise one)")
+    nbytes = C.c_size_t(0)
+    dims = _vjp_dims(problem)
+    rc = lib.mpcqp_plan_jvp_workspace_bytes(C.byref(dims), problem.batch_size, 1, C.byref(nbytes))
+    if rc != 0:
+        _capi.check(rc, "mpcqp_plan_jvp_workspace_bytes")
 
 
 def _reduce(g, like, canon_shape):
@@ -297,6 +318,124 @@ def _plan_vjp_stagewise(work: BatchMPCProblem, plan, gU, gX, want):
     return tuple(out[k] for k in GRAD_KEYS)
 
 
+TANGENT_NAMES = ("initial_state", "goal_state", "target_states", "ineq_vector")
+
+
+def _tangent_operand(t, name, Bn, tail, device):
+    """A tangent ``[B|1, T, *tail]`` as contiguous float64 and its stride between problems (0 when shared), or
+    (None, 0)."""
+    torch = _torch()
+    if t is None:
+        return None, 0
+    t = torch.as_tensor(t, device=device)
+    if t.dim() != 2 + len(tail) or tuple(t.shape[2:]) != tuple(tail) or t.shape[0] not in (1, Bn) or t.shape[1] < 1:
+        want = ", ".join(str(d) for d in tail)
+        raise ProblemDefinitionError(f"{name}: tangent of shape {tuple(t.shape)} is not [{Bn}|1, T, {want}]")
+    t = t.to(device=device, dtype=torch.float64).contiguous()
+    return t, (0 if t.shape[0] == 1 else t[0].numel())
+
+
+def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None, target_states=None,
+             ineq_vector=None, states: bool = False):
+    """Jacobian-vector products of a solved plan: ``(dU [B, T, N, nu], dX [B, T, N+1, nx] or None)``.
+
+    ``plan`` is ``solve_mpc_batch(problem, ..., return_multipliers=True)``; the active set is ``{i : lam_i > 0}`` and, on
+    it, the plan's response to the T tangents passed is solved in one call of ``mpcqp_plan_jvp_batch``. Tangents (each
+    optional, None = zero; at least one is needed, all with the same T <= 256): ``initial_state`` and ``goal_state``
+    ``[B|1, T, nx]``, ``target_states`` ``[B|1, T, N*nx]``, ``ineq_vector`` ``[B|1, T, N, mk]``; a leading 1 shares one set
+    of tangents with every problem. A goal or targets that do not enter the cost get zero responses, as for the VJP.
+    ``dX`` (with ``states=True``) is the rollout's tangent ``Phi dx0 + Psi dU``. Computed in float64 (a float32
+    problem's operands are converted) and returned in the problem's dtype. Problems not solved get zeros, and after the
+    call ``plan.jvp_status`` holds their status (``MPCQP_NOT_PD`` where the active rows' Gram matrix is singular; else
+    0). Envelope: n = N * nu <= 128 (``BackendError`` before anything is launched)."""
+    torch = _torch()
+    lib = _capi.load()
+    Bn, N, nx, nu, mk = (problem.batch_size, problem.nb_timesteps, problem.state_dim, problem.input_dim,
+                         problem.ineq_dim)
+    n, dev = problem.nb_variables, problem.device
+    if mk > 0 and plan.multipliers is None:
+        raise ProblemDefinitionError("plan_jvp needs the plan's multipliers: solve with return_multipliers=True")
+    check_envelope_jvp(problem)
+    tails = ((nx,), (nx,), (N * nx,), (N, mk))
+    ops = [_tangent_operand(t, nm, Bn, tail, dev) for t, nm, tail in zip(
+        (initial_state, goal_state, target_states, ineq_vector), TANGENT_NAMES, tails)]
+    Ts = {t.shape[1] for t, _ in ops if t is not None}
+    if not Ts:
+        raise ProblemDefinitionError("plan_jvp: no tangent given")
+    if len(Ts) > 1:
+        raise ProblemDefinitionError(f"plan_jvp: the tangents disagree on T: {sorted(Ts)}")
+    T = Ts.pop()
+    if T > MAX_TANGENTS:
+        raise ProblemDefinitionError(f"plan_jvp: T = {T} tangents, at most {MAX_TANGENTS} per call")
+    if mk == 0:
+        ops[3] = (None, 0)
+    p64 = _as_float64(problem)
+    f64 = dict(dtype=torch.float64, device=dev)
+    lam = plan.multipliers.to(torch.float64).contiguous() if mk > 0 else None
+    dU = torch.empty((Bn, T, N, nu), **f64)
+    dX = torch.empty((Bn, T, N + 1, nx), **f64) if states else None
+    jvp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    dims, cp = _vjp_dims(p64), p64.c_problem()
+    nbytes = C.c_size_t(0)
+    _capi.check(lib.mpcqp_plan_jvp_workspace_bytes(C.byref(dims), Bn, T, C.byref(nbytes)),
+                "mpcqp_plan_jvp_workspace_bytes")
+    ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=dev)
+    tan = _capi.Tangents(*[_ptr(t) for t, _ in ops], *[st for _, st in ops])
+    rc = lib.mpcqp_plan_jvp_batch(C.byref(dims), C.byref(cp), Bn, T, _ptr(lam), plan.status.data_ptr(), C.byref(tan),
+                                  dU.data_ptr(), _ptr(dX), jvp_status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream_ptr())
+    _capi.check(rc, "mpcqp_plan_jvp_batch")
+    plan.jvp_status = jvp_status
+    plan._jvp_keep = (ws, p64, lam, ops)  # alive until the stream has consumed them
+    dt = problem.dtype
+    return dU.to(dt), (None if dX is None else dX.to(dt))
+
+
+JACOBIAN_WRT = ("initial_state", "goal_state")
+
+
+def plan_jacobian(problem: BatchMPCProblem, plan, wrt: str = "initial_state", states: bool = False):
+    """Feedback Jacobian of a solved plan: ``(J_U [B, N, nu, nx], J_X [B, N+1, nx, nx] or None)`` with
+    ``J_U[b, k, :, j] = dU_k / d(wrt)_j`` on the plan's active set. ``wrt`` is ``"initial_state"`` (``J_U[:, 0]`` is the
+    local gain: ``u ~ plan.U[:, 0] + J_U[:, 0] @ (x - x0)`` while the active set holds) or ``"goal_state"``.
+
+    This is ``plan_jvp`` with the identity as T = nx tangents shared by the batch (stride 0), returned as a permuted
+    view; its rules (multipliers, status, envelope, dtype) apply."""
+    torch = _torch()
+    if wrt not in JACOBIAN_WRT:
+        raise ProblemDefinitionError(f"wrt: expected one of {JACOBIAN_WRT}, got {wrt!r}")
+    eye = torch.eye(problem.state_dim, dtype=torch.float64, device=problem.device)[None]
+    dU, dX = plan_jvp(problem, plan, states=states, **{wrt: eye})
+    return dU.permute(0, 2, 3, 1), (None if dX is None else dX.permute(0, 2, 3, 1))
+
+
+def _is_dual(t) -> bool:
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        return False
+    from torch.autograd import forward_ad
+
+    return forward_ad.unpack_dual(t).tangent is not None
+
+
+def _forward_tangents(ctx, tangents):
+    """(dU [B, N, nu], dX [B, N+1, nx] or None) of the forward-mode pass: one plan_jvp call with T = 1."""
+    work = ctx.work
+    Bn, N = work.batch_size, work.nb_timesteps
+    args = {}
+    for nm, t, canon in zip(TANGENT_NAMES, tangents, ctx.canon):
+        if t is None:
+            continue
+        t = t.reshape(canon)
+        if nm == "ineq_vector":
+            t = t.expand(-1, N, -1)
+        args[nm] = t.unsqueeze(1)
+    if not args:
+        return None, None
+    dU, dX = plan_jvp(work, ctx.plan, states=ctx.states, **args)
+    return dU[:, 0], (None if dX is None else dX[:, 0])
+
+
 def _make_function():
     torch = _torch()
     from torch.autograd.function import once_differentiable
@@ -329,6 +468,21 @@ def _make_function():
             out = [_reduce(g, like, canon) if nd else None
                    for nd, g, like, canon in zip(need, grads, ctx.inputs, ctx.canon)]
             return (None, None, None, None, *out)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            tangents = tangents[4:]
+            if any(t is not None for t in tangents[4:]):  # (refused before the forward; kept as a guard)
+                raise BackendError("forward-mode tangents reach initial_state, goal_state, target_states and "
+                                   "ineq_vector only")
+            dU, dX = _forward_tangents(ctx, tangents[:4])
+            if dU is None:
+                dU = torch.zeros((ctx.work.batch_size, ctx.work.nb_timesteps, ctx.work.input_dim),
+                                 dtype=ctx.work.dtype, device=ctx.work.device)
+            if ctx.states and dX is None:
+                dX = torch.zeros((ctx.work.batch_size, ctx.work.nb_timesteps + 1, ctx.work.state_dim),
+                                 dtype=ctx.work.dtype, device=ctx.work.device)
+            return (dU, dX) if ctx.states else dU
 
     return _PlanFunction
 
@@ -371,7 +525,12 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
     the workspace from the largest number of active rows in the batch, which costs one host sync. Any other value raises
     ``ProblemDefinitionError``.
 
-    When no operand passed requires grad (or grad mode is off), this is ``solve_mpc_batch(problem', **solve_kw)`` on the
+    Forward mode: ``initial_state``, ``goal_state``, ``target_states`` and ``ineq_vector`` may be dual tensors of
+    ``torch.autograd.forward_ad``; the tangents of ``U`` (and ``X``) are then one ``plan_jvp`` call (T = 1) on the plan.
+    A dual model matrix or weight, ``adjoint="stagewise"`` with a dual operand, or n > 128 raises ``BackendError``
+    before anything is launched.
+
+    When no operand passed requires grad (or grad mode is off) and none is dual, this is ``solve_mpc_batch(problem', **solve_kw)`` on the
     problem with the replaced operands, and its plan is returned as is."""
     global _FUNCTION
     torch = _torch()
@@ -380,8 +539,17 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
     passed = (initial_state, goal_state, target_states, ineq_vector, transition_state_matrix, transition_input_matrix,
               ineq_state_matrix, ineq_input_matrix, terminal_cost_weight, stage_state_cost_weight,
               stage_input_cost_weight)
+    dual = [_is_dual(t) for t in passed]
+    if any(dual[4:]):
+        names = MODEL_OPERANDS + WEIGHTS
+        raise BackendError("forward-mode tangents through plans reach initial_state, goal_state, target_states and "
+                           f"ineq_vector; a dual {', '.join(nm for nm, d in zip(names, dual[4:]) if d)} is not served")
+    if any(dual) and adjoint == "stagewise":
+        raise BackendError("forward-mode tangents through plans are served by the condensed tangent solve only, not "
+                           "with adjoint=\"stagewise\"")
     work = _replaced(problem, *passed)
-    need = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in passed)
+    need = any(dual) or (torch.is_grad_enabled()
+                         and any(isinstance(t, torch.Tensor) and t.requires_grad for t in passed))
     if not need:
         plan = solve_mpc_batch(work, **solve_kw)
         U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
@@ -390,6 +558,8 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
         check_envelope_stagewise(work)
     else:
         check_envelope(work)
+        if any(dual):
+            check_envelope_jvp(work)
     if _FUNCTION is None:
         _FUNCTION = _make_function()
     box = {"adjoint": adjoint}

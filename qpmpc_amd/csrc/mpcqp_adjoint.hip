@@ -22,6 +22,15 @@
 //      g_C_k = -(lam_k Y_k' + nu_k X_k'),  g_D_k = -(lam_k w_k' + nu_k u_k')     (coalesced over (k, i, j))
 //  10. g_w = (-Y_N'E_N, -sum_{k<N} Y_k'E_k, -w'U), one block reduction
 // The carve grows by X, Z, pz, s ((N + 1) nx each), nu scattered over all m rows and the reduction's 3 x threads.
+//
+// mpcqp_tangent_kernel (mpcqp_plan_jvp_batch) is the forward-mode counterpart: the same KKT system on the same active set,
+// with T tangents (dx0, dgoal, dtargets, de) as right-hand sides ("Forward sensitivities"):
+//   1. dq_t = w_t psi_N'(phi_N dx0 - dgoal) + w_x Psi'(Phi dx0 - dtargets) (terms as flagged), dh_t = de - C Phi dx0
+//   2. P = L L'; one forward sweep L^-1 over the T + k right-hand sides (-dq_t, then the active rows of G)
+//   3. S = M_A M_A' = R R', mu_t = S^-1 (M_A r_t - dh_A,t)        (forward and backward substitution, over tangents)
+//   4. dU_t = L^-T (r_t - M_A' mu_t)                               (one backward sweep, over tangents); dX_t = Phi dx0 + Psi dU_t
+// Its carve: L (n ld), the T + n right-hand sides ((T + n) ld), S (n ld), mu (T ld), Phi dx0_t (T (N + 1) nx; step 1
+// reads it for dq and dh, and dX reuses it), the active row ids.
 #include <hip/hip_runtime.h>
 
 #include "mpcqp.h"
@@ -466,6 +475,253 @@ int launch_bs(const AdjArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipSt
     return (int)hipGetLastError();
 }
 
+struct TanArgs {
+    int nx, nu, N, mk, n, m, flags, T;
+    double wt, wx;
+    const double *P, *G, *Phi, *Psi;  // condensed (packed per problem, mpcqp_condense_batch)
+    MpcqpOperand C;                   // ineq_state_matrix of the problem (nullable)
+    const double *lam;                // nullable when m = 0
+    const int32_t *status;
+    const double *dx0, *dgoal, *dtgt, *de;  // nullable (a zero tangent); tangent t of a problem at t nx / t nx / t N nx / t m
+    int64_t sx0, sgoal, stgt, se;           // elements between problems (0: shared)
+    double *dU, *dX;                        // [batch][T][n], [batch][T][(N + 1) nx] (dX nullable)
+    int32_t *jvp_status;                    // nullable
+    double *carve_ws;                       // per-problem carves when they do not fit LDS (else null)
+    int64_t carve;                          // doubles per problem
+};
+
+struct TanCarve {
+    int ld;
+    int64_t L, Z, S, mu, x, idx, total;
+};
+
+__host__ __device__ inline TanCarve make_tan_carve(int n, int T, int R)
+{
+    TanCarve c;
+    c.ld = n | 1;
+    c.L = 0;
+    c.Z = c.L + (int64_t)n * c.ld;        // rows 0 .. T-1: the tangents' right-hand sides; T .. T+k-1: the active rows
+    c.S = c.Z + (int64_t)(T + n) * c.ld;  // k x k Gram, stride ld
+    c.mu = c.S + (int64_t)n * c.ld;       // T rows of k: dh_A, then mu
+    c.x = c.mu + (int64_t)T * c.ld;       // T rows of R = (N + 1) nx: Phi dx0_t
+    c.idx = c.x + (int64_t)T * R;         // n + 1 int32 (active row ids)
+    c.total = c.idx + (n + 2) / 2;
+    return c;
+}
+
+template <int BS, bool kLds>
+__global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
+{
+    extern __shared__ double lds_carve[];
+    __shared__ int s_k;
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int n = a.n, m = a.m, nx = a.nx, N = a.N, mk = a.mk, T = a.T;
+    const int R = (N + 1) * nx;
+    const TanCarve cv = make_tan_carve(n, T, R);
+    const int ld = cv.ld;
+    double *base = kLds ? lds_carve : a.carve_ws + b * a.carve;
+    double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *mu = base + cv.mu, *xs = base + cv.x;
+    int *idx = (int *)(base + cv.idx);
+
+    const double *P = a.P + b * (int64_t)n * n;
+    const double *G = a.G ? a.G + b * (int64_t)m * n : nullptr;
+    const double *Phi = a.Phi + b * (int64_t)R * nx;
+    const double *Psi = a.Psi + b * (int64_t)R * n;
+    const double *lam = a.lam ? a.lam + b * (int64_t)m : nullptr;
+    const double *dx0 = a.dx0 ? a.dx0 + b * a.sx0 : nullptr;
+    const double *dgoal = a.dgoal ? a.dgoal + b * a.sgoal : nullptr;
+    const double *dtgt = a.dtgt ? a.dtgt + b * a.stgt : nullptr;
+    const double *de = a.de ? a.de + b * a.se : nullptr;
+    double *dU = a.dU + b * (int64_t)T * n;
+    double *dX = a.dX ? a.dX + b * (int64_t)T * R : nullptr;
+    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
+
+    int verdict = a.status[b];
+    if (verdict == 0) {
+        // lower triangle of P; active rows (wave 0: ballot + prefix count, ids ascending), as mpcqp_adjoint_kernel
+        for (int e = tid; e < n * n; e += BS) {
+            const int i = e / n, j = e % n;
+            if (j <= i) L[i * ld + j] = P[e];
+        }
+        if (tid < 64) {
+            int count = 0;
+            for (int i0 = 0; i0 < m; i0 += 64) {
+                const int i = i0 + tid;
+                const bool act = i < m && lam[i] > 0.0;
+                const unsigned long long mask = __ballot(act);
+                const int pre = __popcll(mask & ((1ull << tid) - 1ull));
+                if (act && count + pre < n) idx[count + pre] = i;
+                count += __popcll(mask);
+            }
+            if (tid == 0) s_k = count;
+        }
+        __syncthreads();
+        const int k = s_k;
+        if (k > n) {
+            verdict = MPCQP_NOT_PD;
+        } else {
+            // 1. xs_t = Phi dx0_t; Z rows 0 .. T-1 = -dq_t; rows T .. T+k-1 = G_A; mu rows = dh_A,t
+            if (dx0) {
+                for (int e = tid; e < T * R; e += BS) {
+                    const int t = e / R, r = e % R;
+                    const double *fr = Phi + (int64_t)r * nx, *x0t = dx0 + (int64_t)t * nx;
+                    double acc = 0.0;
+                    for (int j = 0; j < nx; ++j) acc += fr[j] * x0t[j];
+                    xs[e] = acc;
+                }
+                __syncthreads();
+            }
+            for (int e = tid; e < T * n; e += BS) {
+                const int t = e / n, c = e % n;
+                const double *xt = dx0 ? xs + (int64_t)t * R : nullptr;
+                double acc = 0.0;
+                if (qs && (xt || dtgt)) {
+                    const double *tg = dtgt ? dtgt + (int64_t)t * N * nx : nullptr;
+                    double s = 0.0;
+                    for (int r = 0; r < N * nx; ++r)
+                        s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (tg ? tg[r] : 0.0));
+                    acc += a.wx * s;
+                }
+                if (qt && (xt || dgoal)) {
+                    const double *gl = dgoal ? dgoal + (int64_t)t * nx : nullptr;
+                    double s = 0.0;
+                    for (int i = 0; i < nx; ++i) {
+                        const int r = N * nx + i;
+                        s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (gl ? gl[i] : 0.0));
+                    }
+                    acc += a.wt * s;
+                }
+                Z[t * ld + c] = -acc;
+            }
+            for (int e = tid; e < k * n; e += BS) {
+                const int r = e / n, j = e % n;
+                Z[(T + r) * ld + j] = G[(int64_t)idx[r] * n + j];
+            }
+            for (int e = tid; e < T * k; e += BS) {
+                const int t = e / k, r = e % k, row = idx[r], kk = row / mk;
+                double h = de ? de[(int64_t)t * m + row] : 0.0;
+                if (Cb && dx0) {
+                    const double *Ci = Cb + kk * a.C.step_stride + (row % mk) * nx, *xk = xs + (int64_t)t * R + kk * nx;
+                    for (int i = 0; i < nx; ++i) h -= Ci[i] * xk[i];
+                }
+                mu[t * ld + r] = h;
+            }
+            // 2. P = L L', then one forward sweep L^-1 over all T + k right-hand sides
+            if (!chol_lower<BS>(L, n, ld, tid)) {
+                verdict = MPCQP_NOT_PD;
+            } else {
+                const int nr = T + k;
+                for (int j = 0; j < n; ++j) {
+                    const double inv = 1.0 / L[j * ld + j];
+                    for (int r = tid; r < nr; r += BS) Z[r * ld + j] *= inv;
+                    __syncthreads();
+                    const int w = n - j - 1;
+                    for (int e = tid; e < nr * w; e += BS) {
+                        const int r = e / w, i = j + 1 + e % w;
+                        Z[r * ld + i] -= L[i * ld + j] * Z[r * ld + j];
+                    }
+                    __syncthreads();
+                }
+                // 3. Gram S = M_A M_A' (lower); mu_t = M_A r_t - dh_A,t
+                for (int e = tid; e < k * k; e += BS) {
+                    const int i = e / k, j = e % k;
+                    if (j <= i) {
+                        const double *zi = Z + (T + i) * ld, *zj = Z + (T + j) * ld;
+                        double acc = 0.0;
+                        for (int c = 0; c < n; ++c) acc += zi[c] * zj[c];
+                        S[i * ld + j] = acc;
+                    }
+                }
+                for (int e = tid; e < T * k; e += BS) {
+                    const int t = e / k, i = e % k;
+                    const double *zi = Z + (T + i) * ld, *zt = Z + t * ld;
+                    double acc = 0.0;
+                    for (int c = 0; c < n; ++c) acc += zi[c] * zt[c];
+                    mu[t * ld + i] = acc - mu[t * ld + i];
+                }
+                if (!chol_lower<BS>(S, k, ld, tid)) {
+                    verdict = MPCQP_NOT_PD;
+                } else {
+                    // mu_t = R^-T R^-1 (...), every tangent at once
+                    for (int j = 0; j < k; ++j) {
+                        const double inv = 1.0 / S[j * ld + j];
+                        for (int t = tid; t < T; t += BS) mu[t * ld + j] *= inv;
+                        __syncthreads();
+                        const int w = k - j - 1;
+                        for (int e = tid; e < T * w; e += BS) {
+                            const int t = e / w, i = j + 1 + e % w;
+                            mu[t * ld + i] -= S[i * ld + j] * mu[t * ld + j];
+                        }
+                        __syncthreads();
+                    }
+                    for (int j = k - 1; j >= 0; --j) {
+                        const double inv = 1.0 / S[j * ld + j];
+                        for (int t = tid; t < T; t += BS) mu[t * ld + j] *= inv;
+                        __syncthreads();
+                        for (int e = tid; e < T * j; e += BS) {
+                            const int t = e / j, i = e % j;
+                            mu[t * ld + i] -= S[j * ld + i] * mu[t * ld + j];
+                        }
+                        __syncthreads();
+                    }
+                    // 4. r_t - M_A' mu_t in place, then dU_t = L^-T (...), every tangent at once
+                    for (int e = tid; e < T * n; e += BS) {
+                        const int t = e / n, c = e % n;
+                        double acc = Z[t * ld + c];
+                        for (int r = 0; r < k; ++r) acc -= Z[(T + r) * ld + c] * mu[t * ld + r];
+                        Z[t * ld + c] = acc;
+                    }
+                    __syncthreads();
+                    for (int j = n - 1; j >= 0; --j) {
+                        const double inv = 1.0 / L[j * ld + j];
+                        for (int t = tid; t < T; t += BS) Z[t * ld + j] *= inv;
+                        __syncthreads();
+                        for (int e = tid; e < T * j; e += BS) {
+                            const int t = e / j, i = e % j;
+                            Z[t * ld + i] -= L[j * ld + i] * Z[t * ld + j];
+                        }
+                        __syncthreads();
+                    }
+                    for (int e = tid; e < T * n; e += BS) dU[e] = Z[(e / n) * ld + e % n];
+                    if (dX) {
+                        for (int64_t e = tid; e < (int64_t)T * R; e += BS) {
+                            const int t = (int)(e / R), r = (int)(e % R);
+                            const double *pr = Psi + (int64_t)r * n, *zt = Z + t * ld;
+                            double acc = dx0 ? xs[e] : 0.0;
+                            for (int c = 0; c < n; ++c) acc += pr[c] * zt[c];
+                            dX[e] = acc;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (verdict != 0) {  // (uniform) unsolved or degenerate: all-zero tangents
+        for (int e = tid; e < T * n; e += BS) dU[e] = 0.0;
+        if (dX)
+            for (int64_t e = tid; e < (int64_t)T * R; e += BS) dX[e] = 0.0;
+    }
+    if (a.jvp_status && tid == 0) a.jvp_status[b] = verdict;
+}
+
+template <int BS>
+int launch_tangent_bs(const TanArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
+{
+    if (lds) {
+        auto kern = mpcqp_tangent_kernel<BS, true>;
+        if (lds_bytes > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (e != hipSuccess) return (int)e;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(BS), lds_bytes, st, a);
+    } else {
+        hipLaunchKernelGGL((mpcqp_tangent_kernel<BS, false>), dim3((unsigned)batch), dim3(BS), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 size_t adjoint_carve_bytes(int n, int N, int nx, int m, bool model)
@@ -524,6 +780,57 @@ int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
     if (adjoint_threads(a.n) == 64)
         return l.model ? launch_bs<64, true>(a, lds, bytes, batch, st) : launch_bs<64, false>(a, lds, bytes, batch, st);
     return l.model ? launch_bs<256, true>(a, lds, bytes, batch, st) : launch_bs<256, false>(a, lds, bytes, batch, st);
+}
+
+size_t tangent_carve_bytes(int n, int N, int nx, int ntan)
+{
+    return (size_t)make_tan_carve(n, ntan, (N + 1) * nx).total * sizeof(double);
+}
+
+// (the 64 bytes spare leave room for the kernel's static s_k, as adjoint_carve_in_lds)
+bool tangent_carve_in_lds(int n, int N, int nx, int ntan)
+{
+    return tangent_carve_bytes(n, N, nx, ntan) + 64 <= kLdsBytesPerCU;
+}
+
+int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st)
+{
+    TanArgs a;
+    a.nx = l.nx;
+    a.nu = l.nu;
+    a.N = l.N;
+    a.mk = l.mk;
+    a.n = l.N * l.nu;
+    a.m = l.N * l.mk;
+    a.flags = l.flags;
+    a.T = l.ntan;
+    a.wt = l.wt;
+    a.wx = l.wx;
+    a.P = (const double *)l.P;
+    a.G = (const double *)l.G;
+    a.Phi = (const double *)l.Phi;
+    a.Psi = (const double *)l.Psi;
+    a.C = l.C;
+    a.lam = (const double *)l.lam;
+    a.status = l.status;
+    a.dx0 = (const double *)l.tan.dx0;
+    a.dgoal = (const double *)l.tan.dgoal;
+    a.dtgt = (const double *)l.tan.dtargets;
+    a.de = a.m > 0 ? (const double *)l.tan.de : nullptr;
+    a.sx0 = l.tan.dx0_stride;
+    a.sgoal = l.tan.dgoal_stride;
+    a.stgt = l.tan.dtargets_stride;
+    a.se = l.tan.de_stride;
+    a.dU = (double *)l.dU;
+    a.dX = (double *)l.dX;
+    a.jvp_status = l.jvp_status;
+    const bool lds = tangent_carve_in_lds(a.n, a.N, a.nx, a.T);
+    const size_t bytes = tangent_carve_bytes(a.n, a.N, a.nx, a.T);
+    a.carve_ws = lds ? nullptr : (double *)l.carve_ws;
+    a.carve = (int64_t)(bytes / sizeof(double));
+    if (!lds && !a.carve_ws) return MPCQP_EWORKSPACE;
+    if (adjoint_threads(a.n) == 64) return launch_tangent_bs<64>(a, lds, bytes, batch, st);
+    return launch_tangent_bs<256>(a, lds, bytes, batch, st);
 }
 
 }  // namespace mpcqp

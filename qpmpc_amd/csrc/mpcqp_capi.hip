@@ -1014,7 +1014,8 @@ struct VjpPlan {
     size_t cws_bytes;
 };
 
-static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v, bool model = false)
+// the condensed segments and mpcqp_condense_batch's scratch: every field up to `carve`
+static int condensed_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v)
 {
     int rc = check_dims(dims);
     if (rc) return rc;
@@ -1034,6 +1035,14 @@ static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v, bool model
     v.cws = v.Psi + al256(d * (N + 1) * nx * n);
     v.cws_bytes = cws;
     v.carve = v.cws + al256((int64_t)cws);
+    return 0;
+}
+
+static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v, bool model = false)
+{
+    const int rc = condensed_plan(dims, batch, v);
+    if (rc) return rc;
+    const int64_t nx = dims->nx, N = dims->N, n = N * dims->nu, m = N * dims->mk, d = 8 * batch;
     const bool lds = adjoint_carve_in_lds((int)n, (int)N, (int)nx, (int)m, model);
     v.gx0 = v.carve + (lds ? 0 : al256((int64_t)adjoint_carve_bytes((int)n, (int)N, (int)nx, (int)m, model) * batch));
     v.total = v.gx0 + (model ? al256(d * nx) : 0);
@@ -1140,6 +1149,74 @@ int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *proble
     l.g_D = out->g_D;
     l.g_w = out->g_w;
     return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
+}
+
+namespace {
+constexpr int32_t kMaxTangents = 256;
+
+// mpcqp_plan_jvp_batch's workspace: mpcqp_plan_vjp_batch's condensed segments, then the tangent carves when they do not
+// fit LDS
+static int jvp_plan(const MpcqpDims *dims, int64_t batch, int32_t ntan, VjpPlan &v)
+{
+    const int rc = condensed_plan(dims, batch, v);
+    if (rc) return rc;
+    if (ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
+    const int n = dims->N * dims->nu;
+    const bool lds = tangent_carve_in_lds(n, dims->N, dims->nx, ntan);
+    v.total = v.carve + (lds ? 0 : al256((int64_t)tangent_carve_bytes(n, dims->N, dims->nx, ntan) * batch));
+    return 0;
+}
+}  // namespace
+
+int mpcqp_plan_jvp_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t ntan, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    VjpPlan v;
+    const int rc = jvp_plan(dims, batch, ntan, v);
+    if (rc) return rc;
+    *bytes = (size_t)v.total;
+    return 0;
+}
+
+int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t ntan,
+                         const void *lam, const int32_t *status, const MpcqpTangents *tan, void *dU, void *dX,
+                         int32_t *jvp_status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    VjpPlan v;
+    int rc = jvp_plan(dims, batch, ntan, v);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    if (!tan || !status || !dU || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (tan->dx0_stride < 0 || tan->dgoal_stride < 0 || tan->dtargets_stride < 0 || tan->de_stride < 0)
+        return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
+    char *w = (char *)workspace;
+    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
+                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
+    if (rc) return rc;
+    TangentLaunch l;
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.flags = dims->flags;
+    l.ntan = ntan;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.P = w + v.P;
+    l.G = dims->mk > 0 ? w + v.G : nullptr;
+    l.Phi = w + v.Phi;
+    l.Psi = w + v.Psi;
+    l.C = problem->C;
+    l.lam = dims->mk > 0 ? lam : nullptr;
+    l.status = status;
+    l.tan = *tan;
+    l.dU = dU;
+    l.dX = dX;
+    l.jvp_status = jvp_status;
+    l.carve_ws = (v.total > v.carve) ? w + v.carve : nullptr;
+    return launch_tangent(l, batch, (hipStream_t)stream);
 }
 
 namespace {

@@ -293,6 +293,23 @@ struct AdjointLaunch {
 size_t adjoint_carve_bytes(int n, int N, int nx, int m = 0, bool model = false);
 bool adjoint_carve_in_lds(int n, int N, int nx, int m = 0, bool model = false);
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st);
+// Jacobian-vector product of solved plans (mpcqp_adjoint.hip, mpcqp_tangent_kernel; float64): the adjoint's KKT system with
+// ntan tangents as right-hand sides
+struct TangentLaunch {
+    int nx, nu, N, mk, flags, ntan;
+    double wt, wx;
+    const void *P, *G, *Phi, *Psi;  // mpcqp_condense_batch's outputs, packed per problem
+    MpcqpOperand C;
+    const void *lam;
+    const int32_t *status;
+    MpcqpTangents tan;
+    void *dU, *dX;  // dX nullable
+    int32_t *jvp_status;
+    void *carve_ws;  // batch * tangent_carve_bytes when the carve does not fit LDS
+};
+size_t tangent_carve_bytes(int n, int N, int nx, int ntan);
+bool tangent_carve_in_lds(int n, int N, int nx, int ntan);
+int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st);
 // the stage-wise adjoint (mpcqp_adjoint_stagewise.hip; float64, nx <= 32, nu <= 8, any N): one problem per workgroup on its
 // Riccati recursion, the records and the active rows' whitened vectors in a per-problem region of the workspace
 struct StagewiseAdjointLaunch {

@@ -18,7 +18,7 @@ for obj in sorted(glob.glob(os.path.join(ROOT, "qpmpc_amd/lib/obj/*.o"))):
     for blk in txt.split("  - .agpr_count:")[1:]:
         g = lambda k: (re.search(rf"\.{k}:\s*(\S+)", blk) or [None, "?"])[1]
         name = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip()
-        name = re.sub(r"\(.*", "", name).replace("void mpcqp::", "")
+        name = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "")).replace("void mpcqp::", "")
         if want in name:
             rows.append((os.path.basename(obj).split(".")[0], name, g("vgpr_count"), blk.split()[0], g("sgpr_count"), g("vgpr_spill_count"),
                          g("sgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))
