@@ -113,47 +113,33 @@ def _vjp_dims(problem: BatchMPCProblem) -> _capi.Dims:
     return dims
 
 
-def check_envelope(problem: BatchMPCProblem) -> None:
-    """Raise ``BackendError`` unless ``mpcqp_plan_vjp_batch`` serves this problem's dimensions (nothing is launched)."""
+def check_envelope(problem: BatchMPCProblem, kind: str = "vjp") -> None:
+    """Raise ``BackendError`` unless the export of ``kind`` serves this problem's dimensions (nothing is launched):
+    ``"vjp"``, ``mpcqp_plan_vjp_batch`` (n = N * nu <= 128); ``"jvp"``, ``mpcqp_plan_jvp_batch`` (the same);
+    ``"stagewise"``, ``mpcqp_plan_vjp_stagewise_batch`` (nx <= 32, nu <= 8, any horizon)."""
     lib = _capi.load()
-    n = problem.nb_variables
-    if n > MAX_VARIABLES:
-        raise BackendError(f"gradients through plans are served for n = N * nu <= {MAX_VARIABLES} variables, not {n}, by "
-                           "the condensed adjoint (adjoint=\"stagewise\" serves any horizon for nx <= 32, nu <= 8)")
-    nbytes = C.c_size_t(0)
-    dims = _vjp_dims(problem)
-    rc = lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), problem.batch_size, C.byref(nbytes))
-    if rc != 0:
-        _capi.check(rc, "mpcqp_plan_vjp_workspace_bytes")
+    n, nx, nu = problem.nb_variables, problem.state_dim, problem.input_dim
+    if kind == "stagewise":
+        if nx > STAGEWISE_MAX_NX or nu > STAGEWISE_MAX_NU:
+            raise BackendError(f"the stage-wise adjoint serves nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU}, "
+                               f"not nx = {nx}, nu = {nu}")
+        query, extra = lib.mpcqp_plan_vjp_stagewise_workspace_bytes, (0,)
+    elif kind == "jvp":
+        if n > MAX_VARIABLES:
+            raise BackendError(f"forward sensitivities of plans are served for n = N * nu <= {MAX_VARIABLES} variables, "
+                               f"not {n}, by the condensed tangent solve (there is no stage-wise one)")
+        query, extra = lib.mpcqp_plan_jvp_workspace_bytes, (1,)
+    else:
+        if n > MAX_VARIABLES:
+            raise BackendError(f"gradients through plans are served for n = N * nu <= {MAX_VARIABLES} variables, not {n}, "
+                               "by the condensed adjoint (adjoint=\"stagewise\" serves any horizon for nx <= 32, nu <= 8)")
+        query, extra = lib.mpcqp_plan_vjp_workspace_bytes, ()
+    _workspace_bytes(query, _vjp_dims(problem), problem.batch_size, *extra)
 
 
 def check_envelope_stagewise(problem: BatchMPCProblem) -> None:
-    """Raise ``BackendError`` unless ``mpcqp_plan_vjp_stagewise_batch`` serves this problem's dimensions (nothing is
-    launched): nx <= 32, nu <= 8, any horizon."""
-    lib = _capi.load()
-    nx, nu = problem.state_dim, problem.input_dim
-    if nx > STAGEWISE_MAX_NX or nu > STAGEWISE_MAX_NU:
-        raise BackendError(f"the stage-wise adjoint serves nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU}, "
-                           f"not nx = {nx}, nu = {nu}")
-    nbytes = C.c_size_t(0)
-    dims = _vjp_dims(problem)
-    rc = lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), problem.batch_size, 0, C.byref(nbytes))
-    if rc != 0:
-        _capi.check(rc, "mpcqp_plan_vjp_stagewise_workspace_bytes")
-
-
-def check_envelope_jvp(problem: BatchMPCProblem) -> None:
-    """Raise ``BackendError`` unless ``mpcqp_plan_jvp_batch`` serves this problem's dimensions (nothing is launched)."""
-    lib = _capi.load()
-    n = problem.nb_variables
-    if n > MAX_VARIABLES:
-        raise BackendError(f"forward sensitivities of plans are served for n = N * nu <= {MAX_VARIABLES} variables, not "
-                           f"{n}, by the condensed tangent solve (there is no stage-wise one)")
-    nbytes = C.c_size_t(0)
-    dims = _vjp_dims(problem)
-    rc = lib.mpcqp_plan_jvp_workspace_bytes(C.byref(dims), problem.batch_size, 1, C.byref(nbytes))
-    if rc != 0:
-        _capi.check(rc, "mpcqp_plan_jvp_workspace_bytes")
+    """``check_envelope(problem, "stagewise")``."""
+    check_envelope(problem, "stagewise")
 
 
 def _reduce(g, like, canon_shape):
@@ -166,87 +152,24 @@ def _reduce(g, like, canon_shape):
     return g.reshape(shape).to(dtype=dtype, device=device)
 
 
-def _vjp_inputs(work: BatchMPCProblem, plan, gU, gX):
-    torch = _torch()
-    p64 = _as_float64(work)
-    Bn, N, nx, mk, n = work.batch_size, work.nb_timesteps, work.state_dim, work.ineq_dim, work.nb_variables
-    f64 = dict(dtype=torch.float64, device=work.device)
-    gU = torch.zeros((Bn, n), **f64) if gU is None else gU.reshape(Bn, n).to(torch.float64).contiguous()
-    gX = None if gX is None else gX.reshape(Bn, (N + 1) * nx).to(torch.float64).contiguous()
-    lam = plan.multipliers.to(torch.float64).contiguous() if mk > 0 else None
-    return p64, gU, gX, lam
-
-
-def _workspace_for(query, dims, Bn, device):
-    torch = _torch()
+def _workspace_bytes(query, dims, Bn, *extra) -> int:
+    """The byte count a ``*_workspace_bytes`` export reports for ``Bn`` problems (``extra``: its max_active or ntan)."""
     nbytes = C.c_size_t(0)
-    _capi.check(query(C.byref(dims), Bn, C.byref(nbytes)), query.__name__)
-    return torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=device)
+    _capi.check(query(C.byref(dims), Bn, *extra, C.byref(nbytes)), query.__name__)
+    return nbytes.value
+
+
+def _workspace_for(query, dims, Bn, device, *extra):
+    torch = _torch()
+    return torch.empty((max(_workspace_bytes(query, dims, Bn, *extra), 1),), dtype=torch.uint8, device=device)
 
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _plan_vjp(work: BatchMPCProblem, plan, gU, gX, want):
-    """(g_x0 [B,nx], g_goal [B,nx], g_targets [B,N*nx], g_e [B,N,mk]) in float64 through mpcqp_plan_vjp_batch; entries not
-    in ``want`` are None. Sets ``plan.vjp_status``."""
-    torch = _torch()
-    lib = _capi.load()
-    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
-    Bn, N, nx, mk = work.batch_size, work.nb_timesteps, work.state_dim, work.ineq_dim
-    dev = work.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    g_x0 = torch.empty((Bn, nx), **f64)
-    g_goal = torch.empty((Bn, nx), **f64) if "goal" in want else None
-    g_tgt = torch.empty((Bn, N * nx), **f64) if "targets" in want else None
-    g_e = torch.empty((Bn, N, mk), **f64) if "e" in want and mk > 0 else None
-    vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
-    dims, cp = _vjp_dims(p64), p64.c_problem()
-    ws = _workspace_for(lib.mpcqp_plan_vjp_workspace_bytes, dims, Bn, dev)
-    ptr = _ptr
-    rc = lib.mpcqp_plan_vjp_batch(
-        C.byref(dims), C.byref(cp), Bn, ptr(lam), plan.status.data_ptr(), gU.data_ptr(), ptr(gX), g_x0.data_ptr(),
-        ptr(g_goal), ptr(g_tgt), ptr(g_e), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
-    _capi.check(rc, "mpcqp_plan_vjp_batch")
-    plan.vjp_status = vjp_status
-    plan._vjp_keep = (ws, p64, lam, gU, gX)  # alive until the stream has consumed them
-    if g_e is None and "e" in want:
-        g_e = torch.zeros((Bn, N, mk), **f64)
-    return g_x0, g_goal, g_tgt, g_e
-
-
 GRAD_KEYS = ("x0", "goal", "targets", "e", "A", "B", "C", "D", "wt", "wx", "wu")
-
-
-def _plan_vjp_model(work: BatchMPCProblem, plan, gU, gX, want):
-    """The gradients of ``GRAD_KEYS`` in float64 through mpcqp_plan_vjp_model_batch, per problem: x0 [B,nx], goal [B,nx],
-    targets [B,N*nx], e [B,N,mk], A [B,N,nx,nx], B [B,N,nx,nu], C [B,N,mk,nx], D [B,N,mk,nu] and the three weights [B];
-    entries not in ``want`` are None. Sets ``plan.vjp_status``."""
-    torch = _torch()
-    lib = _capi.load()
-    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
-    Bn, N, nx, nu, mk = work.batch_size, work.nb_timesteps, work.state_dim, work.input_dim, work.ineq_dim
-    dev = work.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    shapes = dict(x0=(nx,), goal=(nx,), targets=(N * nx,), e=(N, mk), A=(N, nx, nx), B=(N, nx, nu), C=(N, mk, nx),
-                  D=(N, mk, nu))
-    out = {k: (torch.empty((Bn,) + shp, **f64) if k in want else None) for k, shp in shapes.items()}
-    g_w = torch.empty((Bn, 3), **f64) if want & {"wt", "wx", "wu"} else None
-    U = plan.U.reshape(Bn, -1).to(torch.float64).contiguous()
-    vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
-    dims, cp = _vjp_dims(p64), p64.c_problem()
-    ws = _workspace_for(lib.mpcqp_plan_vjp_model_workspace_bytes, dims, Bn, dev)
-    res = _capi.VjpModelOut(*[_ptr(out[k]) for k in ("x0", "goal", "targets", "e", "A", "B", "C", "D")], _ptr(g_w))
-    rc = lib.mpcqp_plan_vjp_model_batch(
-        C.byref(dims), C.byref(cp), Bn, _ptr(lam), plan.status.data_ptr(), U.data_ptr(), gU.data_ptr(), _ptr(gX),
-        C.byref(res), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
-    _capi.check(rc, "mpcqp_plan_vjp_model_batch")
-    plan.vjp_status = vjp_status
-    plan._vjp_keep = (ws, p64, lam, U, gU, gX)  # alive until the stream has consumed them
-    for i, k in enumerate(("wt", "wx", "wu")):
-        out[k] = g_w[:, i] if k in want else None
-    return tuple(out[k] for k in GRAD_KEYS)
+BACKWARDS = ("condensed", "model", "stagewise")
 
 
 def _shifted(cp, b0: int):
@@ -259,63 +182,93 @@ def _shifted(cp, b0: int):
     return out
 
 
-def _plan_vjp_stagewise(work: BatchMPCProblem, plan, gU, gX, want):
-    """The gradients of ``GRAD_KEYS`` in float64 through mpcqp_plan_vjp_stagewise_batch, shaped as ``_plan_vjp_model``'s;
-    entries not in ``want`` are None. Sets ``plan.vjp_status``.
+def _vjp(work: BatchMPCProblem, plan, gU, gX, want, backward: str):
+    """The gradients of ``GRAD_KEYS`` in float64, per problem: x0 [B,nx], goal [B,nx], targets [B,N*nx], e [B,N,mk],
+    A [B,N,nx,nx], B [B,N,nx,nu], C [B,N,mk,nx], D [B,N,mk,nu] and the three weights [B]; entries not in ``want`` are
+    None. Sets ``plan.vjp_status``.
 
+    ``backward`` names the export: ``"condensed"``, mpcqp_plan_vjp_batch (x0, always returned, goal, targets and e; the
+    rest None); ``"model"``, mpcqp_plan_vjp_model_batch; ``"stagewise"``, mpcqp_plan_vjp_stagewise_batch, whose
     ``max_active`` is the largest number of active rows (lam > 0) of a solved problem, capped at n: the one host sync of
-    the backward. The batch is split into launches whose workspace stays below ``STAGEWISE_WORKSPACE_CAP``."""
+    the backward. Its batch is split into launches whose workspace stays below ``STAGEWISE_WORKSPACE_CAP``."""
     torch = _torch()
     lib = _capi.load()
-    p64, gU, gX, lam = _vjp_inputs(work, plan, gU, gX)
+    if backward not in BACKWARDS:
+        raise ValueError(f"backward: expected one of {BACKWARDS}, got {backward!r}")
+    p64 = _as_float64(work)
     Bn, N, nx, nu, mk, n = (work.batch_size, work.nb_timesteps, work.state_dim, work.input_dim, work.ineq_dim,
                             work.nb_variables)
     dev = work.device
     f64 = dict(dtype=torch.float64, device=dev)
+    gU = torch.zeros((Bn, n), **f64) if gU is None else gU.reshape(Bn, n).to(torch.float64).contiguous()
+    gX = None if gX is None else gX.reshape(Bn, (N + 1) * nx).to(torch.float64).contiguous()
+    lam = plan.multipliers.to(torch.float64).contiguous() if mk > 0 else None
+    if backward == "condensed":
+        want = {"x0"} | (set(want) & {"goal", "targets", "e"})
     shapes = dict(x0=(nx,), goal=(nx,), targets=(N * nx,), e=(N, mk), A=(N, nx, nx), B=(N, nx, nu), C=(N, mk, nx),
                   D=(N, mk, nu))
     out = {k: (torch.empty((Bn,) + shp, **f64) if k in want else None) for k, shp in shapes.items()}
     g_w = torch.empty((Bn, 3), **f64) if want & {"wt", "wx", "wu"} else None
     model = g_w is not None or any(out[k] is not None for k in ("A", "B", "C", "D"))
-    U = plan.U.reshape(Bn, -1).to(torch.float64).contiguous() if model else None
-    status = plan.status
-    if lam is not None and Bn > 0:
-        act = ((lam > 0) & (status == 0)[:, None]).sum(dim=1)
-        max_active = min(int(act.max().item()), n)  # the host sync
-    else:
-        max_active = 0
-    vjp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
+    U = plan.U.reshape(Bn, -1).to(torch.float64).contiguous() if backward == "model" or model else None
+    status, vjp_status = plan.status, torch.empty((Bn,), dtype=torch.int32, device=dev)
     dims, cp = _vjp_dims(p64), p64.c_problem()
-    one = C.c_size_t(0)
-    _capi.check(lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), 1, max_active, C.byref(one)),
-                "mpcqp_plan_vjp_stagewise_workspace_bytes")
-    chunk = max(1, min(Bn, STAGEWISE_WORKSPACE_CAP // max(one.value, 1)))
-    nbytes = C.c_size_t(0)
-    _capi.check(lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), chunk, max_active, C.byref(nbytes)),
-                "mpcqp_plan_vjp_stagewise_workspace_bytes")
-    ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=dev)
+    keep = [cp]
+    if backward == "condensed":
+        ws = _workspace_for(lib.mpcqp_plan_vjp_workspace_bytes, dims, Bn, dev)
+        rc = lib.mpcqp_plan_vjp_batch(
+            C.byref(dims), C.byref(cp), Bn, _ptr(lam), status.data_ptr(), gU.data_ptr(), _ptr(gX),
+            *[_ptr(out[k]) for k in GRAD_KEYS[:4]], vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+        _capi.check(rc, "mpcqp_plan_vjp_batch")
+    elif backward == "model":
+        ws = _workspace_for(lib.mpcqp_plan_vjp_model_workspace_bytes, dims, Bn, dev)
+        res = _capi.VjpModelOut(*[_ptr(out[k]) for k in GRAD_KEYS[:8]], _ptr(g_w))
+        rc = lib.mpcqp_plan_vjp_model_batch(
+            C.byref(dims), C.byref(cp), Bn, _ptr(lam), status.data_ptr(), U.data_ptr(), gU.data_ptr(), _ptr(gX),
+            C.byref(res), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+        _capi.check(rc, "mpcqp_plan_vjp_model_batch")
+    else:
+        if lam is not None and Bn > 0:
+            act = ((lam > 0) & (status == 0)[:, None]).sum(dim=1)
+            max_active = min(int(act.max().item()), n)  # the host sync
+        else:
+            max_active = 0
+        query = lib.mpcqp_plan_vjp_stagewise_workspace_bytes
+        chunk = max(1, min(Bn, STAGEWISE_WORKSPACE_CAP // max(_workspace_bytes(query, dims, 1, max_active), 1)))
+        ws = _workspace_for(query, dims, chunk, dev, max_active)
 
-    def at(t, b0):
-        return None if t is None else t[b0:].data_ptr()
+        def at(t, b0):
+            return None if t is None else t[b0:].data_ptr()
 
-    keep = []
-    for b0 in range(0, Bn, chunk):
-        nb = min(chunk, Bn - b0)
-        cpb = _shifted(cp, b0)
-        res = _capi.VjpModelOut(*[at(out[k], b0) for k in ("x0", "goal", "targets", "e", "A", "B", "C", "D")],
-                                at(g_w, b0))
-        rc = lib.mpcqp_plan_vjp_stagewise_batch(
-            C.byref(dims), C.byref(cpb), nb, max_active, at(lam, b0), at(status, b0), at(U, b0), at(gU, b0), at(gX, b0),
-            C.byref(res), at(vjp_status, b0), ws.data_ptr(), ws.numel(), _stream_ptr())
-        _capi.check(rc, "mpcqp_plan_vjp_stagewise_batch")
-        keep.append(cpb)
+        for b0 in range(0, Bn, chunk):
+            nb = min(chunk, Bn - b0)
+            cpb = _shifted(cp, b0)
+            res = _capi.VjpModelOut(*[at(out[k], b0) for k in GRAD_KEYS[:8]], at(g_w, b0))
+            rc = lib.mpcqp_plan_vjp_stagewise_batch(
+                C.byref(dims), C.byref(cpb), nb, max_active, at(lam, b0), at(status, b0), at(U, b0), at(gU, b0),
+                at(gX, b0), C.byref(res), at(vjp_status, b0), ws.data_ptr(), ws.numel(), _stream_ptr())
+            _capi.check(rc, "mpcqp_plan_vjp_stagewise_batch")
+            keep.append(cpb)
     plan.vjp_status = vjp_status
     plan._vjp_keep = (ws, p64, lam, U, gU, gX, keep)  # alive until the stream has consumed them
-    if out["e"] is not None and mk == 0:
-        out["e"] = torch.zeros((Bn, N, mk), **f64)
     for i, k in enumerate(("wt", "wx", "wu")):
         out[k] = g_w[:, i] if k in want else None
     return tuple(out[k] for k in GRAD_KEYS)
+
+
+def _plan_vjp(work: BatchMPCProblem, plan, gU, gX, want, backward: str = "condensed"):
+    """``_vjp`` through the export ``backward`` names (mpcqp_plan_vjp_batch by default)."""
+    return _vjp(work, plan, gU, gX, want, backward)
+
+
+def _plan_vjp_model(work: BatchMPCProblem, plan, gU, gX, want):
+    """``_vjp`` through mpcqp_plan_vjp_model_batch."""
+    return _vjp(work, plan, gU, gX, want, "model")
+
+
+def _plan_vjp_stagewise(work: BatchMPCProblem, plan, gU, gX, want):
+    """``_vjp`` through mpcqp_plan_vjp_stagewise_batch."""
+    return _vjp(work, plan, gU, gX, want, "stagewise")
 
 
 TANGENT_NAMES = ("initial_state", "goal_state", "target_states", "ineq_vector")
@@ -355,7 +308,7 @@ def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None
     n, dev = problem.nb_variables, problem.device
     if mk > 0 and plan.multipliers is None:
         raise ProblemDefinitionError("plan_jvp needs the plan's multipliers: solve with return_multipliers=True")
-    check_envelope_jvp(problem)
+    check_envelope(problem, "jvp")
     tails = ((nx,), (nx,), (N * nx,), (N, mk))
     ops = [_tangent_operand(t, nm, Bn, tail, dev) for t, nm, tail in zip(
         (initial_state, goal_state, target_states, ineq_vector), TANGENT_NAMES, tails)]
@@ -376,10 +329,7 @@ def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None
     dX = torch.empty((Bn, T, N + 1, nx), **f64) if states else None
     jvp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
     dims, cp = _vjp_dims(p64), p64.c_problem()
-    nbytes = C.c_size_t(0)
-    _capi.check(lib.mpcqp_plan_jvp_workspace_bytes(C.byref(dims), Bn, T, C.byref(nbytes)),
-                "mpcqp_plan_jvp_workspace_bytes")
-    ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=dev)
+    ws = _workspace_for(lib.mpcqp_plan_jvp_workspace_bytes, dims, Bn, dev, T)
     tan = _capi.Tangents(*[_ptr(t) for t, _ in ops], *[st for _, st in ops])
     rc = lib.mpcqp_plan_jvp_batch(C.byref(dims), C.byref(cp), Bn, T, _ptr(lam), plan.status.data_ptr(), C.byref(tan),
                                   dU.data_ptr(), _ptr(dX), jvp_status.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -464,7 +414,7 @@ def _make_function():
             elif any(need[4:]):
                 grads = _plan_vjp_model(ctx.work, ctx.plan, gU, gX, want)
             else:
-                grads = _plan_vjp(ctx.work, ctx.plan, gU, gX, want) + (None,) * 7
+                grads = _plan_vjp(ctx.work, ctx.plan, gU, gX, want)
             out = [_reduce(g, like, canon) if nd else None
                    for nd, g, like, canon in zip(need, grads, ctx.inputs, ctx.canon)]
             return (None, None, None, None, *out)
@@ -555,11 +505,11 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
         U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
         return U, (plan.states if states else None), plan
     if adjoint == "stagewise":
-        check_envelope_stagewise(work)
+        check_envelope(work, "stagewise")
     else:
         check_envelope(work)
         if any(dual):
-            check_envelope_jvp(work)
+            check_envelope(work, "jvp")
     if _FUNCTION is None:
         _FUNCTION = _make_function()
     box = {"adjoint": adjoint}

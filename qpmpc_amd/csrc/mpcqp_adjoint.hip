@@ -22,6 +22,8 @@
 //      g_C_k = -(lam_k Y_k' + nu_k X_k'),  g_D_k = -(lam_k w_k' + nu_k u_k')     (coalesced over (k, i, j))
 //  10. g_w = (-Y_N'E_N, -sum_{k<N} Y_k'E_k, -w'U), one block reduction
 // The carve grows by X, Z, pz, s ((N + 1) nx each), nu scattered over all m rows and the reduction's 3 x threads.
+// 8 .. 10 are model_epilogue of mpcqp_adjoint_common.h, which the stage-wise adjoint shares (as the factorisations, sweeps,
+// active-row compaction and zero-fill the kernels here are built from).
 //
 // mpcqp_tangent_kernel (mpcqp_plan_jvp_batch) is the forward-mode counterpart: the same KKT system on the same active set,
 // with T tangents (dx0, dgoal, dtargets, de) as right-hand sides ("Forward sensitivities"):
@@ -34,27 +36,10 @@
 #include <hip/hip_runtime.h>
 
 #include "mpcqp.h"
-#include "mpcqp_internal.h"
+#include "mpcqp_adjoint_common.h"
 
 namespace mpcqp {
 namespace {
-
-struct AdjArgs {
-    int nx, nu, N, mk, n, m, flags;
-    double wt, wx;
-    const double *P, *G, *Phi, *Psi;  // condensed (packed per problem, mpcqp_condense_batch)
-    MpcqpOperand C;                   // ineq_state_matrix of the problem (nullable)
-    const double *lam, *gU, *gX;      // gX nullable
-    const int32_t *status;
-    double *g_x0, *g_goal, *g_targets, *g_e;  // all but g_x0 nullable
-    int32_t *vjp_status;                       // nullable
-    double *carve_ws;                          // per-problem carves when they do not fit LDS (else null)
-    int64_t carve;                             // doubles per problem
-    // kModel only
-    MpcqpOperand A, x0, goal, targets;
-    const double *U;                           // the forward plan [batch * n]
-    double *g_A, *g_B, *g_C, *g_D, *g_w;       // nullable, packed per problem
-};
 
 struct Carve {
     int ld;  // odd row stride of the n-wide matrices
@@ -88,208 +73,38 @@ __host__ __device__ inline Carve make_carve(int n, int N, int nx, int threads, i
     return c;
 }
 
-// In-place lower Cholesky of the nn x nn matrix a (stride ld; only the lower triangle is read or written).
-// Uniform result: every thread reads the same pivot after a barrier.
-template <int BS>
-__device__ bool chol_lower(double *a, int nn, int ld, int tid)
-{
-    for (int j = 0; j < nn; ++j) {
-        __syncthreads();
-        const double d = a[j * ld + j];
-        if (!(d > 0.0)) return false;
-        const double sd = sqrt(d), inv = 1.0 / sd;
-        __syncthreads();
-        if (tid == 0) a[j * ld + j] = sd;
-        for (int i = j + 1 + tid; i < nn; i += BS) a[i * ld + j] *= inv;
-        __syncthreads();
-        const int w = nn - j - 1;
-        for (int e = tid; e < w * w; e += BS) {
-            const int i = j + 1 + e / w, c = j + 1 + e % w;
-            if (c <= i) a[i * ld + c] -= a[i * ld + j] * a[c * ld + j];
-        }
-    }
-    __syncthreads();
-    return true;
-}
-
-// x <- R^-1 x, then (transposed) x <- R^-T x for one vector and the lower factor R (stride ld)
-template <int BS>
-__device__ void solve_lower(const double *R, int nn, int ld, double *x, int tid)
-{
-    for (int j = 0; j < nn; ++j) {
-        if (tid == 0) x[j] /= R[j * ld + j];
-        __syncthreads();
-        for (int i = j + 1 + tid; i < nn; i += BS) x[i] -= R[i * ld + j] * x[j];
-        __syncthreads();
-    }
-}
-template <int BS>
-__device__ void solve_lower_t(const double *R, int nn, int ld, double *x, int tid)
-{
-    for (int j = nn - 1; j >= 0; --j) {
-        if (tid == 0) x[j] /= R[j * ld + j];
-        __syncthreads();
-        for (int i = tid; i < j; i += BS) x[i] -= R[j * ld + i] * x[j];
-        __syncthreads();
-    }
-}
-
-// 7 .. 10 of the header, after phase 6 of a solved problem (uniform: every thread of the block gets here). On entry the
-// carve holds w (s), the k active entries of dL/dh (nu, rows idx), y = -Y and v = a; g_x0 is written.
-template <int BS>
-__device__ void model_phase(const AdjArgs &a, const Carve &cv, double *base, const double *Phi, const double *Psi,
-                            const double *lam, int k, int64_t b)
-{
-    const int tid = threadIdx.x;
-    const int n = a.n, m = a.m, nx = a.nx, nu = a.nu, N = a.N, mk = a.mk;
-    const int R = (N + 1) * nx;
-    const double *w = base + cv.s, *nu_a = base + cv.nu, *y = base + cv.y;
-    const int *idx = (const int *)(base + cv.idx);
-    double *p = base + cv.v, *X = base + cv.X, *Zf = base + cv.Zf, *pz = base + cv.pz, *sc = base + cv.sc;
-    double *nuf = base + cv.nuf, *wred = base + cv.wred;
-    const double *U = a.U + b * (int64_t)n;
-    const bool pt = (a.flags & MPCQP_P_TERMINAL) != 0, ps = (a.flags & MPCQP_P_STAGE) != 0;
-    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
-    const double *x0 = (const double *)a.x0.ptr + b * a.x0.batch_stride;
-    const double *goal = qt ? (const double *)a.goal.ptr + b * a.goal.batch_stride : nullptr;
-    const double *tgt = qs ? (const double *)a.targets.ptr + b * a.targets.batch_stride : nullptr;
-    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
-    const double *Ab = (const double *)a.A.ptr + b * a.A.batch_stride;
-
-    // 7. Z = Psi U, X = Phi x0 + Z; nu over every row (zero off the active set)
-    for (int r = tid; r < R; r += BS) {
-        const double *pr = Psi + (int64_t)r * n, *fr = Phi + (int64_t)r * nx;
-        double z = 0.0, f = 0.0;
-        for (int c = 0; c < n; ++c) z += pr[c] * U[c];
-        for (int c = 0; c < nx; ++c) f += fr[c] * x0[c];
-        Zf[r] = z;
-        X[r] = f + z;
-    }
-    for (int i = tid; i < m; i += BS) nuf[i] = 0.0;
-    __syncthreads();
-    for (int r = tid; r < k; r += BS) nuf[idx[r]] = nu_a[r];
-    // 8. right-hand sides of pz and s (p starts as v), with the partial sums of Y'E for g_w
-    double tw = 0.0, sw = 0.0;
-    for (int e = tid; e < R; e += BS) {
-        const int kk = e / nx, i = e % nx;
-        double az = 0.0, bb = 0.0;
-        if (kk < N) {
-            if (ps) {
-                const double E = qs ? X[e] - tgt[e] : Zf[e];
-                bb -= a.wx * E;
-                sw += y[e] * E;
-                if (!qs) az += a.wx * y[e];
-            }
-            if (Cb) {
-                const double *Ck = Cb + kk * a.C.step_stride;
-                for (int r = 0; r < mk; ++r) bb -= Ck[r * nx + i] * lam[kk * mk + r];
-            }
-        } else if (pt) {
-            const double E = qt ? X[e] - goal[i] : Zf[e];
-            bb -= a.wt * E;
-            tw += y[e] * E;
-            if (!qt) az += a.wt * y[e];
-        }
-        pz[e] = az;
-        sc[e] = bb;
-    }
-    __syncthreads();
-    // ... then x_k += A_k' x_{k+1} for k = N - 1 .. 0, the three costates side by side
-    for (int kk = N - 1; kk >= 0; --kk) {
-        const double *Ak = Ab + kk * a.A.step_stride;
-        for (int e = tid; e < 3 * nx; e += BS) {
-            const int which = e / nx, i = e % nx;
-            double *x = which == 0 ? p : (which == 1 ? pz : sc);
-            const double *xn = x + (kk + 1) * nx;
-            double acc = 0.0;
-            for (int j = 0; j < nx; ++j) acc += Ak[j * nx + i] * xn[j];
-            x[kk * nx + i] += acc;
-        }
-        __syncthreads();
-    }
-    // 9. outer products, packed per problem
-    if (a.g_A) {
-        const int64_t NA = (int64_t)N * nx * nx;
-        double *gA = a.g_A + b * NA;
-        for (int64_t e = tid; e < NA; e += BS) {
-            const int kk = (int)(e / (nx * nx)), r = (int)(e % (nx * nx)), i = r / nx, j = r % nx;
-            const int o = (kk + 1) * nx + i, c = kk * nx + j;
-            gA[e] = p[o] * X[c] + pz[o] * Zf[c] - sc[o] * y[c];
-        }
-    }
-    if (a.g_B) {
-        const int64_t NB = (int64_t)N * nx * nu;
-        double *gB = a.g_B + b * NB;
-        for (int64_t e = tid; e < NB; e += BS) {
-            const int kk = (int)(e / (nx * nu)), r = (int)(e % (nx * nu)), i = r / nu, j = r % nu;
-            const int o = (kk + 1) * nx + i, c = kk * nu + j;
-            gB[e] = (p[o] + pz[o]) * U[c] + sc[o] * w[c];
-        }
-    }
-    if (a.g_C) {
-        const int64_t NC = (int64_t)m * nx;
-        double *gC = a.g_C + b * NC;
-        for (int64_t e = tid; e < NC; e += BS) {
-            const int row = (int)(e / nx), i = (int)(e % nx), c = (row / mk) * nx + i;
-            gC[e] = lam[row] * y[c] - nuf[row] * X[c];
-        }
-    }
-    if (a.g_D) {
-        const int64_t ND = (int64_t)m * nu;
-        double *gD = a.g_D + b * ND;
-        for (int64_t e = tid; e < ND; e += BS) {
-            const int row = (int)(e / nu), j = (int)(e % nu), c = (row / mk) * nu + j;
-            gD[e] = -(lam[row] * w[c] + nuf[row] * U[c]);
-        }
-    }
-    // 10. g_w = (-Y_N'E_N, -sum Y_k'E_k, -w'U) with Y = -y: one tree reduction of the three partial sums
-    if (a.g_w) {
-        double uw = 0.0;
-        for (int c = tid; c < n; c += BS) uw += w[c] * U[c];
-        wred[tid] = tw;
-        wred[BS + tid] = sw;
-        wred[2 * BS + tid] = uw;
-        __syncthreads();
-        for (int st = BS / 2; st > 0; st >>= 1) {
-            if (tid < st)
-                for (int q = 0; q < 3; ++q) wred[q * BS + tid] += wred[q * BS + tid + st];
-            __syncthreads();
-        }
-        if (tid < 3) a.g_w[b * 3 + tid] = tid < 2 ? wred[tid * BS] : -wred[2 * BS];
-    }
-}
-
 template <int BS, bool kLds, bool kModel>
-__global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
+__global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjointLaunch a)
 {
     extern __shared__ double lds_carve[];
     __shared__ int s_k;
+    const CondensedKkt &d = a.kkt;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const int n = a.n, m = a.m, nx = a.nx, N = a.N, mk = a.mk;
+    const int n = d.n, m = d.m, nx = d.nx, N = d.N, mk = d.mk;
     const int R = (N + 1) * nx;  // rows of Phi / Psi (blocks 0 .. N)
     const Carve cv = make_carve(n, N, nx, BS, m, kModel);
     const int ld = cv.ld;
-    double *base = kLds ? lds_carve : a.carve_ws + b * a.carve;
+    double *base = kLds ? lds_carve : d.carve_ws + b * cv.total;
     double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *nu = base + cv.nu, *s = base + cv.s;
     double *y = base + cv.y, *v = base + cv.v, *red = base + cv.red;
     int *idx = (int *)(base + cv.idx);
 
-    double *gx0 = a.g_x0 + b * nx;
-    double *ggoal = a.g_goal ? a.g_goal + b * nx : nullptr;
-    double *gtgt = a.g_targets ? a.g_targets + b * (int64_t)N * nx : nullptr;
-    double *ge = a.g_e ? a.g_e + b * (int64_t)m : nullptr;
-    const double *P = a.P + b * (int64_t)n * n;
-    const double *G = a.G ? a.G + b * (int64_t)m * n : nullptr;
-    const double *Phi = a.Phi + b * (int64_t)R * nx;
-    const double *Psi = a.Psi + b * (int64_t)R * n;
-    const double *lam = a.lam + b * (int64_t)m;
+    double *gx0 = (double *)a.out.g_x0 + b * nx;
+    double *ggoal = out_at(a.out.g_goal, b * nx);
+    double *gtgt = out_at(a.out.g_targets, b * (int64_t)N * nx);
+    double *ge = out_at(a.out.g_e, b * (int64_t)m);
+    const double *P = d.P + b * (int64_t)n * n;
+    const double *G = d.G ? d.G + b * (int64_t)m * n : nullptr;
+    const double *Phi = d.Phi + b * (int64_t)R * nx;
+    const double *Psi = d.Psi + b * (int64_t)R * n;
+    const double *lam = d.lam + b * (int64_t)m;
     const double *gU = a.gU + b * (int64_t)n;
     const double *gX = a.gX ? a.gX + b * (int64_t)R : nullptr;
 
-    int verdict = a.status[b];
+    int verdict = d.status[b];
     if (verdict == 0) {
-        // 1. lower triangle of P; Z row 0 = gU + Psi' gX; 3. active rows (wave 0: ballot + prefix count, ids ascending)
+        // 1. lower triangle of P; Z row 0 = gU + Psi' gX; 3. active rows (ids ascending)
         for (int e = tid; e < n * n; e += BS) {
             const int i = e / n, j = e % n;
             if (j <= i) L[i * ld + j] = P[e];
@@ -300,20 +115,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
                 for (int r = 0; r < R; ++r) acc += Psi[(int64_t)r * n + i] * gX[r];
             Z[i] = acc;
         }
-        if (tid < 64) {
-            int count = 0;
-            for (int i0 = 0; i0 < m; i0 += 64) {
-                const int i = i0 + tid;
-                const bool act = i < m && lam[i] > 0.0;
-                const unsigned long long mask = __ballot(act);
-                const int pre = __popcll(mask & ((1ull << tid) - 1ull));
-                if (act && count + pre < n) idx[count + pre] = i;
-                count += __popcll(mask);
-            }
-            if (tid == 0) s_k = count;
-        }
-        __syncthreads();
-        const int k = s_k;
+        const int k = active_rows(lam, m, n, idx, &s_k);
         if (k > n) {
             verdict = MPCQP_NOT_PD;  // more active rows than variables: the forward's multipliers are not a vertex's
         } else {
@@ -325,28 +127,9 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
             if (!chol_lower<BS>(L, n, ld, tid)) {
                 verdict = MPCQP_NOT_PD;
             } else {
-                const int nr = k + 1;
-                for (int j = 0; j < n; ++j) {
-                    const double inv = 1.0 / L[j * ld + j];
-                    for (int r = tid; r < nr; r += BS) Z[r * ld + j] *= inv;
-                    __syncthreads();
-                    const int w = n - j - 1;
-                    for (int e = tid; e < nr * w; e += BS) {
-                        const int r = e / w, i = j + 1 + e % w;
-                        Z[r * ld + i] -= L[i * ld + j] * Z[r * ld + j];
-                    }
-                    __syncthreads();
-                }
+                sweep_lower<BS>(L, n, ld, Z, k + 1, tid);
                 // 5. Gram S = M_A M_A' (lower) and nu = M_A t
-                for (int e = tid; e < k * k; e += BS) {
-                    const int i = e / k, j = e % k;
-                    if (j <= i) {
-                        const double *zi = Z + (i + 1) * ld, *zj = Z + (j + 1) * ld;
-                        double acc = 0.0;
-                        for (int c = 0; c < n; ++c) acc += zi[c] * zj[c];
-                        S[i * ld + j] = acc;
-                    }
-                }
+                gram_lower<BS>(Z, 1, k, n, ld, S, tid);
                 for (int i = tid; i < k; i += BS) {
                     const double *zi = Z + (i + 1) * ld;
                     double acc = 0.0;
@@ -374,32 +157,27 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
                         y[r] = -acc;
                     }
                     __syncthreads();
-                    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
-                    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
+                    const bool qt = (d.flags & MPCQP_Q_TERMINAL) != 0, qs = (d.flags & MPCQP_Q_STAGE) != 0;
+                    const double *Cb = d.C.ptr ? (const double *)d.C.ptr + b * d.C.batch_stride : nullptr;
                     for (int e = tid; e < R; e += BS) {
                         const int kk = e / nx, j = e % nx;
                         double acc = gX ? gX[e] : 0.0;
-                        if (qs && kk < N) acc += a.wx * y[e];
-                        if (qt && kk == N) acc += a.wt * y[e];
+                        if (qs && kk < N) acc += d.wx * y[e];
+                        if (qt && kk == N) acc += d.wt * y[e];
                         if (Cb && kk < N) {
-                            const double *Ck = Cb + kk * a.C.step_stride;
+                            const double *Ck = Cb + kk * d.C.step_stride;
                             for (int r = 0; r < k; ++r) {
                                 const int row = idx[r];
                                 if (row / mk == kk) acc -= Ck[(row % mk) * nx + j] * nu[r];
                             }
                         }
                         v[e] = acc;
-                        if (ggoal && kk == N) ggoal[j] = qt ? -a.wt * y[e] : 0.0;
-                        if (gtgt && kk < N) gtgt[e] = qs ? -a.wx * y[e] : 0.0;
+                        if (ggoal && kk == N) ggoal[j] = qt ? -d.wt * y[e] : 0.0;
+                        if (gtgt && kk < N) gtgt[e] = qs ? -d.wx * y[e] : 0.0;
                     }
                     if (ge) {
                         for (int i = tid; i < m; i += BS) {
-                            // idx is ascending: binary search for row i among the k active ones
-                            int lo = 0, hi = k;
-                            while (lo < hi) {
-                                const int mid = (lo + hi) >> 1;
-                                if (idx[mid] < i) lo = mid + 1; else hi = mid;
-                            }
+                            const int lo = lower_bound(idx, k, i);
                             ge[i] = (lo < k && idx[lo] == i) ? nu[lo] : 0.0;
                         }
                     }
@@ -426,32 +204,32 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
                             gx0[c] = acc;
                         }
                     }
-                    if constexpr (kModel) model_phase<BS>(a, cv, base, Phi, Psi, lam, k, b);
+                    if constexpr (kModel) {
+                        // 7. Z = Psi U, X = Phi x0 + Z; then 8 .. 10 with y = -Y and p starting as v
+                        const double *U = a.U + b * (int64_t)n;
+                        const double *x0 = (const double *)a.x0.ptr + b * a.x0.batch_stride;
+                        double *X = base + cv.X, *Zf = base + cv.Zf;
+                        for (int r = tid; r < R; r += BS) {
+                            const double *pr = Psi + (int64_t)r * n, *fr = Phi + (int64_t)r * nx;
+                            double z = 0.0, f = 0.0;
+                            for (int c = 0; c < n; ++c) z += pr[c] * U[c];
+                            for (int c = 0; c < nx; ++c) f += fr[c] * x0[c];
+                            Zf[r] = z;
+                            X[r] = f + z;
+                        }
+                        const ModelVecs mv{lam, U, s, y,
+                                           qt ? (const double *)a.goal.ptr + b * a.goal.batch_stride : nullptr,
+                                           qs ? (const double *)a.targets.ptr + b * a.targets.batch_stride : nullptr,
+                                           nu, idx, k, v, X, Zf, base + cv.pz, base + cv.sc, base + cv.nuf, base + cv.wred};
+                        model_epilogue<BS, true, true>(d, a.A, d.C, a.out, b, mv);
+                    }
                 }
             }
         }
     }
     if (verdict != 0) {  // (uniform: every thread took the same branches) unsolved or degenerate: all-zero gradients
-        for (int j = tid; j < nx; j += BS) gx0[j] = 0.0;
-        if (ggoal)
-            for (int j = tid; j < nx; j += BS) ggoal[j] = 0.0;
-        if (gtgt)
-            for (int j = tid; j < N * nx; j += BS) gtgt[j] = 0.0;
-        if (ge)
-            for (int j = tid; j < m; j += BS) ge[j] = 0.0;
-        if constexpr (kModel) {
-            const int64_t NA = (int64_t)N * nx * nx, NB = (int64_t)N * nx * a.nu, NC = (int64_t)m * nx,
-                          ND = (int64_t)m * a.nu;
-            if (a.g_A)
-                for (int64_t j = tid; j < NA; j += BS) a.g_A[b * NA + j] = 0.0;
-            if (a.g_B)
-                for (int64_t j = tid; j < NB; j += BS) a.g_B[b * NB + j] = 0.0;
-            if (a.g_C)
-                for (int64_t j = tid; j < NC; j += BS) a.g_C[b * NC + j] = 0.0;
-            if (a.g_D)
-                for (int64_t j = tid; j < ND; j += BS) a.g_D[b * ND + j] = 0.0;
-            if (a.g_w && tid < 3) a.g_w[b * 3 + tid] = 0.0;
-        }
+        zero_outputs<BS>(tid, gx0, nx, ggoal, nx, gtgt, (int64_t)N * nx, ge, m);
+        if constexpr (kModel) zero_model_outputs<BS>(a.out, nx, d.nu, N, m, b, tid);
     }
     if (a.vjp_status && tid == 0) a.vjp_status[b] = verdict;
 }
@@ -460,35 +238,11 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjArgs a)
 inline int adjoint_threads(int n) { return n <= 32 ? 64 : 256; }
 
 template <int BS, bool kModel>
-int launch_bs(const AdjArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
+int launch_adjoint_bs(const AdjointLaunch &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
 {
-    if (lds) {
-        auto kern = mpcqp_adjoint_kernel<BS, true, kModel>;
-        if (lds_bytes > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(BS), lds_bytes, st, a);
-    } else {
-        hipLaunchKernelGGL((mpcqp_adjoint_kernel<BS, false, kModel>), dim3((unsigned)batch), dim3(BS), 0, st, a);
-    }
-    return (int)hipGetLastError();
+    if (lds) return launch_per_problem(mpcqp_adjoint_kernel<BS, true, kModel>, a, BS, lds_bytes, batch, st);
+    return launch_per_problem(mpcqp_adjoint_kernel<BS, false, kModel>, a, BS, 0, batch, st);
 }
-
-struct TanArgs {
-    int nx, nu, N, mk, n, m, flags, T;
-    double wt, wx;
-    const double *P, *G, *Phi, *Psi;  // condensed (packed per problem, mpcqp_condense_batch)
-    MpcqpOperand C;                   // ineq_state_matrix of the problem (nullable)
-    const double *lam;                // nullable when m = 0
-    const int32_t *status;
-    const double *dx0, *dgoal, *dtgt, *de;  // nullable (a zero tangent); tangent t of a problem at t nx / t nx / t N nx / t m
-    int64_t sx0, sgoal, stgt, se;           // elements between problems (0: shared)
-    double *dU, *dX;                        // [batch][T][n], [batch][T][(N + 1) nx] (dX nullable)
-    int32_t *jvp_status;                    // nullable
-    double *carve_ws;                       // per-problem carves when they do not fit LDS (else null)
-    int64_t carve;                          // doubles per problem
-};
 
 struct TanCarve {
     int ld;
@@ -510,55 +264,44 @@ __host__ __device__ inline TanCarve make_tan_carve(int n, int T, int R)
 }
 
 template <int BS, bool kLds>
-__global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
+__global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a)
 {
     extern __shared__ double lds_carve[];
     __shared__ int s_k;
+    const CondensedKkt &d = a.kkt;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const int n = a.n, m = a.m, nx = a.nx, N = a.N, mk = a.mk, T = a.T;
+    const int n = d.n, m = d.m, nx = d.nx, N = d.N, mk = d.mk, T = a.ntan;
     const int R = (N + 1) * nx;
     const TanCarve cv = make_tan_carve(n, T, R);
     const int ld = cv.ld;
-    double *base = kLds ? lds_carve : a.carve_ws + b * a.carve;
+    double *base = kLds ? lds_carve : d.carve_ws + b * cv.total;
     double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *mu = base + cv.mu, *xs = base + cv.x;
     int *idx = (int *)(base + cv.idx);
 
-    const double *P = a.P + b * (int64_t)n * n;
-    const double *G = a.G ? a.G + b * (int64_t)m * n : nullptr;
-    const double *Phi = a.Phi + b * (int64_t)R * nx;
-    const double *Psi = a.Psi + b * (int64_t)R * n;
-    const double *lam = a.lam ? a.lam + b * (int64_t)m : nullptr;
-    const double *dx0 = a.dx0 ? a.dx0 + b * a.sx0 : nullptr;
-    const double *dgoal = a.dgoal ? a.dgoal + b * a.sgoal : nullptr;
-    const double *dtgt = a.dtgt ? a.dtgt + b * a.stgt : nullptr;
-    const double *de = a.de ? a.de + b * a.se : nullptr;
+    const double *P = d.P + b * (int64_t)n * n;
+    const double *G = d.G ? d.G + b * (int64_t)m * n : nullptr;
+    const double *Phi = d.Phi + b * (int64_t)R * nx;
+    const double *Psi = d.Psi + b * (int64_t)R * n;
+    const double *lam = d.lam ? d.lam + b * (int64_t)m : nullptr;
+    // tangent t of a problem at t nx / t nx / t N nx / t m; a null one is zero, a zero stride shares it
+    const double *dx0 = a.tan.dx0 ? (const double *)a.tan.dx0 + b * a.tan.dx0_stride : nullptr;
+    const double *dgoal = a.tan.dgoal ? (const double *)a.tan.dgoal + b * a.tan.dgoal_stride : nullptr;
+    const double *dtgt = a.tan.dtargets ? (const double *)a.tan.dtargets + b * a.tan.dtargets_stride : nullptr;
+    const double *de = a.tan.de ? (const double *)a.tan.de + b * a.tan.de_stride : nullptr;
     double *dU = a.dU + b * (int64_t)T * n;
     double *dX = a.dX ? a.dX + b * (int64_t)T * R : nullptr;
-    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
-    const double *Cb = a.C.ptr ? (const double *)a.C.ptr + b * a.C.batch_stride : nullptr;
+    const bool qt = (d.flags & MPCQP_Q_TERMINAL) != 0, qs = (d.flags & MPCQP_Q_STAGE) != 0;
+    const double *Cb = d.C.ptr ? (const double *)d.C.ptr + b * d.C.batch_stride : nullptr;
 
-    int verdict = a.status[b];
+    int verdict = d.status[b];
     if (verdict == 0) {
-        // lower triangle of P; active rows (wave 0: ballot + prefix count, ids ascending), as mpcqp_adjoint_kernel
+        // lower triangle of P; active rows (ids ascending), as mpcqp_adjoint_kernel
         for (int e = tid; e < n * n; e += BS) {
             const int i = e / n, j = e % n;
             if (j <= i) L[i * ld + j] = P[e];
         }
-        if (tid < 64) {
-            int count = 0;
-            for (int i0 = 0; i0 < m; i0 += 64) {
-                const int i = i0 + tid;
-                const bool act = i < m && lam[i] > 0.0;
-                const unsigned long long mask = __ballot(act);
-                const int pre = __popcll(mask & ((1ull << tid) - 1ull));
-                if (act && count + pre < n) idx[count + pre] = i;
-                count += __popcll(mask);
-            }
-            if (tid == 0) s_k = count;
-        }
-        __syncthreads();
-        const int k = s_k;
+        const int k = active_rows(lam, m, n, idx, &s_k);
         if (k > n) {
             verdict = MPCQP_NOT_PD;
         } else {
@@ -582,7 +325,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
                     double s = 0.0;
                     for (int r = 0; r < N * nx; ++r)
                         s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (tg ? tg[r] : 0.0));
-                    acc += a.wx * s;
+                    acc += d.wx * s;
                 }
                 if (qt && (xt || dgoal)) {
                     const double *gl = dgoal ? dgoal + (int64_t)t * nx : nullptr;
@@ -591,7 +334,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
                         const int r = N * nx + i;
                         s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (gl ? gl[i] : 0.0));
                     }
-                    acc += a.wt * s;
+                    acc += d.wt * s;
                 }
                 Z[t * ld + c] = -acc;
             }
@@ -603,7 +346,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
                 const int t = e / k, r = e % k, row = idx[r], kk = row / mk;
                 double h = de ? de[(int64_t)t * m + row] : 0.0;
                 if (Cb && dx0) {
-                    const double *Ci = Cb + kk * a.C.step_stride + (row % mk) * nx, *xk = xs + (int64_t)t * R + kk * nx;
+                    const double *Ci = Cb + kk * d.C.step_stride + (row % mk) * nx, *xk = xs + (int64_t)t * R + kk * nx;
                     for (int i = 0; i < nx; ++i) h -= Ci[i] * xk[i];
                 }
                 mu[t * ld + r] = h;
@@ -612,28 +355,9 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
             if (!chol_lower<BS>(L, n, ld, tid)) {
                 verdict = MPCQP_NOT_PD;
             } else {
-                const int nr = T + k;
-                for (int j = 0; j < n; ++j) {
-                    const double inv = 1.0 / L[j * ld + j];
-                    for (int r = tid; r < nr; r += BS) Z[r * ld + j] *= inv;
-                    __syncthreads();
-                    const int w = n - j - 1;
-                    for (int e = tid; e < nr * w; e += BS) {
-                        const int r = e / w, i = j + 1 + e % w;
-                        Z[r * ld + i] -= L[i * ld + j] * Z[r * ld + j];
-                    }
-                    __syncthreads();
-                }
+                sweep_lower<BS>(L, n, ld, Z, T + k, tid);
                 // 3. Gram S = M_A M_A' (lower); mu_t = M_A r_t - dh_A,t
-                for (int e = tid; e < k * k; e += BS) {
-                    const int i = e / k, j = e % k;
-                    if (j <= i) {
-                        const double *zi = Z + (T + i) * ld, *zj = Z + (T + j) * ld;
-                        double acc = 0.0;
-                        for (int c = 0; c < n; ++c) acc += zi[c] * zj[c];
-                        S[i * ld + j] = acc;
-                    }
-                }
+                gram_lower<BS>(Z, T, k, n, ld, S, tid);
                 for (int e = tid; e < T * k; e += BS) {
                     const int t = e / k, i = e % k;
                     const double *zi = Z + (T + i) * ld, *zt = Z + t * ld;
@@ -645,27 +369,8 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
                     verdict = MPCQP_NOT_PD;
                 } else {
                     // mu_t = R^-T R^-1 (...), every tangent at once
-                    for (int j = 0; j < k; ++j) {
-                        const double inv = 1.0 / S[j * ld + j];
-                        for (int t = tid; t < T; t += BS) mu[t * ld + j] *= inv;
-                        __syncthreads();
-                        const int w = k - j - 1;
-                        for (int e = tid; e < T * w; e += BS) {
-                            const int t = e / w, i = j + 1 + e % w;
-                            mu[t * ld + i] -= S[i * ld + j] * mu[t * ld + j];
-                        }
-                        __syncthreads();
-                    }
-                    for (int j = k - 1; j >= 0; --j) {
-                        const double inv = 1.0 / S[j * ld + j];
-                        for (int t = tid; t < T; t += BS) mu[t * ld + j] *= inv;
-                        __syncthreads();
-                        for (int e = tid; e < T * j; e += BS) {
-                            const int t = e / j, i = e % j;
-                            mu[t * ld + i] -= S[j * ld + i] * mu[t * ld + j];
-                        }
-                        __syncthreads();
-                    }
+                    sweep_lower<BS>(S, k, ld, mu, T, tid);
+                    sweep_lower_t<BS>(S, k, ld, mu, T, tid);
                     // 4. r_t - M_A' mu_t in place, then dU_t = L^-T (...), every tangent at once
                     for (int e = tid; e < T * n; e += BS) {
                         const int t = e / n, c = e % n;
@@ -674,16 +379,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
                         Z[t * ld + c] = acc;
                     }
                     __syncthreads();
-                    for (int j = n - 1; j >= 0; --j) {
-                        const double inv = 1.0 / L[j * ld + j];
-                        for (int t = tid; t < T; t += BS) Z[t * ld + j] *= inv;
-                        __syncthreads();
-                        for (int e = tid; e < T * j; e += BS) {
-                            const int t = e / j, i = e % j;
-                            Z[t * ld + i] -= L[j * ld + i] * Z[t * ld + j];
-                        }
-                        __syncthreads();
-                    }
+                    sweep_lower_t<BS>(L, n, ld, Z, T, tid);
                     for (int e = tid; e < T * n; e += BS) dU[e] = Z[(e / n) * ld + e % n];
                     if (dX) {
                         for (int64_t e = tid; e < (int64_t)T * R; e += BS) {
@@ -698,28 +394,16 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TanArgs a)
             }
         }
     }
-    if (verdict != 0) {  // (uniform) unsolved or degenerate: all-zero tangents
-        for (int e = tid; e < T * n; e += BS) dU[e] = 0.0;
-        if (dX)
-            for (int64_t e = tid; e < (int64_t)T * R; e += BS) dX[e] = 0.0;
-    }
+    if (verdict != 0)  // (uniform) unsolved or degenerate: all-zero tangents
+        zero_outputs<BS>(tid, dU, (int64_t)T * n, dX, (int64_t)T * R);
     if (a.jvp_status && tid == 0) a.jvp_status[b] = verdict;
 }
 
 template <int BS>
-int launch_tangent_bs(const TanArgs &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
+int launch_tangent_bs(const TangentLaunch &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
 {
-    if (lds) {
-        auto kern = mpcqp_tangent_kernel<BS, true>;
-        if (lds_bytes > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(BS), lds_bytes, st, a);
-    } else {
-        hipLaunchKernelGGL((mpcqp_tangent_kernel<BS, false>), dim3((unsigned)batch), dim3(BS), 0, st, a);
-    }
-    return (int)hipGetLastError();
+    if (lds) return launch_per_problem(mpcqp_tangent_kernel<BS, true>, a, BS, lds_bytes, batch, st);
+    return launch_per_problem(mpcqp_tangent_kernel<BS, false>, a, BS, 0, batch, st);
 }
 
 }  // namespace
@@ -737,49 +421,14 @@ bool adjoint_carve_in_lds(int n, int N, int nx, int m, bool model)
 
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
 {
-    AdjArgs a;
-    a.nx = l.nx;
-    a.nu = l.nu;
-    a.N = l.N;
-    a.mk = l.mk;
-    a.n = l.N * l.nu;
-    a.m = l.N * l.mk;
-    a.flags = l.flags;
-    a.wt = l.wt;
-    a.wx = l.wx;
-    a.P = (const double *)l.P;
-    a.G = (const double *)l.G;
-    a.Phi = (const double *)l.Phi;
-    a.Psi = (const double *)l.Psi;
-    a.C = l.C;
-    a.lam = (const double *)l.lam;
-    a.gU = (const double *)l.gU;
-    a.gX = (const double *)l.gX;
-    a.status = l.status;
-    a.g_x0 = (double *)l.g_x0;
-    a.g_goal = (double *)l.g_goal;
-    a.g_targets = (double *)l.g_targets;
-    a.g_e = (double *)l.g_e;
-    a.vjp_status = l.vjp_status;
-    a.A = l.A;
-    a.x0 = l.x0;
-    a.goal = l.goal;
-    a.targets = l.targets;
-    a.U = (const double *)l.U;
-    a.g_A = (double *)l.g_A;
-    a.g_B = (double *)l.g_B;
-    a.g_C = (double *)l.g_C;
-    a.g_D = (double *)l.g_D;
-    a.g_w = (double *)l.g_w;
-    const bool lds = adjoint_carve_in_lds(a.n, a.N, a.nx, a.m, l.model);
-    const size_t bytes = adjoint_carve_bytes(a.n, a.N, a.nx, a.m, l.model);
-    a.carve_ws = lds ? nullptr : (double *)l.carve_ws;
-    a.carve = (int64_t)(bytes / sizeof(double));
-    if (!lds && !a.carve_ws) return MPCQP_EWORKSPACE;
-    if (l.model && (!a.U || !a.A.ptr || !a.x0.ptr)) return MPCQP_EINVAL;
-    if (adjoint_threads(a.n) == 64)
-        return l.model ? launch_bs<64, true>(a, lds, bytes, batch, st) : launch_bs<64, false>(a, lds, bytes, batch, st);
-    return l.model ? launch_bs<256, true>(a, lds, bytes, batch, st) : launch_bs<256, false>(a, lds, bytes, batch, st);
+    const CondensedKkt &d = l.kkt;
+    const bool lds = adjoint_carve_in_lds(d.n, d.N, d.nx, d.m, l.model);
+    const size_t bytes = adjoint_carve_bytes(d.n, d.N, d.nx, d.m, l.model);
+    if (!lds && !d.carve_ws) return MPCQP_EWORKSPACE;
+    if (l.model && (!l.U || !l.A.ptr || !l.x0.ptr)) return MPCQP_EINVAL;
+    if (adjoint_threads(d.n) == 64)
+        return l.model ? launch_adjoint_bs<64, true>(l, lds, bytes, batch, st) : launch_adjoint_bs<64, false>(l, lds, bytes, batch, st);
+    return l.model ? launch_adjoint_bs<256, true>(l, lds, bytes, batch, st) : launch_adjoint_bs<256, false>(l, lds, bytes, batch, st);
 }
 
 size_t tangent_carve_bytes(int n, int N, int nx, int ntan)
@@ -795,42 +444,12 @@ bool tangent_carve_in_lds(int n, int N, int nx, int ntan)
 
 int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st)
 {
-    TanArgs a;
-    a.nx = l.nx;
-    a.nu = l.nu;
-    a.N = l.N;
-    a.mk = l.mk;
-    a.n = l.N * l.nu;
-    a.m = l.N * l.mk;
-    a.flags = l.flags;
-    a.T = l.ntan;
-    a.wt = l.wt;
-    a.wx = l.wx;
-    a.P = (const double *)l.P;
-    a.G = (const double *)l.G;
-    a.Phi = (const double *)l.Phi;
-    a.Psi = (const double *)l.Psi;
-    a.C = l.C;
-    a.lam = (const double *)l.lam;
-    a.status = l.status;
-    a.dx0 = (const double *)l.tan.dx0;
-    a.dgoal = (const double *)l.tan.dgoal;
-    a.dtgt = (const double *)l.tan.dtargets;
-    a.de = a.m > 0 ? (const double *)l.tan.de : nullptr;
-    a.sx0 = l.tan.dx0_stride;
-    a.sgoal = l.tan.dgoal_stride;
-    a.stgt = l.tan.dtargets_stride;
-    a.se = l.tan.de_stride;
-    a.dU = (double *)l.dU;
-    a.dX = (double *)l.dX;
-    a.jvp_status = l.jvp_status;
-    const bool lds = tangent_carve_in_lds(a.n, a.N, a.nx, a.T);
-    const size_t bytes = tangent_carve_bytes(a.n, a.N, a.nx, a.T);
-    a.carve_ws = lds ? nullptr : (double *)l.carve_ws;
-    a.carve = (int64_t)(bytes / sizeof(double));
-    if (!lds && !a.carve_ws) return MPCQP_EWORKSPACE;
-    if (adjoint_threads(a.n) == 64) return launch_tangent_bs<64>(a, lds, bytes, batch, st);
-    return launch_tangent_bs<256>(a, lds, bytes, batch, st);
+    const CondensedKkt &d = l.kkt;
+    const bool lds = tangent_carve_in_lds(d.n, d.N, d.nx, l.ntan);
+    const size_t bytes = tangent_carve_bytes(d.n, d.N, d.nx, l.ntan);
+    if (!lds && !d.carve_ws) return MPCQP_EWORKSPACE;
+    if (adjoint_threads(d.n) == 64) return launch_tangent_bs<64>(l, lds, bytes, batch, st);
+    return launch_tangent_bs<256>(l, lds, bytes, batch, st);
 }
 
 }  // namespace mpcqp

@@ -1,0 +1,307 @@
+// Device code shared by the adjoint kernels: mpcqp_adjoint.hip (the condensed adjoint and the tangent kernel) and
+// mpcqp_adjoint_stagewise.hip. One problem per workgroup of BS threads; every helper is called by the whole workgroup with
+// uniform arguments.
+#ifndef MPCQP_ADJOINT_COMMON_H_
+#define MPCQP_ADJOINT_COMMON_H_
+
+#include <hip/hip_runtime.h>
+
+#include "mpcqp.h"
+#include "mpcqp_internal.h"
+
+namespace mpcqp {
+
+__device__ inline const double *op_step(const MpcqpOperand &o, int64_t b, int k)
+{
+    return o.ptr ? (const double *)o.ptr + b * o.batch_stride + (int64_t)k * o.step_stride : nullptr;
+}
+
+// problem b's part of a nullable output packed per problem
+__device__ inline double *out_at(void *p, int64_t off) { return p ? (double *)p + off : nullptr; }
+
+// In-place lower Cholesky of the nn x nn matrix a (stride ld; only the lower triangle is read or written).
+// Uniform result: every thread reads the same pivot after a barrier.
+template <int BS>
+__device__ inline bool chol_lower(double *a, int nn, int ld, int tid)
+{
+    for (int j = 0; j < nn; ++j) {
+        __syncthreads();
+        const double d = a[j * ld + j];
+        if (!(d > 0.0)) return false;
+        const double sd = sqrt(d), inv = 1.0 / sd;
+        __syncthreads();
+        if (tid == 0) a[j * ld + j] = sd;
+        for (int i = j + 1 + tid; i < nn; i += BS) a[i * ld + j] *= inv;
+        __syncthreads();
+        const int w = nn - j - 1;
+        for (int e = tid; e < w * w; e += BS) {
+            const int i = j + 1 + e / w, c = j + 1 + e % w;
+            if (c <= i) a[i * ld + c] -= a[i * ld + j] * a[c * ld + j];
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// x <- R^-1 x, then (transposed) x <- R^-T x for one vector and the lower factor R (stride ld)
+template <int BS>
+__device__ inline void solve_lower(const double *R, int nn, int ld, double *x, int tid)
+{
+    for (int j = 0; j < nn; ++j) {
+        if (tid == 0) x[j] /= R[j * ld + j];
+        __syncthreads();
+        for (int i = j + 1 + tid; i < nn; i += BS) x[i] -= R[i * ld + j] * x[j];
+        __syncthreads();
+    }
+}
+template <int BS>
+__device__ inline void solve_lower_t(const double *R, int nn, int ld, double *x, int tid)
+{
+    for (int j = nn - 1; j >= 0; --j) {
+        if (tid == 0) x[j] /= R[j * ld + j];
+        __syncthreads();
+        for (int i = tid; i < j; i += BS) x[i] -= R[j * ld + i] * x[j];
+        __syncthreads();
+    }
+}
+
+// The same solves for nr right-hand sides stored as rows (rows[r * ld + j], the stride of L), column by column:
+// rows <- rows L^-T (each row x <- L^-1 x), and the transposed sweep rows <- rows L^-1 (each row x <- L^-T x)
+template <int BS>
+__device__ inline void sweep_lower(const double *L, int nn, int ld, double *rows, int nr, int tid)
+{
+    for (int j = 0; j < nn; ++j) {
+        const double inv = 1.0 / L[j * ld + j];
+        for (int r = tid; r < nr; r += BS) rows[r * ld + j] *= inv;
+        __syncthreads();
+        const int w = nn - j - 1;
+        for (int e = tid; e < nr * w; e += BS) {
+            const int r = e / w, i = j + 1 + e % w;
+            rows[r * ld + i] -= L[i * ld + j] * rows[r * ld + j];
+        }
+        __syncthreads();
+    }
+}
+template <int BS>
+__device__ inline void sweep_lower_t(const double *L, int nn, int ld, double *rows, int nr, int tid)
+{
+    for (int j = nn - 1; j >= 0; --j) {
+        const double inv = 1.0 / L[j * ld + j];
+        for (int r = tid; r < nr; r += BS) rows[r * ld + j] *= inv;
+        __syncthreads();
+        for (int e = tid; e < nr * j; e += BS) {
+            const int r = e / j, i = e % j;
+            rows[r * ld + i] -= L[j * ld + i] * rows[r * ld + j];
+        }
+        __syncthreads();
+    }
+}
+
+// Lower triangle of S = M M' (stride ld) for the k rows of M, rows r0 .. r0 + k - 1 of Z (n wide, stride ld)
+template <int BS>
+__device__ inline void gram_lower(const double *Z, int r0, int k, int n, int ld, double *S, int tid)
+{
+    for (int e = tid; e < k * k; e += BS) {
+        const int i = e / k, j = e % k;
+        if (j <= i) {
+            const double *zi = Z + (r0 + i) * ld, *zj = Z + (r0 + j) * ld;
+            double acc = 0.0;
+            for (int c = 0; c < n; ++c) acc += zi[c] * zj[c];
+            S[i * ld + j] = acc;
+        }
+    }
+}
+
+// The active rows {i < m : lam_i > 0}, ascending, compacted by wave 0 with a ballot and a prefix count per 64 rows; the
+// first `cap` ids go to idx. Returns their count (which may exceed cap), the same in every thread.
+__device__ inline int active_rows(const double *lam, int m, int cap, int *idx, int *s_k)
+{
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        int count = 0;
+        for (int i0 = 0; i0 < m; i0 += 64) {
+            const int i = i0 + tid;
+            const bool act = i < m && lam[i] > 0.0;
+            const unsigned long long mask = __ballot(act);
+            const int pre = __popcll(mask & ((1ull << tid) - 1ull));
+            if (act && count + pre < cap) idx[count + pre] = i;
+            count += __popcll(mask);
+        }
+        if (tid == 0) *s_k = count;
+    }
+    __syncthreads();
+    return *s_k;
+}
+
+// first position of the ascending ids idx[0 .. k) that is >= key
+__device__ inline int lower_bound(const int *idx, int k, int key)
+{
+    int lo = 0, hi = k;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (idx[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// zeros into the non-null outputs (pointer, length) of a problem that is not solved
+template <int BS>
+__device__ inline void zero_outputs(int tid, double *p, int64_t len)
+{
+    if (p)
+        for (int64_t j = tid; j < len; j += BS) p[j] = 0.0;
+}
+template <int BS, typename... More>
+__device__ inline void zero_outputs(int tid, double *p, int64_t len, More... more)
+{
+    zero_outputs<BS>(tid, p, len);
+    zero_outputs<BS>(tid, more...);
+}
+// ... the model outputs g_A .. g_w of problem b
+template <int BS>
+__device__ inline void zero_model_outputs(const MpcqpVjpModelOut &o, int nx, int nu, int N, int m, int64_t b, int tid)
+{
+    const int64_t NA = (int64_t)N * nx * nx, NB = (int64_t)N * nx * nu, NC = (int64_t)m * nx, ND = (int64_t)m * nu;
+    zero_outputs<BS>(tid, out_at(o.g_A, b * NA), NA, out_at(o.g_B, b * NB), NB, out_at(o.g_C, b * NC), NC,
+                     out_at(o.g_D, b * ND), ND, out_at(o.g_w, b * 3), 3);
+}
+
+// acc - Y x: acc + y x where y holds -Y, acc - y x where it holds Y (the expression each kernel evaluated before)
+template <bool kNegY>
+__device__ inline double sub_y(double acc, double y, double x) { return kNegY ? acc + y * x : acc - y * x; }
+
+// The vectors of model_epilogue, in the calling kernel's carve (problem b's)
+struct ModelVecs {
+    const double *lam, *U, *w, *y, *goal, *tgt;  // y: -Y (kNegY) or Y; goal / tgt: null where the q term is off
+    const double *nua;                            // dL/dh on the k active rows idx (ascending)
+    const int *idx;
+    int k;
+    double *p, *X, *Zf, *pz, *sc, *nuf, *wred;  // p: a = v (kWithP: recursed here), wred: 3 BS
+};
+
+// The model and cost gradients once X = rollout(x0, U), Zf = rollout(0, U), w, Y and the costate p's right-hand side (or
+// p itself) are in place ("Model and cost gradients"): dL/dh over every row, the right-hand sides of
+// pz and s with the partial sums of Y'E, the recursions x_k += A_k' x_{k+1} (of p too when kWithP), the outer products
+// g_A .. g_D and g_w = (-Y_N'E_N, -sum_{k<N} Y_k'E_k, -w'U) by one tree reduction. kNegY: y holds -Y (the condensed
+// adjoint) rather than Y (the stage-wise one). D: the kernel's dimensions (nx, nu, N, mk, n, m, flags, wt, wx).
+template <int BS, bool kNegY, bool kWithP, class D>
+__device__ void model_epilogue(const D &d, const MpcqpOperand &A, const MpcqpOperand &C, const MpcqpVjpModelOut &o,
+                               int64_t b, const ModelVecs &v)
+{
+    const int tid = threadIdx.x;
+    const int n = d.n, m = d.m, nx = d.nx, nu = d.nu, N = d.N, mk = d.mk;
+    const int R = (N + 1) * nx;
+    const bool pt = (d.flags & MPCQP_P_TERMINAL) != 0, ps = (d.flags & MPCQP_P_STAGE) != 0;
+    const bool qt = (d.flags & MPCQP_Q_TERMINAL) != 0, qs = (d.flags & MPCQP_Q_STAGE) != 0;
+    const double *lam = v.lam, *U = v.U, *w = v.w, *y = v.y, *X = v.X, *Zf = v.Zf;
+    double *p = v.p, *pz = v.pz, *sc = v.sc, *nuf = v.nuf, *wred = v.wred;
+    const double *Ab = (const double *)A.ptr + b * A.batch_stride;
+    const double *Cb = C.ptr ? (const double *)C.ptr + b * C.batch_stride : nullptr;
+
+    for (int i = tid; i < m; i += BS) nuf[i] = 0.0;
+    __syncthreads();
+    for (int r = tid; r < v.k; r += BS) nuf[v.idx[r]] = v.nua[r];
+    double tw = 0.0, sw = 0.0;
+    for (int e = tid; e < R; e += BS) {
+        const int kk = e / nx, i = e % nx;
+        double az = 0.0, bb = 0.0;
+        if (kk < N) {
+            if (ps) {
+                const double E = qs ? X[e] - v.tgt[e] : Zf[e];
+                bb -= d.wx * E;
+                sw = sub_y<kNegY>(sw, y[e], E);
+                if (!qs) az = sub_y<kNegY>(az, d.wx, y[e]);
+            }
+            if (Cb) {
+                const double *Ck = Cb + kk * C.step_stride;
+                for (int r = 0; r < mk; ++r) bb -= Ck[r * nx + i] * lam[kk * mk + r];
+            }
+        } else if (pt) {
+            const double E = qt ? X[e] - v.goal[i] : Zf[e];
+            bb -= d.wt * E;
+            tw = sub_y<kNegY>(tw, y[e], E);
+            if (!qt) az = sub_y<kNegY>(az, d.wt, y[e]);
+        }
+        pz[e] = az;
+        sc[e] = bb;
+    }
+    __syncthreads();
+    // x_k += A_k' x_{k+1} for k = N - 1 .. 0, the costates side by side
+    constexpr int first = kWithP ? 0 : 1;
+    for (int kk = N - 1; kk >= 0; --kk) {
+        const double *Ak = Ab + kk * A.step_stride;
+        for (int e = tid; e < (3 - first) * nx; e += BS) {
+            const int which = e / nx + first, i = e % nx;
+            double *x = which == 0 ? p : (which == 1 ? pz : sc);
+            const double *xn = x + (kk + 1) * nx;
+            double acc = 0.0;
+            for (int j = 0; j < nx; ++j) acc += Ak[j * nx + i] * xn[j];
+            x[kk * nx + i] += acc;
+        }
+        __syncthreads();
+    }
+    // outer products, packed per problem
+    if (o.g_A) {
+        const int64_t NA = (int64_t)N * nx * nx;
+        double *gA = (double *)o.g_A + b * NA;
+        for (int64_t e = tid; e < NA; e += BS) {
+            const int kk = (int)(e / (nx * nx)), r = (int)(e % (nx * nx)), i = r / nx, j = r % nx;
+            const int oo = (kk + 1) * nx + i, c = kk * nx + j;
+            gA[e] = sub_y<!kNegY>(p[oo] * X[c] + pz[oo] * Zf[c], sc[oo], y[c]);
+        }
+    }
+    if (o.g_B) {
+        const int64_t NB = (int64_t)N * nx * nu;
+        double *gB = (double *)o.g_B + b * NB;
+        for (int64_t e = tid; e < NB; e += BS) {
+            const int kk = (int)(e / (nx * nu)), r = (int)(e % (nx * nu)), i = r / nu, j = r % nu;
+            const int oo = (kk + 1) * nx + i, c = kk * nu + j;
+            gB[e] = (p[oo] + pz[oo]) * U[c] + sc[oo] * w[c];
+        }
+    }
+    if (o.g_C) {
+        const int64_t NC = (int64_t)m * nx;
+        double *gC = (double *)o.g_C + b * NC;
+        for (int64_t e = tid; e < NC; e += BS) {
+            const int row = (int)(e / nx), i = (int)(e % nx), c = (row / mk) * nx + i;
+            gC[e] = kNegY ? lam[row] * y[c] - nuf[row] * X[c] : -(lam[row] * y[c] + nuf[row] * X[c]);
+        }
+    }
+    if (o.g_D) {
+        const int64_t ND = (int64_t)m * nu;
+        double *gD = (double *)o.g_D + b * ND;
+        for (int64_t e = tid; e < ND; e += BS) {
+            const int row = (int)(e / nu), j = (int)(e % nu), c = (row / mk) * nu + j;
+            gD[e] = -(lam[row] * w[c] + nuf[row] * U[c]);
+        }
+    }
+    if (o.g_w) {
+        double uw = 0.0;
+        for (int c = tid; c < n; c += BS) uw += w[c] * U[c];
+        wred[tid] = tw;
+        wred[BS + tid] = sw;
+        wred[2 * BS + tid] = uw;
+        __syncthreads();
+        for (int st = BS / 2; st > 0; st >>= 1) {
+            if (tid < st)
+                for (int q = 0; q < 3; ++q) wred[q * BS + tid] += wred[q * BS + tid + st];
+            __syncthreads();
+        }
+        if (tid < 3) ((double *)o.g_w)[b * 3 + tid] = tid < 2 ? wred[tid * BS] : -wred[2 * BS];
+    }
+}
+
+// One workgroup of bs threads per problem, lds_bytes of dynamic LDS (the kernel's limit raised past 48 KiB)
+template <class Args>
+int launch_per_problem(void (*kern)(Args), const Args &a, int bs, size_t lds_bytes, int64_t batch, hipStream_t st)
+{
+    if (lds_bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(bs), lds_bytes, st, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mpcqp
+#endif

@@ -17,14 +17,15 @@
 //   5. a = L^-T (t - Y_A' b): one forward sweep from x0 = 0, u_k = -K x + Li' s_k, x <- Acl x + Bw s_k, giving w = a and
 //      Y = Psi a; then v_k = gX_k - w_x Y_k [k < N] - w_t Y_N [k = N] - C_k' b_k (terms gated by MPCQP_Q_STAGE / _TERMINAL),
 //      g_goal = w_t Y_N, g_targets_k = w_x Y_k, g_e = b on the active rows, g_x0 = p_0 of p_k = v_k + A_k' p_{k+1}
-//   6. (any of g_A .. g_w requested) X = rollout(x0, U), Z = rollout(0, U), the costates pz and s of mpcqp_adjoint.hip's
-//      model phase, the outer products and the g_w reduction, as there (Y from phase 5 in place of Psi w)
+//   6. (any of g_A .. g_w requested) X = rollout(x0, U), Z = rollout(0, U), then model_epilogue of
+//      mpcqp_adjoint_common.h as in mpcqp_adjoint.hip: the costates pz and s, the outer products and the g_w reduction
+//      (Y from phase 5 in place of -Psi w)
 // The per-problem region of the workspace (doubles): the N records, the max_active whitened rows of n, S when it does not
 // fit LDS, then t, s, w, Y, v, b, the row ids and, for phase 6, X, Z, pz, s, b over every row and the g_w partial sums.
 #include <hip/hip_runtime.h>
 
 #include "mpcqp.h"
-#include "mpcqp_internal.h"
+#include "mpcqp_adjoint_common.h"
 
 namespace mpcqp {
 namespace {
@@ -34,19 +35,6 @@ constexpr int kMaxNx = 32, kMaxNu = 8;
 constexpr int kSmDoubles = 3 * kMaxNx * kMaxNx + 3 * kMaxNx * kMaxNu + 2 * kMaxNu * kMaxNu;  // Riccati scratch
 constexpr int kSLdsMax = 63;  // max_active whose S (stride max_active | 1) stays in LDS: 63 * 63 * 8 = 31 KB
 
-struct SwArgs {
-    int nx, nu, N, mk, n, m, flags, ka;
-    double wt, wx, wu;
-    MpcqpOperand A, B, C, D, x0, goal, targets;
-    const double *lam, *gU, *gX, *U;
-    const int32_t *status;
-    double *g_x0, *g_goal, *g_targets, *g_e, *g_A, *g_B, *g_C, *g_D, *g_w;
-    int32_t *vjp_status;
-    double *ws;
-    int64_t per;  // doubles per problem
-    bool model;
-};
-
 struct SwCarve {
     int rs, ldS;                                    // doubles per record; stride of S
     int64_t rec, Y, S, t, s, w, Ys, v, bv, idx;     // idx: int32 row ids
@@ -55,7 +43,8 @@ struct SwCarve {
 
 __host__ __device__ inline bool s_in_lds(int ka) { return ka <= kSLdsMax; }
 
-__host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int ka, bool model)
+// (phase 6 included: one size whichever outputs a launch asks for)
+__host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int ka)
 {
     SwCarve c;
     const int64_t n = (int64_t)N * nu, R = (int64_t)(N + 1) * nx, m = (int64_t)N * mk;
@@ -71,14 +60,13 @@ __host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int
     c.v = c.Ys + R;
     c.bv = c.v + R;
     c.idx = c.bv + ka + 1;
-    c.total = c.idx + (ka + 2) / 2;
-    c.X = c.total;
+    c.X = c.idx + (ka + 2) / 2;
     c.Zf = c.X + R;
     c.pz = c.Zf + R;
     c.sc = c.pz + R;
     c.nuf = c.sc + R;
     c.wred = c.nuf + m;
-    if (model) c.total = c.wred + 3 * BS;
+    c.total = c.wred + 3 * BS;
     return c;
 }
 
@@ -92,66 +80,8 @@ __device__ inline Rec rec_at(const double *rec, int k, int rs, int nx, int nu)
     return Rec{r, r + nx * nx, r + nx * nx + nu * nx, r + nx * nx + 2 * nu * nx, r + nx * nx + 3 * nu * nx};
 }
 
-__device__ inline const double *op_step(const MpcqpOperand &o, int64_t b, int k)
-{
-    return o.ptr ? (const double *)o.ptr + b * o.batch_stride + (int64_t)k * o.step_stride : nullptr;
-}
-
-// In-place lower Cholesky of the nn x nn matrix a (stride ld), as in mpcqp_adjoint.hip. Uniform result.
-__device__ bool chol_lower(double *a, int nn, int ld, int tid)
-{
-    for (int j = 0; j < nn; ++j) {
-        __syncthreads();
-        const double d = a[j * ld + j];
-        if (!(d > 0.0)) return false;
-        const double sd = sqrt(d), inv = 1.0 / sd;
-        __syncthreads();
-        if (tid == 0) a[j * ld + j] = sd;
-        for (int i = j + 1 + tid; i < nn; i += BS) a[i * ld + j] *= inv;
-        __syncthreads();
-        const int w = nn - j - 1;
-        for (int e = tid; e < w * w; e += BS) {
-            const int i = j + 1 + e / w, c = j + 1 + e % w;
-            if (c <= i) a[i * ld + c] -= a[i * ld + j] * a[c * ld + j];
-        }
-    }
-    __syncthreads();
-    return true;
-}
-
-__device__ void solve_lower(const double *R, int nn, int ld, double *x, int tid)
-{
-    for (int j = 0; j < nn; ++j) {
-        if (tid == 0) x[j] /= R[j * ld + j];
-        __syncthreads();
-        for (int i = j + 1 + tid; i < nn; i += BS) x[i] -= R[i * ld + j] * x[j];
-        __syncthreads();
-    }
-}
-
-__device__ void solve_lower_t(const double *R, int nn, int ld, double *x, int tid)
-{
-    for (int j = nn - 1; j >= 0; --j) {
-        if (tid == 0) x[j] /= R[j * ld + j];
-        __syncthreads();
-        for (int i = tid; i < j; i += BS) x[i] -= R[j * ld + i] * x[j];
-        __syncthreads();
-    }
-}
-
-// first position of the ascending ids idx[0 .. k) that is >= key
-__device__ inline int lower_bound(const int *idx, int k, int key)
-{
-    int lo = 0, hi = k;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (idx[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // 1. Riccati recursion into the records; false (uniform) where a stage Hessian is not positive definite
-__device__ bool riccati(const SwArgs &a, int64_t b, double *rec, int rs, double *sm, int *s_flag)
+__device__ bool riccati(const StagewiseAdjointLaunch &a, int64_t b, double *rec, int rs, double *sm, int *s_flag)
 {
     const int tid = threadIdx.x, nx = a.nx, nu = a.nu;
     double *P = sm, *PA = P + kMaxNx * kMaxNx, *Ac = PA + kMaxNx * kMaxNx, *PB = Ac + kMaxNx * kMaxNx;
@@ -161,7 +91,7 @@ __device__ bool riccati(const SwArgs &a, int64_t b, double *rec, int rs, double 
     if (tid == 0) *s_flag = 0;
     __syncthreads();
     for (int k = a.N - 1; k >= 0; --k) {
-        const double *Ak = op_step(a.A, b, k), *Bk = op_step(a.B, b, k);
+        const double *Ak = op_step(a.problem.A, b, k), *Bk = op_step(a.problem.B, b, k);
         double *r = rec + (int64_t)k * rs;
         double *rAcl = r, *rK = r + nx * nx, *rFn = rK + nu * nx, *rBw = rFn + nu * nx, *rLi = rBw + nx * nu;
         for (int e = tid; e < nx * nx; e += BS) {  // PA = P A_k
@@ -267,7 +197,7 @@ __device__ bool riccati(const SwArgs &a, int64_t b, double *rec, int rs, double 
 }
 
 template <bool kSLds>
-__global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArgs a)
+__global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const StagewiseAdjointLaunch a)
 {
     extern __shared__ double s_dyn[];
     __shared__ double sm[kSmDoubles];
@@ -276,8 +206,8 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
     const int64_t b = blockIdx.x;
     const int nx = a.nx, nu = a.nu, N = a.N, mk = a.mk, n = a.n, m = a.m;
     const int R = (N + 1) * nx;
-    const SwCarve cv = make_carve(nx, nu, N, mk, a.ka, a.model);
-    double *base = a.ws + b * a.per;
+    const SwCarve cv = make_carve(nx, nu, N, mk, a.ka);
+    double *base = a.workspace + b * cv.total;
     double *rec = base + cv.rec, *Y = base + cv.Y, *S = kSLds ? s_dyn : base + cv.S;
     double *t = base + cv.t, *s = base + cv.s, *w = base + cv.w, *Ys = base + cv.Ys, *v = base + cv.v;
     double *bv = base + cv.bv;
@@ -292,21 +222,8 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
     int k = 0;
     if (verdict == 0 && !riccati(a, b, rec, cv.rs, sm, &s_int[1])) verdict = MPCQP_NOT_PD;
     if (verdict == 0) {
-        // 3a. active rows, ascending (wave 0: ballot + prefix count); only the first max_active ids are kept
-        if (tid < 64) {
-            int count = 0;
-            for (int i0 = 0; i0 < m; i0 += 64) {
-                const int i = i0 + tid;
-                const bool act = i < m && lam[i] > 0.0;
-                const unsigned long long mask = __ballot(act);
-                const int pre = __popcll(mask & ((1ull << tid) - 1ull));
-                if (act && count + pre < a.ka) idx[count + pre] = i;
-                count += __popcll(mask);
-            }
-            if (tid == 0) s_int[0] = count;
-        }
-        __syncthreads();
-        k = s_int[0];
+        // 3a. active rows, ascending; only the first max_active ids are kept
+        k = active_rows(lam, m, a.ka, idx, &s_int[0]);
         if (k > n) verdict = MPCQP_NOT_PD;  // more active rows than variables: not a vertex's multipliers
         else if (k > a.ka) verdict = MPCQP_SLOTS_FULL;
     }
@@ -350,7 +267,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
                 if (on && kk <= ja) {
                     const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
                     if (kk == ja) {
-                        const double *Cr = op_step(a.C, b, kk), *Dr = op_step(a.D, b, kk);
+                        const double *Cr = op_step(a.problem.C, b, kk), *Dr = op_step(a.problem.D, b, kk);
                         if (Cr) Cr += rr * nx;
                         if (Dr) Dr += rr * nu;
                         if (i < nu) {
@@ -401,11 +318,11 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
             }
         }
         __syncthreads();
-        if (!chol_lower(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
+        if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
     }
     if (verdict == 0) {
-        solve_lower(S, k, cv.ldS, bv, tid);
-        solve_lower_t(S, k, cv.ldS, bv, tid);
+        solve_lower<BS>(S, k, cv.ldS, bv, tid);
+        solve_lower_t<BS>(S, k, cv.ldS, bv, tid);
         // 5. s = t - Y_A' b (row a reaches column c when its step is >= c's), then a = L^-T s from x0 = 0
         for (int c = tid; c < n; c += BS) {
             double acc = t[c];
@@ -439,16 +356,16 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
             __syncthreads();
         }
         // v, g_goal, g_targets, g_e
-        double *ggoal = a.g_goal ? a.g_goal + b * nx : nullptr;
-        double *gtgt = a.g_targets ? a.g_targets + b * (int64_t)N * nx : nullptr;
-        double *ge = a.g_e ? a.g_e + b * (int64_t)m : nullptr;
+        double *ggoal = out_at(a.out.g_goal, b * nx);
+        double *gtgt = out_at(a.out.g_targets, b * (int64_t)N * nx);
+        double *ge = out_at(a.out.g_e, b * (int64_t)m);
         for (int e = tid; e < R; e += BS) {
             const int kk = e / nx, j = e % nx;
             double acc = gX ? gX[e] : 0.0;
             if (qs && kk < N) acc -= a.wx * Ys[e];
             if (qt && kk == N) acc -= a.wt * Ys[e];
-            if (kk < N && a.C.ptr) {
-                const double *Ck = op_step(a.C, b, kk);
+            if (kk < N && a.problem.C.ptr) {
+                const double *Ck = op_step(a.problem.C, b, kk);
                 for (int ra = lower_bound(idx, k, kk * mk); ra < k && idx[ra] < (kk + 1) * mk; ++ra)
                     acc -= Ck[(idx[ra] - kk * mk) * nx + j] * bv[ra];
             }
@@ -464,7 +381,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
         __syncthreads();
         // g_x0 = p_0: p_N = v_N, p_k = v_k + A_k' p_{k+1} (in place on v)
         for (int kk = N - 1; kk >= 0; --kk) {
-            const double *Ak = op_step(a.A, b, kk);
+            const double *Ak = op_step(a.problem.A, b, kk);
             if (tid < nx) {
                 double acc = 0.0;
                 for (int j = 0; j < nx; ++j) acc += Ak[j * nx + tid] * v[(kk + 1) * nx + j];
@@ -472,25 +389,19 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
             }
             __syncthreads();
         }
-        if (a.g_x0 && tid < nx) a.g_x0[b * nx + tid] = v[tid];
+        if (a.out.g_x0 && tid < nx) ((double *)a.out.g_x0)[b * nx + tid] = v[tid];
         if (a.model) {
-            // 6. X = rollout(x0, U), Z = rollout(0, U)
-            double *X = base + cv.X, *Zf = base + cv.Zf, *pz = base + cv.pz, *sc = base + cv.sc;
-            double *nuf = base + cv.nuf, *wred = base + cv.wred;
+            // 6. X = rollout(x0, U), Z = rollout(0, U), then the model epilogue with Y (p is v, recursed above)
+            double *X = base + cv.X, *Zf = base + cv.Zf;
             const double *U = a.U + b * (int64_t)n;
-            const bool pt = (a.flags & MPCQP_P_TERMINAL) != 0, ps = (a.flags & MPCQP_P_STAGE) != 0;
-            const double *x0 = (const double *)a.x0.ptr + b * a.x0.batch_stride;
-            const double *goal = qt ? (const double *)a.goal.ptr + b * a.goal.batch_stride : nullptr;
-            const double *tgt = qs ? (const double *)a.targets.ptr + b * a.targets.batch_stride : nullptr;
+            const double *x0 = (const double *)a.problem.x0.ptr + b * a.problem.x0.batch_stride;
             if (tid < nx) {
                 X[tid] = x0[tid];
                 Zf[tid] = 0.0;
             }
-            for (int i = tid; i < m; i += BS) nuf[i] = 0.0;
             __syncthreads();
-            for (int ra = tid; ra < k; ra += BS) nuf[idx[ra]] = bv[ra];
             for (int kk = 0; kk < N; ++kk) {
-                const double *Ak = op_step(a.A, b, kk), *Bk = op_step(a.B, b, kk);
+                const double *Ak = op_step(a.problem.A, b, kk), *Bk = op_step(a.problem.B, b, kk);
                 if (tid < 2 * nx) {
                     double *x = tid < nx ? X : Zf;
                     const int i = tid % nx;
@@ -501,113 +412,17 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const SwArg
                 }
                 __syncthreads();
             }
-            // right-hand sides of pz and s, with the partial sums of Y'E for g_w (g_w = (-Y_N'E_N, -sum Y_k'E_k, -w'U))
-            double tw = 0.0, sw = 0.0;
-            for (int e = tid; e < R; e += BS) {
-                const int kk = e / nx, i = e % nx;
-                double az = 0.0, bb = 0.0;
-                if (kk < N) {
-                    if (ps) {
-                        const double E = qs ? X[e] - tgt[e] : Zf[e];
-                        bb -= a.wx * E;
-                        sw -= Ys[e] * E;
-                        if (!qs) az -= a.wx * Ys[e];
-                    }
-                    if (a.C.ptr) {
-                        const double *Ck = op_step(a.C, b, kk);
-                        for (int r = 0; r < mk; ++r) bb -= Ck[r * nx + i] * lam[kk * mk + r];
-                    }
-                } else if (pt) {
-                    const double E = qt ? X[e] - goal[i] : Zf[e];
-                    bb -= a.wt * E;
-                    tw -= Ys[e] * E;
-                    if (!qt) az -= a.wt * Ys[e];
-                }
-                pz[e] = az;
-                sc[e] = bb;
-            }
-            __syncthreads();
-            for (int kk = N - 1; kk >= 0; --kk) {
-                const double *Ak = op_step(a.A, b, kk);
-                if (tid < 2 * nx) {
-                    double *x = tid < nx ? pz : sc;
-                    const int i = tid % nx;
-                    double acc = 0.0;
-                    for (int j = 0; j < nx; ++j) acc += Ak[j * nx + i] * x[(kk + 1) * nx + j];
-                    x[kk * nx + i] += acc;
-                }
-                __syncthreads();
-            }
-            const double *p = v;
-            if (a.g_A) {
-                const int64_t NA = (int64_t)N * nx * nx;
-                double *gA = a.g_A + b * NA;
-                for (int64_t e = tid; e < NA; e += BS) {
-                    const int kk = (int)(e / (nx * nx)), r = (int)(e % (nx * nx)), i = r / nx, j = r % nx;
-                    const int o = (kk + 1) * nx + i, c = kk * nx + j;
-                    gA[e] = p[o] * X[c] + pz[o] * Zf[c] + sc[o] * Ys[c];
-                }
-            }
-            if (a.g_B) {
-                const int64_t NB = (int64_t)N * nx * nu;
-                double *gB = a.g_B + b * NB;
-                for (int64_t e = tid; e < NB; e += BS) {
-                    const int kk = (int)(e / (nx * nu)), r = (int)(e % (nx * nu)), i = r / nu, j = r % nu;
-                    const int o = (kk + 1) * nx + i, c = kk * nu + j;
-                    gB[e] = (p[o] + pz[o]) * U[c] + sc[o] * w[c];
-                }
-            }
-            if (a.g_C) {
-                const int64_t NC = (int64_t)m * nx;
-                double *gC = a.g_C + b * NC;
-                for (int64_t e = tid; e < NC; e += BS) {
-                    const int row = (int)(e / nx), i = (int)(e % nx), c = (row / mk) * nx + i;
-                    gC[e] = -(lam[row] * Ys[c] + nuf[row] * X[c]);
-                }
-            }
-            if (a.g_D) {
-                const int64_t ND = (int64_t)m * nu;
-                double *gD = a.g_D + b * ND;
-                for (int64_t e = tid; e < ND; e += BS) {
-                    const int row = (int)(e / nu), j = (int)(e % nu), c = (row / mk) * nu + j;
-                    gD[e] = -(lam[row] * w[c] + nuf[row] * U[c]);
-                }
-            }
-            if (a.g_w) {
-                double uw = 0.0;
-                for (int c = tid; c < n; c += BS) uw += w[c] * U[c];
-                wred[tid] = tw;
-                wred[BS + tid] = sw;
-                wred[2 * BS + tid] = uw;
-                __syncthreads();
-                for (int st = BS / 2; st > 0; st >>= 1) {
-                    if (tid < st)
-                        for (int q = 0; q < 3; ++q) wred[q * BS + tid] += wred[q * BS + tid + st];
-                    __syncthreads();
-                }
-                if (tid < 3) a.g_w[b * 3 + tid] = tid < 2 ? wred[tid * BS] : -wred[2 * BS];
-            }
+            const ModelVecs mv{lam, U, w, Ys,
+                               qt ? (const double *)a.problem.goal.ptr + b * a.problem.goal.batch_stride : nullptr,
+                               qs ? (const double *)a.problem.targets.ptr + b * a.problem.targets.batch_stride : nullptr,
+                               bv, idx, k, v, X, Zf, base + cv.pz, base + cv.sc, base + cv.nuf, base + cv.wred};
+            model_epilogue<BS, false, false>(a, a.problem.A, a.problem.C, a.out, b, mv);
         }
     }
     if (verdict != 0) {  // (uniform) unsolved, not positive definite or slots full: all-zero gradients
-        if (a.g_x0)
-            for (int j = tid; j < nx; j += BS) a.g_x0[b * nx + j] = 0.0;
-        if (a.g_goal)
-            for (int j = tid; j < nx; j += BS) a.g_goal[b * nx + j] = 0.0;
-        if (a.g_targets)
-            for (int j = tid; j < N * nx; j += BS) a.g_targets[b * (int64_t)N * nx + j] = 0.0;
-        if (a.g_e)
-            for (int j = tid; j < m; j += BS) a.g_e[b * (int64_t)m + j] = 0.0;
-        const int64_t NA = (int64_t)N * nx * nx, NB = (int64_t)N * nx * nu, NC = (int64_t)m * nx, ND = (int64_t)m * nu;
-        if (a.g_A)
-            for (int64_t j = tid; j < NA; j += BS) a.g_A[b * NA + j] = 0.0;
-        if (a.g_B)
-            for (int64_t j = tid; j < NB; j += BS) a.g_B[b * NB + j] = 0.0;
-        if (a.g_C)
-            for (int64_t j = tid; j < NC; j += BS) a.g_C[b * NC + j] = 0.0;
-        if (a.g_D)
-            for (int64_t j = tid; j < ND; j += BS) a.g_D[b * ND + j] = 0.0;
-        if (a.g_w && tid < 3) a.g_w[b * 3 + tid] = 0.0;
+        zero_outputs<BS>(tid, out_at(a.out.g_x0, b * nx), nx, out_at(a.out.g_goal, b * nx), nx,
+                         out_at(a.out.g_targets, b * (int64_t)N * nx), (int64_t)N * nx, out_at(a.out.g_e, b * (int64_t)m), m);
+        zero_model_outputs<BS>(a.out, nx, nu, N, m, b, tid);
     }
     if (a.vjp_status && tid == 0) a.vjp_status[b] = verdict;
 }
@@ -619,58 +434,16 @@ bool stagewise_adjoint_applies(int nx, int nu) { return nx <= kMaxNx && nu <= kM
 // per problem, phase 6 included (one size whichever outputs a launch asks for)
 size_t stagewise_adjoint_bytes(int nx, int nu, int N, int mk, int max_active)
 {
-    const int ka = max_active > 0 ? max_active : 1;
-    return (size_t)make_carve(nx, nu, N, mk, ka, true).total * sizeof(double);
+    return (size_t)make_carve(nx, nu, N, mk, max_active > 0 ? max_active : 1).total * sizeof(double);
 }
 
 int launch_adjoint_stagewise(const StagewiseAdjointLaunch &l, int64_t batch, hipStream_t st)
 {
-    SwArgs a;
-    a.nx = l.nx;
-    a.nu = l.nu;
-    a.N = l.N;
-    a.mk = l.mk;
-    a.n = l.N * l.nu;
-    a.m = l.N * l.mk;
-    a.flags = l.flags;
-    a.ka = l.max_active > 0 ? l.max_active : 1;
-    a.wt = l.wt;
-    a.wx = l.wx;
-    a.wu = l.wu;
-    a.A = l.problem.A;
-    a.B = l.problem.B;
-    a.C = l.problem.C;
-    a.D = l.problem.D;
-    a.x0 = l.problem.x0;
-    a.goal = l.problem.goal;
-    a.targets = l.problem.targets;
-    a.lam = (const double *)l.lam;
-    a.gU = (const double *)l.gU;
-    a.gX = (const double *)l.gX;
-    a.U = (const double *)l.U;
-    a.status = l.status;
-    a.g_x0 = (double *)l.out.g_x0;
-    a.g_goal = (double *)l.out.g_goal;
-    a.g_targets = (double *)l.out.g_targets;
-    a.g_e = (double *)l.out.g_e;
-    a.g_A = (double *)l.out.g_A;
-    a.g_B = (double *)l.out.g_B;
-    a.g_C = (double *)l.out.g_C;
-    a.g_D = (double *)l.out.g_D;
-    a.g_w = (double *)l.out.g_w;
-    a.model = a.g_A || a.g_B || a.g_C || a.g_D || a.g_w;
-    a.vjp_status = l.vjp_status;
-    a.ws = (double *)l.workspace;
-    a.per = make_carve(a.nx, a.nu, a.N, a.mk, a.ka, true).total;
-    if (!a.ws) return MPCQP_EWORKSPACE;
-    if (a.model && !a.U) return MPCQP_EINVAL;
-    if (s_in_lds(a.ka)) {
-        const size_t lds = (size_t)a.ka * (a.ka | 1) * sizeof(double);
-        hipLaunchKernelGGL(mpcqp_adjoint_stagewise_kernel<true>, dim3((unsigned)batch), dim3(BS), lds, st, a);
-    } else {
-        hipLaunchKernelGGL(mpcqp_adjoint_stagewise_kernel<false>, dim3((unsigned)batch), dim3(BS), 0, st, a);
-    }
-    return (int)hipGetLastError();
+    if (!l.workspace) return MPCQP_EWORKSPACE;
+    if (l.model && !l.U) return MPCQP_EINVAL;
+    if (s_in_lds(l.ka))
+        return launch_per_problem(mpcqp_adjoint_stagewise_kernel<true>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
+    return launch_per_problem(mpcqp_adjoint_stagewise_kernel<false>, l, BS, 0, batch, st);
 }
 
 }  // namespace mpcqp

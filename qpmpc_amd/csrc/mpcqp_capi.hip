@@ -1049,8 +1049,43 @@ static int vjp_plan(const MpcqpDims *dims, int64_t batch, VjpPlan &v, bool model
     return 0;
 }
 
-// Both exports: checks in the order of mpcqp_plan_vjp_batch, the condensing, then one adjoint launch. `l` carries the
-// outputs (and, for the model export, model = true and its operands); the rest is filled here.
+// The condensed exports (mpcqp_plan_vjp_batch, its model twin, mpcqp_plan_jvp_batch) once their plan `v` is made: the
+// problem's checks, the export's own (args_ok), nothing more for an empty batch, else the workspace's size,
+// mpcqp_condense_batch into its segments and the KKT inputs that point at them
+static int condense_kkt(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const void *lam,
+                        const int32_t *status, bool args_ok, const VjpPlan &v, void *workspace, size_t workspace_bytes,
+                        void *stream, CondensedKkt &k)
+{
+    int rc = check_problem(dims, problem);
+    if (rc) return rc;
+    if (!args_ok || !status || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
+    char *w = (char *)workspace;
+    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
+                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
+    if (rc) return rc;
+    k.nx = dims->nx;
+    k.nu = dims->nu;
+    k.N = dims->N;
+    k.mk = dims->mk;
+    k.n = dims->N * dims->nu;
+    k.m = dims->N * dims->mk;
+    k.flags = dims->flags;
+    k.wt = dims->w_terminal;
+    k.wx = dims->w_stage;
+    k.P = (const double *)(w + v.P);
+    k.G = dims->mk > 0 ? (const double *)(w + v.G) : nullptr;
+    k.Phi = (const double *)(w + v.Phi);
+    k.Psi = (const double *)(w + v.Psi);
+    k.C = problem->C;
+    k.lam = dims->mk > 0 ? (const double *)lam : nullptr;
+    k.status = status;
+    k.carve_ws = v.gx0 > v.carve ? (double *)(w + v.carve) : nullptr;
+    return 0;
+}
+
+// Both VJP exports: `l` carries the outputs (and, for the model export, model = true and U); the rest is filled here
 static int plan_vjp(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const void *lam,
                     const int32_t *status, const void *gU, const void *gX, AdjointLaunch &l, void *workspace,
                     size_t workspace_bytes, void *stream)
@@ -1058,41 +1093,18 @@ static int plan_vjp(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t 
     VjpPlan v;
     int rc = vjp_plan(dims, batch, v, l.model);
     if (rc) return rc;
-    if ((rc = check_problem(dims, problem))) return rc;
-    if (!status || !gU || (!l.model && !l.g_x0) || (l.model && !l.U) || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
-    if (batch == 0) return 0;
-    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
-    char *w = (char *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    // the existing condensing, Phi and Psi kept
-    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
-                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
-    if (rc) return rc;
-    l.nx = dims->nx;
-    l.nu = dims->nu;
-    l.N = dims->N;
-    l.mk = dims->mk;
-    l.flags = dims->flags;
-    l.wt = dims->w_terminal;
-    l.wx = dims->w_stage;
-    l.P = w + v.P;
-    l.G = dims->mk > 0 ? w + v.G : nullptr;
-    l.Phi = w + v.Phi;
-    l.Psi = w + v.Psi;
-    l.C = problem->C;
-    l.lam = lam;
-    l.gU = gU;
-    l.gX = gX;
-    l.status = status;
-    if (!l.g_x0) l.g_x0 = w + v.gx0;
-    l.carve_ws = (v.gx0 > v.carve) ? w + v.carve : nullptr;
-    if (l.model) {
-        l.A = problem->A;
-        l.x0 = problem->x0;
-        l.goal = problem->goal;
-        l.targets = problem->targets;
-    }
-    return launch_adjoint(l, batch, st);
+    const bool ok = gU && (l.model ? l.U != nullptr : l.out.g_x0 != nullptr);
+    if ((rc = condense_kkt(dims, problem, batch, lam, status, ok, v, workspace, workspace_bytes, stream, l.kkt)) ||
+        batch == 0)
+        return rc;
+    l.gU = (const double *)gU;
+    l.gX = (const double *)gX;
+    if (!l.out.g_x0) l.out.g_x0 = (char *)workspace + v.gx0;
+    l.A = problem->A;
+    l.x0 = problem->x0;
+    l.goal = problem->goal;
+    l.targets = problem->targets;
+    return launch_adjoint(l, batch, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -1110,11 +1122,8 @@ int mpcqp_plan_vjp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
                          const int32_t *status, const void *gU, const void *gX, void *g_x0, void *g_goal, void *g_targets,
                          void *g_e, int32_t *vjp_status, void *workspace, size_t workspace_bytes, void *stream)
 {
-    AdjointLaunch l;
-    l.g_x0 = g_x0;
-    l.g_goal = g_goal;
-    l.g_targets = g_targets;
-    l.g_e = g_e;
+    AdjointLaunch l{};
+    l.out = MpcqpVjpModelOut{g_x0, g_goal, g_targets, g_e};
     l.vjp_status = vjp_status;
     return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
 }
@@ -1135,19 +1144,11 @@ int mpcqp_plan_vjp_model_batch(const MpcqpDims *dims, const MpcqpProblem *proble
                                size_t workspace_bytes, void *stream)
 {
     if (!out) return MPCQP_EINVAL;
-    AdjointLaunch l;
-    l.g_x0 = out->g_x0;
-    l.g_goal = out->g_goal;
-    l.g_targets = out->g_targets;
-    l.g_e = out->g_e;
+    AdjointLaunch l{};
+    l.out = *out;
     l.vjp_status = vjp_status;
     l.model = true;
-    l.U = U;
-    l.g_A = out->g_A;
-    l.g_B = out->g_B;
-    l.g_C = out->g_C;
-    l.g_D = out->g_D;
-    l.g_w = out->g_w;
+    l.U = (const double *)U;
     return plan_vjp(dims, problem, batch, lam, status, gU, gX, l, workspace, workspace_bytes, stream);
 }
 
@@ -1163,7 +1164,8 @@ static int jvp_plan(const MpcqpDims *dims, int64_t batch, int32_t ntan, VjpPlan 
     if (ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
     const int n = dims->N * dims->nu;
     const bool lds = tangent_carve_in_lds(n, dims->N, dims->nx, ntan);
-    v.total = v.carve + (lds ? 0 : al256((int64_t)tangent_carve_bytes(n, dims->N, dims->nx, ntan) * batch));
+    v.gx0 = v.carve + (lds ? 0 : al256((int64_t)tangent_carve_bytes(n, dims->N, dims->nx, ntan) * batch));
+    v.total = v.gx0;  // (no g_x0 segment)
     return 0;
 }
 }  // namespace
@@ -1185,37 +1187,17 @@ int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
     VjpPlan v;
     int rc = jvp_plan(dims, batch, ntan, v);
     if (rc) return rc;
-    if ((rc = check_problem(dims, problem))) return rc;
-    if (!tan || !status || !dU || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
-    if (tan->dx0_stride < 0 || tan->dgoal_stride < 0 || tan->dtargets_stride < 0 || tan->de_stride < 0)
-        return MPCQP_EINVAL;
-    if (batch == 0) return 0;
-    if (!workspace || workspace_bytes < (size_t)v.total) return MPCQP_EWORKSPACE;
-    char *w = (char *)workspace;
-    rc = mpcqp_condense_batch(dims, problem, batch, w + v.P, w + v.q, w + v.G, w + v.h, w + v.Phi, w + v.Psi,
-                              v.cws_bytes ? w + v.cws : nullptr, v.cws_bytes, stream);
-    if (rc) return rc;
-    TangentLaunch l;
-    l.nx = dims->nx;
-    l.nu = dims->nu;
-    l.N = dims->N;
-    l.mk = dims->mk;
-    l.flags = dims->flags;
+    const bool ok = tan && dU && tan->dx0_stride >= 0 && tan->dgoal_stride >= 0 && tan->dtargets_stride >= 0 &&
+                    tan->de_stride >= 0;
+    TangentLaunch l{};
+    if ((rc = condense_kkt(dims, problem, batch, lam, status, ok, v, workspace, workspace_bytes, stream, l.kkt)) ||
+        batch == 0)
+        return rc;
     l.ntan = ntan;
-    l.wt = dims->w_terminal;
-    l.wx = dims->w_stage;
-    l.P = w + v.P;
-    l.G = dims->mk > 0 ? w + v.G : nullptr;
-    l.Phi = w + v.Phi;
-    l.Psi = w + v.Psi;
-    l.C = problem->C;
-    l.lam = dims->mk > 0 ? lam : nullptr;
-    l.status = status;
     l.tan = *tan;
-    l.dU = dU;
-    l.dX = dX;
+    l.dU = (double *)dU;
+    l.dX = (double *)dX;
     l.jvp_status = jvp_status;
-    l.carve_ws = (v.total > v.carve) ? w + v.carve : nullptr;
     return launch_tangent(l, batch, (hipStream_t)stream);
 }
 
@@ -1257,25 +1239,28 @@ int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
     if (model && !U) return MPCQP_EINVAL;
     if (batch == 0) return 0;
     if (!workspace || workspace_bytes < total) return MPCQP_EWORKSPACE;
-    StagewiseAdjointLaunch l;
+    StagewiseAdjointLaunch l{};
     l.nx = dims->nx;
     l.nu = dims->nu;
     l.N = dims->N;
     l.mk = dims->mk;
+    l.n = dims->N * dims->nu;
+    l.m = dims->N * dims->mk;
     l.flags = dims->flags;
-    l.max_active = max_active;
+    l.ka = max_active > 0 ? max_active : 1;
     l.wt = dims->w_terminal;
     l.wx = dims->w_stage;
     l.wu = dims->w_input;
     l.problem = *problem;
-    l.lam = lam;
-    l.gU = gU;
-    l.gX = gX;
-    l.U = U;
+    l.lam = (const double *)lam;
+    l.gU = (const double *)gU;
+    l.gX = (const double *)gX;
+    l.U = (const double *)U;
     l.status = status;
     l.out = *out;
+    l.model = model;
     l.vjp_status = vjp_status;
-    l.workspace = workspace;
+    l.workspace = (double *)workspace;
     return launch_adjoint_stagewise(l, batch, (hipStream_t)stream);
 }
 

@@ -272,55 +272,56 @@ int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStre
 int launch_phi(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);
 int launch_update(const KernelArgs &ka, int dtype, int64_t phi_bs, int64_t psi_bs, int64_t batch, hipStream_t st);
 int launch_rollout(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);
-// vector-Jacobian product of solved plans (mpcqp_adjoint.hip; float64): one problem per workgroup on the condensed matrices
-struct AdjointLaunch {
-    int nx, nu, N, mk, flags;
+// The condensed KKT inputs of the adjoint and tangent kernels (mpcqp_adjoint.hip; float64), passed to them as they are
+struct CondensedKkt {
+    int nx, nu, N, mk, n, m, flags;  // n = N nu, m = N mk
     double wt, wx;
-    const void *P, *G, *Phi, *Psi;  // mpcqp_condense_batch's outputs, packed per problem
+    const double *P, *G, *Phi, *Psi;  // mpcqp_condense_batch's outputs, packed per problem (G null when m = 0)
     MpcqpOperand C;
-    const void *lam, *gU, *gX;
+    const double *lam;                // null when m = 0
     const int32_t *status;
-    void *g_x0, *g_goal, *g_targets, *g_e;
-    int32_t *vjp_status;
-    void *carve_ws;  // batch * adjoint_carve_bytes when the carve does not fit LDS
+    double *carve_ws;                 // the per-problem carves when they do not fit LDS (else null)
+};
+// vector-Jacobian product of solved plans (mpcqp_adjoint.hip): one problem per workgroup on the condensed matrices
+struct AdjointLaunch {
+    CondensedKkt kkt;
+    const double *gU, *gX;  // gX nullable
+    int32_t *vjp_status;    // nullable
     // model and cost gradients (mpcqp_plan_vjp_model_batch): the kModel kernel, which also reads A, x0, goal, targets
-    // and the plan U, and writes the nullable g_A, g_B, g_C, g_D, g_w
-    bool model = false;
-    MpcqpOperand A{}, x0{}, goal{}, targets{};
-    const void *U = nullptr;
-    void *g_A = nullptr, *g_B = nullptr, *g_C = nullptr, *g_D = nullptr, *g_w = nullptr;
+    // and the plan U
+    bool model;
+    MpcqpOperand A, x0, goal, targets;
+    const double *U;
+    MpcqpVjpModelOut out;   // g_x0 set, the rest nullable; g_A .. g_w are written only with `model`
 };
 size_t adjoint_carve_bytes(int n, int N, int nx, int m = 0, bool model = false);
 bool adjoint_carve_in_lds(int n, int N, int nx, int m = 0, bool model = false);
 int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st);
-// Jacobian-vector product of solved plans (mpcqp_adjoint.hip, mpcqp_tangent_kernel; float64): the adjoint's KKT system with
-// ntan tangents as right-hand sides
+// Jacobian-vector product of solved plans (mpcqp_adjoint.hip, mpcqp_tangent_kernel): the adjoint's KKT system with ntan
+// tangents as right-hand sides
 struct TangentLaunch {
-    int nx, nu, N, mk, flags, ntan;
-    double wt, wx;
-    const void *P, *G, *Phi, *Psi;  // mpcqp_condense_batch's outputs, packed per problem
-    MpcqpOperand C;
-    const void *lam;
-    const int32_t *status;
+    CondensedKkt kkt;
+    int ntan;
     MpcqpTangents tan;
-    void *dU, *dX;  // dX nullable
+    double *dU, *dX;  // dX nullable
     int32_t *jvp_status;
-    void *carve_ws;  // batch * tangent_carve_bytes when the carve does not fit LDS
 };
 size_t tangent_carve_bytes(int n, int N, int nx, int ntan);
 bool tangent_carve_in_lds(int n, int N, int nx, int ntan);
 int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st);
 // the stage-wise adjoint (mpcqp_adjoint_stagewise.hip; float64, nx <= 32, nu <= 8, any N): one problem per workgroup on its
-// Riccati recursion, the records and the active rows' whitened vectors in a per-problem region of the workspace
+// Riccati recursion, the records and the active rows' whitened vectors in a per-problem region of the workspace; passed to
+// the kernel as it is
 struct StagewiseAdjointLaunch {
-    int nx, nu, N, mk, flags, max_active;
+    int nx, nu, N, mk, n, m, flags, ka;  // n = N nu, m = N mk; ka = max(max_active, 1)
     double wt, wx, wu;
     MpcqpProblem problem;
-    const void *lam, *gU, *gX, *U;  // lam nullable when mk = 0, gX nullable, U needed when a model output is requested
+    const double *lam, *gU, *gX, *U;  // lam nullable when mk = 0, gX nullable, U needed when `model`
     const int32_t *status;
-    MpcqpVjpModelOut out;          // every pointer nullable
+    MpcqpVjpModelOut out;  // every pointer nullable
+    bool model;            // one of g_A .. g_w requested
     int32_t *vjp_status;
-    void *workspace;               // batch * stagewise_adjoint_bytes
+    double *workspace;     // batch * stagewise_adjoint_bytes
 };
 bool stagewise_adjoint_applies(int nx, int nu);
 size_t stagewise_adjoint_bytes(int nx, int nu, int N, int mk, int max_active);  // per problem
