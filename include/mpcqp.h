@@ -497,6 +497,28 @@ int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
                          void *dU, void *dX, int32_t *jvp_status,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* The stage-wise tangent: mpcqp_plan_jvp_batch's products at any horizon, without condensing; an additive part of ABI 12
+ * (MPCQP_ABI_VERSION is unchanged). The same KKT system on A = {i : lam_i > 0} is solved on the Riccati recursion of each
+ * problem in whitened coordinates, as mpcqp_plan_vjp_stagewise_batch solves its adjoint ("Stage-wise
+ * forward sensitivities"): the factorisation, the active rows' whitened vectors, their Gram matrix and its Cholesky factor
+ * once per problem; then per tangent the rollout xs of dx0, one backward sweep for r = -L^-1 dq, the multipliers
+ * mu = S^-1 (Y_A r - dh_A) and one forward sweep for dU = L^-T (r - Y_A' mu), dX = xs + Psi dU, 256 / max(nx, nu) tangents
+ * side by side. Inputs, outputs, packing, strides (0 = shared by the batch) and the nullable pointers are
+ * mpcqp_plan_jvp_batch's; `max_active` (>= 0) bounds |A| per problem and sizes the workspace as for
+ * mpcqp_plan_vjp_stagewise_batch: a problem with more active rows gets zeros and jvp_status MPCQP_SLOTS_FULL. Otherwise
+ * per problem: status[b] != 0 gives zeros and jvp_status[b] = status[b] (its multipliers are not read); more active rows
+ * than variables, a stage Hessian or a Gram matrix that is not positive definite gives zeros and MPCQP_NOT_PD; else 0.
+ * Checks, before anything is launched: MPCQP_EINVAL for a negative batch or max_active; MPCQP_EDTYPE unless float64;
+ * MPCQP_EUNSUPPORTED for nx > 32 or nu > 8 (any N is served); MPCQP_EINVAL for ntan outside 1 .. 256, a NULL tan, status
+ * or dU, a negative stride, or a NULL lam when mk > 0; MPCQP_EWORKSPACE for a missing or short workspace. The workspace
+ * is batch regions of the size the query reports (it grows with max_active and, up to one pass of tangents, with ntan). */
+int mpcqp_plan_jvp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, int32_t ntan,
+                                             size_t *bytes);
+int mpcqp_plan_jvp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                                   int32_t max_active, int32_t ntan, const void *lam, const int32_t *status,
+                                   const MpcqpTangents *tan, void *dU, void *dX, int32_t *jvp_status,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of
  * sampling_period/nsub (WheeledInvertedPendulum.integrate,

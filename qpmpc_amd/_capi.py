@@ -61,6 +61,8 @@ EXPORTS = (
     "mpcqp_plan_vjp_stagewise_batch",
     "mpcqp_plan_jvp_workspace_bytes",
     "mpcqp_plan_jvp_batch",
+    "mpcqp_plan_jvp_stagewise_workspace_bytes",
+    "mpcqp_plan_jvp_stagewise_batch",
 )
 
 
@@ -210,6 +212,12 @@ def load():
     lib.mpcqp_plan_jvp_batch.restype = C.c_int
     lib.mpcqp_plan_jvp_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, vp, vp,
                                          C.POINTER(Tangents), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.mpcqp_plan_jvp_stagewise_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_jvp_stagewise_workspace_bytes.argtypes = [C.POINTER(Dims), i64, C.c_int32, C.c_int32,
+                                                             C.POINTER(C.c_size_t)]
+    lib.mpcqp_plan_jvp_stagewise_batch.restype = C.c_int
+    lib.mpcqp_plan_jvp_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, C.c_int32, vp, vp,
+                                                   C.POINTER(Tangents), vp, vp, vp, vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -29,7 +29,8 @@ STAGEWISE_MAX_NX, STAGEWISE_MAX_NU = 32, 8  # envelope of mpcqp_plan_vjp_stagewi
 # the stage-wise backward splits its batch so that one launch's workspace stays below this many bytes
 STAGEWISE_WORKSPACE_CAP = 2 << 30
 ADJOINTS = ("condensed", "stagewise")
-MAX_TANGENTS = 256  # tangents per problem of one mpcqp_plan_jvp_batch call
+FORMULATIONS = ("condensed", "stagewise")  # of the tangent solve: plan_jvp, plan_jacobian, solve_mpc_batch_diff(tangent=)
+MAX_TANGENTS = 256  # tangents per problem of one mpcqp_plan_jvp_batch / mpcqp_plan_jvp_stagewise_batch call
 
 
 def _torch():
@@ -116,7 +117,8 @@ def _vjp_dims(problem: BatchMPCProblem) -> _capi.Dims:
 def check_envelope(problem: BatchMPCProblem, kind: str = "vjp") -> None:
     """Raise ``BackendError`` unless the export of ``kind`` serves this problem's dimensions (nothing is launched):
     ``"vjp"``, ``mpcqp_plan_vjp_batch`` (n = N * nu <= 128); ``"jvp"``, ``mpcqp_plan_jvp_batch`` (the same);
-    ``"stagewise"``, ``mpcqp_plan_vjp_stagewise_batch`` (nx <= 32, nu <= 8, any horizon)."""
+    ``"stagewise"``, ``mpcqp_plan_vjp_stagewise_batch`` (nx <= 32, nu <= 8, any horizon); ``"jvp_stagewise"``,
+    ``mpcqp_plan_jvp_stagewise_batch`` (the same)."""
     lib = _capi.load()
     n, nx, nu = problem.nb_variables, problem.state_dim, problem.input_dim
     if kind == "stagewise":
@@ -124,10 +126,16 @@ def check_envelope(problem: BatchMPCProblem, kind: str = "vjp") -> None:
             raise BackendError(f"the stage-wise adjoint serves nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU}, "
                                f"not nx = {nx}, nu = {nu}")
         query, extra = lib.mpcqp_plan_vjp_stagewise_workspace_bytes, (0,)
+    elif kind == "jvp_stagewise":
+        if nx > STAGEWISE_MAX_NX or nu > STAGEWISE_MAX_NU:
+            raise BackendError(f"the stage-wise tangent solve serves nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU}, "
+                               f"not nx = {nx}, nu = {nu}")
+        query, extra = lib.mpcqp_plan_jvp_stagewise_workspace_bytes, (0, 1)
     elif kind == "jvp":
         if n > MAX_VARIABLES:
             raise BackendError(f"forward sensitivities of plans are served for n = N * nu <= {MAX_VARIABLES} variables, "
-                               f"not {n}, by the condensed tangent solve (there is no stage-wise one)")
+                               f"not {n}, by the condensed tangent solve (formulation=\"stagewise\" serves any horizon for "
+                               f"nx <= {STAGEWISE_MAX_NX}, nu <= {STAGEWISE_MAX_NU})")
         query, extra = lib.mpcqp_plan_jvp_workspace_bytes, (1,)
     else:
         if n > MAX_VARIABLES:
@@ -166,6 +174,27 @@ def _workspace_for(query, dims, Bn, device, *extra):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _max_active(lam, status, n: int) -> int:
+    """The largest number of active rows (lam > 0) of a solved problem, capped at n: one host sync."""
+    if lam is None or lam.shape[0] == 0:
+        return 0
+    act = ((lam > 0) & (status == 0)[:, None]).sum(dim=1)
+    return min(int(act.max().item()), n)
+
+
+def _stagewise_chunks(query, dims, Bn, device, *extra):
+    """``(workspace, [(b0, nb), ...])``: the batch split into launches whose workspace (``query`` with ``extra``) stays
+    below ``STAGEWISE_WORKSPACE_CAP``, and one workspace for the largest of them."""
+    chunk = max(1, min(Bn, STAGEWISE_WORKSPACE_CAP // max(_workspace_bytes(query, dims, 1, *extra), 1)))
+    ws = _workspace_for(query, dims, chunk, device, *extra)
+    return ws, [(b0, min(chunk, Bn - b0)) for b0 in range(0, Bn, chunk)]
+
+
+def _at(t, b0: int):
+    """The address of problem ``b0``'s part of a per-problem tensor (None stays None)."""
+    return None if t is None else t[b0:].data_ptr()
 
 
 GRAD_KEYS = ("x0", "goal", "targets", "e", "A", "B", "C", "D", "wt", "wx", "wu")
@@ -228,20 +257,10 @@ def _vjp(work: BatchMPCProblem, plan, gU, gX, want, backward: str):
             C.byref(res), vjp_status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
         _capi.check(rc, "mpcqp_plan_vjp_model_batch")
     else:
-        if lam is not None and Bn > 0:
-            act = ((lam > 0) & (status == 0)[:, None]).sum(dim=1)
-            max_active = min(int(act.max().item()), n)  # the host sync
-        else:
-            max_active = 0
-        query = lib.mpcqp_plan_vjp_stagewise_workspace_bytes
-        chunk = max(1, min(Bn, STAGEWISE_WORKSPACE_CAP // max(_workspace_bytes(query, dims, 1, max_active), 1)))
-        ws = _workspace_for(query, dims, chunk, dev, max_active)
-
-        def at(t, b0):
-            return None if t is None else t[b0:].data_ptr()
-
-        for b0 in range(0, Bn, chunk):
-            nb = min(chunk, Bn - b0)
+        max_active = _max_active(lam, status, n)  # the host sync
+        ws, chunks = _stagewise_chunks(lib.mpcqp_plan_vjp_stagewise_workspace_bytes, dims, Bn, dev, max_active)
+        at = _at
+        for b0, nb in chunks:
             cpb = _shifted(cp, b0)
             res = _capi.VjpModelOut(*[at(out[k], b0) for k in GRAD_KEYS[:8]], at(g_w, b0))
             rc = lib.mpcqp_plan_vjp_stagewise_batch(
@@ -288,8 +307,14 @@ def _tangent_operand(t, name, Bn, tail, device):
     return t, (0 if t.shape[0] == 1 else t[0].numel())
 
 
+def _formulation(value, name: str = "formulation") -> str:
+    if value not in FORMULATIONS:
+        raise ValueError(f"{name}: expected one of {FORMULATIONS}, got {value!r}")
+    return value
+
+
 def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None, target_states=None,
-             ineq_vector=None, states: bool = False):
+             ineq_vector=None, states: bool = False, *, formulation: str = "condensed"):
     """Jacobian-vector products of a solved plan: ``(dU [B, T, N, nu], dX [B, T, N+1, nx] or None)``.
 
     ``plan`` is ``solve_mpc_batch(problem, ..., return_multipliers=True)``; the active set is ``{i : lam_i > 0}`` and, on
@@ -300,15 +325,31 @@ def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None
     ``dX`` (with ``states=True``) is the rollout's tangent ``Phi dx0 + Psi dU``. Computed in float64 (a float32
     problem's operands are converted) and returned in the problem's dtype. Problems not solved get zeros, and after the
     call ``plan.jvp_status`` holds their status (``MPCQP_NOT_PD`` where the active rows' Gram matrix is singular; else
-    0). Envelope: n = N * nu <= 128 (``BackendError`` before anything is launched)."""
+    0). Envelope: n = N * nu <= 128 (``BackendError`` before anything is launched).
+
+    ``formulation="stagewise"`` solves the same system on each problem's Riccati recursion without condensing
+    (``mpcqp_plan_jvp_stagewise_batch``: one factorisation per problem, the tangents side by side) and serves every
+    horizon and every n for nx <= 32, nu <= 8 (``BackendError`` outside). Like the stage-wise backward it sizes its
+    workspace from the largest number of active rows in the batch (one host sync) and splits the batch so that one
+    launch's workspace stays below ``STAGEWISE_WORKSPACE_CAP``; ``plan.jvp_status`` may then also hold
+    ``MPCQP_NOT_PD`` for a stage Hessian that is not positive definite. Any other value raises ``ValueError``."""
+    dU, dX = _jvp(problem, plan, initial_state, goal_state, target_states, ineq_vector, states, formulation)
+    dt = problem.dtype
+    return dU.to(dt), (None if dX is None else dX.to(dt))
+
+
+def _jvp(problem: BatchMPCProblem, plan, initial_state, goal_state, target_states, ineq_vector, states: bool,
+         formulation: str):
+    """``plan_jvp`` in float64, as the export wrote it (the caller casts to the problem's dtype)."""
     torch = _torch()
     lib = _capi.load()
+    stagewise = _formulation(formulation) == "stagewise"
     Bn, N, nx, nu, mk = (problem.batch_size, problem.nb_timesteps, problem.state_dim, problem.input_dim,
                          problem.ineq_dim)
     n, dev = problem.nb_variables, problem.device
     if mk > 0 and plan.multipliers is None:
         raise ProblemDefinitionError("plan_jvp needs the plan's multipliers: solve with return_multipliers=True")
-    check_envelope(problem, "jvp")
+    check_envelope(problem, "jvp_stagewise" if stagewise else "jvp")
     tails = ((nx,), (nx,), (N * nx,), (N, mk))
     ops = [_tangent_operand(t, nm, Bn, tail, dev) for t, nm, tail in zip(
         (initial_state, goal_state, target_states, ineq_vector), TANGENT_NAMES, tails)]
@@ -329,33 +370,50 @@ def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None
     dX = torch.empty((Bn, T, N + 1, nx), **f64) if states else None
     jvp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
     dims, cp = _vjp_dims(p64), p64.c_problem()
-    ws = _workspace_for(lib.mpcqp_plan_jvp_workspace_bytes, dims, Bn, dev, T)
-    tan = _capi.Tangents(*[_ptr(t) for t, _ in ops], *[st for _, st in ops])
-    rc = lib.mpcqp_plan_jvp_batch(C.byref(dims), C.byref(cp), Bn, T, _ptr(lam), plan.status.data_ptr(), C.byref(tan),
-                                  dU.data_ptr(), _ptr(dX), jvp_status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  _stream_ptr())
-    _capi.check(rc, "mpcqp_plan_jvp_batch")
+    keep = [cp]
+    if stagewise:
+        max_active = _max_active(lam, plan.status, n)  # the host sync
+        ws, chunks = _stagewise_chunks(lib.mpcqp_plan_jvp_stagewise_workspace_bytes, dims, Bn, dev, max_active, T)
+        for b0, nb in chunks:
+            cpb = _shifted(cp, b0)
+            # (a shared tangent, stride 0, is every launch's; the others move on with the problems)
+            tan = _capi.Tangents(*[(_at(t, b0) if st else _ptr(t)) for t, st in ops], *[st for _, st in ops])
+            rc = lib.mpcqp_plan_jvp_stagewise_batch(
+                C.byref(dims), C.byref(cpb), nb, max_active, T, _at(lam, b0), _at(plan.status, b0), C.byref(tan),
+                _at(dU, b0), _at(dX, b0), _at(jvp_status, b0), ws.data_ptr(), ws.numel(), _stream_ptr())
+            _capi.check(rc, "mpcqp_plan_jvp_stagewise_batch")
+            keep.append(cpb)
+    else:
+        ws = _workspace_for(lib.mpcqp_plan_jvp_workspace_bytes, dims, Bn, dev, T)
+        tan = _capi.Tangents(*[_ptr(t) for t, _ in ops], *[st for _, st in ops])
+        rc = lib.mpcqp_plan_jvp_batch(C.byref(dims), C.byref(cp), Bn, T, _ptr(lam), plan.status.data_ptr(),
+                                      C.byref(tan), dU.data_ptr(), _ptr(dX), jvp_status.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream_ptr())
+        _capi.check(rc, "mpcqp_plan_jvp_batch")
     plan.jvp_status = jvp_status
-    plan._jvp_keep = (ws, p64, lam, ops)  # alive until the stream has consumed them
-    dt = problem.dtype
-    return dU.to(dt), (None if dX is None else dX.to(dt))
+    plan._jvp_keep = (ws, p64, lam, ops, keep)  # alive until the stream has consumed them
+    return dU, dX
 
 
 JACOBIAN_WRT = ("initial_state", "goal_state")
 
 
-def plan_jacobian(problem: BatchMPCProblem, plan, wrt: str = "initial_state", states: bool = False):
+def plan_jacobian(problem: BatchMPCProblem, plan, wrt: str = "initial_state", states: bool = False, *,
+                  formulation: str = "condensed"):
     """Feedback Jacobian of a solved plan: ``(J_U [B, N, nu, nx], J_X [B, N+1, nx, nx] or None)`` with
     ``J_U[b, k, :, j] = dU_k / d(wrt)_j`` on the plan's active set. ``wrt`` is ``"initial_state"`` (``J_U[:, 0]`` is the
     local gain: ``u ~ plan.U[:, 0] + J_U[:, 0] @ (x - x0)`` while the active set holds) or ``"goal_state"``.
 
     This is ``plan_jvp`` with the identity as T = nx tangents shared by the batch (stride 0), returned as a permuted
-    view; its rules (multipliers, status, envelope, dtype) apply."""
+    view; its rules (multipliers, status, envelope, dtype) apply, and so does its ``formulation``: ``"stagewise"`` gives
+    the Jacobian at any horizon (nx <= 32, nu <= 8) on one factorisation per problem (DESIGN.md section 9 has the
+    measured cost beside one stage-wise backward)."""
     torch = _torch()
+    _formulation(formulation)
     if wrt not in JACOBIAN_WRT:
         raise ProblemDefinitionError(f"wrt: expected one of {JACOBIAN_WRT}, got {wrt!r}")
     eye = torch.eye(problem.state_dim, dtype=torch.float64, device=problem.device)[None]
-    dU, dX = plan_jvp(problem, plan, states=states, **{wrt: eye})
+    dU, dX = plan_jvp(problem, plan, states=states, formulation=formulation, **{wrt: eye})
     return dU.permute(0, 2, 3, 1), (None if dX is None else dX.permute(0, 2, 3, 1))
 
 
@@ -382,7 +440,7 @@ def _forward_tangents(ctx, tangents):
         args[nm] = t.unsqueeze(1)
     if not args:
         return None, None
-    dU, dX = plan_jvp(work, ctx.plan, states=ctx.states, **args)
+    dU, dX = plan_jvp(work, ctx.plan, states=ctx.states, formulation=ctx.tangent, **args)
     return dU[:, 0], (None if dX is None else dX[:, 0])
 
 
@@ -397,6 +455,7 @@ def _make_function():
             U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
             box["plan"] = plan
             ctx.work, ctx.plan, ctx.states, ctx.adjoint = work, plan, states, box["adjoint"]
+            ctx.tangent = box["tangent"]
             ctx.inputs = tuple(None if t is None else (t.shape, t.dtype, t.device) for t in operands)
             canon = (work.initial_state, work.goal_state, work.target_states, work.e, work.A, work.B, work.C, work.D)
             # a weight is one value for the batch: shape (1,) sums its per-problem gradients
@@ -444,7 +503,7 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
                          ineq_vector=None, states: bool = False, *, transition_state_matrix=None,
                          transition_input_matrix=None, ineq_state_matrix=None, ineq_input_matrix=None,
                          terminal_cost_weight=None, stage_state_cost_weight=None, stage_input_cost_weight=None,
-                         adjoint: str = "condensed", **solve_kw):
+                         adjoint: str = "condensed", tangent: str = "condensed", **solve_kw):
     """Solve a batch like ``solve_mpc_batch`` and return ``(U, X, plan)`` whose ``U`` [B, N, nu] and, with ``states=True``,
     ``X`` [B, N+1, nx] carry a ``grad_fn`` (``X`` is None otherwise).
 
@@ -478,7 +537,10 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
     Forward mode: ``initial_state``, ``goal_state``, ``target_states`` and ``ineq_vector`` may be dual tensors of
     ``torch.autograd.forward_ad``; the tangents of ``U`` (and ``X``) are then one ``plan_jvp`` call (T = 1) on the plan.
     A dual model matrix or weight, ``adjoint="stagewise"`` with a dual operand, or n > 128 raises ``BackendError``
-    before anything is launched.
+    before anything is launched. With ``tangent="stagewise"`` that call is the stage-wise one
+    (``plan_jvp(..., formulation="stagewise")``): dual operands are then served at any horizon for nx <= 32, nu <= 8,
+    whatever ``adjoint`` is (a dual model matrix or weight is still refused). Any other value of ``tangent`` raises
+    ``ValueError``.
 
     When no operand passed requires grad (or grad mode is off) and none is dual, this is ``solve_mpc_batch(problem', **solve_kw)`` on the
     problem with the replaced operands, and its plan is returned as is."""
@@ -489,14 +551,15 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
     passed = (initial_state, goal_state, target_states, ineq_vector, transition_state_matrix, transition_input_matrix,
               ineq_state_matrix, ineq_input_matrix, terminal_cost_weight, stage_state_cost_weight,
               stage_input_cost_weight)
+    _formulation(tangent, "tangent")
     dual = [_is_dual(t) for t in passed]
     if any(dual[4:]):
         names = MODEL_OPERANDS + WEIGHTS
         raise BackendError("forward-mode tangents through plans reach initial_state, goal_state, target_states and "
                            f"ineq_vector; a dual {', '.join(nm for nm, d in zip(names, dual[4:]) if d)} is not served")
-    if any(dual) and adjoint == "stagewise":
-        raise BackendError("forward-mode tangents through plans are served by the condensed tangent solve only, not "
-                           "with adjoint=\"stagewise\"")
+    if any(dual) and adjoint == "stagewise" and tangent != "stagewise":
+        raise BackendError("forward-mode tangents through plans are served by the condensed tangent solve unless "
+                           "tangent=\"stagewise\" is passed; adjoint=\"stagewise\" picks the backward only")
     work = _replaced(problem, *passed)
     need = any(dual) or (torch.is_grad_enabled()
                          and any(isinstance(t, torch.Tensor) and t.requires_grad for t in passed))
@@ -504,15 +567,17 @@ def solve_mpc_batch_diff(problem: BatchMPCProblem, initial_state=None, goal_stat
         plan = solve_mpc_batch(work, **solve_kw)
         U = plan.U.view(work.batch_size, work.nb_timesteps, work.input_dim)
         return U, (plan.states if states else None), plan
-    if adjoint == "stagewise":
-        check_envelope(work, "stagewise")
-    else:
-        check_envelope(work)
-        if any(dual):
-            check_envelope(work, "jvp")
+    stage_tan = any(dual) and tangent == "stagewise"
+    if stage_tan:
+        check_envelope(work, "jvp_stagewise")
+    # the backward's envelope; with a stage-wise tangent only where an operand asks for a backward too
+    if not stage_tan or (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in passed)):
+        check_envelope(work, "stagewise" if adjoint == "stagewise" else "vjp")
+    if any(dual) and not stage_tan:
+        check_envelope(work, "jvp")
     if _FUNCTION is None:
         _FUNCTION = _make_function()
-    box = {"adjoint": adjoint}
+    box = {"adjoint": adjoint, "tangent": tangent}
     tens = [t if isinstance(t, torch.Tensor) else None for t in passed]
     out = _FUNCTION.apply(work, bool(states), dict(solve_kw), box, *tens)
     U, X = out if states else (out, None)

@@ -22,6 +22,9 @@
 //      (Y from phase 5 in place of -Psi w)
 // The per-problem region of the workspace (doubles): the N records, the max_active whitened rows of n, S when it does not
 // fit LDS, then t, s, w, Y, v, b, the row ids and, for phase 6, X, Z, pz, s, b over every row and the g_w partial sums.
+//
+// The stage-wise tangent (mpcqp_plan_jvp_stagewise_batch, mpcqp_tangent_stagewise_kernel below) is the forward-mode
+// counterpart on the same factorisation: phases 1, 3 and 4 are device functions that both kernels call.
 #include <hip/hip_runtime.h>
 
 #include "mpcqp.h"
@@ -33,27 +36,42 @@ namespace {
 constexpr int BS = 256;
 constexpr int kMaxNx = 32, kMaxNu = 8;
 constexpr int kSmDoubles = 3 * kMaxNx * kMaxNx + 3 * kMaxNx * kMaxNu + 2 * kMaxNu * kMaxNu;  // Riccati scratch
+constexpr int kPassLds = 2 * BS;  // one buffer of a pass of tangents: BS / max(nx, nu) slots of nx + nu <= 2 max(nx, nu)
 constexpr int kSLdsMax = 63;  // max_active whose S (stride max_active | 1) stays in LDS: 63 * 63 * 8 = 31 KB
 
-struct SwCarve {
-    int rs, ldS;                                    // doubles per record; stride of S
-    int64_t rec, Y, S, t, s, w, Ys, v, bv, idx;     // idx: int32 row ids
-    int64_t X, Zf, pz, sc, nuf, wred, total;
+// the part of a problem's region that both kernels lay out alike: the N records, the max_active whitened rows of n, S when
+// it does not fit LDS; `end` is where the kernel's own vectors start
+struct SwBase {
+    int rs, ldS;  // doubles per record; stride of S
+    int64_t rec, Y, S, end;
 };
 
 __host__ __device__ inline bool s_in_lds(int ka) { return ka <= kSLdsMax; }
+
+__host__ __device__ inline SwBase make_base(int nx, int nu, int N, int ka)
+{
+    SwBase c;
+    c.rs = nx * nx + 2 * nu * nx + nx * nu + nu * nu;
+    c.ldS = ka | 1;
+    c.rec = 0;
+    c.Y = c.rec + (int64_t)N * c.rs;
+    c.S = c.Y + (int64_t)ka * N * nu;
+    c.end = c.S + (s_in_lds(ka) ? 0 : (int64_t)ka * c.ldS);
+    return c;
+}
+
+struct SwCarve : SwBase {
+    int64_t t, s, w, Ys, v, bv, idx;  // idx: int32 row ids
+    int64_t X, Zf, pz, sc, nuf, wred, total;
+};
 
 // (phase 6 included: one size whichever outputs a launch asks for)
 __host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int ka)
 {
     SwCarve c;
+    static_cast<SwBase &>(c) = make_base(nx, nu, N, ka);
     const int64_t n = (int64_t)N * nu, R = (int64_t)(N + 1) * nx, m = (int64_t)N * mk;
-    c.rs = nx * nx + 2 * nu * nx + nx * nu + nu * nu;
-    c.ldS = ka | 1;
-    c.rec = 0;
-    c.Y = c.rec + (int64_t)N * c.rs;
-    c.S = c.Y + (int64_t)ka * n;
-    c.t = c.S + (s_in_lds(ka) ? 0 : (int64_t)ka * c.ldS);
+    c.t = c.end;
     c.s = c.t + n;
     c.w = c.s + n;
     c.Ys = c.w + n;
@@ -70,6 +88,29 @@ __host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int
     return c;
 }
 
+// The stage-wise tangent kernel's region: the base, the row ids, then the scratch of ONE pass of tangents (tg = min(ntan,
+// tangent_slots): the passes reuse it): xs = rollout(dx0, 0) [tg x (N + 1) nx] and dh_A, then mu [tg x ldS]. r, s and dU
+// share the caller's dU.
+struct SwTanCarve : SwBase {
+    int tg;
+    int64_t idx, xs, mu, total;
+};
+
+__host__ __device__ inline int tangent_slots(int nx, int nu) { return BS / (nx > nu ? nx : nu); }
+
+__host__ __device__ inline SwTanCarve make_tan_carve(int nx, int nu, int N, int ka, int ntan)
+{
+    SwTanCarve c;
+    static_cast<SwBase &>(c) = make_base(nx, nu, N, ka);
+    const int slots = tangent_slots(nx, nu);
+    c.tg = ntan < slots ? ntan : slots;
+    c.idx = c.end;
+    c.xs = c.idx + (ka + 2) / 2;
+    c.mu = c.xs + (int64_t)c.tg * (N + 1) * nx;
+    c.total = c.mu + (int64_t)c.tg * c.ldS;
+    return c;
+}
+
 // record of step k: Acl [nx x nx], K [nu x nx], Fn [nu x nx], Bw [nx x nu], Li [nu x nu] (lower)
 struct Rec {
     const double *Acl, *K, *Fn, *Bw, *Li;
@@ -81,7 +122,9 @@ __device__ inline Rec rec_at(const double *rec, int k, int rs, int nx, int nu)
 }
 
 // 1. Riccati recursion into the records; false (uniform) where a stage Hessian is not positive definite
-__device__ bool riccati(const StagewiseAdjointLaunch &a, int64_t b, double *rec, int rs, double *sm, int *s_flag)
+// (D: the kernel's launch structure -- nx, nu, N, flags, wt, wx, wu, problem)
+template <class D>
+__device__ bool riccati(const D &a, int64_t b, double *rec, int rs, double *sm, int *s_flag)
 {
     const int tid = threadIdx.x, nx = a.nx, nu = a.nu;
     double *P = sm, *PA = P + kMaxNx * kMaxNx, *Ac = PA + kMaxNx * kMaxNx, *PB = Ac + kMaxNx * kMaxNx;
@@ -196,13 +239,100 @@ __device__ bool riccati(const StagewiseAdjointLaunch &a, int64_t b, double *rec,
     return true;
 }
 
+// 3b. The whitened active rows Y [k x n] (ids idx, ascending): BS / max(nx, nu) backward sweeps side by side, lanes over
+// state components, each from its own step down to 0; one barrier per step for the whole group. pb: 2 x BS doubles of LDS.
+__device__ void whiten_rows(const MpcqpProblem &problem, int64_t b, const double *rec, int rs, int nx, int nu, int mk, int n,
+                            const int *idx, int k, double *Y, double *pb)
+{
+    const int tid = threadIdx.x, Wd = nx > nu ? nx : nu;
+    const int slots = BS / Wd, sl = tid / Wd, i = tid % Wd;
+    for (int r0 = 0; r0 < k; r0 += slots) {
+        const int ra = r0 + sl;
+        const bool on = sl < slots && ra < k;
+        const int row = on ? idx[ra] : 0, ja = row / (mk > 0 ? mk : 1), rr = row - ja * mk;
+        const int last = (r0 + slots < k ? r0 + slots : k) - 1;
+        const int jmax = idx[last] / mk;
+        double *yrow = Y + (int64_t)ra * n;
+        for (int kk = jmax; kk >= 0; --kk) {
+            const double *cur = pb + ((jmax - kk) & 1) * BS + sl * Wd;
+            double *nxt = pb + ((jmax - kk + 1) & 1) * BS + sl * Wd;
+            if (on && kk <= ja) {
+                const Rec rk = rec_at(rec, kk, rs, nx, nu);
+                if (kk == ja) {
+                    const double *Cr = op_step(problem.C, b, kk), *Dr = op_step(problem.D, b, kk);
+                    if (Cr) Cr += rr * nx;
+                    if (Dr) Dr += rr * nu;
+                    if (i < nu) {
+                        double acc = 0.0;
+                        if (Dr)
+                            for (int l = 0; l <= i; ++l) acc += rk.Li[i * nu + l] * Dr[l];
+                        yrow[kk * nu + i] = acc;
+                    }
+                    if (i < nx) {
+                        double acc = Cr ? Cr[i] : 0.0;
+                        if (Dr)
+                            for (int c = 0; c < nu; ++c) acc -= rk.K[c * nx + i] * Dr[c];
+                        nxt[i] = acc;
+                    }
+                } else {
+                    if (i < nu) {
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
+                        yrow[kk * nu + i] = acc;
+                    }
+                    if (i < nx) {
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
+                        nxt[i] = acc;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+}
+
+// sum over the wavefront, the same in every lane
+__device__ inline double wave_sum(double acc)
+{
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    return acc;
+}
+
+// 4. S = Y_A Y_A' (lower, stride ldS) and, when `rhs` is given, bv = Y_A rhs: S_ab is a dot product over min(j_a, j_b) + 1
+// steps; one wavefront per row of S, lanes along the rows' common support
+__device__ void gram_rows(const double *Y, const int *idx, int k, int mk, int nu, int n, double *S, int ldS, const double *rhs,
+                          double *bv)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int ra = wave; ra < k; ra += BS / 64) {
+        const int ja = idx[ra] / mk;
+        const double *ya = Y + (int64_t)ra * n;
+        for (int rb = 0; rb <= ra + (rhs ? 1 : 0); ++rb) {
+            const bool last = rb == ra + 1;
+            const int jb = last ? ja : idx[rb] / mk;
+            const int len = ((ja < jb ? ja : jb) + 1) * nu;
+            const double *yb = last ? rhs : Y + (int64_t)rb * n;
+            double acc = 0.0;
+            for (int c = lane; c < len; c += 64) acc += ya[c] * yb[c];
+            acc = wave_sum(acc);
+            if (lane == 0) {
+                if (last) bv[ra] = acc;
+                else S[ra * ldS + rb] = acc;
+            }
+        }
+    }
+    __syncthreads();
+}
+
 template <bool kSLds>
 __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const StagewiseAdjointLaunch a)
 {
     extern __shared__ double s_dyn[];
     __shared__ double sm[kSmDoubles];
     __shared__ int s_int[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
     const int nx = a.nx, nu = a.nu, N = a.N, mk = a.mk, n = a.n, m = a.m;
     const int R = (N + 1) * nx;
@@ -216,7 +346,6 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const Stage
     const double *gU = a.gU + b * (int64_t)n;
     const double *gX = a.gX ? a.gX + b * (int64_t)R : nullptr;
     const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
-    const int Wd = nx > nu ? nx : nu;
 
     int verdict = a.status[b];
     int k = 0;
@@ -251,73 +380,9 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const Stage
             }
             __syncthreads();
         }
-        // 3b. whitened active rows: BS / Wd sweeps side by side, each from its own step down to 0
-        const int slots = BS / Wd, sl = tid / Wd, i = tid % Wd;
-        double *pb = sm + 2 * kMaxNx;  // 2 x BS
-        for (int r0 = 0; r0 < k; r0 += slots) {
-            const int ra = r0 + sl;
-            const bool on = sl < slots && ra < k;
-            const int row = on ? idx[ra] : 0, ja = row / (mk > 0 ? mk : 1), rr = row - ja * mk;
-            const int last = (r0 + slots < k ? r0 + slots : k) - 1;
-            const int jmax = idx[last] / mk;
-            double *yrow = Y + (int64_t)ra * n;
-            for (int kk = jmax; kk >= 0; --kk) {
-                const double *cur = pb + ((jmax - kk) & 1) * BS + sl * Wd;
-                double *nxt = pb + ((jmax - kk + 1) & 1) * BS + sl * Wd;
-                if (on && kk <= ja) {
-                    const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
-                    if (kk == ja) {
-                        const double *Cr = op_step(a.problem.C, b, kk), *Dr = op_step(a.problem.D, b, kk);
-                        if (Cr) Cr += rr * nx;
-                        if (Dr) Dr += rr * nu;
-                        if (i < nu) {
-                            double acc = 0.0;
-                            if (Dr)
-                                for (int l = 0; l <= i; ++l) acc += rk.Li[i * nu + l] * Dr[l];
-                            yrow[kk * nu + i] = acc;
-                        }
-                        if (i < nx) {
-                            double acc = Cr ? Cr[i] : 0.0;
-                            if (Dr)
-                                for (int c = 0; c < nu; ++c) acc -= rk.K[c * nx + i] * Dr[c];
-                            nxt[i] = acc;
-                        }
-                    } else {
-                        if (i < nu) {
-                            double acc = 0.0;
-                            for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
-                            yrow[kk * nu + i] = acc;
-                        }
-                        if (i < nx) {
-                            double acc = 0.0;
-                            for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
-                            nxt[i] = acc;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        __syncthreads();
-        // 4. S = Y_A Y_A' (lower) and Y_A t: one wavefront per row of S, lanes along the rows' common support
-        for (int ra = wave; ra < k; ra += BS / 64) {
-            const int ja = idx[ra] / mk;
-            const double *ya = Y + (int64_t)ra * n;
-            for (int rb = 0; rb <= ra + 1; ++rb) {
-                const bool rhs = rb == ra + 1;
-                const int jb = rhs ? ja : idx[rb] / mk;
-                const int len = ((ja < jb ? ja : jb) + 1) * nu;
-                const double *yb = rhs ? t : Y + (int64_t)rb * n;
-                double acc = 0.0;
-                for (int c = lane; c < len; c += 64) acc += ya[c] * yb[c];
-                for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-                if (lane == 0) {
-                    if (rhs) bv[ra] = acc;
-                    else S[ra * cv.ldS + rb] = acc;
-                }
-            }
-        }
-        __syncthreads();
+        // 3b. the whitened active rows, 4. their Gram matrix and Y_A t
+        whiten_rows(a.problem, b, rec, cv.rs, nx, nu, mk, n, idx, k, Y, sm + 2 * kMaxNx);
+        gram_rows(Y, idx, k, mk, nu, n, S, cv.ldS, t, bv);
         if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
     }
     if (verdict == 0) {
@@ -427,6 +492,180 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const Stage
     if (a.vjp_status && tid == 0) a.vjp_status[b] = verdict;
 }
 
+// mpcqp_tangent_stagewise_kernel (mpcqp_plan_jvp_stagewise_batch): the forward-mode counterpart at any horizon, T tangents
+// (dx0, dgoal, dtargets, de) per problem on ONE factorisation ("Stage-wise forward sensitivities").
+// Phases 1, 3 and 4 above run once (no right-hand side in phase 4); then, per pass of BS / max(nx, nu) tangents side by
+// side (lanes over state components, one barrier per step for the whole group, as the row sweeps of phase 3b):
+//   a. xs = rollout(dx0, 0) with A_k                                         (skipped when dx0 is NULL: xs = 0)
+//   b. r = -L^-1 Psi' c: phase 2's backward sweep with gU = 0, gX = -c,  c_k = w_x (xs_k - dtargets_k) [k < N],
+//      c_N = w_t (xs_N - dgoal) (terms gated by MPCQP_Q_STAGE / _TERMINAL); r goes to the tangent's dU
+//   c. mu = S^-1 (Y_A r - dh_A), dh_A = de_A - (C xs)_A: one wavefront per (row, tangent), then the two substitutions with
+//      S = R R' for the whole pass (sweep_lower / sweep_lower_t)
+//   d. s = r - Y_A' mu in place, then phase 5's forward sweep from x = 0 in place: dU = L^-T s, dX = xs + (the state)
+// A tangent's arithmetic does not depend on its slot, its pass or T.
+template <bool kSLds>
+__global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const StagewiseTangentLaunch a)
+{
+    extern __shared__ double s_dyn[];
+    __shared__ double sm[kSmDoubles];
+    __shared__ int s_int[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t b = blockIdx.x;
+    const int nx = a.nx, nu = a.nu, N = a.N, mk = a.mk, n = a.n, m = a.m, T = a.ntan;
+    const int R = (N + 1) * nx;
+    const SwTanCarve cv = make_tan_carve(nx, nu, N, a.ka, T);
+    double *base = a.workspace + b * cv.total;
+    double *rec = base + cv.rec, *Y = base + cv.Y, *S = kSLds ? s_dyn : base + cv.S;
+    double *xs = base + cv.xs, *mu = base + cv.mu;
+    int *idx = (int *)(base + cv.idx);
+    const double *lam = a.lam ? a.lam + b * (int64_t)m : nullptr;
+    // tangent t of a problem at t nx / t nx / t N nx / t m; a null one is zero, a zero stride shares it
+    const double *dx0 = a.tan.dx0 ? (const double *)a.tan.dx0 + b * a.tan.dx0_stride : nullptr;
+    const double *dgoal = a.tan.dgoal ? (const double *)a.tan.dgoal + b * a.tan.dgoal_stride : nullptr;
+    const double *dtgt = a.tan.dtargets ? (const double *)a.tan.dtargets + b * a.tan.dtargets_stride : nullptr;
+    const double *de = a.tan.de ? (const double *)a.tan.de + b * a.tan.de_stride : nullptr;
+    double *dU = a.dU + b * (int64_t)T * n;
+    double *dX = a.dX ? a.dX + b * (int64_t)T * R : nullptr;
+    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+
+    int verdict = a.status[b];
+    int k = 0;
+    if (verdict == 0 && !riccati(a, b, rec, cv.rs, sm, &s_int[1])) verdict = MPCQP_NOT_PD;
+    if (verdict == 0) {
+        k = active_rows(lam, m, a.ka, idx, &s_int[0]);
+        if (k > n) verdict = MPCQP_NOT_PD;
+        else if (k > a.ka) verdict = MPCQP_SLOTS_FULL;
+    }
+    if (verdict == 0 && k > 0) {
+        whiten_rows(a.problem, b, rec, cv.rs, nx, nu, mk, n, idx, k, Y, sm);
+        gram_rows(Y, idx, k, mk, nu, n, S, cv.ldS, nullptr, nullptr);
+        if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
+    }
+    if (verdict == 0) {
+        const int Wd = nx > nu ? nx : nu, slots = BS / Wd, sl = tid / Wd, i = tid % Wd;
+        const int ls = nx + nu;  // a slot's LDS: the carried state, then the step's s_k (phase d)
+        double *buf = sm;        // 2 x kPassLds (the Riccati scratch is free now)
+        for (int t0 = 0; t0 < T; t0 += slots) {
+            const int tg = T - t0 < slots ? T - t0 : slots;
+            const bool on = sl < tg;
+            const int64_t tt = t0 + (on ? sl : 0);
+            double *xst = xs + (int64_t)(on ? sl : 0) * R, *dUt = dU + tt * n, *dXt = dX ? dX + tt * R : nullptr;
+            const double *x0t = dx0 ? dx0 + tt * nx : nullptr, *glt = dgoal ? dgoal + tt * nx : nullptr;
+            const double *tgt = dtgt ? dtgt + tt * N * nx : nullptr;
+            // a. xs = rollout(dx0, 0)
+            if (dx0) {
+                if (on && i < nx) {
+                    const double x = x0t[i];
+                    buf[sl * ls + i] = x;
+                    xst[i] = x;
+                }
+                __syncthreads();
+                for (int kk = 0; kk < N; ++kk) {
+                    const double *cur = buf + (kk & 1) * kPassLds + sl * ls;
+                    double *nxt = buf + ((kk + 1) & 1) * kPassLds + sl * ls;
+                    if (on && i < nx) {
+                        const double *Ak = op_step(a.problem.A, b, kk);
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc += Ak[i * nx + l] * cur[l];
+                        nxt[i] = acc;
+                        xst[(kk + 1) * nx + i] = acc;
+                    }
+                    __syncthreads();
+                }
+            }
+            // b. r = -L^-1 Psi' c into dU (lane i reads back the xs components it wrote itself)
+            if (on && i < nx) {
+                double c = 0.0;
+                if (qt) c = a.wt * ((dx0 ? xst[N * nx + i] : 0.0) - (glt ? glt[i] : 0.0));
+                buf[sl * ls + i] = -c;
+            }
+            __syncthreads();
+            for (int kk = N - 1; kk >= 0; --kk) {
+                const double *cur = buf + ((N - 1 - kk) & 1) * kPassLds + sl * ls;
+                double *nxt = buf + ((N - kk) & 1) * kPassLds + sl * ls;
+                if (on) {
+                    const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
+                    if (i < nu) {
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
+                        dUt[kk * nu + i] = acc;
+                    }
+                    if (i < nx) {
+                        double acc = 0.0;
+                        if (qs) acc = -a.wx * ((dx0 ? xst[kk * nx + i] : 0.0) - (tgt ? tgt[kk * nx + i] : 0.0));
+                        for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
+                        nxt[i] = acc;
+                    }
+                }
+                __syncthreads();
+            }
+            if (k > 0) {
+                // c. mu = Y_A r - dh_A = Y_A r + (C xs)_A - de_A: one wavefront per (row, tangent), lanes along the row's
+                // support (the first nx lanes add the C xs terms); then mu <- S^-1 mu for the pass
+                for (int e = wave; e < k * tg; e += BS / 64) {
+                    const int ra = e / tg, g = e % tg;
+                    const int row = idx[ra], ja = row / mk;
+                    const double *ya = Y + (int64_t)ra * n, *rt = dU + (int64_t)(t0 + g) * n;
+                    const int len = (ja + 1) * nu;
+                    double acc = 0.0;
+                    for (int c = lane; c < len; c += 64) acc += ya[c] * rt[c];
+                    if (dx0 && a.problem.C.ptr && lane < nx)
+                        acc += op_step(a.problem.C, b, ja)[(row - ja * mk) * nx + lane] * xs[(int64_t)g * R + ja * nx + lane];
+                    acc = wave_sum(acc);
+                    if (lane == 0) mu[g * cv.ldS + ra] = acc - (de ? de[(int64_t)(t0 + g) * m + row] : 0.0);
+                }
+                __syncthreads();
+                sweep_lower<BS>(S, k, cv.ldS, mu, tg, tid);
+                sweep_lower_t<BS>(S, k, cv.ldS, mu, tg, tid);
+                // d. s = r - Y_A' mu in place (row a reaches column c when its step is >= c's)
+                for (int e = tid; e < tg * n; e += BS) {
+                    const int g = e / n, c = e % n;
+                    double *sc = dU + (int64_t)(t0 + g) * n + c;
+                    const double *mg = mu + g * cv.ldS;
+                    double acc = *sc;
+                    for (int ra = lower_bound(idx, k, (c / nu) * mk); ra < k; ++ra) acc -= Y[(int64_t)ra * n + c] * mg[ra];
+                    *sc = acc;
+                }
+                __syncthreads();
+            }
+            // d (second half). dU = L^-T s in place, from x = 0: the step's s_k is staged in LDS one step ahead of the u_k that replaces it
+            if (on) {
+                if (i < nx) {
+                    buf[sl * ls + i] = 0.0;
+                    if (dXt) dXt[i] = dx0 ? x0t[i] : 0.0;
+                }
+                if (i < nu) buf[sl * ls + nx + i] = dUt[i];
+            }
+            __syncthreads();
+            for (int kk = 0; kk < N; ++kk) {
+                const double *cur = buf + (kk & 1) * kPassLds + sl * ls, *sk = cur + nx;
+                double *nxt = buf + ((kk + 1) & 1) * kPassLds + sl * ls;
+                if (on) {
+                    const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
+                    if (i < nu) {
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc -= rk.K[i * nx + l] * cur[l];
+                        for (int l = i; l < nu; ++l) acc += rk.Li[l * nu + i] * sk[l];
+                        dUt[kk * nu + i] = acc;
+                        if (kk + 1 < N) nxt[nx + i] = dUt[(kk + 1) * nu + i];
+                    }
+                    if (i < nx) {
+                        double acc = 0.0;
+                        for (int l = 0; l < nx; ++l) acc += rk.Acl[i * nx + l] * cur[l];
+                        for (int c = 0; c < nu; ++c) acc += rk.Bw[i * nu + c] * sk[c];
+                        nxt[i] = acc;
+                        if (dXt) dXt[(kk + 1) * nx + i] = (dx0 ? xst[(kk + 1) * nx + i] : 0.0) + acc;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (verdict != 0)  // (uniform) unsolved, not positive definite or slots full: all-zero tangents
+        zero_outputs<BS>(tid, dU, (int64_t)T * n, dX, (int64_t)T * R);
+    if (a.jvp_status && tid == 0) a.jvp_status[b] = verdict;
+}
+
 }  // namespace
 
 bool stagewise_adjoint_applies(int nx, int nu) { return nx <= kMaxNx && nu <= kMaxNu; }
@@ -444,6 +683,20 @@ int launch_adjoint_stagewise(const StagewiseAdjointLaunch &l, int64_t batch, hip
     if (s_in_lds(l.ka))
         return launch_per_problem(mpcqp_adjoint_stagewise_kernel<true>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
     return launch_per_problem(mpcqp_adjoint_stagewise_kernel<false>, l, BS, 0, batch, st);
+}
+
+// per problem: the records, the whitened rows, S beyond LDS, the row ids and one pass of tangents' scratch
+size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan)
+{
+    return (size_t)make_tan_carve(nx, nu, N, max_active > 0 ? max_active : 1, ntan).total * sizeof(double);
+}
+
+int launch_tangent_stagewise(const StagewiseTangentLaunch &l, int64_t batch, hipStream_t st)
+{
+    if (!l.workspace) return MPCQP_EWORKSPACE;
+    if (s_in_lds(l.ka))
+        return launch_per_problem(mpcqp_tangent_stagewise_kernel<true>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
+    return launch_per_problem(mpcqp_tangent_stagewise_kernel<false>, l, BS, 0, batch, st);
 }
 
 }  // namespace mpcqp

@@ -1202,14 +1202,22 @@ int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
 }
 
 namespace {
-// mpcqp_plan_vjp_stagewise_batch's workspace: one region per problem (mpcqp_adjoint_stagewise.hip's carve, phase 6 included)
-static int vjp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t &total)
+// what both stage-wise plan-derivative exports check of their dimensions, in this order
+static int stagewise_checks(const MpcqpDims *dims, int64_t batch, int32_t max_active)
 {
-    int rc = check_dims(dims);
+    const int rc = check_dims(dims);
     if (rc) return rc;
     if (batch < 0 || max_active < 0) return MPCQP_EINVAL;
     if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
     if (!stagewise_adjoint_applies(dims->nx, dims->nu)) return MPCQP_EUNSUPPORTED;
+    return 0;
+}
+
+// mpcqp_plan_vjp_stagewise_batch's workspace: one region per problem (mpcqp_adjoint_stagewise.hip's carve, phase 6 included)
+static int vjp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t &total)
+{
+    const int rc = stagewise_checks(dims, batch, max_active);
+    if (rc) return rc;
     total = (size_t)al256((int64_t)stagewise_adjoint_bytes(dims->nx, dims->nu, dims->N, dims->mk, max_active) * batch);
     return 0;
 }
@@ -1262,6 +1270,68 @@ int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
     l.vjp_status = vjp_status;
     l.workspace = (double *)workspace;
     return launch_adjoint_stagewise(l, batch, (hipStream_t)stream);
+}
+
+namespace {
+// mpcqp_plan_jvp_stagewise_batch's workspace: one region per problem (mpcqp_adjoint_stagewise.hip's tangent carve)
+static int jvp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, int32_t ntan, size_t &total)
+{
+    const int rc = stagewise_checks(dims, batch, max_active);
+    if (rc) return rc;
+    if (ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
+    total = (size_t)al256((int64_t)stagewise_tangent_bytes(dims->nx, dims->nu, dims->N, max_active, ntan) * batch);
+    return 0;
+}
+}  // namespace
+
+int mpcqp_plan_jvp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, int32_t ntan,
+                                             size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    size_t total = 0;
+    const int rc = jvp_stagewise_plan(dims, batch, max_active, ntan, total);
+    if (rc) return rc;
+    *bytes = total;
+    return 0;
+}
+
+int mpcqp_plan_jvp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t max_active,
+                                   int32_t ntan, const void *lam, const int32_t *status, const MpcqpTangents *tan,
+                                   void *dU, void *dX, int32_t *jvp_status, void *workspace, size_t workspace_bytes,
+                                   void *stream)
+{
+    size_t total = 0;
+    int rc = jvp_stagewise_plan(dims, batch, max_active, ntan, total);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    if (!tan || !status || !dU || (dims->mk > 0 && !lam) || tan->dx0_stride < 0 || tan->dgoal_stride < 0 ||
+        tan->dtargets_stride < 0 || tan->de_stride < 0)
+        return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < total) return MPCQP_EWORKSPACE;
+    StagewiseTangentLaunch l{};
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.n = dims->N * dims->nu;
+    l.m = dims->N * dims->mk;
+    l.flags = dims->flags;
+    l.ka = max_active > 0 ? max_active : 1;
+    l.ntan = ntan;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.wu = dims->w_input;
+    l.problem = *problem;
+    l.lam = dims->mk > 0 ? (const double *)lam : nullptr;
+    l.status = status;
+    l.tan = *tan;
+    if (dims->mk == 0) l.tan.de = nullptr;
+    l.dU = (double *)dU;
+    l.dX = (double *)dX;
+    l.jvp_status = jvp_status;
+    l.workspace = (double *)workspace;
+    return launch_tangent_stagewise(l, batch, (hipStream_t)stream);
 }
 
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const MpcqpSolveOpts *opts,

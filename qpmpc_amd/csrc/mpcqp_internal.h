@@ -326,6 +326,21 @@ struct StagewiseAdjointLaunch {
 bool stagewise_adjoint_applies(int nx, int nu);
 size_t stagewise_adjoint_bytes(int nx, int nu, int N, int mk, int max_active);  // per problem
 int launch_adjoint_stagewise(const StagewiseAdjointLaunch &l, int64_t batch, hipStream_t st);
+// the stage-wise tangent (mpcqp_adjoint_stagewise.hip, mpcqp_tangent_stagewise_kernel; the same envelope): ntan tangents per
+// problem on the adjoint's factorisation -- its records, whitened rows and Gram factor -- in passes of 256 / max(nx, nu)
+struct StagewiseTangentLaunch {
+    int nx, nu, N, mk, n, m, flags, ka, ntan;  // ka = max(max_active, 1)
+    double wt, wx, wu;
+    MpcqpProblem problem;
+    const double *lam;  // nullable when mk = 0
+    const int32_t *status;
+    MpcqpTangents tan;
+    double *dU, *dX;  // dX nullable
+    int32_t *jvp_status;
+    double *workspace;  // batch * stagewise_tangent_bytes
+};
+size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan);  // per problem
+int launch_tangent_stagewise(const StagewiseTangentLaunch &l, int64_t batch, hipStream_t st);
 
 }  // namespace mpcqp
 #endif
