@@ -519,6 +519,47 @@ int mpcqp_plan_jvp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
                                    const MpcqpTangents *tan, void *dU, void *dX, int32_t *jvp_status,
                                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* Tangents of the model matrices and the cost weights, beside MpcqpTangents; an additive part of ABI 12
+ * (MPCQP_ABI_VERSION is unchanged). Every pointer nullable (NULL = zero); packed per step: within one problem tangent t of
+ * dA sits at offset t*N*nx*nx ([ntan][N][nx][nx]), of dB at t*N*nx*nu, of dC at t*N*mk*nx, of dD at t*N*mk*nu and of dw at
+ * t*3 (dw_t, dw_x, dw_u: terminal, stage, input, the order of g_w). A stride is the number of elements between two
+ * problems' tangents, 0 = one set shared by the batch. A tangent of a C or D the problem does not have is the tangent at
+ * zero, as for the VJP; a weight whose P term dims->flags does not have contributes nothing. */
+typedef struct MpcqpModelTangents {
+    const void *dA, *dB, *dC, *dD, *dw;
+    int64_t dA_stride, dB_stride, dC_stride, dD_stride, dw_stride;
+} MpcqpModelTangents;
+
+/* mpcqp_plan_jvp_batch / mpcqp_plan_jvp_stagewise_batch with tangents of A, B, C, D and the weights as well. At the plan
+ * (U, lam) on A = {i : lam_i > 0}, with X = rollout(x0, U), Z = rollout(0, U) and E_k = X_k - r_k where the q term is
+ * flagged, Z_k where only the P term is, 0 where neither (E_N likewise with the goal), the costate of stationarity is
+ *     s_k = w_x E_k + C_k' lam_k (k < N),  s_N = w_t E_N,   pi_N = s_N,  pi_k = s_k + A_k' pi_{k+1}
+ * (0 = w_u u_k + B_k' pi_{k+1} + D_k' lam_k), and per tangent, U and lam held fixed:
+ *     xs_0 = dx0,  xs_{k+1} = A_k xs_k + dA_k X_k + dB_k u_k          (zs the same from 0 with Z_k: a P-only term's)
+ *     dE_k = xs_k - dtargets_k (MPCQP_Q_STAGE) | zs_k (MPCQP_P_STAGE only) | 0;   dE_N likewise with dgoal
+ *     c_k  = [P_STAGE] dw_x E_k + w_x dE_k + dC_k' lam_k + dA_k' pi_{k+1} (k < N),   c_N = [P_TERMINAL] dw_t E_N + w_t dE_N
+ *     g_k  = dw_u u_k + dB_k' pi_{k+1} + dD_k' lam_k,   dq = Psi' c + g
+ *     dh_k = de_k - C_k xs_k - dC_k X_k - dD_k u_k
+ *     [P G_A'; G_A 0] [dU; dlam_A] = [-dq; dh_A],   dX = xs + Psi dU
+ * ("Model and weight tangents"). `U` is the plan [batch][n]; `tan` may be NULL when `mtan` is not and
+ * the other way round. Envelope, checks, their order, status and jvp_status rules, outputs and workspace rules are those
+ * of the export without `_model`; in addition MPCQP_EINVAL for a NULL U, for tan and mtan both NULL or without any
+ * non-NULL tangent between them, or a negative stride. With every pointer of mtan NULL (or mtan NULL) the call launches
+ * what the export without `_model` launches and its outputs are bitwise the same. The workspace queries are their own
+ * (the carve holds X, Z, pi and zs as well). */
+int mpcqp_plan_jvp_model_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t ntan, size_t *bytes);
+int mpcqp_plan_jvp_model_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t ntan,
+                               const void *lam, const int32_t *status, const void *U, const MpcqpTangents *tan,
+                               const MpcqpModelTangents *mtan, void *dU, void *dX, int32_t *jvp_status,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int mpcqp_plan_jvp_model_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active,
+                                                   int32_t ntan, size_t *bytes);
+int mpcqp_plan_jvp_model_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                                         int32_t max_active, int32_t ntan, const void *lam, const int32_t *status,
+                                         const void *U, const MpcqpTangents *tan, const MpcqpModelTangents *mtan,
+                                         void *dU, void *dX, int32_t *jvp_status,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of
  * sampling_period/nsub (WheeledInvertedPendulum.integrate,

@@ -5,7 +5,8 @@ Same public names as the reference (qpmpc/__init__.py:9-21) -- ``MPCProblem``,
 reason this package exists: ``BatchMPCProblem``, ``solve_mpc_batch``,
 ``BatchMPCQP``, ``solve_qp_batch``, ``rollout_batch`` -- and ``solve_mpc_batch_diff``, whose plans
 carry gradients to x0, goal, targets and e, and ``plan_jvp`` / ``plan_jacobian``, their forward sensitivities, condensed
-(n <= 128) or, with ``formulation="stagewise"``, at any horizon (extensions: the reference has no gradients).
+(n <= 128) or, with ``formulation="stagewise"``, at any horizon, along tangents of the model matrices and the cost weights too
+(extensions: the reference has no gradients).
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of
 ``include/mpcqp.h``; without the compiled library or without a GPU every

@@ -63,6 +63,10 @@ EXPORTS = (
     "mpcqp_plan_jvp_batch",
     "mpcqp_plan_jvp_stagewise_workspace_bytes",
     "mpcqp_plan_jvp_stagewise_batch",
+    "mpcqp_plan_jvp_model_workspace_bytes",
+    "mpcqp_plan_jvp_model_batch",
+    "mpcqp_plan_jvp_model_stagewise_workspace_bytes",
+    "mpcqp_plan_jvp_model_stagewise_batch",
 )
 
 
@@ -89,6 +93,11 @@ class VjpModelOut(C.Structure):
 class Tangents(C.Structure):
     _fields_ = ([(name, C.c_void_p) for name in ("dx0", "dgoal", "dtargets", "de")]
                 + [(name + "_stride", C.c_int64) for name in ("dx0", "dgoal", "dtargets", "de")])
+
+
+class ModelTangents(C.Structure):
+    _fields_ = ([(name, C.c_void_p) for name in ("dA", "dB", "dC", "dD", "dw")]
+                + [(name + "_stride", C.c_int64) for name in ("dA", "dB", "dC", "dD", "dw")])
 
 
 class SolveOpts(C.Structure):
@@ -218,6 +227,18 @@ def load():
     lib.mpcqp_plan_jvp_stagewise_batch.restype = C.c_int
     lib.mpcqp_plan_jvp_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, C.c_int32, vp, vp,
                                                    C.POINTER(Tangents), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.mpcqp_plan_jvp_model_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_jvp_model_workspace_bytes.argtypes = lib.mpcqp_plan_jvp_workspace_bytes.argtypes
+    lib.mpcqp_plan_jvp_model_batch.restype = C.c_int
+    lib.mpcqp_plan_jvp_model_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, vp, vp, vp,
+                                               C.POINTER(Tangents), C.POINTER(ModelTangents), vp, vp, vp, vp,
+                                               C.c_size_t, vp]
+    lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes.restype = C.c_int
+    lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes.argtypes = lib.mpcqp_plan_jvp_stagewise_workspace_bytes.argtypes
+    lib.mpcqp_plan_jvp_model_stagewise_batch.restype = C.c_int
+    lib.mpcqp_plan_jvp_model_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, C.c_int32,
+                                                         vp, vp, vp, C.POINTER(Tangents), C.POINTER(ModelTangents), vp,
+                                                         vp, vp, vp, C.c_size_t, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -12,7 +12,9 @@ Forward mode: ``plan_jvp`` pushes tangents of the initial state, the goal, the t
 with one call of ``mpcqp_plan_jvp_batch`` (the same KKT system on the same active set, the tangents as right-hand sides:
 ``mpcqp_tangent_kernel`` in mpcqp_adjoint.hip); ``plan_jacobian`` is its feedback Jacobian ``dU/dx0`` (or ``dU/dgoal``),
 and ``solve_mpc_batch_diff`` serves ``torch.autograd.forward_ad`` dual tensors through it ("Forward
-sensitivities").
+sensitivities"). ``plan_jvp`` also takes tangents of the model matrices A, B, C, D and of the three cost weights
+(``mpcqp_plan_jvp_model_batch`` / ``mpcqp_plan_jvp_model_stagewise_batch``; DESIGN.md section 9, "Model and weight
+tangents"), and ``plan_jacobian(wrt="cost_weights")`` is the plan's derivative with respect to the weights.
 
 The reference has no counterpart: its plans are NumPy arrays.
 """
@@ -115,7 +117,8 @@ def _vjp_dims(problem: BatchMPCProblem) -> _capi.Dims:
 
 
 def check_envelope(problem: BatchMPCProblem, kind: str = "vjp") -> None:
-    """Raise ``BackendError`` unless the export of ``kind`` serves this problem's dimensions (nothing is launched):
+    """Raise ``BackendError`` unless the export of ``kind`` serves this problem's dimensions (nothing is launched; the
+    ``_model`` tangent exports have the envelopes of ``"jvp"`` and ``"jvp_stagewise"``):
     ``"vjp"``, ``mpcqp_plan_vjp_batch`` (n = N * nu <= 128); ``"jvp"``, ``mpcqp_plan_jvp_batch`` (the same);
     ``"stagewise"``, ``mpcqp_plan_vjp_stagewise_batch`` (nx <= 32, nu <= 8, any horizon); ``"jvp_stagewise"``,
     ``mpcqp_plan_jvp_stagewise_batch`` (the same)."""
@@ -307,6 +310,45 @@ def _tangent_operand(t, name, Bn, tail, device):
     return t, (0 if t.shape[0] == 1 else t[0].numel())
 
 
+def _model_tangent_operand(t, name, Bn, N, tail, device):
+    """A model tangent ``[B|1, T, N|1, *tail]`` as contiguous float64 ``[B|1, T, N, *tail]`` (a step dimension of 1 is
+    expanded: a time-invariant perturbation) and its stride between problems (0 when shared), or (None, 0)."""
+    torch = _torch()
+    if t is None:
+        return None, 0
+    t = torch.as_tensor(t, device=device)
+    if (t.dim() != 3 + len(tail) or tuple(t.shape[3:]) != tuple(tail) or t.shape[0] not in (1, Bn) or t.shape[1] < 1
+            or t.shape[2] not in (1, N)):
+        want = ", ".join(str(d) for d in tail)
+        raise ProblemDefinitionError(f"{name}: tangent of shape {tuple(t.shape)} is not [{Bn}|1, T, {N}|1, {want}]")
+    t = t.to(device=device, dtype=torch.float64).expand(-1, -1, N, *([-1] * len(tail))).contiguous()
+    return t, (0 if t.shape[0] == 1 else t[0].numel())
+
+
+def _weight_tangents(weights, Bn, device):
+    """The three weights' tangents ``[B|1, T]`` (None = zero) as one contiguous float64 ``[B|1, T, 3]`` in the order of
+    g_w (terminal, stage, input) and its stride between problems, or (None, 0) when none is given."""
+    torch = _torch()
+    given = []
+    for name, t in zip(WEIGHTS, weights):
+        if t is None:
+            continue
+        t = torch.as_tensor(t, device=device)
+        if t.dim() != 2 or t.shape[0] not in (1, Bn) or t.shape[1] < 1:
+            raise ProblemDefinitionError(f"{name}: tangent of shape {tuple(t.shape)} is not [{Bn}|1, T]")
+        given.append((name, t.to(device=device, dtype=torch.float64)))
+    if not given:
+        return None, 0
+    Ts = {t.shape[1] for _, t in given}
+    if len(Ts) > 1:
+        raise ProblemDefinitionError(f"plan_jvp: the tangents disagree on T: {sorted(Ts)}")
+    lead = max(t.shape[0] for _, t in given)
+    dw = torch.zeros((lead, Ts.pop(), 3), dtype=torch.float64, device=device)
+    for name, t in given:
+        dw[:, :, WEIGHTS.index(name)] = t
+    return dw, (0 if lead == 1 else dw[0].numel())
+
+
 def _formulation(value, name: str = "formulation") -> str:
     if value not in FORMULATIONS:
         raise ValueError(f"{name}: expected one of {FORMULATIONS}, got {value!r}")
@@ -314,7 +356,9 @@ def _formulation(value, name: str = "formulation") -> str:
 
 
 def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None, target_states=None,
-             ineq_vector=None, states: bool = False, *, formulation: str = "condensed"):
+             ineq_vector=None, states: bool = False, *, formulation: str = "condensed", transition_state_matrix=None,
+             transition_input_matrix=None, ineq_state_matrix=None, ineq_input_matrix=None, terminal_cost_weight=None,
+             stage_state_cost_weight=None, stage_input_cost_weight=None):
     """Jacobian-vector products of a solved plan: ``(dU [B, T, N, nu], dX [B, T, N+1, nx] or None)``.
 
     ``plan`` is ``solve_mpc_batch(problem, ..., return_multipliers=True)``; the active set is ``{i : lam_i > 0}`` and, on
@@ -332,15 +376,30 @@ def plan_jvp(problem: BatchMPCProblem, plan, initial_state=None, goal_state=None
     horizon and every n for nx <= 32, nu <= 8 (``BackendError`` outside). Like the stage-wise backward it sizes its
     workspace from the largest number of active rows in the batch (one host sync) and splits the batch so that one
     launch's workspace stays below ``STAGEWISE_WORKSPACE_CAP``; ``plan.jvp_status`` may then also hold
-    ``MPCQP_NOT_PD`` for a stage Hessian that is not positive definite. Any other value raises ``ValueError``."""
-    dU, dX = _jvp(problem, plan, initial_state, goal_state, target_states, ineq_vector, states, formulation)
+    ``MPCQP_NOT_PD`` for a stage Hessian that is not positive definite. Any other value raises ``ValueError``.
+
+    Tangents of the model and the cost weights (keyword-only, named as ``solve_mpc_batch_diff`` names the operands, the
+    same T): ``transition_state_matrix`` ``[B|1, T, N|1, nx, nx]``, ``transition_input_matrix`` ``[B|1, T, N|1, nx, nu]``,
+    ``ineq_state_matrix`` ``[B|1, T, N|1, mk, nx]``, ``ineq_input_matrix`` ``[B|1, T, N|1, mk, nu]`` (a step dimension
+    of 1 is a time-invariant perturbation, expanded to N) and ``terminal_cost_weight``, ``stage_state_cost_weight``,
+    ``stage_input_cost_weight`` ``[B|1, T]``. The plan then moves as if the pendulum were longer or the terminal weight
+    doubled: the plan and its multipliers are held on the active set, and the tangents enter the same KKT system as
+    right-hand sides ("Model and weight tangents"). When one of them is given the call is
+    ``mpcqp_plan_jvp_model_batch`` (``mpcqp_plan_jvp_model_stagewise_batch`` with ``formulation="stagewise"``);
+    otherwise it is the export above, as before. The tangent of an ``ineq_state_matrix`` or ``ineq_input_matrix`` the
+    problem does not have is the one at zero; a weight whose cost term the problem does not have contributes nothing."""
+    model = (transition_state_matrix, transition_input_matrix, ineq_state_matrix, ineq_input_matrix)
+    weights = (terminal_cost_weight, stage_state_cost_weight, stage_input_cost_weight)
+    dU, dX = _jvp(problem, plan, initial_state, goal_state, target_states, ineq_vector, states, formulation, model,
+                  weights)
     dt = problem.dtype
     return dU.to(dt), (None if dX is None else dX.to(dt))
 
 
 def _jvp(problem: BatchMPCProblem, plan, initial_state, goal_state, target_states, ineq_vector, states: bool,
-         formulation: str):
-    """``plan_jvp`` in float64, as the export wrote it (the caller casts to the problem's dtype)."""
+         formulation: str, model=(None,) * 4, weights=(None,) * 3):
+    """``plan_jvp`` in float64, as the export wrote it (the caller casts to the problem's dtype). ``model``: the tangents
+    of A, B, C, D; ``weights``: of the three weights."""
     torch = _torch()
     lib = _capi.load()
     stagewise = _formulation(formulation) == "stagewise"
@@ -353,7 +412,13 @@ def _jvp(problem: BatchMPCProblem, plan, initial_state, goal_state, target_state
     tails = ((nx,), (nx,), (N * nx,), (N, mk))
     ops = [_tangent_operand(t, nm, Bn, tail, dev) for t, nm, tail in zip(
         (initial_state, goal_state, target_states, ineq_vector), TANGENT_NAMES, tails)]
-    Ts = {t.shape[1] for t, _ in ops if t is not None}
+    mtails = ((nx, nx), (nx, nu), (mk, nx), (mk, nu))
+    mops = [_model_tangent_operand(t, nm, Bn, N, tail, dev) for t, nm, tail in zip(model, MODEL_OPERANDS, mtails)]
+    mops.append(_weight_tangents(weights, Bn, dev))
+    if mk == 0:
+        mops[2] = mops[3] = (None, 0)
+    with_model = any(t is not None for t, _ in mops)
+    Ts = {t.shape[1] for t, _ in ops + mops if t is not None}
     if not Ts:
         raise ProblemDefinitionError("plan_jvp: no tangent given")
     if len(Ts) > 1:
@@ -371,7 +436,34 @@ def _jvp(problem: BatchMPCProblem, plan, initial_state, goal_state, target_state
     jvp_status = torch.empty((Bn,), dtype=torch.int32, device=dev)
     dims, cp = _vjp_dims(p64), p64.c_problem()
     keep = [cp]
-    if stagewise:
+    if with_model:
+        U = plan.U.reshape(Bn, n).to(torch.float64).contiguous()
+        keep.append(U)
+        if stagewise:
+            max_active = _max_active(lam, plan.status, n)  # the host sync
+            ws, chunks = _stagewise_chunks(lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes, dims, Bn, dev,
+                                           max_active, T)
+            for b0, nb in chunks:
+                cpb = _shifted(cp, b0)
+                tan = _capi.Tangents(*[(_at(t, b0) if st else _ptr(t)) for t, st in ops], *[st for _, st in ops])
+                mtan = _capi.ModelTangents(*[(_at(t, b0) if st else _ptr(t)) for t, st in mops],
+                                           *[st for _, st in mops])
+                rc = lib.mpcqp_plan_jvp_model_stagewise_batch(
+                    C.byref(dims), C.byref(cpb), nb, max_active, T, _at(lam, b0), _at(plan.status, b0), _at(U, b0),
+                    C.byref(tan), C.byref(mtan), _at(dU, b0), _at(dX, b0), _at(jvp_status, b0), ws.data_ptr(),
+                    ws.numel(), _stream_ptr())
+                _capi.check(rc, "mpcqp_plan_jvp_model_stagewise_batch")
+                keep.append(cpb)
+        else:
+            ws = _workspace_for(lib.mpcqp_plan_jvp_model_workspace_bytes, dims, Bn, dev, T)
+            tan = _capi.Tangents(*[_ptr(t) for t, _ in ops], *[st for _, st in ops])
+            mtan = _capi.ModelTangents(*[_ptr(t) for t, _ in mops], *[st for _, st in mops])
+            rc = lib.mpcqp_plan_jvp_model_batch(
+                C.byref(dims), C.byref(cp), Bn, T, _ptr(lam), plan.status.data_ptr(), U.data_ptr(), C.byref(tan),
+                C.byref(mtan), dU.data_ptr(), _ptr(dX), jvp_status.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream_ptr())
+            _capi.check(rc, "mpcqp_plan_jvp_model_batch")
+    elif stagewise:
         max_active = _max_active(lam, plan.status, n)  # the host sync
         ws, chunks = _stagewise_chunks(lib.mpcqp_plan_jvp_stagewise_workspace_bytes, dims, Bn, dev, max_active, T)
         for b0, nb in chunks:
@@ -391,11 +483,11 @@ def _jvp(problem: BatchMPCProblem, plan, initial_state, goal_state, target_state
                                       ws.numel(), _stream_ptr())
         _capi.check(rc, "mpcqp_plan_jvp_batch")
     plan.jvp_status = jvp_status
-    plan._jvp_keep = (ws, p64, lam, ops, keep)  # alive until the stream has consumed them
+    plan._jvp_keep = (ws, p64, lam, ops, mops, keep)  # alive until the stream has consumed them
     return dU, dX
 
 
-JACOBIAN_WRT = ("initial_state", "goal_state")
+JACOBIAN_WRT = ("initial_state", "goal_state", "cost_weights")
 
 
 def plan_jacobian(problem: BatchMPCProblem, plan, wrt: str = "initial_state", states: bool = False, *,
@@ -407,11 +499,21 @@ def plan_jacobian(problem: BatchMPCProblem, plan, wrt: str = "initial_state", st
     This is ``plan_jvp`` with the identity as T = nx tangents shared by the batch (stride 0), returned as a permuted
     view; its rules (multipliers, status, envelope, dtype) apply, and so does its ``formulation``: ``"stagewise"`` gives
     the Jacobian at any horizon (nx <= 32, nu <= 8) on one factorisation per problem (DESIGN.md section 9 has the
-    measured cost beside one stage-wise backward)."""
+    measured cost beside one stage-wise backward).
+
+    ``wrt="cost_weights"`` gives ``J_U [B, N, nu, 3]`` (and ``J_X [B, N+1, nx, 3]``): the plan's derivative with respect
+    to the terminal, stage-state and stage-input cost weights, in this order, from one 3 x 3 identity of weight tangents
+    shared by the batch (``mpcqp_plan_jvp_model_batch``; a weight whose cost term the problem does not have gets zeros)."""
     torch = _torch()
     _formulation(formulation)
     if wrt not in JACOBIAN_WRT:
         raise ProblemDefinitionError(f"wrt: expected one of {JACOBIAN_WRT}, got {wrt!r}")
+    if wrt == "cost_weights":
+        eye = torch.eye(3, dtype=torch.float64, device=problem.device)
+        dU, dX = _jvp(problem, plan, None, None, None, None, states, formulation,
+                      weights=tuple(eye[j][None] for j in range(3)))
+        dU, dX = dU.to(problem.dtype), (None if dX is None else dX.to(problem.dtype))
+        return dU.permute(0, 2, 3, 1), (None if dX is None else dX.permute(0, 2, 3, 1))
     eye = torch.eye(problem.state_dim, dtype=torch.float64, device=problem.device)[None]
     dU, dX = plan_jvp(problem, plan, states=states, formulation=formulation, **{wrt: eye})
     return dU.permute(0, 2, 3, 1), (None if dX is None else dX.permute(0, 2, 3, 1))

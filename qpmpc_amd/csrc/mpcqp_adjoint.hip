@@ -33,7 +33,12 @@
 //   4. dU_t = L^-T (r_t - M_A' mu_t)                               (one backward sweep, over tangents); dX_t = Phi dx0 + Psi dU_t
 // Its carve: L (n ld), the T + n right-hand sides ((T + n) ld), S (n ld), mu (T ld), Phi dx0_t (T (N + 1) nx; step 1
 // reads it for dq and dh, and dX reuses it), the active row ids.
+//
+// Its kModel instantiation (mpcqp_plan_jvp_model_batch) takes tangents of A, B, C, D and the weights as well: see the comment
+// above the kernel. Its carve grows by X, Z, pi ((N + 1) nx each) and T (N + 1) nx for zs (then c).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "mpcqp.h"
 #include "mpcqp_adjoint_common.h"
@@ -247,9 +252,10 @@ int launch_adjoint_bs(const AdjointLaunch &a, bool lds, size_t lds_bytes, int64_
 struct TanCarve {
     int ld;
     int64_t L, Z, S, mu, x, idx, total;
+    int64_t X, Zf, pi, zs;  // model: appended after idx (total includes them only when model)
 };
 
-__host__ __device__ inline TanCarve make_tan_carve(int n, int T, int R)
+__host__ __device__ inline TanCarve make_tan_carve(int n, int T, int R, bool model = false)
 {
     TanCarve c;
     c.ld = n | 1;
@@ -260,11 +266,22 @@ __host__ __device__ inline TanCarve make_tan_carve(int n, int T, int R)
     c.x = c.mu + (int64_t)T * c.ld;       // T rows of R = (N + 1) nx: Phi dx0_t
     c.idx = c.x + (int64_t)T * R;         // n + 1 int32 (active row ids)
     c.total = c.idx + (n + 2) / 2;
+    c.X = c.total;      // R: Phi x0 + Psi U
+    c.Zf = c.X + R;     // R: Psi U
+    c.pi = c.Zf + R;    // R: the costate of the stationarity condition
+    c.zs = c.pi + R;    // T rows of R: the tangents zs of Zf, then c in place
+    if (model) c.total = c.zs + (int64_t)T * R;
     return c;
 }
 
-template <int BS, bool kLds>
-__global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a)
+// kModel (mpcqp_plan_jvp_model_batch; DESIGN.md section 9, "Model and weight tangents"): tangents of A, B, C, D and the
+// weights as well. Before step 1: Z = Psi U and X = Phi x0 + Z in one pass, the costate pi (stationarity_costate), then xs
+// (and zs where a P-only term reads it) of all tangents side by side by the recursion with its forcing term, one barrier
+// per step, in place of the Phi dx0 pass; c overwrites zs entry by entry. Step 1 then has Z rows -(Psi' c + g) and the two
+// more terms of dh (tangent_c, tangent_g, tangent_dh of mpcqp_adjoint_common.h); the rest is the kernel as it was.
+template <int BS, bool kLds, bool kModel>
+__global__ void __launch_bounds__(BS)
+mpcqp_tangent_kernel(const typename std::conditional<kModel, TangentModelLaunch, TangentLaunch>::type a)
 {
     extern __shared__ double lds_carve[];
     __shared__ int s_k;
@@ -273,10 +290,11 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a
     const int64_t b = blockIdx.x;
     const int n = d.n, m = d.m, nx = d.nx, N = d.N, mk = d.mk, T = a.ntan;
     const int R = (N + 1) * nx;
-    const TanCarve cv = make_tan_carve(n, T, R);
+    const TanCarve cv = make_tan_carve(n, T, R, kModel);
     const int ld = cv.ld;
     double *base = kLds ? lds_carve : d.carve_ws + b * cv.total;
     double *L = base + cv.L, *Z = base + cv.Z, *S = base + cv.S, *mu = base + cv.mu, *xs = base + cv.x;
+    ModelTanVecs mv{};
     int *idx = (int *)(base + cv.idx);
 
     const double *P = d.P + b * (int64_t)n * n;
@@ -306,37 +324,89 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a
             verdict = MPCQP_NOT_PD;
         } else {
             // 1. xs_t = Phi dx0_t; Z rows 0 .. T-1 = -dq_t; rows T .. T+k-1 = G_A; mu rows = dh_A,t
-            if (dx0) {
-                for (int e = tid; e < T * R; e += BS) {
-                    const int t = e / R, r = e % R;
-                    const double *fr = Phi + (int64_t)r * nx, *x0t = dx0 + (int64_t)t * nx;
-                    double acc = 0.0;
-                    for (int j = 0; j < nx; ++j) acc += fr[j] * x0t[j];
-                    xs[e] = acc;
+            if constexpr (kModel) {
+                const double *U = a.U + b * (int64_t)n;
+                const double *x0 = (const double *)a.x0.ptr + b * a.x0.batch_stride;
+                double *X = base + cv.X, *Zf = base + cv.Zf, *pi = base + cv.pi, *zs = base + cv.zs;
+                for (int r = tid; r < R; r += BS) {
+                    const double *pr = Psi + (int64_t)r * n, *fr = Phi + (int64_t)r * nx;
+                    double z = 0.0, f = 0.0;
+                    for (int c = 0; c < n; ++c) z += pr[c] * U[c];
+                    for (int c = 0; c < nx; ++c) f += fr[c] * x0[c];
+                    Zf[r] = z;
+                    X[r] = f + z;
+                }
+                mv = ModelTanVecs{tan_at(a.mtan.dA, a.mtan.dA_stride, b), tan_at(a.mtan.dB, a.mtan.dB_stride, b),
+                                  tan_at(a.mtan.dC, a.mtan.dC_stride, b), tan_at(a.mtan.dD, a.mtan.dD_stride, b),
+                                  tan_at(a.mtan.dw, a.mtan.dw_stride, b), X, Zf, pi, U, lam,
+                                  qt ? (const double *)a.goal.ptr + b * a.goal.batch_stride : nullptr,
+                                  qs ? (const double *)a.targets.ptr + b * a.targets.batch_stride : nullptr};
+                __syncthreads();
+                stationarity_costate<BS>(d, a.A, d.C, b, mv, pi);
+                // xs (which = 0) and zs (which = 1) of every tangent, one barrier per step
+                const int nw = tangent_needs_zs(d.flags) ? 2 : 1;
+                for (int e = tid; e < nw * T * nx; e += BS) {
+                    const int which = e / (T * nx), t = (e / nx) % T, i = e % nx;
+                    (which ? zs : xs)[(int64_t)t * R + i] = (!which && dx0) ? dx0[(int64_t)t * nx + i] : 0.0;
                 }
                 __syncthreads();
-            }
-            for (int e = tid; e < T * n; e += BS) {
-                const int t = e / n, c = e % n;
-                const double *xt = dx0 ? xs + (int64_t)t * R : nullptr;
-                double acc = 0.0;
-                if (qs && (xt || dtgt)) {
-                    const double *tg = dtgt ? dtgt + (int64_t)t * N * nx : nullptr;
-                    double s = 0.0;
-                    for (int r = 0; r < N * nx; ++r)
-                        s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (tg ? tg[r] : 0.0));
-                    acc += d.wx * s;
-                }
-                if (qt && (xt || dgoal)) {
-                    const double *gl = dgoal ? dgoal + (int64_t)t * nx : nullptr;
-                    double s = 0.0;
-                    for (int i = 0; i < nx; ++i) {
-                        const int r = N * nx + i;
-                        s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (gl ? gl[i] : 0.0));
+                for (int kk = 0; kk < N; ++kk) {
+                    const double *Ak = op_step(a.A, b, kk);
+                    for (int e = tid; e < nw * T * nx; e += BS) {
+                        const int which = e / (T * nx), t = (e / nx) % T, i = e % nx;
+                        double *x = (which ? zs : xs) + (int64_t)t * R;
+                        double acc = tangent_forcing(d, mv, which ? Zf : X, t, kk, i);
+                        for (int l = 0; l < nx; ++l) acc += Ak[i * nx + l] * x[kk * nx + l];
+                        x[(kk + 1) * nx + i] = acc;
                     }
-                    acc += d.wt * s;
+                    __syncthreads();
                 }
-                Z[t * ld + c] = -acc;
+                for (int e = tid; e < T * R; e += BS) {
+                    const int t = e / R, r = e % R;
+                    zs[e] = tangent_c(d, mv, t, r, xs[e], nw == 2 ? zs[e] : 0.0, dtgt ? dtgt + (int64_t)t * N * nx : nullptr,
+                                      dgoal ? dgoal + (int64_t)t * nx : nullptr);
+                }
+                __syncthreads();
+                for (int e = tid; e < T * n; e += BS) {
+                    const int t = e / n, c = e % n;
+                    const double *ct = zs + (int64_t)t * R;
+                    double acc = tangent_g(d, mv, t, c);
+                    for (int r = 0; r < R; ++r) acc += Psi[(int64_t)r * n + c] * ct[r];
+                    Z[t * ld + c] = -acc;
+                }
+            } else {
+                if (dx0) {
+                    for (int e = tid; e < T * R; e += BS) {
+                        const int t = e / R, r = e % R;
+                        const double *fr = Phi + (int64_t)r * nx, *x0t = dx0 + (int64_t)t * nx;
+                        double acc = 0.0;
+                        for (int j = 0; j < nx; ++j) acc += fr[j] * x0t[j];
+                        xs[e] = acc;
+                    }
+                    __syncthreads();
+                }
+                for (int e = tid; e < T * n; e += BS) {
+                    const int t = e / n, c = e % n;
+                    const double *xt = dx0 ? xs + (int64_t)t * R : nullptr;
+                    double acc = 0.0;
+                    if (qs && (xt || dtgt)) {
+                        const double *tg = dtgt ? dtgt + (int64_t)t * N * nx : nullptr;
+                        double s = 0.0;
+                        for (int r = 0; r < N * nx; ++r)
+                            s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (tg ? tg[r] : 0.0));
+                        acc += d.wx * s;
+                    }
+                    if (qt && (xt || dgoal)) {
+                        const double *gl = dgoal ? dgoal + (int64_t)t * nx : nullptr;
+                        double s = 0.0;
+                        for (int i = 0; i < nx; ++i) {
+                            const int r = N * nx + i;
+                            s += Psi[(int64_t)r * n + c] * ((xt ? xt[r] : 0.0) - (gl ? gl[i] : 0.0));
+                        }
+                        acc += d.wt * s;
+                    }
+                    Z[t * ld + c] = -acc;
+                }
             }
             for (int e = tid; e < k * n; e += BS) {
                 const int r = e / n, j = e % n;
@@ -345,10 +415,11 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a
             for (int e = tid; e < T * k; e += BS) {
                 const int t = e / k, r = e % k, row = idx[r], kk = row / mk;
                 double h = de ? de[(int64_t)t * m + row] : 0.0;
-                if (Cb && dx0) {
+                if (Cb && (kModel || dx0)) {
                     const double *Ci = Cb + kk * d.C.step_stride + (row % mk) * nx, *xk = xs + (int64_t)t * R + kk * nx;
                     for (int i = 0; i < nx; ++i) h -= Ci[i] * xk[i];
                 }
+                if constexpr (kModel) h -= tangent_dh(d, mv, t, row);
                 mu[t * ld + r] = h;
             }
             // 2. P = L L', then one forward sweep L^-1 over all T + k right-hand sides
@@ -385,7 +456,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a
                         for (int64_t e = tid; e < (int64_t)T * R; e += BS) {
                             const int t = (int)(e / R), r = (int)(e % R);
                             const double *pr = Psi + (int64_t)r * n, *zt = Z + t * ld;
-                            double acc = dx0 ? xs[e] : 0.0;
+                            double acc = (kModel || dx0) ? xs[e] : 0.0;
                             for (int c = 0; c < n; ++c) acc += pr[c] * zt[c];
                             dX[e] = acc;
                         }
@@ -402,8 +473,14 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_kernel(const TangentLaunch a
 template <int BS>
 int launch_tangent_bs(const TangentLaunch &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
 {
-    if (lds) return launch_per_problem(mpcqp_tangent_kernel<BS, true>, a, BS, lds_bytes, batch, st);
-    return launch_per_problem(mpcqp_tangent_kernel<BS, false>, a, BS, 0, batch, st);
+    if (lds) return launch_per_problem(mpcqp_tangent_kernel<BS, true, false>, a, BS, lds_bytes, batch, st);
+    return launch_per_problem(mpcqp_tangent_kernel<BS, false, false>, a, BS, 0, batch, st);
+}
+template <int BS>
+int launch_tangent_model_bs(const TangentModelLaunch &a, bool lds, size_t lds_bytes, int64_t batch, hipStream_t st)
+{
+    if (lds) return launch_per_problem(mpcqp_tangent_kernel<BS, true, true>, a, BS, lds_bytes, batch, st);
+    return launch_per_problem(mpcqp_tangent_kernel<BS, false, true>, a, BS, 0, batch, st);
 }
 
 }  // namespace
@@ -431,15 +508,15 @@ int launch_adjoint(const AdjointLaunch &l, int64_t batch, hipStream_t st)
     return l.model ? launch_adjoint_bs<256, true>(l, lds, bytes, batch, st) : launch_adjoint_bs<256, false>(l, lds, bytes, batch, st);
 }
 
-size_t tangent_carve_bytes(int n, int N, int nx, int ntan)
+size_t tangent_carve_bytes(int n, int N, int nx, int ntan, bool model)
 {
-    return (size_t)make_tan_carve(n, ntan, (N + 1) * nx).total * sizeof(double);
+    return (size_t)make_tan_carve(n, ntan, (N + 1) * nx, model).total * sizeof(double);
 }
 
 // (the 64 bytes spare leave room for the kernel's static s_k, as adjoint_carve_in_lds)
-bool tangent_carve_in_lds(int n, int N, int nx, int ntan)
+bool tangent_carve_in_lds(int n, int N, int nx, int ntan, bool model)
 {
-    return tangent_carve_bytes(n, N, nx, ntan) + 64 <= kLdsBytesPerCU;
+    return tangent_carve_bytes(n, N, nx, ntan, model) + 64 <= kLdsBytesPerCU;
 }
 
 int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st)
@@ -450,6 +527,17 @@ int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st)
     if (!lds && !d.carve_ws) return MPCQP_EWORKSPACE;
     if (adjoint_threads(d.n) == 64) return launch_tangent_bs<64>(l, lds, bytes, batch, st);
     return launch_tangent_bs<256>(l, lds, bytes, batch, st);
+}
+
+int launch_tangent_model(const TangentModelLaunch &l, int64_t batch, hipStream_t st)
+{
+    const CondensedKkt &d = l.kkt;
+    const bool lds = tangent_carve_in_lds(d.n, d.N, d.nx, l.ntan, true);
+    const size_t bytes = tangent_carve_bytes(d.n, d.N, d.nx, l.ntan, true);
+    if (!lds && !d.carve_ws) return MPCQP_EWORKSPACE;
+    if (!l.U || !l.A.ptr || !l.x0.ptr) return MPCQP_EINVAL;
+    if (adjoint_threads(d.n) == 64) return launch_tangent_model_bs<64>(l, lds, bytes, batch, st);
+    return launch_tangent_model_bs<256>(l, lds, bytes, batch, st);
 }
 
 }  // namespace mpcqp

@@ -291,6 +291,145 @@ __device__ void model_epilogue(const D &d, const MpcqpOperand &A, const MpcqpOpe
     }
 }
 
+// ---- model and weight tangents ("Model and weight tangents"): what the kModel instantiations of
+// mpcqp_tangent_kernel and mpcqp_tangent_stagewise_kernel share. With U and lam held fixed a tangent of A, B, C, D and the
+// weights adds a forcing term to the rollout xs (and zs), terms to the cost tangent's per-state vector c, the per-input
+// vector g (dq = Psi' c + g) and two terms to dh; all read the trajectories X = rollout(x0, U), Zf = rollout(0, U) and the
+// costate pi of the stationarity condition.
+
+// Problem b's model tangents (null = zero; tangent t at t N nx nx, t N nx nu, t N mk nx, t N mk nu, 3 t) and the vectors
+// their terms read, in the calling kernel's carve
+struct ModelTanVecs {
+    const double *dA, *dB, *dC, *dD, *dw;
+    const double *X, *Zf, *pi, *U, *lam, *goal, *tgt;  // goal / tgt: null where the q term is off
+};
+
+__device__ inline const double *tan_at(const void *p, int64_t stride, int64_t b)
+{
+    return p ? (const double *)p + b * stride : nullptr;
+}
+
+// a P-only term (flagged P, not Q) reads the tangent zs of the forced response
+__host__ __device__ inline bool tangent_needs_zs(int flags)
+{
+    return ((flags & MPCQP_P_STAGE) && !(flags & MPCQP_Q_STAGE)) || ((flags & MPCQP_P_TERMINAL) && !(flags & MPCQP_Q_TERMINAL));
+}
+
+// pi = the costate of the stationarity condition, (N + 1) nx: s_k = w_x E_k + C_k' lam_k (k < N), s_N = w_t E_N, then
+// pi_k = s_k + A_k' pi_{k+1}, serial over k on nx lanes. E_k = X_k - r_k where the q term is flagged, Zf_k where only the P
+// term is, 0 where neither. v.X, v.Zf must be in place (a barrier behind them); ends with a barrier.
+template <int BS, class D>
+__device__ inline void stationarity_costate(const D &d, const MpcqpOperand &A, const MpcqpOperand &C, int64_t b,
+                                            const ModelTanVecs &v, double *pi)
+{
+    const int tid = threadIdx.x, nx = d.nx, N = d.N, mk = d.mk, R = (N + 1) * nx;
+    const bool pt = (d.flags & MPCQP_P_TERMINAL) != 0, ps = (d.flags & MPCQP_P_STAGE) != 0;
+    for (int e = tid; e < R; e += BS) {
+        const int kk = e / nx, i = e % nx;
+        double acc = 0.0;
+        if (kk < N) {
+            if (ps) acc = d.wx * (v.tgt ? v.X[e] - v.tgt[e] : v.Zf[e]);
+            if (const double *Ck = op_step(C, b, kk))
+                for (int r = 0; r < mk; ++r) acc += Ck[r * nx + i] * v.lam[kk * mk + r];
+        } else if (pt) {
+            acc = d.wt * (v.goal ? v.X[e] - v.goal[i] : v.Zf[e]);
+        }
+        pi[e] = acc;
+    }
+    __syncthreads();
+    for (int kk = N - 1; kk >= 0; --kk) {
+        const double *Ak = op_step(A, b, kk);
+        for (int i = tid; i < nx; i += BS) {
+            double acc = 0.0;
+            for (int j = 0; j < nx; ++j) acc += Ak[j * nx + i] * pi[(kk + 1) * nx + j];
+            pi[kk * nx + i] += acc;
+        }
+        __syncthreads();
+    }
+}
+
+// component i of the forcing term dA_k traj_k + dB_k u_k of tangent t's rollout (traj: X for xs, Zf for zs)
+template <class D>
+__device__ inline double tangent_forcing(const D &d, const ModelTanVecs &v, const double *traj, int t, int kk, int i)
+{
+    const int nx = d.nx, nu = d.nu;
+    const int64_t tk = (int64_t)t * d.N + kk;
+    double acc = 0.0;
+    if (v.dA) {
+        const double *row = v.dA + (tk * nx + i) * nx;
+        for (int l = 0; l < nx; ++l) acc += row[l] * traj[kk * nx + l];
+    }
+    if (v.dB) {
+        const double *row = v.dB + (tk * nx + i) * nu;
+        for (int c = 0; c < nu; ++c) acc += row[c] * v.U[kk * nu + c];
+    }
+    return acc;
+}
+
+// c of tangent t at state entry e = kk nx + i: [P] dw E + w dE + dC_k' lam_k + dA_k' pi_{k+1}; xs, zs: the tangent's
+// rollouts at e; dtgt, dgoal: the tangent's dtargets / dgoal (null = zero)
+template <class D>
+__device__ inline double tangent_c(const D &d, const ModelTanVecs &v, int t, int e, double xs, double zs,
+                                   const double *dtgt, const double *dgoal)
+{
+    const int nx = d.nx, N = d.N, mk = d.mk, kk = e / nx, i = e % nx;
+    const bool pt = (d.flags & MPCQP_P_TERMINAL) != 0, ps = (d.flags & MPCQP_P_STAGE) != 0;
+    const bool qt = (d.flags & MPCQP_Q_TERMINAL) != 0, qs = (d.flags & MPCQP_Q_STAGE) != 0;
+    const double *dw = v.dw ? v.dw + 3 * (int64_t)t : nullptr;
+    double acc = 0.0;
+    if (kk < N) {
+        const int64_t tk = (int64_t)t * N + kk;
+        if (qs) acc = d.wx * (xs - (dtgt ? dtgt[e] : 0.0));
+        else if (ps) acc = d.wx * zs;
+        if (ps && dw) acc += dw[1] * (qs ? v.X[e] - v.tgt[e] : v.Zf[e]);
+        if (v.dC) {
+            const double *dCk = v.dC + tk * mk * nx;
+            for (int r = 0; r < mk; ++r) acc += dCk[r * nx + i] * v.lam[kk * mk + r];
+        }
+        if (v.dA) {
+            const double *dAk = v.dA + tk * nx * nx;
+            for (int j = 0; j < nx; ++j) acc += dAk[j * nx + i] * v.pi[(kk + 1) * nx + j];
+        }
+    } else {
+        if (qt) acc = d.wt * (xs - (dgoal ? dgoal[i] : 0.0));
+        else if (pt) acc = d.wt * zs;
+        if (pt && dw) acc += dw[0] * (qt ? v.X[e] - v.goal[i] : v.Zf[e]);
+    }
+    return acc;
+}
+
+// g of tangent t at input entry col = kk nu + j: dw_u u + dB_k' pi_{k+1} + dD_k' lam_k
+template <class D>
+__device__ inline double tangent_g(const D &d, const ModelTanVecs &v, int t, int col)
+{
+    const int nx = d.nx, nu = d.nu, mk = d.mk, kk = col / nu, j = col % nu;
+    const int64_t tk = (int64_t)t * d.N + kk;
+    double acc = v.dw ? v.dw[3 * (int64_t)t + 2] * v.U[col] : 0.0;
+    if (v.dB) {
+        const double *dBk = v.dB + tk * nx * nu;
+        for (int i = 0; i < nx; ++i) acc += dBk[i * nu + j] * v.pi[(kk + 1) * nx + i];
+    }
+    if (v.dD) {
+        const double *dDk = v.dD + tk * mk * nu;
+        for (int r = 0; r < mk; ++r) acc += dDk[r * nu + j] * v.lam[kk * mk + r];
+    }
+    return acc;
+}
+
+// what the model tangent takes from dh at `row`: dC_k X_k + dD_k u_k (dh = de - C xs - this)
+template <class D>
+__device__ inline double tangent_dh(const D &d, const ModelTanVecs &v, int t, int row)
+{
+    const int nx = d.nx, nu = d.nu, mk = d.mk, kk = row / mk;
+    const int64_t tr = (int64_t)t * d.N * mk + row;
+    double acc = 0.0;
+    if (v.dC)
+        for (int i = 0; i < nx; ++i) acc += v.dC[tr * nx + i] * v.X[kk * nx + i];
+    if (v.dD)
+        for (int j = 0; j < nu; ++j) acc += v.dD[tr * nu + j] * v.U[kk * nu + j];
+    return acc;
+}
+
 // One workgroup of bs threads per problem, lds_bytes of dynamic LDS (the kernel's limit raised past 48 KiB)
 template <class Args>
 int launch_per_problem(void (*kern)(Args), const Args &a, int bs, size_t lds_bytes, int64_t batch, hipStream_t st)

@@ -27,6 +27,8 @@
 // counterpart on the same factorisation: phases 1, 3 and 4 are device functions that both kernels call.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "mpcqp.h"
 #include "mpcqp_adjoint_common.h"
 
@@ -94,11 +96,12 @@ __host__ __device__ inline SwCarve make_carve(int nx, int nu, int N, int mk, int
 struct SwTanCarve : SwBase {
     int tg;
     int64_t idx, xs, mu, total;
+    int64_t X, Zf, pi, zs;  // model: appended after mu (total includes them only when model); zs: the pass's second slot
 };
 
 __host__ __device__ inline int tangent_slots(int nx, int nu) { return BS / (nx > nu ? nx : nu); }
 
-__host__ __device__ inline SwTanCarve make_tan_carve(int nx, int nu, int N, int ka, int ntan)
+__host__ __device__ inline SwTanCarve make_tan_carve(int nx, int nu, int N, int ka, int ntan, bool model = false)
 {
     SwTanCarve c;
     static_cast<SwBase &>(c) = make_base(nx, nu, N, ka);
@@ -108,6 +111,12 @@ __host__ __device__ inline SwTanCarve make_tan_carve(int nx, int nu, int N, int 
     c.xs = c.idx + (ka + 2) / 2;
     c.mu = c.xs + (int64_t)c.tg * (N + 1) * nx;
     c.total = c.mu + (int64_t)c.tg * c.ldS;
+    const int64_t R = (int64_t)(N + 1) * nx;
+    c.X = c.total;
+    c.Zf = c.X + R;
+    c.pi = c.Zf + R;
+    c.zs = c.pi + R;
+    if (model) c.total = c.zs + c.tg * R;
     return c;
 }
 
@@ -503,8 +512,15 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const Stage
 //      S = R R' for the whole pass (sweep_lower / sweep_lower_t)
 //   d. s = r - Y_A' mu in place, then phase 5's forward sweep from x = 0 in place: dU = L^-T s, dX = xs + (the state)
 // A tangent's arithmetic does not depend on its slot, its pass or T.
-template <bool kSLds>
-__global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const StagewiseTangentLaunch a)
+//
+// kModel (mpcqp_plan_jvp_model_stagewise_batch; DESIGN.md section 9, "Model and weight tangents"): tangents of A, B, C, D
+// and the weights as well. Once per problem X = rollout(x0, U), Z = rollout(0, U) (as phase 6 above) and the costate pi
+// (stationarity_costate); per pass the rollout of a. has its forcing term and carries zs in a second slot where a P-only
+// term reads it, the sweep of b. starts from gX = -c, gU = -g (the step's g staged in LDS one step ahead, as d. stages
+// s_k), and dh has its two more terms (tangent_c, tangent_g, tangent_dh of mpcqp_adjoint_common.h).
+template <bool kSLds, bool kModel>
+__global__ void __launch_bounds__(BS)
+mpcqp_tangent_stagewise_kernel(const typename std::conditional<kModel, StagewiseTangentModelLaunch, StagewiseTangentLaunch>::type a)
 {
     extern __shared__ double s_dyn[];
     __shared__ double sm[kSmDoubles];
@@ -513,7 +529,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
     const int64_t b = blockIdx.x;
     const int nx = a.nx, nu = a.nu, N = a.N, mk = a.mk, n = a.n, m = a.m, T = a.ntan;
     const int R = (N + 1) * nx;
-    const SwTanCarve cv = make_tan_carve(nx, nu, N, a.ka, T);
+    const SwTanCarve cv = make_tan_carve(nx, nu, N, a.ka, T, kModel);
     double *base = a.workspace + b * cv.total;
     double *rec = base + cv.rec, *Y = base + cv.Y, *S = kSLds ? s_dyn : base + cv.S;
     double *xs = base + cv.xs, *mu = base + cv.mu;
@@ -527,6 +543,8 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
     double *dU = a.dU + b * (int64_t)T * n;
     double *dX = a.dX ? a.dX + b * (int64_t)T * R : nullptr;
     const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+    const bool has_xs = kModel || dx0;  // xs holds the tangents' rollouts (else they are zero)
+    ModelTanVecs mv{};
 
     int verdict = a.status[b];
     int k = 0;
@@ -541,10 +559,43 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
         gram_rows(Y, idx, k, mk, nu, n, S, cv.ldS, nullptr, nullptr);
         if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
     }
+    if constexpr (kModel) {
+        if (verdict == 0) {
+            // X = rollout(x0, U), Z = rollout(0, U), then the costate pi
+            double *X = base + cv.X, *Zf = base + cv.Zf, *pi = base + cv.pi;
+            const double *U = a.U + b * (int64_t)n;
+            const double *x0 = (const double *)a.problem.x0.ptr + b * a.problem.x0.batch_stride;
+            if (tid < nx) {
+                X[tid] = x0[tid];
+                Zf[tid] = 0.0;
+            }
+            __syncthreads();
+            for (int kk = 0; kk < N; ++kk) {
+                const double *Ak = op_step(a.problem.A, b, kk), *Bk = op_step(a.problem.B, b, kk);
+                if (tid < 2 * nx) {
+                    double *x = tid < nx ? X : Zf;
+                    const int i = tid % nx;
+                    double acc = 0.0;
+                    for (int l = 0; l < nx; ++l) acc += Ak[i * nx + l] * x[kk * nx + l];
+                    for (int c = 0; c < nu; ++c) acc += Bk[i * nu + c] * U[kk * nu + c];
+                    x[(kk + 1) * nx + i] = acc;
+                }
+                __syncthreads();
+            }
+            mv = ModelTanVecs{tan_at(a.mtan.dA, a.mtan.dA_stride, b), tan_at(a.mtan.dB, a.mtan.dB_stride, b),
+                              tan_at(a.mtan.dC, a.mtan.dC_stride, b), tan_at(a.mtan.dD, a.mtan.dD_stride, b),
+                              tan_at(a.mtan.dw, a.mtan.dw_stride, b), X, Zf, pi, U, lam,
+                              qt ? (const double *)a.problem.goal.ptr + b * a.problem.goal.batch_stride : nullptr,
+                              qs ? (const double *)a.problem.targets.ptr + b * a.problem.targets.batch_stride : nullptr};
+            stationarity_costate<BS>(a, a.problem.A, a.problem.C, b, mv, pi);
+        }
+    }
     if (verdict == 0) {
         const int Wd = nx > nu ? nx : nu, slots = BS / Wd, sl = tid / Wd, i = tid % Wd;
-        const int ls = nx + nu;  // a slot's LDS: the carried state, then the step's s_k (phase d)
+        const int ls = nx + nu;  // a slot's LDS: the carried state, then the step's s_k (phase d) or g_k (phase b, kModel)
         double *buf = sm;        // 2 x kPassLds (the Riccati scratch is free now)
+        double *zbuf = sm + 2 * kPassLds;  // kModel: 2 x kPassLds more, the carried zs
+        const bool with_zs = kModel && tangent_needs_zs(a.flags);
         for (int t0 = 0; t0 < T; t0 += slots) {
             const int tg = T - t0 < slots ? T - t0 : slots;
             const bool on = sl < tg;
@@ -552,8 +603,38 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
             double *xst = xs + (int64_t)(on ? sl : 0) * R, *dUt = dU + tt * n, *dXt = dX ? dX + tt * R : nullptr;
             const double *x0t = dx0 ? dx0 + tt * nx : nullptr, *glt = dgoal ? dgoal + tt * nx : nullptr;
             const double *tgt = dtgt ? dtgt + tt * N * nx : nullptr;
+            double *zst = base + cv.zs + (int64_t)(on ? sl : 0) * R;  // (kModel)
             // a. xs = rollout(dx0, 0)
-            if (dx0) {
+            if constexpr (kModel) {
+                // ... with the forcing term dA_k X_k + dB_k u_k, and zs the same from 0 with Z_k
+                if (on && i < nx) {
+                    const double x = x0t ? x0t[i] : 0.0;
+                    buf[sl * ls + i] = x;
+                    xst[i] = x;
+                    if (with_zs) {
+                        zbuf[sl * ls + i] = 0.0;
+                        zst[i] = 0.0;
+                    }
+                }
+                __syncthreads();
+                for (int kk = 0; kk < N; ++kk) {
+                    const int cb = (kk & 1) * kPassLds + sl * ls, nb = ((kk + 1) & 1) * kPassLds + sl * ls;
+                    if (on && i < nx) {
+                        const double *Ak = op_step(a.problem.A, b, kk);
+                        double acc = tangent_forcing(a, mv, mv.X, (int)tt, kk, i);
+                        for (int l = 0; l < nx; ++l) acc += Ak[i * nx + l] * buf[cb + l];
+                        buf[nb + i] = acc;
+                        xst[(kk + 1) * nx + i] = acc;
+                        if (with_zs) {
+                            double az = tangent_forcing(a, mv, mv.Zf, (int)tt, kk, i);
+                            for (int l = 0; l < nx; ++l) az += Ak[i * nx + l] * zbuf[cb + l];
+                            zbuf[nb + i] = az;
+                            zst[(kk + 1) * nx + i] = az;
+                        }
+                    }
+                    __syncthreads();
+                }
+            } else if (dx0) {
                 if (on && i < nx) {
                     const double x = x0t[i];
                     buf[sl * ls + i] = x;
@@ -574,30 +655,64 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
                 }
             }
             // b. r = -L^-1 Psi' c into dU (lane i reads back the xs components it wrote itself)
-            if (on && i < nx) {
-                double c = 0.0;
-                if (qt) c = a.wt * ((dx0 ? xst[N * nx + i] : 0.0) - (glt ? glt[i] : 0.0));
-                buf[sl * ls + i] = -c;
-            }
-            __syncthreads();
-            for (int kk = N - 1; kk >= 0; --kk) {
-                const double *cur = buf + ((N - 1 - kk) & 1) * kPassLds + sl * ls;
-                double *nxt = buf + ((N - kk) & 1) * kPassLds + sl * ls;
+            if constexpr (kModel) {
+                // ... r = -L^-1 (Psi' c + g): phase 2's sweep with gX = -c, gU = -g
                 if (on) {
-                    const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
-                    if (i < nu) {
-                        double acc = 0.0;
-                        for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
-                        dUt[kk * nu + i] = acc;
-                    }
                     if (i < nx) {
-                        double acc = 0.0;
-                        if (qs) acc = -a.wx * ((dx0 ? xst[kk * nx + i] : 0.0) - (tgt ? tgt[kk * nx + i] : 0.0));
-                        for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
-                        nxt[i] = acc;
+                        const int e = N * nx + i;
+                        buf[sl * ls + i] = -tangent_c(a, mv, (int)tt, e, xst[e], with_zs ? zst[e] : 0.0, tgt, glt);
                     }
+                    if (i < nu) buf[sl * ls + nx + i] = -tangent_g(a, mv, (int)tt, (N - 1) * nu + i);
                 }
                 __syncthreads();
+                for (int kk = N - 1; kk >= 0; --kk) {
+                    const double *cur = buf + ((N - 1 - kk) & 1) * kPassLds + sl * ls, *rk_ = cur + nx;
+                    double *nxt = buf + ((N - kk) & 1) * kPassLds + sl * ls;
+                    if (on) {
+                        const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
+                        if (i < nu) {
+                            double acc = 0.0;
+                            for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
+                            for (int l = 0; l <= i; ++l) acc += rk.Li[i * nu + l] * rk_[l];
+                            dUt[kk * nu + i] = acc;
+                            if (kk > 0) nxt[nx + i] = -tangent_g(a, mv, (int)tt, (kk - 1) * nu + i);
+                        }
+                        if (i < nx) {
+                            const int e = kk * nx + i;
+                            double acc = -tangent_c(a, mv, (int)tt, e, xst[e], with_zs ? zst[e] : 0.0, tgt, glt);
+                            for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
+                            for (int c = 0; c < nu; ++c) acc -= rk.K[c * nx + i] * rk_[c];
+                            nxt[i] = acc;
+                        }
+                    }
+                    __syncthreads();
+                }
+            } else {
+                if (on && i < nx) {
+                    double c = 0.0;
+                    if (qt) c = a.wt * ((dx0 ? xst[N * nx + i] : 0.0) - (glt ? glt[i] : 0.0));
+                    buf[sl * ls + i] = -c;
+                }
+                __syncthreads();
+                for (int kk = N - 1; kk >= 0; --kk) {
+                    const double *cur = buf + ((N - 1 - kk) & 1) * kPassLds + sl * ls;
+                    double *nxt = buf + ((N - kk) & 1) * kPassLds + sl * ls;
+                    if (on) {
+                        const Rec rk = rec_at(rec, kk, cv.rs, nx, nu);
+                        if (i < nu) {
+                            double acc = 0.0;
+                            for (int l = 0; l < nx; ++l) acc += rk.Fn[i * nx + l] * cur[l];
+                            dUt[kk * nu + i] = acc;
+                        }
+                        if (i < nx) {
+                            double acc = 0.0;
+                            if (qs) acc = -a.wx * ((dx0 ? xst[kk * nx + i] : 0.0) - (tgt ? tgt[kk * nx + i] : 0.0));
+                            for (int l = 0; l < nx; ++l) acc += rk.Acl[l * nx + i] * cur[l];
+                            nxt[i] = acc;
+                        }
+                    }
+                    __syncthreads();
+                }
             }
             if (k > 0) {
                 // c. mu = Y_A r - dh_A = Y_A r + (C xs)_A - de_A: one wavefront per (row, tangent), lanes along the row's
@@ -609,9 +724,12 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
                     const int len = (ja + 1) * nu;
                     double acc = 0.0;
                     for (int c = lane; c < len; c += 64) acc += ya[c] * rt[c];
-                    if (dx0 && a.problem.C.ptr && lane < nx)
+                    if (has_xs && a.problem.C.ptr && lane < nx)
                         acc += op_step(a.problem.C, b, ja)[(row - ja * mk) * nx + lane] * xs[(int64_t)g * R + ja * nx + lane];
                     acc = wave_sum(acc);
+                    if constexpr (kModel) {
+                        if (lane == 0) acc += tangent_dh(a, mv, t0 + g, row);
+                    }
                     if (lane == 0) mu[g * cv.ldS + ra] = acc - (de ? de[(int64_t)(t0 + g) * m + row] : 0.0);
                 }
                 __syncthreads();
@@ -654,7 +772,7 @@ __global__ void __launch_bounds__(BS) mpcqp_tangent_stagewise_kernel(const Stage
                         for (int l = 0; l < nx; ++l) acc += rk.Acl[i * nx + l] * cur[l];
                         for (int c = 0; c < nu; ++c) acc += rk.Bw[i * nu + c] * sk[c];
                         nxt[i] = acc;
-                        if (dXt) dXt[(kk + 1) * nx + i] = (dx0 ? xst[(kk + 1) * nx + i] : 0.0) + acc;
+                        if (dXt) dXt[(kk + 1) * nx + i] = (has_xs ? xst[(kk + 1) * nx + i] : 0.0) + acc;
                     }
                 }
                 __syncthreads();
@@ -686,17 +804,26 @@ int launch_adjoint_stagewise(const StagewiseAdjointLaunch &l, int64_t batch, hip
 }
 
 // per problem: the records, the whitened rows, S beyond LDS, the row ids and one pass of tangents' scratch
-size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan)
+size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan, bool model)
 {
-    return (size_t)make_tan_carve(nx, nu, N, max_active > 0 ? max_active : 1, ntan).total * sizeof(double);
+    return (size_t)make_tan_carve(nx, nu, N, max_active > 0 ? max_active : 1, ntan, model).total * sizeof(double);
 }
 
 int launch_tangent_stagewise(const StagewiseTangentLaunch &l, int64_t batch, hipStream_t st)
 {
     if (!l.workspace) return MPCQP_EWORKSPACE;
     if (s_in_lds(l.ka))
-        return launch_per_problem(mpcqp_tangent_stagewise_kernel<true>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
-    return launch_per_problem(mpcqp_tangent_stagewise_kernel<false>, l, BS, 0, batch, st);
+        return launch_per_problem(mpcqp_tangent_stagewise_kernel<true, false>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
+    return launch_per_problem(mpcqp_tangent_stagewise_kernel<false, false>, l, BS, 0, batch, st);
+}
+
+int launch_tangent_model_stagewise(const StagewiseTangentModelLaunch &l, int64_t batch, hipStream_t st)
+{
+    if (!l.workspace) return MPCQP_EWORKSPACE;
+    if (!l.U) return MPCQP_EINVAL;
+    if (s_in_lds(l.ka))
+        return launch_per_problem(mpcqp_tangent_stagewise_kernel<true, true>, l, BS, (size_t)l.ka * (l.ka | 1) * sizeof(double), batch, st);
+    return launch_per_problem(mpcqp_tangent_stagewise_kernel<false, true>, l, BS, 0, batch, st);
 }
 
 }  // namespace mpcqp

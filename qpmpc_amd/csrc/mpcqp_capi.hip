@@ -1157,16 +1157,35 @@ constexpr int32_t kMaxTangents = 256;
 
 // mpcqp_plan_jvp_batch's workspace: mpcqp_plan_vjp_batch's condensed segments, then the tangent carves when they do not
 // fit LDS
-static int jvp_plan(const MpcqpDims *dims, int64_t batch, int32_t ntan, VjpPlan &v)
+// (model: the longer carve of the kModel kernel, mpcqp_plan_jvp_model_batch)
+static int jvp_plan(const MpcqpDims *dims, int64_t batch, int32_t ntan, VjpPlan &v, bool model = false)
 {
     const int rc = condensed_plan(dims, batch, v);
     if (rc) return rc;
     if (ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
     const int n = dims->N * dims->nu;
-    const bool lds = tangent_carve_in_lds(n, dims->N, dims->nx, ntan);
-    v.gx0 = v.carve + (lds ? 0 : al256((int64_t)tangent_carve_bytes(n, dims->N, dims->nx, ntan) * batch));
+    const bool lds = tangent_carve_in_lds(n, dims->N, dims->nx, ntan, model);
+    v.gx0 = v.carve + (lds ? 0 : al256((int64_t)tangent_carve_bytes(n, dims->N, dims->nx, ntan, model) * batch));
     v.total = v.gx0;  // (no g_x0 segment)
     return 0;
+}
+
+static bool tangents_ok(const MpcqpTangents *t)
+{
+    return t->dx0_stride >= 0 && t->dgoal_stride >= 0 && t->dtargets_stride >= 0 && t->de_stride >= 0;
+}
+
+// what the two model exports ask of their tangents: one of the structures, a tangent in one of them, no negative stride.
+// `tan` and `mtan` come back as copies (zeroed where NULL), `model` as whether mtan holds a tangent.
+static bool model_tangents_ok(const MpcqpTangents *tan_in, const MpcqpModelTangents *mtan_in, MpcqpTangents &tan,
+                              MpcqpModelTangents &mtan, bool &model)
+{
+    tan = tan_in ? *tan_in : MpcqpTangents{};
+    mtan = mtan_in ? *mtan_in : MpcqpModelTangents{};
+    model = mtan.dA || mtan.dB || mtan.dC || mtan.dD || mtan.dw;
+    const bool any = model || tan.dx0 || tan.dgoal || tan.dtargets || tan.de;
+    return any && tangents_ok(&tan) && mtan.dA_stride >= 0 && mtan.dB_stride >= 0 && mtan.dC_stride >= 0 &&
+           mtan.dD_stride >= 0 && mtan.dw_stride >= 0;
 }
 }  // namespace
 
@@ -1199,6 +1218,45 @@ int mpcqp_plan_jvp_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int
     l.dX = (double *)dX;
     l.jvp_status = jvp_status;
     return launch_tangent(l, batch, (hipStream_t)stream);
+}
+
+int mpcqp_plan_jvp_model_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t ntan, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    VjpPlan v;
+    const int rc = jvp_plan(dims, batch, ntan, v, true);
+    if (rc) return rc;
+    *bytes = (size_t)v.total;
+    return 0;
+}
+
+int mpcqp_plan_jvp_model_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, int32_t ntan,
+                               const void *lam, const int32_t *status, const void *U, const MpcqpTangents *tan,
+                               const MpcqpModelTangents *mtan, void *dU, void *dX, int32_t *jvp_status, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    VjpPlan v;
+    int rc = jvp_plan(dims, batch, ntan, v, true);
+    if (rc) return rc;
+    TangentModelLaunch l{};
+    bool model = false;
+    const bool ok = model_tangents_ok(tan, mtan, l.tan, l.mtan, model) && dU && U;
+    if ((rc = condense_kkt(dims, problem, batch, lam, status, ok, v, workspace, workspace_bytes, stream, l.kkt)) ||
+        batch == 0)
+        return rc;
+    l.ntan = ntan;
+    l.dU = (double *)dU;
+    l.dX = (double *)dX;
+    l.jvp_status = jvp_status;
+    // without a model tangent: mpcqp_plan_jvp_batch's launch (its carve fits wherever the longer one does)
+    if (!model) return launch_tangent(l, batch, (hipStream_t)stream);
+    if (dims->mk == 0) l.mtan.dC = l.mtan.dD = nullptr;
+    l.A = problem->A;
+    l.x0 = problem->x0;
+    l.goal = problem->goal;
+    l.targets = problem->targets;
+    l.U = (const double *)U;
+    return launch_tangent_model(l, batch, (hipStream_t)stream);
 }
 
 namespace {
@@ -1274,13 +1332,42 @@ int mpcqp_plan_vjp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
 
 namespace {
 // mpcqp_plan_jvp_stagewise_batch's workspace: one region per problem (mpcqp_adjoint_stagewise.hip's tangent carve)
-static int jvp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, int32_t ntan, size_t &total)
+// (model: the longer region of the kModel kernel, mpcqp_plan_jvp_model_stagewise_batch)
+static int jvp_stagewise_plan(const MpcqpDims *dims, int64_t batch, int32_t max_active, int32_t ntan, size_t &total,
+                              bool model = false)
 {
     const int rc = stagewise_checks(dims, batch, max_active);
     if (rc) return rc;
     if (ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
-    total = (size_t)al256((int64_t)stagewise_tangent_bytes(dims->nx, dims->nu, dims->N, max_active, ntan) * batch);
+    total = (size_t)al256((int64_t)stagewise_tangent_bytes(dims->nx, dims->nu, dims->N, max_active, ntan, model) * batch);
     return 0;
+}
+
+// the fields of a stage-wise tangent launch that both exports fill alike
+static void fill_stagewise_tangent(StagewiseTangentLaunch &l, const MpcqpDims *dims, const MpcqpProblem *problem,
+                                   int32_t max_active, int32_t ntan, const void *lam, const int32_t *status, void *dU,
+                                   void *dX, int32_t *jvp_status, void *workspace)
+{
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.n = dims->N * dims->nu;
+    l.m = dims->N * dims->mk;
+    l.flags = dims->flags;
+    l.ka = max_active > 0 ? max_active : 1;
+    l.ntan = ntan;
+    l.wt = dims->w_terminal;
+    l.wx = dims->w_stage;
+    l.wu = dims->w_input;
+    l.problem = *problem;
+    l.lam = dims->mk > 0 ? (const double *)lam : nullptr;
+    l.status = status;
+    if (dims->mk == 0) l.tan.de = nullptr;
+    l.dU = (double *)dU;
+    l.dX = (double *)dX;
+    l.jvp_status = jvp_status;
+    l.workspace = (double *)workspace;
 }
 }  // namespace
 
@@ -1310,28 +1397,44 @@ int mpcqp_plan_jvp_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *pr
     if (batch == 0) return 0;
     if (!workspace || workspace_bytes < total) return MPCQP_EWORKSPACE;
     StagewiseTangentLaunch l{};
-    l.nx = dims->nx;
-    l.nu = dims->nu;
-    l.N = dims->N;
-    l.mk = dims->mk;
-    l.n = dims->N * dims->nu;
-    l.m = dims->N * dims->mk;
-    l.flags = dims->flags;
-    l.ka = max_active > 0 ? max_active : 1;
-    l.ntan = ntan;
-    l.wt = dims->w_terminal;
-    l.wx = dims->w_stage;
-    l.wu = dims->w_input;
-    l.problem = *problem;
-    l.lam = dims->mk > 0 ? (const double *)lam : nullptr;
-    l.status = status;
     l.tan = *tan;
-    if (dims->mk == 0) l.tan.de = nullptr;
-    l.dU = (double *)dU;
-    l.dX = (double *)dX;
-    l.jvp_status = jvp_status;
-    l.workspace = (double *)workspace;
+    fill_stagewise_tangent(l, dims, problem, max_active, ntan, lam, status, dU, dX, jvp_status, workspace);
     return launch_tangent_stagewise(l, batch, (hipStream_t)stream);
+}
+
+int mpcqp_plan_jvp_model_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active,
+                                                   int32_t ntan, size_t *bytes)
+{
+    if (!bytes) return MPCQP_EINVAL;
+    size_t total = 0;
+    const int rc = jvp_stagewise_plan(dims, batch, max_active, ntan, total, true);
+    if (rc) return rc;
+    *bytes = total;
+    return 0;
+}
+
+int mpcqp_plan_jvp_model_stagewise_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
+                                         int32_t max_active, int32_t ntan, const void *lam, const int32_t *status,
+                                         const void *U, const MpcqpTangents *tan, const MpcqpModelTangents *mtan,
+                                         void *dU, void *dX, int32_t *jvp_status, void *workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    size_t total = 0;
+    int rc = jvp_stagewise_plan(dims, batch, max_active, ntan, total, true);
+    if (rc) return rc;
+    if ((rc = check_problem(dims, problem))) return rc;
+    StagewiseTangentModelLaunch l{};
+    bool model = false;
+    if (!model_tangents_ok(tan, mtan, l.tan, l.mtan, model) || !status || !dU || !U || (dims->mk > 0 && !lam))
+        return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    if (!workspace || workspace_bytes < total) return MPCQP_EWORKSPACE;
+    fill_stagewise_tangent(l, dims, problem, max_active, ntan, lam, status, dU, dX, jvp_status, workspace);
+    // without a model tangent: mpcqp_plan_jvp_stagewise_batch's launch (its regions fit in the longer ones)
+    if (!model) return launch_tangent_stagewise(l, batch, (hipStream_t)stream);
+    if (dims->mk == 0) l.mtan.dC = l.mtan.dD = nullptr;
+    l.U = (const double *)U;
+    return launch_tangent_model_stagewise(l, batch, (hipStream_t)stream);
 }
 
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch, const MpcqpSolveOpts *opts,

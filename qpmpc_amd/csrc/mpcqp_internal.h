@@ -306,9 +306,17 @@ struct TangentLaunch {
     double *dU, *dX;  // dX nullable
     int32_t *jvp_status;
 };
-size_t tangent_carve_bytes(int n, int N, int nx, int ntan);
-bool tangent_carve_in_lds(int n, int N, int nx, int ntan);
+size_t tangent_carve_bytes(int n, int N, int nx, int ntan, bool model = false);
+bool tangent_carve_in_lds(int n, int N, int nx, int ntan, bool model = false);
 int launch_tangent(const TangentLaunch &l, int64_t batch, hipStream_t st);
+// ... with tangents of A, B, C, D and the weights as well (mpcqp_plan_jvp_model_batch): the kModel kernel, which also reads
+// A, x0, goal, targets and the plan U. The kernel without them takes TangentLaunch as it always did.
+struct TangentModelLaunch : TangentLaunch {
+    MpcqpModelTangents mtan;
+    MpcqpOperand A, x0, goal, targets;
+    const double *U;
+};
+int launch_tangent_model(const TangentModelLaunch &l, int64_t batch, hipStream_t st);
 // the stage-wise adjoint (mpcqp_adjoint_stagewise.hip; float64, nx <= 32, nu <= 8, any N): one problem per workgroup on its
 // Riccati recursion, the records and the active rows' whitened vectors in a per-problem region of the workspace; passed to
 // the kernel as it is
@@ -339,8 +347,14 @@ struct StagewiseTangentLaunch {
     int32_t *jvp_status;
     double *workspace;  // batch * stagewise_tangent_bytes
 };
-size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan);  // per problem
+size_t stagewise_tangent_bytes(int nx, int nu, int N, int max_active, int ntan, bool model = false);  // per problem
 int launch_tangent_stagewise(const StagewiseTangentLaunch &l, int64_t batch, hipStream_t st);
+// ... with tangents of A, B, C, D and the weights as well (mpcqp_plan_jvp_model_stagewise_batch): the kModel kernel
+struct StagewiseTangentModelLaunch : StagewiseTangentLaunch {
+    MpcqpModelTangents mtan;
+    const double *U;
+};
+int launch_tangent_model_stagewise(const StagewiseTangentModelLaunch &l, int64_t batch, hipStream_t st);
 
 }  // namespace mpcqp
 #endif
