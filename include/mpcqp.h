@@ -172,7 +172,7 @@ typedef struct MpcqpProblem {
                                  takes it from more than two problems per SIMD of the device up: 2049 and more on an MI355X, where a
                                  wavefront per SIMD with four problems beats two wavefronts with two, and launches of several
                                  rounds keep two such wavefronts on every SIMD; smaller batches leave SIMDs idle either way;
-                                 problems of 33 .. 64 rows with nx <= 8 run on its four-rows-per-lane copy, mpcqp_quad4.hip, at
+                                 problems of 33 .. 64 rows with nx <= 8 run on its four-rows-per-lane build, mpcqp_quadg.hip, at
                                  every batch size).
                                  MPCQP_EUNSUPPORTED where the kernel does not apply (nx > 16, more than four rows per step -- eight with nx <= 8 --, warm
                                  starts, seed steps, a pairing order together with input rows / a stage cost). The shared-model solves (mpcqp_solve_model_batch / _bounds_batch) take

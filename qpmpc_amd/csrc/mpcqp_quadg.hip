@@ -1,15 +1,23 @@
-// mpcqp_quad4.hip -- gfx950: the four-problems-per-wavefront kernel of mpcqp_quad.hip for problems with MORE THAN 32 ROWS: n <= 16
-// variables, 33 <= m <= 64 inequality rows (three or four rows per step at N = 16: a state box next to an input box), nx <= 8, float64,
-// cold launches. Replaces the same reference code (qpmpc/mpc_qp.py:53-149 for the build, qpsolvers.solve_problem at
-// qpmpc/solve_mpc.py:43 for the solve); until the end of round 6 such problems fell to the workgroup / one-per-wavefront kernels,
-// 9-12 x slower than the same problem with two rows per step.
+// mpcqp_quadg.hip -- gfx950: the general four-problems-per-wavefront kernel with the constraint rows a lane holds as a template
+// parameter (ROWS). One problem per 16-lane DPP row, n <= 16 variables, float64, cold fused build+solve launches, every cost and
+// constraint layout: input rows D_k next to / instead of the state rows C_k, a stage cost with per-step targets, terminal cost, one to
+// eight rows per step. Replaces the same reference code as mpcqp_quad.hip (qpmpc/mpc_qp.py:53-149 for the build,
+// qpsolvers.solve_problem at qpmpc/solve_mpc.py:43 for the solve).
 //
-// Same method, same layout as mpcqp_quad.hip (read that file first: the comments below are its comments) with FOUR constraint rows per
-// lane instead of two -- rows l, l + 16, l + 32, l + 48 of M in registers, their slacks, norms and flags as arrays of four -- and the
-// selection key carrying a six-bit row id. It is a copy and not a template parameter of that kernel on purpose: renaming the tuned
-// kernel's per-row scalars to arrays alone cost the headline launch 2.4 % (profiles/HISTORY.md). One wavefront per SIMD at most
-// (~330 registers of the 512 a lone wavefront may hold); 49.9 KB of LDS per wavefront (M image 64 x 16), three wavefronts per CU.
-// Only the general build (GEN) in the one-round carve is instantiated.
+// Same method and layout as mpcqp_quad.hip (read that file first: layout, solver and the reasons for four problems per wavefront are
+// described there); the per-row state (slacks, norms, bounds, flags) is an array of ROWS entries. Instantiated with
+//   ROWS = 4: 33 <= m <= 64 or five to eight rows per step (a state box next to an input box at N = 16), nx = 2 .. 8 -- rows l, l + 16,
+//             l + 32, l + 48 of M in registers, a six-bit row id in the selection key. One wavefront per SIMD at most (~330 registers of
+//             the 512 a lone wavefront may hold); 49.9 KB of LDS per wavefront, three per CU (slim: 36.9 KB, four). Such problems fell to
+//             the workgroup / one-per-wavefront kernels before, 9-12 x slower than the same problem with two rows per step.
+// ROWS = 2 (m <= 32) compiles and is what the general build woven into mpcqp_quad.hip (its template parameter GEN) is to become; it is
+// not instantiated yet: its slim instantiations need 8 bytes more scratch than that build's (profiles/HISTORY.md, "One general
+// four-per-wavefront kernel"). The lean kernel stays out of this template for good: written with arrays instead of its scalars, with
+// the same arithmetic, the headline launch ran 2.4 % slower (profiles/HISTORY.md). The device helpers and the LDS carve both files use
+// are in mpcqp_quad_common.h.
+//
+// This source is compiled twice for the build time: as itself (nx = 2 .. 4) and, with MPCQP_QUADG_WIDE_UNIT defined, through
+// mpcqp_quadgw.hip (nx = 5 .. 8, the streamed build).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -17,213 +25,22 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_quad_common.h"
+
+#ifndef QUAD4_MKG
+#define QUAD4_MKG 8  // rows per step the build is unrolled for with four rows per lane
+#endif
 
 namespace mpcqp {
 
-namespace quad4 {
+using namespace quad;
 
-constexpr int NV = 16;    // padded number of variables / slots = lanes per problem
-constexpr int MMAX = 64;  // constraints a problem can hold (four per lane)
-constexpr int ROWS = 4;   // constraint rows per lane
-#ifndef QUAD4_MKG
-#define QUAD4_MKG 8       // rows per step the general build is unrolled for
-#endif
-// row stride of the M image: 18 (144 B: rows start in distinct 16-B slots, conflict-free stores) in the roomy carve, 16 in the slim one
-constexpr int MK = 2;     // inequality rows per step
-
-template <int CTRL> __device__ __forceinline__ unsigned dpp_u(unsigned x)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-constexpr int ROR8 = 0x128, ROR4 = 0x124, ROR2 = 0x122, ROR1 = 0x121;  // rotate within a row of 16
-
-// all-reduce (min) over the 16 lanes of each row
-__device__ __forceinline__ unsigned row_min(unsigned v)
-{
-    v = min(v, dpp_u<ROR8>(v));
-    v = min(v, dpp_u<ROR4>(v));
-    v = min(v, dpp_u<ROR2>(v));
-    v = min(v, dpp_u<ROR1>(v));
-    return v;
-}
-// value of lane `idx` (0..15; per lane, usually uniform inside a row) of the caller's own row
-__device__ __forceinline__ int row_get(int x, int rb, int idx) { return __builtin_amdgcn_ds_bpermute((rb + idx) << 2, x); }
-__device__ __forceinline__ double row_get(double x, int rb, int idx)
-{
-    const int a = (rb + idx) << 2;
-    const int lo = __builtin_amdgcn_ds_bpermute(a, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(a, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-// true in every lane of a row iff `pred` holds in one of its lanes
-__device__ __forceinline__ bool row_any(bool pred, int rb)
-{
-    const unsigned long long b = __ballot(pred);
-    return ((unsigned)(b >> rb) & 0xffffu) != 0u;
-}
-// order-preserving map of a double onto two unsigned words
-__device__ __forceinline__ void ordered(double x, unsigned &hi, unsigned &lo)
-{
-    const unsigned h = (unsigned)__double2hiint(x), l = (unsigned)__double2loint(x);
-    const bool neg = h & 0x80000000u;
-    hi = neg ? ~h : (h | 0x80000000u);
-    lo = neg ? ~l : l;
-}
-__device__ __forceinline__ void ld16(double (&d)[NV], const double *src)
-{
-    const double2 *p = reinterpret_cast<const double2 *>(src);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        const double2 t = p[i];
-        d[2 * i] = t.x;
-        d[2 * i + 1] = t.y;
-    }
-}
-__device__ __forceinline__ void st16(double *dst, const double (&s)[NV])
-{
-    double2 *p = reinterpret_cast<double2 *>(dst);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        double2 t;
-        t.x = s[2 * i];
-        t.y = s[2 * i + 1];
-        p[i] = t;
-    }
-}
-__device__ __forceinline__ double dot16(const double (&a)[NV], const double (&b)[NV])
-{
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; k += 4) {
-        acc0 += a[k] * b[k];
-        acc1 += a[k + 1] * b[k + 1];
-        acc2 += a[k + 2] * b[k + 2];
-        acc3 += a[k + 3] * b[k + 3];
-    }
-    return (acc0 + acc1) + (acc2 + acc3);
-}
-// two dot products with one vector, two chains each (a lone wavefront issues a dependent FMA every 8.5 cycles and an
-// independent one every 5.1: four chains in flight are enough, and accumulators are registers the loop does not have)
-__device__ __forceinline__ void dot16x2(const double (&a)[NV], const double (&b)[NV], const double (&x)[NV], double &ra, double &rb)
-{
-    double a0 = a[0] * x[0], a1 = a[1] * x[1], b0 = b[0] * x[0], b1 = b[1] * x[1];
-#pragma unroll
-    for (int k = 2; k < NV; k += 2) {
-        a0 = fma(a[k], x[k], a0);
-        b0 = fma(b[k], x[k], b0);
-        a1 = fma(a[k + 1], x[k + 1], a1);
-        b1 = fma(b[k + 1], x[k + 1], b1);
-    }
-    ra = a0 + a1;
-    rb = b0 + b1;
-}
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
-
-// The value held by lane N of the caller's 16-lane row, in every lane of that row (v_mov_b64_dpp row_newbcast:N).
-template <int N> __device__ __forceinline__ double row_bcast(double x) { return __builtin_amdgcn_mov_dpp(x, 0x150 + N, 0xf, 0xf, true); }
-// acc += (x of lane N of the caller's row) * m in ONE instruction (v_fmac_f64_dpp). The compiler cannot see inside the asm:
-// a register written by a VALU instruction needs two wait states before a DPP read, so every batch of these is preceded by
-// dpp_ready(x) on its broadcast source (tools/check_dpp_hazards.py verifies that on the assembly).
-template <int N> __device__ __forceinline__ void fmac_bcast(double &acc, double x, double m)
-{
-    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(m), "n"(N));
-}
-__device__ __forceinline__ void dpp_ready(double &x) { asm volatile("s_nop 1" : "+v"(x)); }
-// Compile-time loop: f(integral_constant<int, I>) for I = B .. E-1. The DPP lane select is an immediate, so the loops over lanes
-// are unrolled by the front end (a `switch` on an unrolled loop's counter is only folded AFTER the unroller has priced the
-// body with all sixteen cases in it -- the fused factorisation then exceeds the unroller's budget and stays a loop of jump tables).
-template <int I> using ic = std::integral_constant<int, I>;
-template <int B, int E, typename F> __device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (B < E) {
-        f(ic<B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-// sum_k (x_k of lane k of the caller's row) * m[k]: a dot product with a vector spread over the row's lanes, two chains
-__device__ __forceinline__ double dot_bcast(double x, const double (&m)[NV], double init)
-{
-    double a0 = init, a1 = 0.0;
-    dpp_ready(x);
-    static_for<0, NV / 2>([&](auto kk) {
-        constexpr int k = 2 * decltype(kk)::value;
-        fmac_bcast<k>(a0, x, m[k]);
-        fmac_bcast<k + 1>(a1, x, m[k + 1]);
-    });
-    return a0 + a1;
-}
-
-// 1/x from the hardware estimate plus two Newton steps (operands are never subnormal or zero when the result is used)
-__device__ __forceinline__ double fast_rcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    e = fma(-x, y, 1.0);
-    return fma(y, e, y);
-}
-// 1/sqrt(x) from the hardware estimate, one Newton step and one third-order step (x is a positive, normal number wherever the
-// result is used: a pivot of a positive definite matrix, a squared row norm; the library's rsqrt spends two thirds of its
-// instructions on subnormals and infinities)
-__device__ __forceinline__ double fast_rsqrt(double x)
-{
-    double y = __builtin_amdgcn_rsq(x);
-    double e = fma(-x * y, y, 1.0);
-    y = fma(0.5 * y, e, y);
-    e = fma(-x * y, y, 1.0);
-    return fma(y * e, fma(0.375, e, 0.5), y);
-}
-// The wavefronts of a workgroup share nothing and a wavefront's LDS operations complete in order: only the COMPILER has
-// to keep the order of an exchange (no s_barrier, no queue drain).
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// LDS carve of ONE problem, in doubles. Two of them, ONE wavefront per SIMD in both (the kernel holds 334 / 373 registers):
-//  * ROOMY (up to three wavefronts per CU): M image 64 x 16, the full L^-T image, a T image for the rare refinement, the leaving slot's
-//    row, the slots' constraint ids: 1560 doubles = 12.2 KB per problem, 49.9 KB per wavefront, three on a CU's 160 KB.
-//  * SLIM (launches beyond three wavefronts per CU: 3073 problems and more on an MI355X): the M image and the strict upper triangle of
-//    L^-T, packed (the diagonal stays in a register): 1152 doubles, 36.9 KB per wavefront, FOUR on a CU. Gone: the T image (T' rho by
-//    row sums over the lanes), the leaving slot's row (fetched from its lane by ds_bpermute in the rare drop trip), the slots' ids
-//    (DPP). 4096 problems with m = 64: 119 us roomy (two rounds of three per CU), 81 us slim (one round).
-template <bool SLIM> struct Carve {
-    static constexpr int LDM = 16;  // (64 x 16: three wavefronts of 49.9 KB on a CU; with 18 only two)
-    static constexpr int OFF_M = 0;  // build: G image by column, 16 x GS (GS = 65: 1040 doubles, over the start of the region behind the
-                                     // M image, which is not alive yet) | main: M image, 64 x LDM
-    static constexpr int OFF_LT = MMAX * LDM;  // roomy: rows of L^-T, 16 x 16 | slim: strict upper triangle by rows, packed: row l at
-                                               // l (31 - l) / 2, 15 - l entries
-    static constexpr int NLT = SLIM ? NV * (NV - 1) / 2 + 8 : NV * NV;  // (slim: eight spare doubles keep the G image inside the carve)
-    static constexpr int OFF_T = OFF_LT + NLT;                    // roomy only from here on: T by rows (refinement)
-    static constexpr int OFF_KA = OFF_T + NV * NV;                // the row of a leaving slot
-    static constexpr int OFF_ACT = OFF_KA + NV;                   // 16 int32: constraint held by each slot
-    static constexpr int PER = SLIM ? OFF_LT + NLT : OFF_ACT + NV / 2;  // 640 | 1112 doubles per problem
-    static_assert(NV * 65 <= PER, "the G image must fit the problem's carve");
-    static_assert(PER % 2 == 0 && (!SLIM || PER * 4 * 8 <= 40 * 1024), "16-byte alignment; slim: 40 KB per wavefront (four on a CU)");
-};
-
-constexpr double DEP = 1e-14;      // |z|^2 / |M_p|^2 below this: M_p depends on the active rows
-constexpr double DEP_FAST = 1e-6;  // K_p . M_p is trusted as |z|^2 only above this (mpcqp_pair.hip); |K_p|^2 otherwise
-
-// a[i] for a lane-uniform-per-row index i = 0 .. 3 (straight-line selects)
-template <typename X> __device__ __forceinline__ X pick(const X (&a)[4], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); }
-
-}  // namespace quad4
-
-using namespace quad4;
-
-// ORD: the launch carries a pairing order (MpcqpSolveOpts.order): row i of the launch takes problem order[i].
-// WPB: wavefronts per workgroup (they share nothing).
-// MODEL: the launch shares one factored model (mpcqp_factor_model: gA points at it); the per-problem vectors are x0, goal, targets and,
-//        optionally, the bounds e. No build, no factorisation: M, L^-T and the linear maps of h and w are read from the model.
-// GEN:   the build serves every cost and constraint layout of one to four rows per step (round 6): input rows D_k next to / instead of
-//        the state rows C_k, a stage cost w_x sum |x_k - xref_k|^2 (the Gram matrix accumulated over every Psi_k of the chain, as
-//        mpcqp_pair.hip's generic build does) -- the reference's own wheeled-inverted-pendulum example
-//        (examples/wheeled_inverted_pendulum.py:90-94: input box, stage + terminal cost) is of this kind.
-template <int NX, bool ORD, int WPB, bool SLIM, bool MODEL = false, bool GEN = false>
-__global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in both carves: ~330 registers)
-    mpcqp_quad4_kernel(const double *__restrict__ gA, const double *__restrict__ gB, const double *__restrict__ gC,
+// NX:   state dimension the build is unrolled for (nx = 7 .. 16: the padded sizes 8, 12, 16 of the streamed build).
+// ROWS: constraint rows per lane, 2 or 4.
+// SLIM: the small LDS carve (mpcqp_quad_common.h).
+template <int NX, int ROWS, bool SLIM>
+__global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four rows per lane: one wavefront per SIMD in both carves)
+    mpcqp_quadg_kernel(const double *__restrict__ gA, const double *__restrict__ gB, const double *__restrict__ gC,
                       const double *__restrict__ ge, const double *__restrict__ gx0, const double *__restrict__ ggoal,
                       const double *__restrict__ gtgt, double *__restrict__ oU, double *__restrict__ olam, int32_t *__restrict__ ostatus,
                       int32_t *__restrict__ oiters, const KernelArgs ka, const int64_t batch)
@@ -239,21 +56,17 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
                      "s"(batch));
     }
     const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
     const int rb = lane & 48;  // first lane of this row
     const int l = lane & 15;   // lane inside the row
-    int64_t prob = 4 * ((int64_t)blockIdx.x * WPB + wv) + (rb >> 4);
+    int64_t prob = 4 * (int64_t)blockIdx.x + (rb >> 4);
     const bool valid = prob < batch;  // a batch that is no multiple of four leaves rows idle: they repeat the last problem, store nothing
     prob = valid ? prob : batch - 1;
-    if constexpr (ORD) {  // (an index outside the batch is clamped: a bad order costs wrong pairings, never an access out of bounds)
-        const int64_t o = ka.order[prob];
-        prob = o < 0 ? 0 : (o >= batch ? batch - 1 : o);
-    }
-    using CV = Carve<SLIM>;
-    constexpr int LDM = CV::LDM, PER = CV::PER;
-    T *sm = (T *)smem_raw + (4 * wv + (rb >> 4)) * PER;
+    using CV = Carve<SLIM, ROWS>;
+    constexpr int MMAX = CV::MMAX, LDM = CV::LDM, PER = CV::PER;
+    constexpr int GS = CV::GS;  // the G image is stored by COLUMN with an odd stride
+    T *sm = (T *)smem_raw + (rb >> 4) * PER;
     const int n = ka.n, m = ka.m;
-    int rowi[ROWS];   // the constraints of this lane: rows l, l + 16, l + 32, l + 48
+    int rowi[ROWS];   // the constraints of this lane: rows l, l + 16 (, l + 32, l + 48)
     bool isc[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -261,7 +74,6 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         isc[r] = rowi[r] < m;
     }
     const T INF = HUGE_VAL;
-    constexpr int GS = 65;  // the G image is stored by COLUMN with an odd stride
     T *Gimg = sm + CV::OFF_M, *Ml = sm + CV::OFF_M;
     T *LTp = sm + CV::OFF_LT + (l * (31 - l)) / 2 - (l + 1);  // slim: LTp[k] = entry (l, k) of L^-T, k > l
     T *LTimg = sm + CV::OFF_LT, *Timg = sm + CV::OFF_T, *kAv = sm + CV::OFF_KA;  // roomy
@@ -281,7 +93,6 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
     bool notpd = false;
     T RM[ROWS][NV], RLt[NV];
     T wv_ = T(0);  // w = L^-1 q, component l
-    static_assert(!MODEL && GEN && !ORD, "mpcqp_quad4.hip: the general build only");
     {
     // ---------------------------------------------------------------- build (mpc_qp.py:53-114)
     T Pr[NV];  // row l of P, then of L
@@ -292,27 +103,33 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
     {
         // WIDE (round 6, NX = 8 / 12 / 16 as padded sizes for nx = 7 .. 16): the operands of a step do not fit registers for the whole
         // horizon -- they are streamed, two steps ahead of the chain, and the chain is a loop over the steps (see below)
-        constexpr bool WIDE = GEN && NX > 6;
+        constexpr bool WIDE = NX > 6;
         const int nx = WIDE ? ka.nx : NX;
         const int nu = ka.nu, N = ka.N;
-        // rows per step: two in the lean build; one to four in the general one (a run-time number: the chain's loops over the rows of
-        // a step are unrolled four wide behind wavefront-uniform tests)
-        constexpr int MKG = GEN ? QUAD4_MKG : MK;  // (this file: up to EIGHT rows per step -- m <= 64 holds them for horizons of up to eight steps)
-        const int mk = GEN ? ka.mk : MK;
-        auto stepof = [&](int row) { return mk == 2 ? row >> 1 : (mk == 1 ? row : (mk == 4 ? row >> 2 : (mk == 8 ? row >> 3 : row / mk))); };
+        // rows per step: a run-time number, one to MKG (the chain's loops over the rows of a step are unrolled MKG wide behind
+        // wavefront-uniform tests). Two rows per lane: up to four; four rows per lane: up to EIGHT -- m <= 64 holds them for horizons
+        // of up to eight steps
+        constexpr int MKG = ROWS == 2 ? 4 : QUAD4_MKG;
+        const int mk = ka.mk;
+        auto stepof = [&](int row) {
+            if constexpr (ROWS == 2)
+                return mk == 2 ? row >> 1 : (mk == 1 ? row : (mk == 4 ? row >> 2 : row / 3));
+            else
+                return mk == 2 ? row >> 1 : (mk == 1 ? row : (mk == 4 ? row >> 2 : (mk == 8 ? row >> 3 : row / mk)));
+        };
         const T *A = gA + prob * ka.A.batch_stride;
         const T *B = gB + prob * ka.B.batch_stride;
-        const bool hasC = !GEN || gC != nullptr;
+        const bool hasC = gC != nullptr;
         const T *Cm = hasC ? gC + prob * ka.C.batch_stride : A;  // (no state rows: the lanes load valid addresses, the products are dropped)
         const T *x0 = gx0 + prob * ka.x0.batch_stride;
         const T *goal = ggoal ? ggoal + prob * ka.goal.batch_stride : nullptr;
         const int sA = ka.A.step_stride ? nx * nx : 0, sB = ka.B.step_stride ? nx * nu : 0, sC = (hasC && ka.C.step_stride) ? mk * nx : 0;
         const bool termP = ka.flags & MPCQP_P_TERMINAL, termQ = (ka.flags & MPCQP_Q_TERMINAL) && goal;
-        // (GEN) input rows and the stage cost
-        const T *Dm = (GEN && ka.D.ptr) ? (const T *)ka.D.ptr + prob * ka.D.batch_stride : nullptr;
-        const T *tgt = (GEN && gtgt) ? gtgt + prob * ka.targets.batch_stride : nullptr;
-        const int sD = (GEN && ka.D.step_stride) ? mk * nu : 0;
-        const bool stageP = GEN && (ka.flags & MPCQP_P_STAGE), stageQ = GEN && (ka.flags & MPCQP_Q_STAGE) && tgt;
+        // input rows and the stage cost
+        const T *Dm = ka.D.ptr ? (const T *)ka.D.ptr + prob * ka.D.batch_stride : nullptr;
+        const T *tgt = gtgt ? gtgt + prob * ka.targets.batch_stride : nullptr;
+        const int sD = ka.D.step_stride ? mk * nu : 0;
+        const bool stageP = ka.flags & MPCQP_P_STAGE, stageQ = (ka.flags & MPCQP_Q_STAGE) && tgt;
         constexpr int NAe = NX * NX, NEe = NAe + MKG * NX;  // elements of [A_k | C_k]
         const int NEr = hasC ? NAe + mk * NX : NAe;          // ... that exist
         const bool col = (l < n);
@@ -340,8 +157,8 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         }
 #pragma unroll
         for (int r = 0; r < NX; ++r) bcol[r] = (col && r < nx) ? B[j * sB + (r < nx ? r : 0) * nu + ii] : T(0);
-        // (GEN) this lane's column of D_j: the G entries of its variable, rows (j, 0) and (j, 1). Lane 15's cells of the image carry
-        // the free response through the chain: when it owns a variable (n = 16: an input of the LAST step) the two rows of that step
+        // This lane's column of D_j: the G entries of its variable, rows (j, 0) .. (j, mk - 1). Lane 15's cells of the image carry
+        // the free response through the chain: when it owns a variable (n = 16: an input of the LAST step) the rows of that step
         // fetch its entries of D straight from memory, behind the chain. Targets: lane e keeps xref element e, e + 16, e + 32, e + 48
         // (N nx <= 64), the chain fetches them as row broadcasts.
         T dcol[MKG], d15[ROWS], tg[NX];  // (targets: N nx <= 16 nx values, one per lane and register)
@@ -351,7 +168,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         for (int r = 0; r < ROWS; ++r) d15[r] = T(0);
 #pragma unroll
         for (int i2 = 0; i2 < MKG; ++i2) dcol[i2] = T(0);
-        if constexpr (GEN) {
+        {
             if (Dm) {
 #pragma unroll
                 for (int i2 = 0; i2 < MKG; ++i2) dcol[i2] = (col && !xl15 && i2 < mk) ? Dm[j * sD + i2 * nu + ii] : T(0);
@@ -369,7 +186,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         if constexpr (!WIDE) {
         // lane e of the row keeps element e (and e + 16) of [A_k | C_k] for every step k, straight from HBM; the chain
         // fetches an operand as a DPP row broadcast (lanes without an element load a valid address and are never read)
-        constexpr int NOP = (NEe + 15) / 16;  // operand registers per step: two up to nx = 4, three / four for nx = 5 / 6
+        constexpr int NOP = (NEe + 15) / 16;  // operand registers per step (ROWS = 2: two up to nx = 4, three / four for nx = 5 / 6)
         T op[NOP][NV];
         static_for<0, NOP>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
@@ -398,39 +215,26 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         static_for<0, NV>([&](auto kk) {
             constexpr int k = decltype(kk)::value;
             if (k < N) {
-                static_for<0, NOP>([&](auto rc) { dpp_ready(op[decltype(rc)::value][k]); });  // (as in the streamed build below)
+                // (four rows per lane: the operands pinned as in the streamed build below -- that kernel runs on more than 256
+                // registers. Two rows per lane: the all-steps build stays within the vector registers, no pin)
+                if constexpr (ROWS == 4) static_for<0, NOP>([&](auto rc) { dpp_ready(op[decltype(rc)::value][k]); });
                 // (lane 15 stores C_k Phi_k x0 into column 15 of the image -- zero in G by construction --: the rows read their
                 // entry of it behind the chain)
-                if constexpr (!GEN) {
-                    T g[MK];
-                    static_for<0, MK>([&](auto i2c) {
-                        constexpr int i2 = decltype(i2c)::value;
+                static_for<0, MKG>([&](auto i2c) {
+                    constexpr int i2 = decltype(i2c)::value;
+                    if (i2 < mk) {  // (wavefront-uniform)
                         T acc = T(0);
-                        static_for<0, NX>([&](auto sc) {
-                            constexpr int s2 = decltype(sc)::value;
-                            mac(ic<NAe + i2 * NX + s2>{}, kk, acc, v[s2]);
-                        });
-                        g[i2] = acc;
-                    });
-#pragma unroll
-                    for (int i2 = 0; i2 < MK; ++i2) Gimg[l * GS + k * MK + i2] = g[i2];
-                } else {
-                    static_for<0, MKG>([&](auto i2c) {
-                        constexpr int i2 = decltype(i2c)::value;
-                        if (i2 < mk) {  // (wavefront-uniform)
-                            T acc = T(0);
-                            if (hasC) {
-                                static_for<0, NX>([&](auto sc) {
-                                    constexpr int s2 = decltype(sc)::value;
-                                    mac(ic<NAe + i2 * NX + s2>{}, kk, acc, v[s2]);
-                                });
-                            }
-                            acc += (j == k) ? dcol[i2] : T(0);
-                            Gimg[l * GS + k * mk + i2] = acc;
+                        if (hasC) {
+                            static_for<0, NX>([&](auto sc) {
+                                constexpr int s2 = decltype(sc)::value;
+                                mac(ic<NAe + i2 * NX + s2>{}, kk, acc, v[s2]);
+                            });
                         }
-                    });
-                }
-                if constexpr (GEN && k >= 1) {
+                        acc += (j == k) ? dcol[i2] : T(0);
+                        Gimg[l * GS + k * mk + i2] = acc;
+                    }
+                });
+                if constexpr (k >= 1) {
                     // stage cost on x_k: P += w_x Psi_k' Psi_k, q += w_x Psi_k' (Phi_k x0 - xref_k)  (mpc_qp.py:99-105, 129-149; lane 15's
                     // own column is zero in every Psi_k of the chain, its registers hold the free response)
                     if (stageP || stageQ) {
@@ -586,24 +390,22 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         wsync();  // the G image is complete
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) hval[r] = isc[r] ? evl[r] - Gimg[(NV - 1) * GS + rowi[r]] : INF;  // h_i = e_i - C_k Phi_k x0 (column 15 of the image)
-        if constexpr (GEN) {  // (column 15 of G: the last step's input rows)
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) g15[r] = d15[r];
-        }
+        for (int r = 0; r < ROWS; ++r) g15[r] = d15[r];  // (column 15 of G: the last step's input rows)
     }
     tick(1);
     // ------------------------------------------------------------ factorise + forward substitution, one pass
     // Right-looking Cholesky; step j scales column j of L and applies it at once to everything that waits for it:
     //   P[:, k] -= L[:, j] L[k][j]                       (trailing columns of P)
-    //   x[k]    -= (x[j] / L_jj) L[k][j], x[j] /= L_jj   for the rows x = G_l, G_{l+16}, e_l: -> M_l, M_{l+16}, (L^-T)_l
+    //   x[k]    -= (x[j] / L_jj) L[k][j], x[j] /= L_jj   for the rows x = G_l, G_{l+16}, .., e_l: -> M_l, M_{l+16}, .., (L^-T)_l
     //   q_k     -= L[k][j] w_j, w_j = q_j / L_jj         (q_k in lane k: L[k][j] is local, w_j the broadcast)
-    // L[k][j] of lane k is a DPP row broadcast; the four FMA streams are independent of each other.
+    // L[k][j] of lane k is a DPP row broadcast; the ROWS + 2 FMA streams are independent of each other.
     {
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
             // (column 15 of G is zero: the column of the horizon's last step, or of no variable -- its cells hold the free response)
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) RM[r][k] = (isc[r] && k < NV - 1) ? Gimg[k * GS + rowi[r]] : (GEN && k == NV - 1 ? g15[r] : T(0));
+            for (int r = 0; r < ROWS; ++r) RM[r][k] = (isc[r] && k < NV - 1) ? Gimg[k * GS + rowi[r]] : (k == NV - 1 ? g15[r] : T(0));
             RLt[k] = (l == k) ? T(1) : T(0);
         }
         static_for<0, NV>([&](auto jc) {
@@ -621,22 +423,23 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
             wv_ = (l == j) ? wj : wv_;
             {
                 T src = pij, wsrc = wj;
-                asm volatile("s_nop 1" : "+v"(src), "+v"(nl), "+v"(wsrc) : "v"(RM[0][j]), "v"(RM[1][j]), "v"(RM[2][j]), "v"(RM[3][j]), "v"(RLt[j]));  // (the DPP wait states)
+                // (the DPP wait states)
+                if constexpr (ROWS == 2)
+                    asm volatile("s_nop 1" : "+v"(src), "+v"(nl), "+v"(wsrc) : "v"(RM[0][j]), "v"(RM[1][j]), "v"(RLt[j]));
+                else
+                    asm volatile("s_nop 1" : "+v"(src), "+v"(nl), "+v"(wsrc) : "v"(RM[0][j]), "v"(RM[1][j]), "v"(RM[2][j]), "v"(RM[3][j]), "v"(RLt[j]));
                 fmac_bcast<j>(qa, wsrc, nl);  // q_k -= L[k][j] w_j (lanes k <= j hold values nobody reads again)
                 static_for<j + 1, NV>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     fmac_bcast<k>(Pr[k], src, nt2);     // P[k][j] from lane k
-                    fmac_bcast<k>(RM[0][k], nl, RM[0][j]);  // -L[k][j] from lane k
-                    fmac_bcast<k>(RM[1][k], nl, RM[1][j]);
-                    fmac_bcast<k>(RM[2][k], nl, RM[2][j]);
-                    fmac_bcast<k>(RM[3][k], nl, RM[3][j]);
+                    static_for<0, ROWS>([&](auto rc) { fmac_bcast<k>(RM[decltype(rc)::value][k], nl, RM[decltype(rc)::value][j]); });  // -L[k][j] from lane k
                     fmac_bcast<k>(RLt[k], nl, RLt[j]);
                 });
             }
         });
         wsync();  // the M image below reuses the G image
     }
-    }  // (!MODEL)
+    }
     tick(2);
     tick(3);
     int status = MPCQP_MAX_ITER, iters = 0;
@@ -689,11 +492,11 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
     T lam = T(0);      // multiplier of slot l
     int myact = 0;     // constraint held by slot l
     bool occ = false;  // slot l occupied
+    // e: this lane's constraints may be selected: they have a bound and are not active (the slack of an active row is never read: it
+    // stays whatever the steps make of it, zero up to rounding)
     bool e[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) e[r] = sel[r];
-    // e: this lane's constraints may be selected: they have a bound and are not active (the slack of an
-                                // active row is never read: it stays whatever the steps make of it, zero up to rounding)
     // row-uniform state
     int nq = 0, p = 0, ldrop = 0;
     unsigned mask = 0;  // occupied slots
@@ -713,7 +516,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         for (int r = 0; r < ROWS; ++r) {
             const unsigned h = ~(unsigned)__double2hiint(s[r] * invn[r]);
             const bool v = want & e[r] & (s[r] < -tolh[r]);
-            const unsigned kk = v ? ((h & ~63u) | (unsigned)rowi[r]) : 0xffffffffu;
+            const unsigned kk = v ? ((h & ~(unsigned)(MMAX - 1)) | (unsigned)rowi[r]) : 0xffffffffu;  // (a five- / six-bit row id)
             kmin = min(kmin, kk);
         }
         const unsigned mkey = row_min(kmin);
@@ -721,7 +524,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
         const bool got = want & !none;
         done = done | none;
         status = none ? (int)MPCQP_SOLVED : status;
-        p = got ? (int)(mkey & 63u) : p;
+        p = got ? (int)(mkey & (unsigned)(MMAX - 1)) : p;
         up = got ? T(0) : up;
         needp = needp & !got;
     };
@@ -758,7 +561,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
             const bool drp = !done & dropping;  // ... or drops a slot
             const int pr = p >> 4;              // (row-uniform) which of the lane's registers row p is
             const int pl = p & 15;
-            // ---- r_a = T_a . M_p ; -z_l = H_l . M_p ; then -M_i . z = sum_k M_i[k] (-z_k) for this lane's two rows, with -z
+            // ---- r_a = T_a . M_p ; -z_l = H_l . M_p ; then -M_i . z = sum_k M_i[k] (-z_k) for this lane's rows, with -z
             //      spread over the row: the projected rows K_i = H M_i of mpcqp_pair.hip are NOT maintained (32 FMAs of update
             //      and 32 of dot products per trip against the 32 of these two)
             const T hd = dot16(RH, mp);
@@ -964,7 +767,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
             for (int a = 0; a < NV; ++a) ma[a] = Ml[aa[a] * LDM + l];
             return dot_bcast(cf, ma, T(0));
         };
-        // slacks of this lane's two rows at the point y (component k in lane k)
+        // slacks of this lane's rows at the point y (component k in lane k)
         T fresh[ROWS];
         auto slacks = [&](T yv) {
 #pragma unroll
@@ -1084,7 +887,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) lo[r] = T(0);
     if (olam) {  // multipliers by constraint: every occupied slot drops its multiplier at its row's place
-        T *lamv = Ml;  // (the M image is dead: every row has finished; 64 doubles)
+        T *lamv = Ml;  // (the M image is dead: every row has finished; MMAX doubles)
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) lamv[rowi[r]] = T(0);
         wsync();
@@ -1108,21 +911,7 @@ __global__ void __launch_bounds__(64 * WPB, 1)  // (one wavefront per SIMD in bo
 }
 
 // ------------------------------------------------------------ host side
-// cold launches of problems with n <= 16 and 33 .. 64 rows, or five to eight rows per step (m <= 64), nx <= 8 (the streamed build's
-// padded size 8 serves nx = 7, 8); everything else keeps the kernel it had
-#ifndef MPCQP_QUAD_WIDE_UNIT
-bool quad4_applies(const KernelArgs &ka)
-{
-    if (ka.n > NV || ka.m > MMAX || (ka.m <= 32 && ka.mk <= 4) || ka.nx < 2 || ka.nx > 8) return false;  // (m <= 32 with mk <= 4: mpcqp_quad.hip)
-    if (ka.mk < 1 || ka.mk > 8 || (!ka.C.ptr && !ka.D.ptr)) return false;
-    if (ka.N * ka.mk != ka.m || ka.N > NV) return false;
-    if (ka.warm_state || ka.order || (ka.opt_flags & (MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE))) return false;
-    return true;
-}
-
-#endif
-
-template <int NX> static int launch_quad4_t(const KernelArgs &ka, int64_t batch, hipStream_t st)
+template <int NX, int ROWS> static int launch_quadg_t(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
     const int64_t waves = (batch + 3) / 4;
     auto go = [&](auto kern, size_t per) -> int {
@@ -1136,35 +925,45 @@ template <int NX> static int launch_quad4_t(const KernelArgs &ka, int64_t batch,
                            (const double *)ka.targets.ptr, (double *)ka.U, (double *)ka.lam, ka.status, ka.iters, ka, batch);
         return (int)hipGetLastError();
     };
-    // The roomy carve (49.9 KB per wavefront) puts three wavefronts on a CU, the slim one (36.9 KB: packed L^-T, no T image, the leaving
-    // slot's row by ds_bpermute) four: launches that do not fit three per CU take the slim one (STILL one wavefront per SIMD: the kernel
-    // holds ~330 registers in either)
-    const bool slim = waves > 3 * (int64_t)(device_simds_now() / 4);
-    return slim ? go(mpcqp_quad4_kernel<NX, false, 1, true, false, true>, Carve<true>::PER)
-                : go(mpcqp_quad4_kernel<NX, false, 1, false, false, true>, Carve<false>::PER);
+    // Two rows per lane: one round (at most one wavefront per SIMD) runs the roomy carve; several rounds the slim one, two wavefronts
+    // per SIMD. Four rows per lane: the roomy carve (49.9 KB per wavefront) puts three wavefronts on a CU, the slim one (36.9 KB: packed
+    // L^-T, no T image, the leaving slot's row by ds_bpermute) four: launches that do not fit three per CU take the slim one (STILL one
+    // wavefront per SIMD: the kernel holds ~330 registers in either)
+    const bool slim = ROWS == 2 ? waves > device_simds_now() : waves > 3 * (int64_t)(device_simds_now() / 4);
+    return slim ? go(mpcqp_quadg_kernel<NX, ROWS, true>, Carve<true, ROWS>::PER) : go(mpcqp_quadg_kernel<NX, ROWS, false>, Carve<false, ROWS>::PER);
 }
 
-// (compiled twice, like mpcqp_quad.hip: as itself -- nx = 2 .. 4 -- and through mpcqp_quad4w.hip -- nx = 5 .. 8, the streamed build --)
-#ifdef MPCQP_QUAD_WIDE_UNIT
+#ifndef MPCQP_QUADG_WIDE_UNIT
+// four rows per lane: cold launches of problems with n <= 16 and 33 .. 64 rows, or five to eight rows per step (m <= 64), nx <= 8 (the
+// streamed build's padded size 8 serves nx = 5 .. 8); everything else keeps the kernel it had
+bool quad4_applies(const KernelArgs &ka)
+{
+    if (ka.n > NV || ka.m > 64 || (ka.m <= 32 && ka.mk <= 4) || ka.nx < 2 || ka.nx > 8) return false;  // (m <= 32 with mk <= 4: two rows per lane)
+    if (ka.mk < 1 || ka.mk > 8 || (!ka.C.ptr && !ka.D.ptr)) return false;
+    if (ka.N * ka.mk != ka.m || ka.N > NV) return false;
+    if (ka.warm_state || ka.order || (ka.opt_flags & (MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE))) return false;
+    return true;
+}
+
+int launch_quad4_wide(const KernelArgs &ka, int64_t batch, hipStream_t st);  // (mpcqp_quadgw.hip)
+
+int launch_quad4(const KernelArgs &ka, int64_t batch, hipStream_t st)
+{
+    switch (ka.nx) {
+    case 2: return launch_quadg_t<2, 4>(ka, batch, st);
+    case 3: return launch_quadg_t<3, 4>(ka, batch, st);
+    case 4: return launch_quadg_t<4, 4>(ka, batch, st);
+    default: return launch_quad4_wide(ka, batch, st);
+    }
+}
+#else
 int launch_quad4_wide(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
     // nx = 5 .. 8: the streamed build in its padded size 8. (Not the all-steps-in-registers build for nx = 5, 6: with eight rows per
     // step it keeps 80 / 96 operand registers alive next to this kernel's ~330, the allocator parks some in accumulation registers and
     // moves them back right in front of the hand-written v_fmac_f64_dpp that reads them -- without the two wait states a DPP read
     // needs: wrong plans (tools/check_dpp_hazards.py finds some of those sites, the oracle found the rest).)
-    return launch_quad4_t<8>(ka, batch, st);
-}
-#else
-int launch_quad4_wide(const KernelArgs &ka, int64_t batch, hipStream_t st);  // (mpcqp_quad4w.hip)
-
-int launch_quad4(const KernelArgs &ka, int64_t batch, hipStream_t st)
-{
-    switch (ka.nx) {
-    case 2: return launch_quad4_t<2>(ka, batch, st);
-    case 3: return launch_quad4_t<3>(ka, batch, st);
-    case 4: return launch_quad4_t<4>(ka, batch, st);
-    default: return launch_quad4_wide(ka, batch, st);
-    }
+    return launch_quadg_t<8, 4>(ka, batch, st);
 }
 #endif
 

@@ -456,7 +456,7 @@ def test_random_campaign_over_the_whole_envelope_of_the_general_build():
 
 @pytest.mark.parametrize("nx", [2, 3, 4, 5, 6, 8])
 def test_more_than_32_rows_take_the_four_rows_per_lane_copy(nx):
-    """csrc/mpcqp_quad4.hip (end of round 6): n <= 16 with 33 .. 64 rows (three / four rows per step on horizons of 9 .. 16 steps) --
+    """csrc/mpcqp_quadg.hip (end of round 6): n <= 16 with 33 .. 64 rows (three / four rows per step on horizons of 9 .. 16 steps) --
     default dispatch = forced launch, bit for bit; statuses and plans against the oracle; iteration counts against the
     one-per-wavefront kernel that served these problems before (same method)."""
     from qpmpc_amd import _capi, solve_mpc_batch

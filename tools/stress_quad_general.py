@@ -4,7 +4,7 @@ envelope -- nx 2..16, nu 1..4, every horizon with n <= 16, 1..4 rows per step (m
 without a stage cost, time-invariant or per-step operands, loose to very tight bounds -- forced through the kernel
 (MPCQP_OPT_FOUR_PER_WAVE) against the C oracle: statuses equal, plans within 1e-7 relative.
 usage: stress_quad_general.py [rounds] [batch]   (STRESS_SEED; STRESS_ROWS64=1: also problems of 33 .. 64 rows, the four-rows-per-lane
-copy of the kernel in csrc/mpcqp_quad4.hip)"""
+copy of the kernel in csrc/mpcqp_quadg.hip)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np, torch
@@ -19,7 +19,7 @@ def run(rounds, batch, seed, verbose=True):
     for it in range(rounds):
         nx, nu = int(rng.integers(2, 17)), int(rng.integers(1, 5))
         N = int(rng.integers(1, 16 // nu + 1))
-        rows64 = bool(os.environ.get("STRESS_ROWS64"))  # (up to 64 rows and up to eight rows per step: mpcqp_quad4.hip)
+        rows64 = bool(os.environ.get("STRESS_ROWS64"))  # (up to 64 rows and up to eight rows per step: mpcqp_quadg.hip)
         mk = int(rng.integers(1, min(8 if rows64 else 4, (64 if rows64 else 32) // N) + 1))
         if (N * mk > 32 or mk > 4) and nx > 8:
             nx = int(rng.integers(2, 9))  # (more than 32 rows: that kernel serves nx <= 8)
