@@ -22,6 +22,23 @@
  *  - matrices are row-major and densely packed; one batch item after another
  *    unless a stride says otherwise;
  *  - constraints are  G u <= h ; the QP is  min 1/2 u'Pu + q'u.
+ *
+ * Memory contract (tests/test_gpu_memory_discipline.py holds every export to it)
+ *  - a launch reads its operands and writes its outputs inside the extents this header names and nowhere else: an operand of
+ *    `batch` problems ends with the last problem's block ((batch - 1) * batch_stride + block elements), an output is packed
+ *    unless a stride is named, the workspace is exactly what the matching *_workspace_bytes query reports for the same
+ *    dimensions, batch and slot / tangent counts; no alignment beyond the element's own is assumed past a buffer's end;
+ *  - the initial content of the workspace, of every output and of a cold launch's warm_state is never read: a launch writes
+ *    what it later reads. The exceptions are the documented sequences -- MPCQP_OPT_REUSE_FACTOR / _PIPELINE_FACTOR read the
+ *    factor image a launch with MPCQP_OPT_KEEP_FACTOR left in the same workspace, warm_start != 0 reads the record (and, for
+ *    the narrow stage-wise kernel, the rows in the workspace) of the launch before, mpcqp_condense_phase_batch phase 2 reads
+ *    what phase 1 left in Psi and the workspace, and the `states` / `stats` arguments of the closed-loop exports are in/out;
+ *  - outputs per problem: status[b] and iters[b] are written for every problem; U (x) of a problem with status[b] != 0 is all
+ *    zeros (an empty plan, never NaN); lam[b] is defined for solved problems only. The derivative exports write zeros and the
+ *    forward status for problems that were not solved (see each of them);
+ *  - an output passed as NULL where that is allowed is not written and changes nothing in the others; a problem that a pairing
+ *    `order` leaves out keeps its old outputs; the elements between two rows of a strided argument (u_stride) are not touched;
+ *  - read-only arguments (everything declared const, the operands, the model of the solve_model exports) are never written.
  */
 #ifndef MPCQP_H_
 #define MPCQP_H_
@@ -316,7 +333,9 @@ int mpcqp_update_vectors_batch(const MpcqpDims *dims, const MpcqpProblem *proble
 /* Replaces qpsolvers.solve_problem(Problem(P,q,G,h), solver=...) at its call
  * site qpmpc/solve_mpc.py:43 for a batch of dense strictly convex QPs:
  * x[batch*n], lam[batch*m] (multipliers of G u <= h, nullable),
- * status[batch], iters[batch] (nullable). Dual active-set method. */
+ * status[batch], iters[batch] (nullable). Dual active-set method.
+ * A problem with status[b] != 0 gets x[b] = zeros and its status and iters; its lam[b] is undefined. The workspace's initial
+ * content is never read. */
 int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P,
                       const void *q, const void *G, const void *h, int64_t batch,
                       const MpcqpSolveOpts *opts, void *x, void *lam,
@@ -334,7 +353,10 @@ int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P,
  * kernel's (mpcqp_workspace_bytes prices the sum), so the factor images and the rows a warm record points at survive it, and it
  * leaves the warm record as the narrow kernel wrote it (the next warm start re-checks it). For an item the wide kernel re-solved,
  * U, lam, status and iters are the wide kernel's: iters counts its iterations only, the narrow kernel's are not added. The
- * multi-period launches (mpcqp_wip_periods_batch) have no second opinion. */
+ * multi-period launches (mpcqp_wip_periods_batch) have no second opinion.
+ * A problem with status[b] != 0 gets U[b] = zeros and its status and iters; its lam[b] is undefined. lam and iters may be NULL.
+ * The initial content of the workspace and of a cold launch's warm_state is never read (MPCQP_OPT_REUSE_FACTOR /
+ * _PIPELINE_FACTOR and warm_start != 0 read what the launch before left there, as documented at MpcqpSolveOpts). */
 int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem,
                             int64_t batch, const MpcqpSolveOpts *opts, void *U,
                             void *lam, int32_t *status, int32_t *iters,
@@ -355,7 +377,9 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem,
  * the width; its workspace is sized by the query with max_active = -1 (default slots) or -k (k slots). As in
  * mpcqp_build_solve_batch, what the narrow kernel leaves MPCQP_MAX_ITER / MPCQP_INFEASIBLE is solved once more by the wide kernel
  * (same slots, same stream, its own region after the narrow kernel's workspace: the query reports the sum) before the call
- * returns, stateful launches included; iters of such an item is the wide kernel's count. */
+ * returns, stateful launches included; iters of such an item is the wide kernel's count.
+ * A problem with status[b] != 0 (MPCQP_SLOTS_FULL included) gets U[b] = zeros and its status and iters; its lam[b] is undefined.
+ * The workspace's initial content is never read, the stateful sequences of mpcqp_build_solve_batch apart. */
 int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes);
 int mpcqp_stagewise_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
                                 const MpcqpSolveOpts *opts, int32_t max_active, void *U, void *lam,
@@ -385,7 +409,8 @@ int mpcqp_factor_model(const MpcqpDims *dims, const void *P, const void *G,
 /* Solve `batch` problems that share `model`: only x0 [nx], goal [nx] and targets [N nx]
  * differ (batch_stride 0 = shared; goal/targets may be NULL when their cost term is
  * not flagged). Replaces update_cost_vector + update_constraint_vector + the solver
- * call for every problem. Outputs as mpcqp_build_solve_batch. */
+ * call for every problem. Outputs as mpcqp_build_solve_batch: U[b] = zeros, status and iters for a problem with status[b] != 0,
+ * its lam[b] undefined; lam and iters may be NULL. `model` is only read; there is no workspace. */
 int mpcqp_solve_model_batch(const MpcqpDims *dims, const void *model,
                             const MpcqpOperand *x0, const MpcqpOperand *goal,
                             const MpcqpOperand *targets, int64_t batch,
@@ -397,7 +422,7 @@ int mpcqp_solve_model_batch(const MpcqpDims *dims, const void *model,
  * that examples/lipm_walking_controller.py:179-213 (update_goal_and_constraints) rewrites every control period while
  * A, B, C stay, i.e. update_constraint_vector (mpc_qp.py:151-163) with a new e. h = e - (C Phi) x0 uses the model's map.
  * e == NULL or e->ptr == NULL is mpcqp_solve_model_batch. Served by the pair kernel (n <= 16, m <= 32, float64);
- * MPCQP_EUNSUPPORTED elsewhere. */
+ * MPCQP_EUNSUPPORTED elsewhere. Outputs for unsolved problems as mpcqp_solve_model_batch. */
 int mpcqp_solve_model_bounds_batch(const MpcqpDims *dims, const void *model, const MpcqpOperand *e,
                                    const MpcqpOperand *x0, const MpcqpOperand *goal,
                                    const MpcqpOperand *targets, int64_t batch,
@@ -589,7 +614,9 @@ int mpcqp_wip_advance_stats_batch(int32_t dtype, void *states, const void *U, in
  * the loop). states [batch, 4] is updated in place; loop_stats (int64 [batch, 2], device, may be NULL): [b][0] += 1 if
  * the plan was not found, [b][1] += iterations. Only for problems mpcqp_build_solve_batch hands to the stage-wise
  * kernel (float64, nx = 4, nu = 1, 16 < N <= 128, per-loop x0 / goal / targets): MPCQP_EUNSUPPORTED otherwise -- the
- * caller then launches the solve and mpcqp_wip_advance_stats_batch separately. Workspace: mpcqp_workspace_bytes. */
+ * caller then launches the solve and mpcqp_wip_advance_stats_batch separately. Workspace: mpcqp_workspace_bytes.
+ * U, lam, status and iters as mpcqp_build_solve_batch (status[b] != 0: U[b] = zeros, lam[b] undefined; the plant then steps with
+ * a zero input); the workspace's initial content is never read, MPCQP_OPT_REUSE_FACTOR / _PIPELINE_FACTOR launches apart. */
 int mpcqp_wip_period_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
                            const MpcqpSolveOpts *opts, void *U, void *lam, int32_t *status, int32_t *iters,
                            void *workspace, size_t workspace_bytes, void *states, int64_t *loop_stats,
