@@ -38,7 +38,8 @@
  *    forward status for problems that were not solved (see each of them);
  *  - an output passed as NULL where that is allowed is not written and changes nothing in the others; a problem that a pairing
  *    `order` leaves out keeps its old outputs; the elements between two rows of a strided argument (u_stride) are not touched;
- *  - read-only arguments (everything declared const, the operands, the model of the solve_model exports) are never written.
+ *  - read-only arguments (everything declared const, the operands, the model of the solve_model exports) are never written;
+ *  - mpcqp_model_vjp_batch / mpcqp_model_jvp_batch touch nothing outside the named extents and the model (mpcqp_model_bytes).
  */
 #ifndef MPCQP_H_
 #define MPCQP_H_
@@ -584,6 +585,46 @@ int mpcqp_plan_jvp_model_stagewise_batch(const MpcqpDims *dims, const MpcqpProbl
                                          const void *U, const MpcqpTangents *tan, const MpcqpModelTangents *mtan,
                                          void *dU, void *dX, int32_t *jvp_status,
                                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- derivatives of shared-model plans: no second build, no workspace; an additive part of ABI 12
+ * (MPCQP_ABI_VERSION is unchanged). What mpcqp_plan_vjp_batch / mpcqp_plan_jvp_batch compute, for problems that share a
+ * factored model, from the model itself: they replace those exports' condensing of every problem (P, q, G, h, Phi, Psi
+ * into a workspace) and factorisation of every P by products with the model's M = G L^-T, L^-T and maps. With
+ * d = L^-1 q = Wx x0 - Wg goal - Wt targets, h = e - Hx x0 and S = M_A M_A' on A = {i : lam_i > 0} (the rule of every
+ * derivative export: a tight row with lam_i = 0 is inactive, the result is one element of the generalized Jacobian),
+ *     VJP:  t = L^-1 (gU + Psi' gX),  nu = S^-1 M_A t,  w = t - M_A' nu,
+ *           g_x0 = -Wx' w - Hx' nu + p_0,  g_goal = Wg' w,  g_targets = Wt' w,  g_e = nu on A, 0 elsewhere
+ *     JVP:  r = -(Wx dx0 - Wg dgoal - Wt dtargets),  mu = S^-1 (M_A r - (de - Hx dx0)_A),  dU = L^-T (r - M_A' mu),
+ *           dX = rollout(dx0, dU)
+ * ("Shared-model derivatives"). Psi' gX and p_0 come from the costate recursion p_N = gX_N,
+ * p_k = gX_k + A_k' p_{k+1}, (Psi' gX)_k = B_k' p_{k+1}, and dX from the rollout, through A and B as operands (the model
+ * holds neither Phi nor Psi; a batch stride of 0 shares them): A and B are read only when gX (dX) is not NULL.
+ * `model` is what mpcqp_factor_model wrote for the same dims and is only read; lam [batch*m] and status [batch] are the
+ * forward's (mpcqp_solve_model_batch / mpcqp_solve_model_bounds_batch with lam != NULL). Per-problem bounds need nothing
+ * more: at a given active set the derivative depends on neither e nor x0. Terms follow dims->flags: a goal or targets that
+ * do not enter q get zero gradients, and their tangents contribute nothing.
+ * Inputs and outputs, packed: gU [batch*n], gX [batch*(N+1)*nx] (nullable), g_x0 [batch*nx], g_goal [batch*nx],
+ * g_targets [batch*N*nx], g_e [batch*N*mk] (all but g_x0 nullable); the tangents, their layout ([batch][ntan][...], a
+ * stride of 0 = one set shared by the batch), ntan in 1 .. 256, dU [batch][ntan][n] and dX [batch][ntan][(N+1)*nx]
+ * (nullable) are mpcqp_plan_jvp_batch's. A reduction over operands the batch shares is the caller's.
+ * Per problem: status[b] != 0 gives zeros in every output and vjp_status[b] / jvp_status[b] = status[b] (its multipliers
+ * are not read); more active rows than variables, or an S that is not positive definite (the pivot test of the other
+ * derivative exports), gives zeros and MPCQP_NOT_PD; a model whose factorisation failed gives every problem zeros and
+ * MPCQP_NOT_PD; else 0. vjp_status and jvp_status are nullable.
+ * Checks, before anything is launched: MPCQP_EDTYPE unless float64; MPCQP_EUNSUPPORTED for n > 64 (such problems have
+ * mpcqp_plan_vjp_batch / mpcqp_plan_jvp_batch) and for a state so wide that the workgroup kernel's vectors do not fit a
+ * CU's LDS beside S (8 (n (n | 1) + 4 n + 2 nx + n / 2 + 1) bytes > 160 KiB: nx beyond some ten thousand); MPCQP_EINVAL for a NULL model, status, gU, g_x0, dU or tan, a negative
+ * batch, a NULL lam when mk > 0, a non-NULL gX or dX without A or B, a negative stride, or ntan outside 1 .. 256.
+ * Models of at most 16 variables, 32 rows and nx <= 16 run sixteen lanes per problem, four problems per wavefront, on an
+ * LDS image of the model staged once per workgroup (at most 1024 workgroups of sixteen problems a round: larger batches
+ * take further rounds); the others one workgroup per problem with S in LDS. */
+int mpcqp_model_vjp_batch(const MpcqpDims *dims, const void *model, int64_t batch, const void *lam,
+                          const int32_t *status, const void *gU, const void *gX, const MpcqpOperand *A,
+                          const MpcqpOperand *B, void *g_x0, void *g_goal, void *g_targets, void *g_e,
+                          int32_t *vjp_status, void *stream);
+int mpcqp_model_jvp_batch(const MpcqpDims *dims, const void *model, int64_t batch, int32_t ntan, const void *lam,
+                          const int32_t *status, const MpcqpTangents *tan, const MpcqpOperand *A,
+                          const MpcqpOperand *B, void *dU, void *dX, int32_t *jvp_status, void *stream);
 
 /* One period of `batch` wheeled-inverted-pendulum control loops, fused: apply the first
  * input of each plan (U[b*u_stride]) to the nonlinear plant for `nsub` Taylor sub-steps of

@@ -67,6 +67,8 @@ EXPORTS = (
     "mpcqp_plan_jvp_model_batch",
     "mpcqp_plan_jvp_model_stagewise_workspace_bytes",
     "mpcqp_plan_jvp_model_stagewise_batch",
+    "mpcqp_model_vjp_batch",
+    "mpcqp_model_jvp_batch",
 )
 
 
@@ -239,6 +241,12 @@ def load():
     lib.mpcqp_plan_jvp_model_stagewise_batch.argtypes = [C.POINTER(Dims), C.POINTER(Problem), i64, C.c_int32, C.c_int32,
                                                          vp, vp, vp, C.POINTER(Tangents), C.POINTER(ModelTangents), vp,
                                                          vp, vp, vp, C.c_size_t, vp]
+    lib.mpcqp_model_vjp_batch.restype = C.c_int
+    lib.mpcqp_model_vjp_batch.argtypes = [C.POINTER(Dims), vp, i64, vp, vp, vp, vp, C.POINTER(Operand), C.POINTER(Operand),
+                                          vp, vp, vp, vp, vp, vp]
+    lib.mpcqp_model_jvp_batch.restype = C.c_int
+    lib.mpcqp_model_jvp_batch.argtypes = [C.POINTER(Dims), vp, i64, C.c_int32, vp, vp, C.POINTER(Tangents),
+                                          C.POINTER(Operand), C.POINTER(Operand), vp, vp, vp, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

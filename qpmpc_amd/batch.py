@@ -822,6 +822,7 @@ class SharedModel:
                                     nbytes.value, _stream_ptr())
         _capi.check(rc, "mpcqp_factor_model")
         self._keep = qp  # inputs of the asynchronous factorisation
+        self._twin64 = None  # a float32 model's float64 twin, factored on the first derivative call (model_diff.py)
 
     def problem_for(self, x0, goal=None, targets=None, e=None) -> BatchMPCProblem:
         """A batch sharing this model's operands with the given states (and, optionally, its own bounds e)."""
@@ -839,6 +840,44 @@ class SharedModel:
         run = self.prepare(self.problem_for(x0, goal, targets), return_multipliers, max_iter, feas_tol, **opt_kw)
         run.launch()
         return run.plan
+
+    def solve_diff(self, x0, goal=None, targets=None, ineq_vector=None, states: bool = False, **solve_kw):
+        """Solve like :meth:`solve` and return ``(U, X, plan)`` whose ``U`` [B, N, nu] and, with ``states=True``, ``X``
+        [B, N+1, nx] carry a ``grad_fn``, like ``solve_mpc_batch_diff`` (``X`` is None otherwise).
+
+        The forward is the model solve with multipliers; an ``ineq_vector`` (``[B|1, N|1, mk]``, ``[N|1, mk]`` or
+        ``[mk]``) gives every problem bounds of its own (``mpcqp_solve_model_bounds_batch``; otherwise the model's are
+        used). The backward is one ``mpcqp_model_vjp_batch`` call on the factored model: no second build, no
+        workspace ("Shared-model derivatives"). Gradients reach whichever of ``x0``, ``goal``,
+        ``targets`` and ``ineq_vector`` were passed as tensors requiring grad; an operand shared by the batch gets the
+        sum over the batch. ``torch.autograd.forward_ad`` duals on the same four are one ``mpcqp_model_jvp_batch`` call
+        (T = 1). The active set is ``{i : lam_i > 0}``; problems that were not solved get zero gradients, and after the
+        backward ``plan.vjp_status`` holds their status (``MPCQP_NOT_PD`` where the active rows' Gram matrix is
+        singular). A float32 model factors a float64 twin on the first derivative call and casts the results back.
+        Envelope: n = N * nu <= 64 (``BackendError`` before anything is launched; ``solve_mpc_batch_diff`` serves
+        larger problems, and gradients with respect to the model matrices and weights). With nothing requiring grad
+        and nothing dual this is :meth:`solve`."""
+        from . import model_diff
+
+        return model_diff.solve_diff(self, x0, goal, targets, ineq_vector, states, **solve_kw)
+
+    def plan_jvp(self, plan, initial_state=None, goal_state=None, target_states=None, ineq_vector=None,
+                 states: bool = False):
+        """Jacobian-vector products of a plan of this model, ``(dU [B, T, N, nu], dX [B, T, N+1, nx] or None)``: the
+        module-level ``plan_jvp`` (tangent shapes ``[B|1, T, ...]``, a leading 1 shares one set with the batch, T <=
+        256) by one ``mpcqp_model_jvp_batch`` call. ``plan`` was solved with ``return_multipliers=True``; after the call
+        ``plan.jvp_status`` holds the per-problem outcome. Envelope: n <= 64."""
+        from . import model_diff
+
+        return model_diff.plan_jvp(self, plan, initial_state, goal_state, target_states, ineq_vector, states)
+
+    def plan_jacobian(self, plan, wrt: str = "initial_state", states: bool = False):
+        """Feedback Jacobian ``(J_U [B, N, nu, nx], J_X [B, N+1, nx, nx] or None)`` of a plan of this model with respect
+        to ``"initial_state"`` or ``"goal_state"``: :meth:`plan_jvp` with one identity shared by the batch.
+        ``J_U[:, 0]`` is the local gain of the controller."""
+        from . import model_diff
+
+        return model_diff.plan_jacobian(self, plan, wrt, states)
 
 
 class PreparedModelSolve:

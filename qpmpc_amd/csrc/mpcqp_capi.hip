@@ -1260,6 +1260,98 @@ int mpcqp_plan_jvp_model_batch(const MpcqpDims *dims, const MpcqpProblem *proble
 }
 
 namespace {
+// what both shared-model derivative exports check of their dimensions, in this order, and the fields they share
+static int model_diff_checks(const MpcqpDims *dims, ModelDiffLaunch &l)
+{
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
+    const int64_t n = (int64_t)dims->N * dims->nu, m = (int64_t)dims->N * dims->mk;
+    if (n > 64) return MPCQP_EUNSUPPORTED;
+    if (!model_diff_small_applies(dims->nx, (int)n, (int)m) &&
+        model_diff_general_lds_bytes(dims->nx, (int)n) > kLdsBytesPerCU)
+        return MPCQP_EUNSUPPORTED;
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.mk = dims->mk;
+    l.n = (int)n;
+    l.m = (int)m;
+    l.flags = dims->flags;
+    return 0;
+}
+
+static bool strides_ok(const MpcqpOperand *A, const MpcqpOperand *B)
+{
+    return A->batch_stride >= 0 && A->step_stride >= 0 && B->batch_stride >= 0 && B->step_stride >= 0;
+}
+
+// the kernel by the model's size: sixteen lanes per problem where the model has the small-problem kernels' 16 columns
+static int launch_model_diff(const ModelDiffLaunch &l, void *stream)
+{
+    if (model_diff_small_applies(l.nx, l.n, l.m)) return launch_model_diff_small(l, (hipStream_t)stream);
+    return launch_model_diff_general(l, (hipStream_t)stream);
+}
+}  // namespace
+
+int mpcqp_model_vjp_batch(const MpcqpDims *dims, const void *model, int64_t batch, const void *lam,
+                          const int32_t *status, const void *gU, const void *gX, const MpcqpOperand *A,
+                          const MpcqpOperand *B, void *g_x0, void *g_goal, void *g_targets, void *g_e,
+                          int32_t *vjp_status, void *stream)
+{
+    ModelDiffLaunch l{};
+    int rc = model_diff_checks(dims, l);
+    if (rc) return rc;
+    if (!model || !status || !gU || !g_x0 || batch < 0 || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (gX && (!A || !B || !A->ptr || !B->ptr || !strides_ok(A, B))) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    l.batch = batch;
+    l.model = (const double *)model;
+    l.lam = dims->mk > 0 ? (const double *)lam : nullptr;
+    l.status = status;
+    l.gU = (const double *)gU;
+    l.gX = (const double *)gX;
+    if (gX) {
+        l.A = *A;
+        l.B = *B;
+    }
+    l.g_x0 = (double *)g_x0;
+    l.g_goal = (double *)g_goal;
+    l.g_targets = (double *)g_targets;
+    l.g_e = dims->mk > 0 ? (double *)g_e : nullptr;
+    l.out_status = vjp_status;
+    return launch_model_diff(l, stream);
+}
+
+int mpcqp_model_jvp_batch(const MpcqpDims *dims, const void *model, int64_t batch, int32_t ntan, const void *lam,
+                          const int32_t *status, const MpcqpTangents *tan, const MpcqpOperand *A,
+                          const MpcqpOperand *B, void *dU, void *dX, int32_t *jvp_status, void *stream)
+{
+    ModelDiffLaunch l{};
+    int rc = model_diff_checks(dims, l);
+    if (rc) return rc;
+    if (!model || !status || !dU || !tan || batch < 0 || (dims->mk > 0 && !lam)) return MPCQP_EINVAL;
+    if (dX && (!A || !B || !A->ptr || !B->ptr || !strides_ok(A, B))) return MPCQP_EINVAL;
+    if (!tangents_ok(tan) || ntan < 1 || ntan > kMaxTangents) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    l.batch = batch;
+    l.ntan = ntan;
+    l.model = (const double *)model;
+    l.lam = dims->mk > 0 ? (const double *)lam : nullptr;
+    l.status = status;
+    l.tan = *tan;
+    if (dims->mk == 0) l.tan.de = nullptr;
+    if (dX) {
+        l.A = *A;
+        l.B = *B;
+    }
+    l.dU = (double *)dU;
+    l.dX = (double *)dX;
+    l.out_status = jvp_status;
+    return launch_model_diff(l, stream);
+}
+
+namespace {
 // what both stage-wise plan-derivative exports check of their dimensions, in this order
 static int stagewise_checks(const MpcqpDims *dims, int64_t batch, int32_t max_active)
 {

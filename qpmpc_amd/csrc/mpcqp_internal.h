@@ -193,12 +193,18 @@ template <typename T> __device__ __forceinline__ T lane_get(T x, int l)  // (l: 
         return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
     }
 }
-template <typename T> __device__ __forceinline__ T wave_sum_dpp(T v)
+// the sum over each 16-lane row, in every lane of the row
+template <typename T> __device__ __forceinline__ T row_sum_dpp(T v)
 {
     v += dpp_mov<0xb1>(v);   // quad_perm [1,0,3,2]
     v += dpp_mov<0x4e>(v);   // quad_perm [2,3,0,1]
     v += dpp_mov<0x141>(v);  // row_half_mirror
     v += dpp_mov<0x140>(v);  // row_mirror
+    return v;
+}
+template <typename T> __device__ __forceinline__ T wave_sum_dpp(T v)
+{
+    v = row_sum_dpp(v);
     return (lane_get(v, 0) + lane_get(v, 16)) + (lane_get(v, 32) + lane_get(v, 48));
 }
 // (value, index) arg-min; ties -> lowest index (a total order: any reduction tree gives the same pair); every lane gets it
@@ -355,6 +361,28 @@ struct StagewiseTangentModelLaunch : StagewiseTangentLaunch {
     const double *U;
 };
 int launch_tangent_model_stagewise(const StagewiseTangentModelLaunch &l, int64_t batch, hipStream_t st);
+// derivatives of plans of a factored shared model (mpcqp_model_adjoint.hip; float64, n <= 64): the KKT adjoint (ntan == 0)
+// or ntan tangents on the model's whitened matrices, without a workspace; passed to the kernels as it is
+struct ModelDiffLaunch {
+    int nx, nu, N, mk, n, m, flags, ntan;  // n = N nu, m = N mk; ntan: 0 = the VJP
+    int64_t batch;
+    const double *model;                   // what mpcqp_factor_model wrote (ModelLayout)
+    const double *lam;                     // null when m = 0
+    const int32_t *status;
+    MpcqpOperand A, B;                     // read with gX / dX only (else their ptr may be null)
+    const double *gU, *gX;                 // VJP; gX nullable
+    double *g_x0, *g_goal, *g_targets, *g_e;  // VJP; all but g_x0 nullable
+    MpcqpTangents tan;                     // JVP
+    double *dU, *dX;                       // JVP; dX nullable
+    int32_t *out_status;                   // vjp_status / jvp_status, nullable
+};
+// the small kernel (sixteen lanes per problem; n <= 16, m <= 32, nx <= 16) runs at most this many workgroups of sixteen
+// problems a round: larger batches take further rounds on the same workgroups, whose LDS image of the model is staged once
+constexpr int kModelDiffMaxGrid = 1024;
+bool model_diff_small_applies(int nx, int n, int m);
+int launch_model_diff_small(const ModelDiffLaunch &l, hipStream_t st);
+size_t model_diff_general_lds_bytes(int nx, int n);
+int launch_model_diff_general(const ModelDiffLaunch &l, hipStream_t st);
 
 }  // namespace mpcqp
 #endif

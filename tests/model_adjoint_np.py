@@ -1,0 +1,146 @@
+"""NumPy restatement of the shared-model derivatives (mpcqp_model_vjp_batch / mpcqp_model_jvp_batch, DESIGN.md section 9,
+"Shared-model derivatives"), from the whitened quantities of a factored model.
+
+``NumpyModel(w)`` factors the operands a workload's problems share as ``SharedModel.__init__`` does: the NumPy condensing
+of the pseudo-problems with zero and unit states gives P, G and the bases of q and h; then L = chol(P) (numpy.linalg),
+M = G L^-T and the maps  d = L^-1 q = Wx x0 - Wg goal - Wt targets,  h = e - Hx x0.  With A = {i : lam_i > 0} and
+S = M_A M_A':
+    vjp:  t = L^-1 (gU + Psi' gX),  nu = S^-1 M_A t,  w = t - M_A' nu,
+          g_x0 = -Wx' w - Hx' nu + p_0,  g_goal = Wg' w,  g_targets = Wt' w,  g_e = nu on A
+          (p_N = gX_N, p_k = gX_k + A_k' p_{k+1}, (Psi' gX)_k = B_k' p_{k+1})
+    jvp:  r = -(Wx dx0 - Wg dgoal - Wt dtargets),  mu = S^-1 (M_A r - (de - Hx dx0)_A),  dU = L^-T (r - M_A' mu),
+          dX = rollout(dx0, dU)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle.condense_np import condense
+from qpmpc_amd.workloads import problem_from_workload
+
+import adjoint_np as AN
+
+
+class NumpyModel:
+    def __init__(self, w: dict):
+        base = AN.single(w, 0)
+        N = self.N = int(w["N"])
+        nx = self.nx = np.asarray(w["x0"]).shape[-1]
+        self.A, self.B = base["A"][0], base["B"][0]  # [N, nx, nx], [N, nx, nu]
+        self.nu = self.B.shape[-1]
+
+        def pseudo(x0=None, goal=None, targets=None):
+            w1 = dict(base)
+            w1["x0"] = (np.zeros(nx) if x0 is None else x0)[None]
+            w1["goal"] = (np.zeros(nx) if goal is None else goal)[None]
+            w1["targets"] = (np.zeros(N * nx) if targets is None else targets)[None]
+            cq = condense(problem_from_workload(w1, 0))
+            return cq
+
+        zero = pseudo()
+        self.P, self.G, self.h0 = zero.P, zero.G, zero.h
+        n, m = self.P.shape[0], self.G.shape[0]
+        self.n, self.m = n, m
+        Qx = np.stack([pseudo(x0=v).q for v in np.eye(nx)], axis=1)
+        Hx = np.stack([zero.h - pseudo(x0=v).h for v in np.eye(nx)], axis=1) if m else np.zeros((0, nx))
+        Qg = np.stack([pseudo(goal=v).q for v in np.eye(nx)], axis=1)
+        Qt = np.stack([pseudo(targets=v).q for v in np.eye(N * nx)], axis=1)
+        assert np.abs(zero.q).max() == 0.0
+        self.L = np.linalg.cholesky(self.P)
+        self.M = np.linalg.solve(self.L, self.G.T).T if m else np.zeros((0, n))
+        self.Wx = np.linalg.solve(self.L, Qx)
+        self.Wg = -np.linalg.solve(self.L, Qg)  # zero where the goal does not enter q
+        self.Wt = -np.linalg.solve(self.L, Qt)  # zero where the targets do not enter q
+        self.Hx = Hx
+
+    def _factor(self, lam):
+        act = np.flatnonzero(np.asarray(lam) > 0.0) if self.m else np.zeros(0, dtype=int)
+        MA = self.M[act]
+        return act, MA, MA @ MA.T
+
+    def singular(self, lam) -> bool:
+        """More active rows than variables, or a Gram matrix NumPy's Cholesky refuses."""
+        act, _, S = self._factor(lam)
+        if len(act) > self.n:
+            return True
+        try:
+            np.linalg.cholesky(S) if len(act) else None
+        except np.linalg.LinAlgError:
+            return True
+        return False
+
+    def vjp(self, lam, gU, gX=None) -> dict:
+        N, nx, nu = self.N, self.nx, self.nu
+        u = np.asarray(gU, dtype=float).ravel().copy()
+        p = np.zeros(nx)
+        if gX is not None:
+            gX = np.asarray(gX, dtype=float).reshape(N + 1, nx)
+            p = gX[N].copy()
+            for k in range(N - 1, -1, -1):
+                u[k * nu:(k + 1) * nu] += self.B[k].T @ p
+                p = gX[k] + self.A[k].T @ p
+        t = np.linalg.solve(self.L, u)
+        act, MA, S = self._factor(lam)
+        nu_a = np.linalg.solve(S, MA @ t) if len(act) else np.zeros(0)
+        w = t - MA.T @ nu_a
+        ge = np.zeros(self.m)
+        ge[act] = nu_a
+        return dict(x0=-self.Wx.T @ w - self.Hx[act].T @ nu_a + p, goal=self.Wg.T @ w, targets=self.Wt.T @ w, e=ge)
+
+    def jvp(self, lam, tan: dict) -> dict:
+        N, nx, nu = self.N, self.nx, self.nu
+        z = dict(x0=np.zeros(nx), goal=np.zeros(nx), targets=np.zeros(N * nx), e=np.zeros(self.m))
+        z.update({k: np.asarray(v, dtype=float).ravel() for k, v in tan.items() if v is not None})
+        r = -(self.Wx @ z["x0"] - self.Wg @ z["goal"] - self.Wt @ z["targets"])
+        dh = z["e"] - self.Hx @ z["x0"]
+        act, MA, S = self._factor(lam)
+        mu = np.linalg.solve(S, MA @ r - dh[act]) if len(act) else np.zeros(0)
+        dU = np.linalg.solve(self.L.T, r - MA.T @ mu)
+        X = [z["x0"]]
+        for k in range(N):
+            X.append(self.A[k] @ X[-1] + self.B[k] @ dU[k * nu:(k + 1) * nu])
+        return dict(U=dU, X=np.concatenate(X))
+
+
+# ---- the shared-operand families of the shared-model derivative tests (CPU and GPU), bounds tightened until most
+# problems have active rows
+def mixed_batch(batch: int, seed: int = 5, nx: int = 4, nu: int = 2, N: int = 8, zero_row: bool = False) -> dict:
+    """Stage and terminal cost, rows on the inputs (D) and on a state (C): nx = 4, nu = 2, N = 8 by default.
+    ``zero_row`` adds a fourth row per step whose C and D are zero (0 <= 1, a padding row: never active in a solve; with
+    a hand-made positive multiplier its diagonal entry of the Gram matrix is exactly 0)."""
+    rng = np.random.default_rng(seed)
+    A = np.eye(nx) + 0.15 * rng.standard_normal((nx, nx))
+    B = 0.5 * rng.standard_normal((nx, nu))
+    mk = 4 if zero_row else 3
+    C = np.zeros((mk, nx))
+    D = np.zeros((mk, nu))
+    D[0, 0], D[1, 0], C[2, 0], D[2, 1] = 1.0, -1.0, 1.0, 0.5
+    e = np.array([0.3, 0.3, 0.4, 1.0][:mk])
+    x0 = 0.5 * rng.standard_normal((batch, nx))
+    goal = 0.5 * rng.standard_normal((batch, nx))
+    targets = 0.3 * rng.standard_normal((batch, N * nx))
+    return dict(A=A, B=B, C=C, D=D, e=e, N=N, wt=2.0, wx=0.5, wu=1e-2, x0=x0, goal=goal, targets=targets, name="mixed")
+
+
+def families() -> dict:
+    from qpmpc_amd import workloads as W
+
+    tri = W.triple_integrator_batch(32, heterogeneous=False)
+    tri["e"] = np.array([2.0, 2.0])
+    hum = W.humanoid_batch(48)
+    hum["x0"] = hum["x0"] * np.array([0.5, 0.5, 0.5])
+    wip = W.wip_batch(24, N=20, ltv=False)
+    wip.pop("pendulum", None)
+    wip["e"] = 0.25 * np.asarray(wip["e"])
+    return dict(triple=tri, humanoid=hum, wip=wip, mixed=mixed_batch(24))
+
+
+def census(w: dict):
+    """Per problem of a workload, by the C oracle: (U, lam, status, usable) with usable = solved, at least one active row
+    and strictly complementary."""
+    out = []
+    for b in range(np.asarray(w["x0"]).shape[0]):
+        U, lam, slack, st = AN.solve(AN.single(w, b))
+        ok = st == 0 and bool((lam > 0).any()) and AN.strictly_complementary(lam, slack)
+        out.append((U, lam, st, ok))
+    return out
