@@ -31,6 +31,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_adjoint_common.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 namespace {
@@ -302,13 +303,6 @@ __device__ void whiten_rows(const MpcqpProblem &problem, int64_t b, const double
     __syncthreads();
 }
 
-// sum over the wavefront, the same in every lane
-__device__ inline double wave_sum(double acc)
-{
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    return acc;
-}
-
 // 4. S = Y_A Y_A' (lower, stride ldS) and, when `rhs` is given, bv = Y_A rhs: S_ab is a dot product over min(j_a, j_b) + 1
 // steps; one wavefront per row of S, lanes along the rows' common support
 __device__ void gram_rows(const double *Y, const int *idx, int k, int mk, int nu, int n, double *S, int ldS, const double *rhs,
@@ -325,7 +319,7 @@ __device__ void gram_rows(const double *Y, const int *idx, int k, int mk, int nu
             const double *yb = last ? rhs : Y + (int64_t)rb * n;
             double acc = 0.0;
             for (int c = lane; c < len; c += 64) acc += ya[c] * yb[c];
-            acc = wave_sum(acc);
+            acc = wave_sum_shfl(acc);
             if (lane == 0) {
                 if (last) bv[ra] = acc;
                 else S[ra * ldS + rb] = acc;
@@ -726,7 +720,7 @@ mpcqp_tangent_stagewise_kernel(const typename std::conditional<kModel, Stagewise
                     for (int c = lane; c < len; c += 64) acc += ya[c] * rt[c];
                     if (has_xs && a.problem.C.ptr && lane < nx)
                         acc += op_step(a.problem.C, b, ja)[(row - ja * mk) * nx + lane] * xs[(int64_t)g * R + ja * nx + lane];
-                    acc = wave_sum(acc);
+                    acc = wave_sum_shfl(acc);
                     if constexpr (kModel) {
                         if (lane == 0) acc += tangent_dh(a, mv, t0 + g, row);
                     }

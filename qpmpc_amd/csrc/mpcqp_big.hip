@@ -16,6 +16,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
@@ -387,13 +388,13 @@ __global__ void __launch_bounds__(512, 4) mpcqp_gram_mfma_f32_kernel(const Kerne
         }
         if (J < I) {
             // mirrored tile P[32 J + j][32 I + i], written with i across the lanes (coalesced)
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            wave_fence();
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int jl = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 P[(int64_t)(32 * J + jl) * n + 32 * I + l31] = tr[wv][l31 * 33 + jl];
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            wave_fence();
         }
     }
     if (tid < n) oq[prob * (int64_t)n + tid] = qacc;

@@ -23,6 +23,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
@@ -34,15 +35,9 @@ __device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 // channels (measured on the stage-wise kernel: 8x). 160 extra elements break the alignment.
 __host__ __device__ inline int64_t ws_stride_elems(int n) { return (int64_t)2 * n * n + 160; }
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 template <int NWV, typename T> __device__ __forceinline__ T block_sum(T v, T *red, int tid)
 {
-    v = wave_sum(v);
+    v = wave_sum_shfl(v);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
@@ -54,15 +49,7 @@ template <int NWV, typename T> __device__ __forceinline__ T block_sum(T v, T *re
 // arg-min of (v, i) over the block; ties -> lowest index
 template <int NWV, typename T> __device__ __forceinline__ void block_argmin(T &v, int &i, T *redv, int *redi, int tid)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const T ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if (ov < v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
+    wave_argmin_shfl(v, i);
     __syncthreads();
     if ((tid & 63) == 0) {
         redv[tid >> 6] = v;
@@ -78,7 +65,7 @@ template <int NWV, typename T> __device__ __forceinline__ void block_argmin(T &v
             i = redi[w];
         }
 }
-// 1/sqrt(x) and 1/x from the hardware estimates plus Newton steps (full precision of T; the IEEE
+// 1/sqrt(x) from the hardware estimate plus Newton steps, like fast_rcp (full precision of T; the IEEE
 // sqrt + divide sequences are ~100 instructions each in float64 and sit on the factorisation's
 // critical path once per column)
 __device__ __forceinline__ double fast_rsqrt(double x)
@@ -92,19 +79,6 @@ __device__ __forceinline__ float fast_rsqrt(float x)
     const float y = __builtin_amdgcn_rsqf(x);
     return y * (1.5f - 0.5f * x * y * y);
 }
-__device__ __forceinline__ double fast_recip(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    e = fma(-x, y, 1.0);
-    return fma(y, e, y);
-}
-__device__ __forceinline__ float fast_recip(float x)
-{
-    const float y = __builtin_amdgcn_rcpf(x);
-    return fmaf(y, fmaf(-x, y, 1.0f), y);
-}
 }  // namespace bigs
 using namespace bigs;
 
@@ -117,8 +91,7 @@ __device__ __forceinline__ bool factor_invert_scalar(T *Li, int n, int tid, T *r
 {
     auto sync = [&]() __attribute__((always_inline)) {
         if constexpr (WAVE) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_sync();
         } else {
             __syncthreads();
         }
@@ -171,7 +144,7 @@ __device__ __forceinline__ bool factor_invert_scalar(T *Li, int n, int tid, T *r
             int rowi = 0;
             for (int i = 0; i < n; rowi += ++i) {
                 const T *ri = Li + rowi;
-                const T dinv = fast_recip(ri[i]);
+                const T dinv = fast_rcp(ri[i]);
                 T x = T(0);
                 if (wbase < i) {
                     T a0 = T(0), a1 = T(0), a2 = T(0), a3 = T(0);
@@ -217,10 +190,6 @@ __device__ __forceinline__ bool factor_invert_scalar(T *Li, int n, int tid, T *r
 // the scalar version in another summation order. ~3600 MFMAs per 256 x 256 problem.
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ float rlane(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
 // row inside a 32 x 32 accumulator tile held by register t of this lane (column = lane & 31)
 __device__ __forceinline__ int crow(int t, int lane) { return (t & 3) + 8 * (t >> 2) + 4 * (lane >> 5); }
 
@@ -247,7 +216,7 @@ __device__ __forceinline__ bool diag_block_invert(float *Li, int J, int lane, fl
 #pragma unroll
     for (int c = 0; c < 32; ++c) {
         if (lane < 32) colbuf[r] = d[c];  // column c before scaling
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         float cv[32];
 #pragma unroll
         for (int g = c / 4; g < 8; ++g) {
@@ -257,7 +226,7 @@ __device__ __forceinline__ bool diag_block_invert(float *Li, int J, int lane, fl
             cv[4 * g + 2] = v[2];
             cv[4 * g + 3] = v[3];
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         const float piv = cv[c];
         ok = ok && (piv > 0.0f);
         float rinv = __builtin_amdgcn_rsqf(piv);  // v_rsq_f32 + one Newton step
@@ -278,7 +247,7 @@ __device__ __forceinline__ bool diag_block_invert(float *Li, int J, int lane, fl
         for (int c = 0; c < 32; ++c)
             if (c <= r) row[c] = d[c];
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     // lane r = column r of W = L^-1
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
@@ -290,7 +259,7 @@ __device__ __forceinline__ bool diag_block_invert(float *Li, int J, int lane, fl
         asm volatile("" : "+v"(w[i]));  // computed here, not sunk into the predicated stores below
         __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     if (lane < 32) {
 #pragma unroll
         for (int i = 0; i < 32; ++i)
@@ -460,7 +429,7 @@ __device__ __forceinline__ bool diag_block_invert64(double *Li, int J, int lane,
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
         if (lane < 16) colbuf[r] = d[c];  // column c before scaling
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         double cv[16];
 #pragma unroll
         for (int g = c / 2; g < 8; ++g) {
@@ -468,7 +437,7 @@ __device__ __forceinline__ bool diag_block_invert64(double *Li, int J, int lane,
             cv[2 * g] = v[0];
             cv[2 * g + 1] = v[1];
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         const double piv = cv[c];
         ok = ok && (piv > 0.0);
         const double rinv = fast_rsqrt(piv);
@@ -487,7 +456,7 @@ __device__ __forceinline__ bool diag_block_invert64(double *Li, int J, int lane,
         for (int c = 0; c < 16; ++c)
             if (c <= r) row[c] = d[c];
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     // lane r = column r of W = L^-1
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -499,7 +468,7 @@ __device__ __forceinline__ bool diag_block_invert64(double *Li, int J, int lane,
         asm volatile("" : "+v"(w[i]));
         __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     if (lane < 16) {
 #pragma unroll
         for (int i = 0; i < 16; ++i)
@@ -761,7 +730,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                         for (int u = 0; u < nu; ++u) acc += br[u] * zx[k * nu + u];
                         dxs[(k + 1) * nx + tid] = acc;
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    wave_fence();
                 }
             }
             __syncthreads();
@@ -1061,7 +1030,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                         for (int u = 0; u < nx; ++u) acc += Ak[a * nx + u] * Sc[u * nx + b];
                         T1[e2] = acc;
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    wave_fence();
                     for (int e2 = l; gC && e2 < nx * nx; e2 += 64) {
                         const int a = e2 / nx, b = e2 - a * nx;
                         T acc = T(0);
@@ -1306,7 +1275,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                 if (gC && tid < 64) {
                     T *mu = fe + 4 * nx + 3 * nx * nx;  // two buffers of nx
                     if (tid < nx) mu[tid] = opC[k * sCk + r * nx + tid];
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    wave_fence();
                     for (int j = k - 1; j >= 0; --j) {
                         const T *mc = mu + ((k - 1 - j) & 1) * nx;
                         T *mn = mu + ((k - j) & 1) * nx;
@@ -1321,7 +1290,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                             for (int a = 0; a < nx; ++a) acc += Aj[a * nx + b] * mc[a];
                             mn[b] = acc;
                         }
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        wave_fence();
                     }
                 }
             } else if constexpr (STRUCT) {
@@ -1371,7 +1340,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                 for (int a = tid >> 6; a < nq; a += NWV) {
                     T acc = T(0);
                     for (int k = tid & 63; k < n; k += 64) acc += Tm[(int64_t)a * n + k] * mp[k];
-                    acc = wave_sum(acc);
+                    acc = wave_sum_shfl(acc);
                     if ((tid & 63) == 0) rv[a] = acc;
                 }
                 __syncthreads();
@@ -1479,7 +1448,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                     for (int a = tid >> 6; a < nq; a += NWV) {
                         T acc = T(0);
                         for (int k = tid & 63; k < n; k += 64) acc += Tm[(int64_t)a * n + k] * tmp[k];
-                        acc = wave_sum(acc);
+                        acc = wave_sum_shfl(acc);
                         if ((tid & 63) == 0) rv[a] = acc;  // rv reused: T_a . T_l
                     }
                     __syncthreads();
@@ -1544,7 +1513,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                     for (int a = tid >> 6; a < nq; a += BS / 64) {  // dlam_a = -T_a . t (one wavefront per row)
                         T acc = T(0);
                         for (int k = tid & 63; k < n; k += 64) acc += Tm[(int64_t)a * n + k] * tmp[k];
-                        acc = wave_sum(acc);
+                        acc = wave_sum_shfl(acc);
                         if ((tid & 63) == 0) {
                             const T v = lam[a] - acc;
                             lam[a] = v < T(0) ? T(0) : v;

@@ -27,32 +27,11 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
 // ------------------------------------------------------------- reductions
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ void wave_argmin(T &v, int &i)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const T ov = __shfl_xor(v, off);
-        const int oi = __shfl_xor(i, off);
-        if (ov < v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
 // Workgroup barrier. With __launch_bounds__(64) the backend lowers s_barrier of
 // a single-wave workgroup to a wave_barrier (no hardware barrier is issued).
 __device__ __forceinline__ void bsync() { __syncthreads(); }
@@ -60,7 +39,7 @@ __device__ __forceinline__ void bsync() { __syncthreads(); }
 template <typename T, int WAVES>
 __device__ __forceinline__ T block_sum(T v, T *redv, int tid)
 {
-    v = wave_sum(v);
+    v = wave_sum_shfl(v);
     if constexpr (WAVES > 1) {
         if ((tid & 63) == 0) redv[tid >> 6] = v;
         bsync();
@@ -75,7 +54,7 @@ __device__ __forceinline__ T block_sum(T v, T *redv, int tid)
 template <typename T, int WAVES>
 __device__ __forceinline__ void block_argmin(T &v, int &i, T *redv, int *redi, int tid)
 {
-    wave_argmin(v, i);
+    wave_argmin_shfl(v, i);
     if constexpr (WAVES > 1) {
         if ((tid & 63) == 0) {
             redv[tid >> 6] = v;

@@ -23,6 +23,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 #include "mpcqp_adjoint_common.h"
 
 namespace mpcqp {

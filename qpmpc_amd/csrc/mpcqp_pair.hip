@@ -43,7 +43,7 @@
 // Cholesky factor, L[k][j] in the forward substitution, the operands of the Psi chain (lane e keeps
 // element e of [A_k | C_k] for every step), v_b in the Gram accumulation, component k of the update
 // vector in the fast loop -- it is a 64-bit DPP row broadcast folded into the FMA
-// (v_fmac_f64_dpp ... row_newbcast:n), not an LDS round trip: both 16-lane rows of a half hold what
+// (fmac_bcast: the DPP FMA with row_newbcast:n), not an LDS round trip: both 16-lane rows of a half hold what
 // the other needs (a v_permlane16_swap pair copies one row over the other). LDS is left with the
 // images addressed by run-time indices: the G image, M (row p of the selected constraint), T by
 // columns in the refinement, the rows of L^-T.
@@ -53,6 +53,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 #ifndef PAIR_EARLY_ARGS
 #define PAIR_EARLY_ARGS 2
@@ -61,25 +62,19 @@ namespace mpcqp {
 
 namespace pair {
 
-constexpr int NV = 16;    // padded number of variables / slots
+constexpr int NV = kRowLanes;  // padded number of variables / slots
 constexpr int HL = 32;    // lanes per problem
 constexpr int MMAX = 32;  // constraints a half can hold
 constexpr int LDM = 18;   // row stride of the L and M images (144 B: rows start in distinct 16-B slots)
 
 // ------------------------------------------------------------ lane primitives
-template <int CTRL> __device__ __forceinline__ unsigned dpp_u(unsigned x)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-constexpr int ROR8 = 0x128, ROR4 = 0x124, ROR2 = 0x122, ROR1 = 0x121;  // rotate within a row of 16
-
 // all-reduce (min) over the 32 lanes of each half
 __device__ __forceinline__ unsigned half_min(unsigned v)
 {
-    v = min(v, dpp_u<ROR8>(v));
-    v = min(v, dpp_u<ROR4>(v));
-    v = min(v, dpp_u<ROR2>(v));
-    v = min(v, dpp_u<ROR1>(v));
+    v = min(v, dpp<ROR8>(v));
+    v = min(v, dpp<ROR4>(v));
+    v = min(v, dpp<ROR2>(v));
+    v = min(v, dpp<ROR1>(v));
     // rows 1 and 3 of the first operand are exchanged with rows 0 and 2 of the second
     const auto sw = __builtin_amdgcn_permlane16_swap(v, v, false, false);
     return min((unsigned)sw[0], (unsigned)sw[1]);
@@ -87,10 +82,10 @@ __device__ __forceinline__ unsigned half_min(unsigned v)
 // all-reduce (or) over the 32 lanes of each half
 __device__ __forceinline__ unsigned half_or(unsigned v)
 {
-    v |= dpp_u<ROR8>(v);
-    v |= dpp_u<ROR4>(v);
-    v |= dpp_u<ROR2>(v);
-    v |= dpp_u<ROR1>(v);
+    v |= dpp<ROR8>(v);
+    v |= dpp<ROR4>(v);
+    v |= dpp<ROR2>(v);
+    v |= dpp<ROR1>(v);
     const auto sw = __builtin_amdgcn_permlane16_swap(v, v, false, false);
     return (unsigned)sw[0] | (unsigned)sw[1];
 }
@@ -113,65 +108,7 @@ __device__ __forceinline__ bool half_any(bool pred, int hb)
     return ((unsigned)(b >> hb)) != 0u;
 }
 
-// order-preserving map of a double onto two unsigned words
-__device__ __forceinline__ void ordered(double x, unsigned &hi, unsigned &lo)
-{
-    const unsigned h = (unsigned)__double2hiint(x), l = (unsigned)__double2loint(x);
-    const bool neg = h & 0x80000000u;
-    hi = neg ? ~h : (h | 0x80000000u);
-    lo = neg ? ~l : l;
-}
-
-// ------------------------------------------------------------ 16-vectors in LDS
-__device__ __forceinline__ void ld16(double (&d)[NV], const double *src)
-{
-    const double2 *p = reinterpret_cast<const double2 *>(src);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        const double2 t = p[i];
-        d[2 * i] = t.x;
-        d[2 * i + 1] = t.y;
-    }
-}
-__device__ __forceinline__ void st16(double *dst, const double (&s)[NV])
-{
-    double2 *p = reinterpret_cast<double2 *>(dst);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        double2 t;
-        t.x = s[2 * i];
-        t.y = s[2 * i + 1];
-        p[i] = t;
-    }
-}
-__device__ __forceinline__ double dot16(const double (&a)[NV], const double (&b)[NV])
-{
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; k += 4) {
-        acc0 += a[k] * b[k];
-        acc1 += a[k + 1] * b[k + 1];
-        acc2 += a[k + 2] * b[k + 2];
-        acc3 += a[k + 3] * b[k + 3];
-    }
-    return (acc0 + acc1) + (acc2 + acc3);
-}
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
-
-// The value held by lane N of the caller's 16-lane row, in every lane of that row: a 64-bit DPP move
-// (v_mov_b64_dpp row_newbcast:N) -- a register-to-register broadcast on the vector pipe, no LDS round trip.
-template <int N> __device__ __forceinline__ double row_bcast(double x)
-{
-    return __builtin_amdgcn_mov_dpp(x, 0x150 + N, 0xf, 0xf, true);
-}
-// acc += (x of lane N of the caller's row) * m in ONE instruction (v_fmac_f64_dpp). The compiler does not fold the DPP
-// move into the FMA, and it cannot see inside the asm: a register written by a VALU instruction needs two wait states
-// before a DPP read, so every batch of these is preceded by dpp_ready(x) on its broadcast source.
-template <int N> __device__ __forceinline__ void fmac_bcast(double &acc, double x, double m)
-{
-    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(m), "n"(N));
-}
-__device__ __forceinline__ void dpp_ready(double &x) { asm volatile("s_nop 1" : "+v"(x)); }
+// fmac_bcast with the lane given by a loop counter of a fully unrolled loop (see row_bcast_at)
 __device__ __forceinline__ void fmac_bcast_at(double &acc, double x, double m, int k)
 {
     switch (k) {
@@ -223,24 +160,6 @@ __device__ __forceinline__ double row_bcast_at(double x, int k)
     case 14: return row_bcast<14>(x);
     default: return row_bcast<15>(x);
     }
-}
-
-// 1/x from the hardware estimate plus two Newton steps (operands are never subnormal
-// or zero when the result is used)
-__device__ __forceinline__ double fast_rcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    e = fma(-x, y, 1.0);
-    return fma(y, e, y);
-}
-// One wavefront per workgroup: its LDS operations complete in order, so only the
-// COMPILER has to keep the order of an exchange (no s_barrier, no queue drain).
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
 }
 
 struct Lay {     // LDS carve of ONE problem in doubles (host-computed, passed by value)
@@ -433,7 +352,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
 #pragma unroll
         for (int b = 0; b < NV; ++b) Pr[b] = (hl == b) ? (col ? wu : T(1)) : T(0);
         T qa = T(0);
-        wsync();
+        wave_sync();
         tick(9);
         if constexpr (!LEAN) {
 #pragma unroll
@@ -553,12 +472,12 @@ __global__ void __launch_bounds__(64 * WPB, 2)
         }
         tick(10);
         gram((T)ka.wt, termP, termQ, gref);  // v = Psi_N
-        wsync();
+        wave_sync();
         tick(11);
         if (low) Gimg[hl * GS + m] = col ? qa : T(0);  // the q row
-        wsync();
+        wave_sync();
         hv[hl] = (isc && L.nC) ? eval - hp[hl] : eval;  // h_i = e_i - C_k Phi_k x0
-        wsync();
+        wave_sync();
     }
 
     tick(1);
@@ -571,9 +490,9 @@ __global__ void __launch_bounds__(64 * WPB, 2)
     T myinv = T(1);  // lanes j and 16 + j keep 1 / L_jj
     if constexpr (!MODEL) {
         if (low) st16(Ll + hl * LDM, Pr);
-        wsync();
+        wave_sync();
         ld16(Pr, Ll + l15 * LDM);
-        wsync();
+        wave_sync();
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const T pij = Pr[j];                    // P[i][j] of this lane's row, before scaling
@@ -591,7 +510,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             if (l15 == j) myinv = rinv;
             pin(Pr[j]);
         }
-        wsync();  // (keeps the next phase's LDS loads out of the factorisation: register pressure)
+        wave_sync();  // (keeps the next phase's LDS loads out of the factorisation: register pressure)
         __builtin_amdgcn_sched_barrier(0);
     }
     tick(2);
@@ -656,7 +575,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 for (int j2 = 0; j2 < nT; ++j2) wk -= model[ml.off_Wt + (size_t)hl * nT + j2] * tgt[j2];
             y0v[hl] = wk;
         }
-        wsync();
+        wave_sync();
     } else {
         // Rows fetched only now: constraint lanes their row of G; lane 0 takes q in RT, lanes 16..31
         // the identity (-> rows of L^-T), the other slot lanes zero.
@@ -689,7 +608,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
 #pragma unroll
             for (int k = j + 1; k < NV; ++k) asm volatile("" : "+v"(RM[k]), "+v"(RT[k]));
         }
-        wsync();  // the M image below reuses the L image
+        wave_sync();  // the M image below reuses the L image
     }
     tick(3);
     int status = MPCQP_MAX_ITER, iters = 0;
@@ -729,7 +648,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
 #pragma unroll
     for (int k = 0; k < NV; ++k) RT[k] = (!low && l15 == k) ? T(1) : T(0);  // T = N* starts empty, H = I
     zv[l15] = T(0);  // the pending rank-one update's vector
-    wsync();
+    wave_sync();
     const T hval = hv[hl];
     T s;
     {
@@ -811,14 +730,14 @@ __global__ void __launch_bounds__(64 * WPB, 2)
         const int a = wid;
         const bool okrow = low && a >= 0 && a < m && hv[(a >= 0 && a < m) ? a : 0] < T(1e29);
         slotof[hl] = -1;
-        wsync();
+        wave_sync();
         if (okrow) slotof[a] = hl;  // two slots naming one row: one of them wins
-        wsync();
+        wave_sync();
         const bool win = okrow && slotof[a] == hl;
         const int mypos = slotof[hl];
         const unsigned wmask = (unsigned)(__ballot(win) >> hb) & 0xffffu;
         const int cnt = __builtin_popcount(wmask);
-        wsync();
+        wave_sync();
         bool finite = true;
 #pragma unroll
         for (int k = 0; k < NV; ++k) finite = finite && (fabs(wrow[k]) < T(1e150));  // false for NaN / inf too
@@ -838,7 +757,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             done = true;  // straight to the multiplier solve
             needp = false;
         }
-        wsync();
+        wave_sync();
     }
     // The projector H = I - M_A' T (rows in lanes 16..31) and the projected rows K_i = H M_i that go with a stored
     // operator, for the halves in `take`. Built only when such a half really enters the active-set loop: a stored
@@ -848,7 +767,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             st16(Timg + hl * NV, RT);  // T by rows
             actv[hl] = occ ? myact : 0;
         }
-        wsync();
+        wave_sync();
         T hrow[NV];
         int kk = l15;
         asm volatile("" : "+v"(kk));
@@ -864,9 +783,9 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 for (int k = 0; k < NV; ++k) hrow[k] -= ma * ta[k];
             }
         }
-        wsync();
+        wave_sync();
         if (!low) st16(Timg + l15 * NV, hrow);  // H by rows (symmetric)
-        wsync();
+        wave_sync();
         {
             T kr[NV];
 #pragma unroll
@@ -889,7 +808,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
 #pragma unroll
             for (int k = 0; k < NV; ++k) RT[k] = hrow[k];
         }
-        wsync();
+        wave_sync();
     };
     // ------------------------------------------------------------ seeded start
     // The rows violated at the unconstrained minimiser predict the final active set well when the bounds are simple
@@ -1008,10 +927,10 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 }
             }
             if (WARM && __ballot(pstore) != 0ull) {  // warm-start repair chain: the next slot to leave publishes its row
-                wsync();
+                wave_sync();
                 if (pstore) st16(kAv, RT);
                 pstore = false;
-                wsync();
+                wave_sync();
             }
             cT = cK = T(0);
             pdrop = false;
@@ -1106,10 +1025,10 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 const bool any = rep & (mkey != 0xffffffffu);
                 const int ln = (int)(mkey & 31u);
                 const int cl = half_get(myact, hb, ln);
-                wsync();
+                wave_sync();
                 if (any && hl == ln) st16(kAv, RT);  // (the pending update was applied at the top of this trip)
                 if (any && hl == cl) pos = -1;
-                wsync();
+                wave_sync();
                 ldrop = any ? ln : ldrop;
                 dropping = dropping | any;
                 ndrop = any;
@@ -1276,7 +1195,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 const bool more = mine && nk != 0xffffffffu;
                 const int nl = more ? (int)nk : 0;
                 const int cl = half_get(myact, hb, nl);
-                wsync();
+                wave_sync();
                 pstore = more && hl == nl;  // its row AFTER this pass: stored once the pending update is applied
                 if (more && hl == cl) pos = -1;
                 if (more) {
@@ -1290,7 +1209,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             if (__ballot(partial) != 0ull) {
                 // partial step: the next trip removes slot l from T (no update is pending for this half)
                 const int cl = half_get(myact, hb, l);
-                wsync();
+                wave_sync();
                 if (partial && hl == l) st16(kAv, RT);
                 if (partial) {
                     if (hl == cl) pos = -1;
@@ -1298,13 +1217,13 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                     ldrop = l;
                 }
             }
-            wsync();
+            wave_sync();
         }
         tick(5);
         if (WARM && __ballot(recold) != 0ull) {
-            wsync();
+            wave_sync();
             if (recold) cold_reset();
-            wsync();
+            wave_sync();
             if (__ballot(!finished && done) == 0ull) continue;
         }
         if (__ballot(!finished) == 0ull) break;
@@ -1321,23 +1240,23 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             const T f = hv[hl] - dot16(mi, yy);
             return isc ? f : INF;
         };
-        wsync();
+        wave_sync();
         if (low) actv[hl] = occ ? myact : 0;
         if (__ballot(!wfix && !finished) != 0ull) {
             rv[vofs] = lam;
-            wsync();
+            wave_sync();
             {
                 T rr[NV];
                 ld16(rr, rv);
                 y -= ma_dot(rr);  // y = y0 - M_A' lam
             }
             zv[vofs] = y;
-            wsync();
+            wave_sync();
             ld16(yy, zv);
             fresh = slacks();
         } else {
             zv[vofs] = y;
-            wsync();
+            wave_sync();
             ld16(yy, zv);
         }
         T lraw = lam;  // multipliers before the clamp at zero (repair phase)
@@ -1352,10 +1271,10 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                                   : (occ && !finished && !(fabs(rho) <= T(REFTOL) * (T(1) + fabs(half_get(hval, hb, myact)))));
         if (__ballot(needref) != 0ull) {
             // dlam = -W rho_A = -T (T' rho_A)
-            wsync();
+            wave_sync();
             kAv[vofs] = rho;
             if (low) st16(Timg + hl * NV, RT);  // T by columns is only needed here
-            wsync();
+            wave_sync();
             T uk;
             {
                 T rr[NV];
@@ -1370,7 +1289,7 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 uk = a0 + a1;  // (T' rho)_k, lane k < 16
             }
             rv[vofs] = low ? uk : T(0);
-            wsync();
+            wave_sync();
             T dl;
             {
                 T rr[NV];
@@ -1385,9 +1304,9 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             // with dl as it is (not clamped) y moves exactly onto the active hyperplanes
             if constexpr (WARM) {
                 // (a stored operator is not trusted: y must stay y0 - M_A' lam for the acceptance test to mean anything)
-                wsync();
+                wave_sync();
                 rv[vofs] = dl;
-                wsync();
+                wave_sync();
                 T rr[NV];
                 ld16(rr, rv);
                 y -= ma_dot(rr);
@@ -1396,9 +1315,9 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 // M_A' T = I - H is the identity (T is this launch's own operator)
                 y += uk;
             }
-            wsync();
+            wave_sync();
             zv[vofs] = y;
-            wsync();
+            wave_sync();
             ld16(yy, zv);
             fresh = slacks();
         }
@@ -1421,10 +1340,10 @@ __global__ void __launch_bounds__(64 * WPB, 2)
                 needp = false;
             }
             const int cl = half_get(myact, hb, ldrop);
-            wsync();
+            wave_sync();
             if (rep && dropping && hl == ldrop) st16(kAv, RT);
             if (rep && dropping && hl == cl) pos = -1;
-            wsync();
+            wave_sync();
             if (rep && !dropping) {
                 // every multiplier is >= 0: (y, A) is an S-pair. It goes through the acceptance test below
                 // (lam, y and the slacks are those of this very set); violated rows, if any, enter through the
@@ -1474,9 +1393,9 @@ __global__ void __launch_bounds__(64 * WPB, 2)
             }
         }
         if (WARM && __ballot(coldnow) != 0ull) {
-            wsync();
+            wave_sync();
             if (coldnow) cold_reset();
-            wsync();
+            wave_sync();
         }
         if (__ballot(!finished) == 0ull) break;
     }

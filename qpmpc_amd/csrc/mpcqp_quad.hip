@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         }
         qa = col ? qa : T(0);
         tick(11);
-        wsync();  // the G image is complete
+        wave_sync();  // the G image is complete
         hval0 = isc0 ? eval0 - Gimg[(NV - 1) * GS + row0] : INF;  // h_i = e_i - C_k Phi_k x0 (column 15 of the image)
         hval1 = isc1 ? eval1 - Gimg[(NV - 1) * GS + row1] : INF;
         if constexpr (GEN) {  // (column 15 of G: the last step's input rows)
@@ -494,7 +494,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                 });
             }
         });
-        wsync();  // the M image below reuses the G image
+        wave_sync();  // the M image below reuses the G image
     }
     }  // (!MODEL)
     tick(2);
@@ -589,7 +589,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     // pending rank-one update R += c v, applied at the top of the next trip -- the ONE site that writes the register rows,
     // selects and fetches
     T zn = T(0), cT = T(0), cH = T(0);
-    wsync();
+    wave_sync();
     tick(4);
     for (;;) {
         // ===================================================== active-set loop
@@ -769,7 +769,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                 // partial step: the next trip removes slot lq from T (no update is pending for this row: RT is current)
                 const int cl = row_get(myact, rb, lq);
                 if constexpr (!SLIM) {
-                    wsync();
+                    wave_sync();
                     if (partial && l == lq) st16(kAv, RT);
                 }
                 if (partial) {
@@ -780,7 +780,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                     dropping = true;
                     ldrop = lq;
                 }
-                if constexpr (!SLIM) wsync();
+                if constexpr (!SLIM) wave_sync();
             }
         }
         tick(5);
@@ -793,7 +793,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
             static_for<0, NV>([&](auto ac) { aa[decltype(ac)::value] = __builtin_amdgcn_update_dpp(0, mine, 0x150 + decltype(ac)::value, 0xf, 0xf, false); });
         } else {
             actv[l] = occ ? myact : 0;
-            wsync();
+            wave_sync();
             const int4 *ap = reinterpret_cast<const int4 *>(actv);
 #pragma unroll
             for (int q = 0; q < NV / 4; ++q) {
@@ -851,7 +851,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                 });
             } else {
                 st16(Timg + l * NV, RT);
-                wsync();
+                wave_sync();
                 T tc[NV];
 #pragma unroll
                 for (int a = 0; a < NV; ++a) tc[a] = Timg[a * NV + l];
@@ -866,7 +866,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
             // with dl as it is (not clamped) y moves exactly onto the active hyperplanes: y - M_A' dl = y + M_A' T (T' rho)
             // = y + T' rho, because T' rho lies in the range of M_A' where M_A' T = I - H is the identity
             y += uk;
-            wsync();
+            wave_sync();
             slacks(y);
         }
         // ---- acceptance: no inactive row violated, every active row on its bound, lam >= 0 -- with stationarity by
@@ -915,7 +915,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                 finished = true;
             }
         }
-        wsync();
+        wave_sync();
         if (__ballot(!finished) == 0ull) break;
     }
     tick(6);
@@ -925,9 +925,9 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         T *lamv = Ml;  // (the M image is dead: every row has finished; 32 doubles)
         lamv[row0] = T(0);
         lamv[row1] = T(0);
-        wsync();
+        wave_sync();
         if (occ) lamv[myact] = lam;
-        wsync();
+        wave_sync();
         lo0 = ok ? lamv[row0] : T(0);
         lo1 = ok ? lamv[row1] : T(0);
     }

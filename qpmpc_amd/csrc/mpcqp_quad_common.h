@@ -1,7 +1,7 @@
 // mpcqp_quad_common.h -- what the four-problems-per-wavefront kernels share: the lean / shared-model kernel of mpcqp_quad.hip and the
 // general kernel of mpcqp_quadg.hip (two or four constraint rows per lane). Device helpers of a problem that owns ONE 16-lane DPP row
-// (reductions and broadcasts inside the row, the hand-written v_fmac_f64_dpp and the pin that gives it its wait states, 16-wide
-// loads, stores and dot products, the fast reciprocals) and the LDS carve of one problem.
+// beyond the lane primitives of mpcqp_lane.h (a lane's value and a predicate inside the row, the two-vector and the broadcast dot
+// products, the compile-time loop, the fast reciprocal square root) and the LDS carve of one problem.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,28 +10,14 @@
 #include <type_traits>
 
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
 namespace quad {
 
-constexpr int NV = 16;  // padded number of variables / slots = lanes per problem
+constexpr int NV = kRowLanes;  // padded number of variables / slots = lanes per problem
 
-template <int CTRL> __device__ __forceinline__ unsigned dpp_u(unsigned x)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
-}
-constexpr int ROR8 = 0x128, ROR4 = 0x124, ROR2 = 0x122, ROR1 = 0x121;  // rotate within a row of 16
-
-// all-reduce (min) over the 16 lanes of each row
-__device__ __forceinline__ unsigned row_min(unsigned v)
-{
-    v = min(v, dpp_u<ROR8>(v));
-    v = min(v, dpp_u<ROR4>(v));
-    v = min(v, dpp_u<ROR2>(v));
-    v = min(v, dpp_u<ROR1>(v));
-    return v;
-}
 // value of lane `idx` (0..15; per lane, usually uniform inside a row) of the caller's own row
 __device__ __forceinline__ int row_get(int x, int rb, int idx) { return __builtin_amdgcn_ds_bpermute((rb + idx) << 2, x); }
 __device__ __forceinline__ double row_get(double x, int rb, int idx)
@@ -46,47 +32,6 @@ __device__ __forceinline__ bool row_any(bool pred, int rb)
 {
     const unsigned long long b = __ballot(pred);
     return ((unsigned)(b >> rb) & 0xffffu) != 0u;
-}
-// order-preserving map of a double onto two unsigned words
-__device__ __forceinline__ void ordered(double x, unsigned &hi, unsigned &lo)
-{
-    const unsigned h = (unsigned)__double2hiint(x), l = (unsigned)__double2loint(x);
-    const bool neg = h & 0x80000000u;
-    hi = neg ? ~h : (h | 0x80000000u);
-    lo = neg ? ~l : l;
-}
-__device__ __forceinline__ void ld16(double (&d)[NV], const double *src)
-{
-    const double2 *p = reinterpret_cast<const double2 *>(src);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        const double2 t = p[i];
-        d[2 * i] = t.x;
-        d[2 * i + 1] = t.y;
-    }
-}
-__device__ __forceinline__ void st16(double *dst, const double (&s)[NV])
-{
-    double2 *p = reinterpret_cast<double2 *>(dst);
-#pragma unroll
-    for (int i = 0; i < NV / 2; ++i) {
-        double2 t;
-        t.x = s[2 * i];
-        t.y = s[2 * i + 1];
-        p[i] = t;
-    }
-}
-__device__ __forceinline__ double dot16(const double (&a)[NV], const double (&b)[NV])
-{
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-#pragma unroll
-    for (int k = 0; k < NV; k += 4) {
-        acc0 += a[k] * b[k];
-        acc1 += a[k + 1] * b[k + 1];
-        acc2 += a[k + 2] * b[k + 2];
-        acc3 += a[k + 3] * b[k + 3];
-    }
-    return (acc0 + acc1) + (acc2 + acc3);
 }
 // two dot products with one vector, two chains each (a lone wavefront issues a dependent FMA every 8.5 cycles and an
 // independent one every 5.1: four chains in flight are enough, and accumulators are registers the loop does not have)
@@ -103,18 +48,6 @@ __device__ __forceinline__ void dot16x2(const double (&a)[NV], const double (&b)
     ra = a0 + a1;
     rb = b0 + b1;
 }
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
-
-// The value held by lane N of the caller's 16-lane row, in every lane of that row (v_mov_b64_dpp row_newbcast:N).
-template <int N> __device__ __forceinline__ double row_bcast(double x) { return __builtin_amdgcn_mov_dpp(x, 0x150 + N, 0xf, 0xf, true); }
-// acc += (x of lane N of the caller's row) * m in ONE instruction (v_fmac_f64_dpp). The compiler cannot see inside the asm:
-// a register written by a VALU instruction needs two wait states before a DPP read, so every batch of these is preceded by
-// dpp_ready(x) on its broadcast source (tools/check_dpp_hazards.py verifies that on the assembly).
-template <int N> __device__ __forceinline__ void fmac_bcast(double &acc, double x, double m)
-{
-    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(m), "n"(N));
-}
-__device__ __forceinline__ void dpp_ready(double &x) { asm volatile("s_nop 1" : "+v"(x)); }
 // Compile-time loop: f(integral_constant<int, I>) for I = B .. E-1. The DPP lane select is an immediate, so the loops over lanes
 // are unrolled by the front end (a `switch` on an unrolled loop's counter is only folded AFTER the unroller has priced the
 // body with all sixteen cases in it -- the fused factorisation then exceeds the unroller's budget and stays a loop of jump tables).
@@ -139,15 +72,6 @@ __device__ __forceinline__ double dot_bcast(double x, const double (&m)[NV], dou
     return a0 + a1;
 }
 
-// 1/x from the hardware estimate plus two Newton steps (operands are never subnormal or zero when the result is used)
-__device__ __forceinline__ double fast_rcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    e = fma(-x, y, 1.0);
-    return fma(y, e, y);
-}
 // 1/sqrt(x) from the hardware estimate, one Newton step and one third-order step (x is a positive, normal number wherever the
 // result is used: a pivot of a positive definite matrix, a squared row norm; the library's rsqrt spends two thirds of its
 // instructions on subnormals and infinities)
@@ -159,14 +83,6 @@ __device__ __forceinline__ double fast_rsqrt(double x)
     e = fma(-x * y, y, 1.0);
     return fma(y * e, fma(0.375, e, 0.5), y);
 }
-// The wavefronts of a workgroup share nothing and a wavefront's LDS operations complete in order: only the COMPILER has
-// to keep the order of an exchange (no s_barrier, no queue drain).
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // LDS carve of ONE problem, in doubles, for ROWS constraint rows per lane (the M image holds 16 ROWS rows). Two of each:
 //  ROWS = 2 (up to 32 rows)
 //  * ROOMY (launches of one round: at most one wavefront per SIMD, so LDS is free): M image 32 x 18 (row stride 18 = 144 B: rows start

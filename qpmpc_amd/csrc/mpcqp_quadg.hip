@@ -387,7 +387,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
         }
         qa = col ? qa : T(0);
         tick(11);
-        wsync();  // the G image is complete
+        wave_sync();  // the G image is complete
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) hval[r] = isc[r] ? evl[r] - Gimg[(NV - 1) * GS + rowi[r]] : INF;  // h_i = e_i - C_k Phi_k x0 (column 15 of the image)
 #pragma unroll
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
                 });
             }
         });
-        wsync();  // the M image below reuses the G image
+        wave_sync();  // the M image below reuses the G image
     }
     }
     tick(2);
@@ -543,7 +543,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
     // pending rank-one update R += c v, applied at the top of the next trip -- the ONE site that writes the register rows,
     // selects and fetches
     T zn = T(0), cT = T(0), cH = T(0);
-    wsync();
+    wave_sync();
     tick(4);
     for (;;) {
         // ===================================================== active-set loop
@@ -725,7 +725,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
                 // partial step: the next trip removes slot lq from T (no update is pending for this row: RT is current)
                 const int cl = row_get(myact, rb, lq);
                 if constexpr (!SLIM) {
-                    wsync();
+                    wave_sync();
                     if (partial && l == lq) st16(kAv, RT);
                 }
                 if (partial) {
@@ -736,7 +736,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
                     dropping = true;
                     ldrop = lq;
                 }
-                if constexpr (!SLIM) wsync();
+                if constexpr (!SLIM) wave_sync();
             }
         }
         tick(5);
@@ -749,7 +749,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
             static_for<0, NV>([&](auto ac) { aa[decltype(ac)::value] = __builtin_amdgcn_update_dpp(0, mine, 0x150 + decltype(ac)::value, 0xf, 0xf, false); });
         } else {
             actv[l] = occ ? myact : 0;
-            wsync();
+            wave_sync();
             const int4 *ap = reinterpret_cast<const int4 *>(actv);
 #pragma unroll
             for (int q = 0; q < NV / 4; ++q) {
@@ -811,7 +811,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
                 });
             } else {
                 st16(Timg + l * NV, RT);
-                wsync();
+                wave_sync();
                 T tc[NV];
 #pragma unroll
                 for (int a = 0; a < NV; ++a) tc[a] = Timg[a * NV + l];
@@ -826,7 +826,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
             // with dl as it is (not clamped) y moves exactly onto the active hyperplanes: y - M_A' dl = y + M_A' T (T' rho)
             // = y + T' rho, because T' rho lies in the range of M_A' where M_A' T = I - H is the identity
             y += uk;
-            wsync();
+            wave_sync();
             slacks(y);
         }
         // ---- acceptance: no inactive row violated, every active row on its bound, lam >= 0 -- with stationarity by
@@ -878,7 +878,7 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
                 finished = true;
             }
         }
-        wsync();
+        wave_sync();
         if (__ballot(!finished) == 0ull) break;
     }
     tick(6);
@@ -890,9 +890,9 @@ __global__ void __launch_bounds__(64, (ROWS == 2 && SLIM) ? 2 : 1)  // (four row
         T *lamv = Ml;  // (the M image is dead: every row has finished; MMAX doubles)
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) lamv[rowi[r]] = T(0);
-        wsync();
+        wave_sync();
         if (occ) lamv[myact] = lam;
-        wsync();
+        wave_sync();
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) lo[r] = ok ? lamv[rowi[r]] : T(0);
     }
@@ -961,7 +961,7 @@ int launch_quad4_wide(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
     // nx = 5 .. 8: the streamed build in its padded size 8. (Not the all-steps-in-registers build for nx = 5, 6: with eight rows per
     // step it keeps 80 / 96 operand registers alive next to this kernel's ~330, the allocator parks some in accumulation registers and
-    // moves them back right in front of the hand-written v_fmac_f64_dpp that reads them -- without the two wait states a DPP read
+    // moves them back right in front of the hand-written DPP FMA (fmac_bcast) that reads them -- without the two wait states a DPP read
     // needs: wrong plans (tools/check_dpp_hazards.py finds some of those sites, the oracle found the rest).)
     return launch_quadg_t<8, 4>(ka, batch, st);
 }

@@ -38,6 +38,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 #include "mpcqp_plant.h"
 
 namespace mpcqp {
@@ -121,43 +122,9 @@ __host__ __device__ inline Ws make_ws(int nx, int nu, int N, int mk, int maxq)
     return w;
 }
 
-__device__ __forceinline__ double rl(double x, int lane)  // lane must be wave-uniform
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-// reciprocal: hardware estimate + two Newton steps (the IEEE division sequence is ~15 dependent instructions)
-__device__ __forceinline__ double frcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    y = fma(fma(-x, y, 1.0), y, y);
-    return fma(fma(-x, y, 1.0), y, y);
-}
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
-// (value, index) arg-min over the wavefront; ties -> lowest index; every lane gets the result
-__device__ __forceinline__ void wave_argmin(double &v, int &idx) { wave_argmin_dpp(v, idx); }
-// stores of one lane become visible to the other lanes of the wavefront (same CU, same L1)
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// hand-over through LDS inside ONE wavefront: its LDS operations execute in order, so nothing has to be waited for --
-// only the compiler must not move the accesses across this point
-__device__ __forceinline__ void lsync()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 }  // namespace stage
 
 using namespace stage;
-
-// bytes per problem of the warm-state record (MpcqpSolveOpts.warm_state) for `maxq` slots
-__host__ __device__ size_t stage_warm_bytes(int maxq) { return ((size_t)(4 + 2 * maxq) * sizeof(int) + 15) & ~(size_t)15; }
 
 // PIPE (MPCQP_OPT_PIPELINE_FACTOR; serial instantiations): TWO wavefronts per problem. Wavefront 0 solves with the factor a
 // previous launch left in the workspace (as MPCQP_OPT_REUSE_FACTOR does), wavefront 1 -- on another SIMD, at the same time --
@@ -434,7 +401,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
 #pragma unroll
                         for (int j = 0; j < NPQ; ++j) dst[j][na + i0 + 64 * u] = v[j][u];
             }
-            wsync();
+            wave_sync_workgroup();
         }
         auto request = [&](int d, int k) {
             if constexpr (PIPE) {
@@ -469,7 +436,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             if constexpr (NU == 1) {
                 const double S = Sm + wu;
                 notpd |= !(S > 0.0);
-                Si[0] = frcp(S);
+                Si[0] = fast_rcp_e_first(S);
                 Kd = Si[0] * BPA;
                 Aclo = Am - Bk * Kd;
             } else {
@@ -480,11 +447,11 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                         return __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(Sm)),
                                                 __builtin_amdgcn_ds_bpermute(src, __double2loint(Sm)));
                     } else {
-                        return rl(Sm, 16 * rr + cc);
+                        return lane_get_halves(Sm, 16 * rr + cc);
                     }
                 };
                 const double s00 = sget(0, 0) + wu, s01 = sget(0, 1), s10 = sget(1, 0), s11 = sget(1, 1) + wu;
-                const double det = s00 * s11 - s01 * s10, id = frcp(det);
+                const double det = s00 * s11 - s01 * s10, id = fast_rcp_e_first(det);
                 notpd |= !(s00 > 0.0) | !(det > 0.0);
                 Si[0] = s11 * id;
                 Si[1] = -s01 * id;
@@ -557,13 +524,13 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 else
                     (wsbase + pq * wl.total + wl.Fimg + (int64_t)(slot ^ 1) * N * FS)[FSI] = __builtin_nan("");
             }
-            wsync();
+            wave_sync_workgroup();
             tick(10);
             return;
         }
     }
     notpd = __ballot(notpd) != 0ull;
-    wsync();
+    wave_sync_workgroup();
     if constexpr (PIPE) {
         if (factor_wave) {  // this wavefront's work is done: mark a factor that does not exist, like KEEP does
             if (notpd && lane == 0) img_next[FSI] = __builtin_nan("");
@@ -575,7 +542,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
         // the factor image travels between LDS and the workspace as it is (coalesced, one round trip); a factor that
         // does not exist is marked by a NaN in its first S^-1 so that a launch reusing it reports MPCQP_NOT_PD as well
         if (!reuse && notpd && lane == 0) Fl[FSI] = __builtin_nan("");
-        if (!reuse && notpd) wsync();
+        if (!reuse && notpd) wave_sync_workgroup();
         if (reuse) {
             // straight into LDS (global_load_lds_dwordx4: 1 KB per instruction, no staging registers), every request in
             // flight at once: ONE round trip for the image (a load -> LDS store loop paid one per turn of eight requests)
@@ -591,7 +558,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 for (int c = 0; c < nfull; ++c)
                     __builtin_amdgcn_global_load_lds((glb_void *)(src + c * 64 + lane), (lds_void *)(dst + c * 64), 16, 0, 0);
                 if (nfull * 64 + lane < n2) dst[nfull * 64 + lane] = src[nfull * 64 + lane];
-                wsync();
+                wave_sync_workgroup();
             }
             notpd = Fl[FSI] != Fl[FSI];
         } else if (keep) {
@@ -691,9 +658,9 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             double nxt[NX];
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
-                double a = rl(off[i], src);
+                double a = lane_get_halves(off[i], src);
 #pragma unroll
-                for (int q = 0; q < NX; ++q) a += rl(Qf[i * NX + q], src) * cur[q];
+                for (int q = 0; q < NX; ++q) a += lane_get_halves(Qf[i * NX + q], src) * cur[q];
                 nxt[i] = a;
             }
 #pragma unroll
@@ -741,9 +708,9 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             double nxt[NX];
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
-                double a = rl(off[i], src);
+                double a = lane_get_halves(off[i], src);
 #pragma unroll
-                for (int q = 0; q < NX; ++q) a += rl(Qb[i * NX + q], src) * cur[q];
+                for (int q = 0; q < NX; ++q) a += lane_get_halves(Qb[i * NX + q], src) * cur[q];
                 nxt[i] = a;
             }
 #pragma unroll
@@ -910,7 +877,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
     // tools/ubench/mfma_f64_4x4.hip); a second product off the chain gives the feed-forward term (backward) or the input
     // (forward). The operands are requested STAGE_SRD steps ahead through running pointers (no clamping: the image has that
     // many steps of slack on either side); S^-1 is folded into the feed-forward rows by the factor; nothing is stored under an
-    // exec mask. ~12 instructions per step. Round 4: component q in quad q of a row, eight dependent v_fmac_f64_dpp per step,
+    // exec mask. ~12 instructions per step. Round 4: component q in quad q of a row, eight dependent DPP FMAs per step,
     // 22 instructions, ~165 cycles.
     constexpr int SRD = STAGE_SRD;  // request distance of the serial sweeps, in steps (their operands sit in LDS: ~100+ cycles, a step is ~80)
     // A value that only one lane (or one lane per quad) has to store is stored by EVERY lane, each to an address of its own:
@@ -1126,7 +1093,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
     if constexpr (serial)
         lsync();  // (the feed-forward terms go from lane to lane through LDS: nothing to wait for)
     else
-        wsync();
+        wave_sync_workgroup();
     tick(3);
     if (!notpd) {
         if constexpr (serial)
@@ -1134,7 +1101,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
         else
             forward(gx0, U0, X0);
     }
-    if constexpr (!serial) wsync();  // (serial: the slack pass below reads the trajectory where the sweep staged it, in LDS)
+    if constexpr (!serial) wave_sync_workgroup();  // (serial: the slack pass below reads the trajectory where the sweep staged it, in LDS)
     tick(4);
     const double tol = ka.tol;
     // The same pass makes the FIRST selection (the values are in registers: the loop's own selection pass would wait for
@@ -1178,7 +1145,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
     // (the slacks, norms and slot table just stored are read by other lanes from the first iteration on. SERIAL cold start: the
     // first selection comes from registers, so the wait for those stores is taken only if a row IS violated -- below)
     constexpr bool late_fence = SERIAL && !WARM;
-    if constexpr (!late_fence) wsync();
+    if constexpr (!late_fence) wave_sync_workgroup();
 
     tick(5);
     // ================================================================= active-set loop
@@ -1189,7 +1156,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
     bool early_plan = false;
     if constexpr (late_fence) {
         if (!notpd) {
-            wave_argmin(best, bi);  // (the loop's own reduction of the reduced pair changes nothing)
+            wave_argmin_dpp(best, bi);  // (the loop's own reduction of the reduced pair changes nothing)
             early_plan = !(best < INF);
         }
     }
@@ -1202,19 +1169,19 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
         const double wll = Wm[(int64_t)l * maxq + l];
         const double iw = 1.0 / wll;
         for (int a = lane; a < nq; a += 64) cv[a] = Wm[(int64_t)l * maxq + a];  // row l before the update
-        wsync();
+        wave_sync_workgroup();
         for (int a = lane; a < nq; a += 64) {
             const double wa = cv[a];
             for (int b = 0; b < nq; ++b) Wm[(int64_t)b * maxq + a] -= cv[b] * wa * iw;
         }
-        wsync();
+        wave_sync_workgroup();
         const int last = nq - 1;
         const int64_t drow = wg(actk[l]) * mk + actr[l];
         if (l != last) {
             for (int a = lane; a < nq; a += 64) Wm[(int64_t)l * maxq + a] = Wm[(int64_t)last * maxq + a];
-            wsync();
+            wave_sync_workgroup();
             for (int b = lane; b < nq; b += 64) Wm[(int64_t)b * maxq + l] = Wm[(int64_t)b * maxq + last];
-            wsync();
+            wave_sync_workgroup();
             const double *vs = Vs + (int64_t)last * NP * NU, *xs = XVs + (int64_t)last * NP * NX;
             double *vd = Vs + (int64_t)l * NP * NU, *xd = XVs + (int64_t)l * NP * NX;
             for (int k = k0; k < k1; ++k) {
@@ -1291,12 +1258,12 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
         dirty = __ballot(dirty) != 0ull;
         offa = __ballot(offa) != 0ull;
         rough = __ballot(rough) != 0ull;
-        wsync();
+        wave_sync_workgroup();
     };
     // back to the empty active set at the unconstrained minimiser
     auto cold_start = [&]() {
         for (int a = lane; a < nq; a += 64) rowslot[wg(actk[a]) * mk + actr[a]] = -1;
-        wsync();
+        wave_sync_workgroup();
         nq = 0;
         bool d = false, o = false;
         eval_point(false, d, o);
@@ -1322,16 +1289,16 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             bad |= k < 0 || k >= N || r < 0 || r >= mk;
         }
         if (__ballot(bad) != 0ull) nqs = 0;
-        wsync();
+        wave_sync_workgroup();
         for (int a = lane; a < nqs; a += 64) rowslot[wg(actk[a]) * mk + actr[a]] = a;
-        wsync();
+        wave_sync_workgroup();
         bad = false;
         for (int a = lane; a < nqs; a += 64) bad |= rowslot[wg(actk[a]) * mk + actr[a]] != a;  // (a row listed twice)
         nq = nqs;
         if (__ballot(bad) != 0ull) cold_start();
         while (nq > 0) {
             for (int a = lane; a < nq; a += 64) cv[a] = sl[wg(actk[a]) * mk + actr[a]];  // slacks at the unconstrained minimiser
-            wsync();
+            wave_sync_workgroup();
             double lmin = INF;
             int l = 0x7fffffff;
             bool nan = false;
@@ -1349,13 +1316,13 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 cold_start();
                 break;
             }
-            wave_argmin(lmin, l);
-            wsync();
+            wave_argmin_dpp(lmin, l);
+            wave_sync_workgroup();
             if (!(lmin < 0.0)) break;
             drop_slot(l);
             --nq;
             ++iters;
-            wsync();
+            wave_sync_workgroup();
         }
         if (nq > 0) {
             bool d = false, o = false;
@@ -1383,14 +1350,14 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 }
             const bool first_sel = presel;
             presel = false;
-            wave_argmin(best, bi);
+            wave_argmin_dpp(best, bi);
             if (!(best < INF)) {
                 status = MPCQP_SOLVED;
                 if (first_sel) unconstrained = true;  // nothing was violated at the unconstrained minimiser: it is the plan
                 break;
             }
             if constexpr (late_fence)
-                if (first_sel) wsync();
+                if (first_sel) wave_sync_workgroup();
             const int kp = bi / mk, rp = bi - kp * mk;
             const int64_t wp = wg(kp), bw = wp * mk + rp;  // workspace index of step kp / of row p
             double qrow[NX], rrow[NU];
@@ -1409,7 +1376,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             if constexpr (serial)
                 lsync();
             else
-                wsync();
+                wave_sync_workgroup();
             if constexpr (serial)
                 forward_s(0.0, Vp, Xp);
             else
@@ -1417,7 +1384,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
             // SERIAL: the candidate's vectors are read where the sweep staged them, in LDS (step order) -- no wait for the workspace
             // copy, which only the slot copy of a row that becomes active reads (each lane its own chunk)
             const double *Vc = SERIAL ? ul : Vp, *Xc = SERIAL ? xl : Xp;
-            if constexpr (!serial) wsync();
+            if constexpr (!serial) wave_sync_workgroup();
             tacc(9);  // sweeps
             const double dpp = gdot(kp, SERIAL ? (int64_t)kp : wp, rp, Vc, Xc);
             while (!added) {
@@ -1431,7 +1398,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 if constexpr (serial)
                     lsync();  // (c goes from lane to lane through LDS)
                 else
-                    wsync();
+                    wave_sync_workgroup();
                 double cr = 0.0;
                 for (int a = lane; a < nq; a += 64) {
                     double acc = 0.0;
@@ -1439,11 +1406,11 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                     rv[a] = acc;
                     cr += acc * cv[a];
                 }
-                cr = wave_sum(cr);
+                cr = wave_sum_dpp(cr);
                 if constexpr (serial)
                     lsync();  // (r likewise)
                 else
-                    wsync();
+                    wave_sync_workgroup();
                 tacc(10);  // c, r = W c
                 const double d2 = dpp - cr;
                 const bool can_move = (nq < nvar) && (d2 > 1e-13 * dpp) && (d2 > 0.0);
@@ -1460,7 +1427,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                         }
                     }
                 }
-                wave_argmin(t1, l);
+                wave_argmin_dpp(t1, l);
                 const double sp = sl[bw];
                 const double t2 = can_move ? -sp / d2 : INF;
                 const double t = t1 < t2 ? t1 : t2;
@@ -1509,7 +1476,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                     lamv[a] = v < 0.0 ? 0.0 : v;
                 }
                 up += t;
-                wsync();
+                wave_sync_workgroup();
                 tacc(13);  // slack update
                 if (full) {
                     // p becomes active in slot nq: W is bordered, the candidate's vectors move into the slot
@@ -1542,7 +1509,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                     drop_slot(l);
                     --nq;
                 }
-                wsync();
+                wave_sync_workgroup();
                 tacc(-1);  // (W update, slot copy: the rest)
             }
             if (fail) break;
@@ -1569,12 +1536,12 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                     for (int b = 0; b < nq; ++b) acc += Wm[(int64_t)b * maxq + a] * cv[b];  // W is symmetric
                     rv[a] = acc;
                 }
-                wsync();
+                wave_sync_workgroup();
                 for (int a = lane; a < nq; a += 64) {
                     const double v = lamv[a] - rv[a];
                     lamv[a] = v < 0.0 ? 0.0 : v;
                 }
-                wsync();
+                wave_sync_workgroup();
                 dirty = offa = false;
                 eval_point(true, dirty, offa);
             }
@@ -1643,7 +1610,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
         if constexpr (SERIAL) {
             a = ok ? __shfl(u_first[0], 0) : 0.0;
         } else {
-            wsync();
+            wave_sync_workgroup();
             a = ok ? ((const double *)ka.U)[prob * (int64_t)N * NU] : 0.0;
         }
         wip_period_wave<double>(lane, (double *)ka.ep_states + prob * 4, ep_s0, a, N, ka.ep_Tp, ka.ep_vel, ka.ep_omega2, ka.ep_g,
@@ -1683,7 +1650,7 @@ __global__ void __launch_bounds__(PIPE ? (PWT == 4 ? 320 : 128) : 64, PIPE && PW
                 // writes have to be complete at the barrier: the global stores (plan, next problem, counters) drain behind it
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             } else {
-                wsync();
+                wave_sync_workgroup();
                 __builtin_amdgcn_s_dcache_inv();
                 if constexpr (PIPE) __syncthreads();
             }

@@ -39,6 +39,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 #ifndef STAGEG_VPASS
 // passes of the final verification: each one re-evaluates every slack from scratch and, while an active row is off its bound,
@@ -340,9 +341,6 @@ __global__ void __launch_bounds__(BS, 2) mpcqp_stageg_kernel(const KernelArgs ka
     const int XS = nx + nu, oT = 0, oF = nx;
     const int RG = ring_doubles / (2 * (PSW + XS)) < 1 ? 1 : (ring_doubles / (2 * (PSW + XS)) > 16 ? 16 : ring_doubles / (2 * (PSW + XS)));
     const int HALF = RG * (PSW + XS);
-    auto rlane = [&](T x, int l) {  // (l: compile-time after unrolling)
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-    };
     // sum_l row[l rs] v_l over the (clamped) 32 components of the vector held one per lane in `v`: every LDS read issued before
     // the first use, four partial sums (a dependent float64 FMA issues every 8 cycles, an independent one every 4)
     auto dot32 = [&](const T *row, int rs, T v) {
@@ -362,7 +360,7 @@ __global__ void __launch_bounds__(BS, 2) mpcqp_stageg_kernel(const KernelArgs ka
             T a = 0.0;
             const T r0 = row[0];
 #pragma unroll
-            for (int l = 0; l < NXM; ++l) a += r0 * rlane(v, l);
+            for (int l = 0; l < NXM; ++l) a += r0 * lane_get_halves(v, l);
             return a;
         }
 #endif
@@ -372,10 +370,10 @@ __global__ void __launch_bounds__(BS, 2) mpcqp_stageg_kernel(const KernelArgs ka
         T a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
         for (int l = 0; l < NXM; l += 4) {
-            a0 += rv_[l] * rlane(v, l);
-            a1 += rv_[l + 1] * rlane(v, l + 1);
-            a2 += rv_[l + 2] * rlane(v, l + 2);
-            a3 += rv_[l + 3] * rlane(v, l + 3);
+            a0 += rv_[l] * lane_get_halves(v, l);
+            a1 += rv_[l + 1] * lane_get_halves(v, l + 1);
+            a2 += rv_[l + 2] * lane_get_halves(v, l + 2);
+            a3 += rv_[l + 3] * lane_get_halves(v, l + 3);
         }
         return (a0 + a1) + (a2 + a3);
     };
@@ -455,8 +453,8 @@ __global__ void __launch_bounds__(BS, 2) mpcqp_stageg_kernel(const KernelArgs ka
                     T f0 = 0.0, f1 = 0.0;
 #pragma unroll
                     for (int bb = 0; bb < NUM; bb += 2) {
-                        f0 -= srow[bb < nu ? bb : 0] * rlane(tm, 32 + bb);
-                        f1 -= srow[bb + 1 < nu ? bb + 1 : 0] * rlane(tm, 32 + bb + 1);
+                        f0 -= srow[bb < nu ? bb : 0] * lane_get_halves(tm, 32 + bb);
+                        f1 -= srow[bb + 1 < nu ? bb + 1 : 0] * lane_get_halves(tm, 32 + bb + 1);
                     }
                     const T f = f0 + f1;
                     if (roleT) ffv[k * nu + ti] = f;
@@ -495,8 +493,8 @@ __global__ void __launch_bounds__(BS, 2) mpcqp_stageg_kernel(const KernelArgs ka
                     T b0 = 0.0, b1 = 0.0;  // B ff (no branch per term: see the backward sweep)
 #pragma unroll
                     for (int a = 0; a < NUM; a += 2) {
-                        b0 += brow[a < nu ? a : 0] * rlane(ffown, 32 + a);
-                        b1 += brow[a + 1 < nu ? a + 1 : 0] * rlane(ffown, 32 + a + 1);
+                        b0 += brow[a < nu ? a : 0] * lane_get_halves(ffown, 32 + a);
+                        b1 += brow[a + 1 < nu ? a + 1 : 0] * lane_get_halves(ffown, 32 + a + 1);
                     }
                     if (roleP) acc += b0 + b1;
                     if (roleT) Vout[k * nu + ti] = acc;

@@ -31,6 +31,7 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
@@ -161,20 +162,6 @@ inline Ws make_ws(int nx, int nu, int N, int mk, int maxq, bool ginv, size_t esz
     return w;
 }
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v) { return wave_sum_dpp(v); }
-template <typename T> __device__ __forceinline__ void wave_argmin(T &v, int &idx) { wave_argmin_dpp(v, idx); }
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-// hand-over through LDS inside ONE wavefront: its LDS operations execute in order, so nothing has to be waited for --
-// only the compiler must not move the accesses across this point
-__device__ __forceinline__ void lsync()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 template <typename T> struct Tol;
 template <> struct Tol<double> { static constexpr double dep = 1e-13; };
 template <> struct Tol<float> { static constexpr float dep = 1e-6f; };
@@ -244,18 +231,6 @@ __device__ __forceinline__ void mm_t(T *C, const T *A, const T *B, const T *Add,
     }
 }
 
-// reciprocal: hardware estimate + Newton steps (the IEEE division sequence is ~10 instructions, this is 3 / 5)
-__device__ __forceinline__ float frcp(float x)
-{
-    const float r = __builtin_amdgcn_rcpf(x);
-    return fmaf(fmaf(-x, r, 1.0f), r, r);
-}
-__device__ __forceinline__ double frcp(double x)
-{
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return fma(fma(-x, r, 1.0), r, r);
-}
 // reciprocal square root: hardware estimate + Newton steps
 __device__ __forceinline__ float frsq(float x)
 {
@@ -275,21 +250,21 @@ template <typename T> struct Ldl4 {
     __device__ __forceinline__ bool factor(const T (&s)[10])  // s = (s00, s10, s11, s20, s21, s22, s30, s31, s32, s33)
     {
         const T d0 = s[0];
-        id[0] = frcp(d0);
+        id[0] = fast_rcp_e_first(d0);
         l[0] = s[1] * id[0];
         l[1] = s[3] * id[0];
         l[2] = s[6] * id[0];
         const T d1 = s[2] - l[0] * s[1];
-        id[1] = frcp(d1);
+        id[1] = fast_rcp_e_first(d1);
         const T t21 = s[4] - l[1] * s[1], t31 = s[7] - l[2] * s[1];
         l[3] = t21 * id[1];
         l[4] = t31 * id[1];
         const T d2 = s[5] - l[1] * s[3] - l[3] * t21;
-        id[2] = frcp(d2);
+        id[2] = fast_rcp_e_first(d2);
         const T t32 = s[8] - l[2] * s[3] - l[4] * t21;
         l[5] = t32 * id[2];
         const T d3 = s[9] - l[2] * s[6] - l[4] * t31 - l[5] * t32;
-        id[3] = frcp(d3);
+        id[3] = fast_rcp_e_first(d3);
         sd[0] = frsq(d0);
         sd[1] = frsq(d1);
         sd[2] = frsq(d2);
@@ -370,12 +345,6 @@ template <typename T, int K> __device__ __forceinline__ T multi_sum(const T (&p)
     d += lane_xor<16>(d);
     d += lane_xor<32>(d);
     return d;
-}
-// lane j's value as a wave-uniform scalar (v_readlane)
-__device__ __forceinline__ float rl(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
-__device__ __forceinline__ double rl(double v, int j)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
 }
 
 }  // namespace stagew
@@ -586,7 +555,7 @@ __global__ void __launch_bounds__(64)
                 for (int i = 0, e = 0; i < 4; ++i)
 #pragma unroll
                     for (int j = 0; j <= i; ++j, ++e)
-                        sv[e] = rl(H[TI], 16 * i + Mfma<T>::rowmap(NXC + j)) + ((i == j) ? (i < nu ? wu : T(1)) : T(0));
+                        sv[e] = lane_get_halves(H[TI], 16 * i + Mfma<T>::rowmap(NXC + j)) + ((i == j) ? (i < nu ? wu : T(1)) : T(0));
                 notpd |= !ldl.factor(sv);
             }
             // S^-1 spread over the input block: lane (pg, input column b) holds S^-1[pg][b]
@@ -685,14 +654,14 @@ __global__ void __launch_bounds__(64)
         for (int d = 0; d < PD - 1; ++d)
             if (k - d >= 0) rstep(d, k - d);
         if (lane < 8) cst[lane] = lane == 1 ? T(1) : T(0);
-        wsync();
+        wave_sync_workgroup();
     } else {
         // ---- nx > 12: 16 x 16 tiles in LDS
         for (int i = lane; i < (int)(cst - Pm) + 8; i += 64) Pm[i] = T(0);  // every tile and the constants
-        wsync();
+        wave_sync_workgroup();
         if (lane < nx) Pm[lane * LD + lane] = wt;
         if (lane == 0) cst[1] = T(1);
-        wsync();
+        wave_sync_workgroup();
         // where this lane's record values come from (LDS offsets from Pm; fixed along the horizon): entry (blk, kk) of a
         // record is the stacked matrix at row rowmap(lane % 16) of block blk, column 4 kk + lane / 16
         int srcb[NB], srcf[NF];
@@ -775,14 +744,14 @@ __global__ void __launch_bounds__(64)
             }
             Pm[offB] = pfb;
             Pm[offBt] = pfb;
-            wsync();
+            wave_sync_workgroup();
             request(k > 0 ? k - 1 : 0);
             mm_t<T, LD, LD, LD, 16, 16, NXC, false>(PAm, Pm, Am, nullptr, pg, c16);    // PA = P A
             mm_t<T, LD, 4, 4, 16, 4, NXC, false>(PBm, Pm, Bm, nullptr, pg, c16);      // PB = P B
-            wsync();
+            wave_sync_workgroup();
             mm_t<T, LD, 4, 4, 4, 4, NXC, false>(Sm, Btm, PBm, nullptr, pg, c16);     // B' P B
             mm_t<T, LD, LD, LD, 4, 16, NXC, false>(BPAm, Btm, PAm, nullptr, pg, c16); // B' P A
-            wsync();
+            wave_sync_workgroup();
             // S = w_u I + B'PB (nu <= 4, identity on the padding) is factored L D L' in registers, every lane the same; lane
             // (., c) then solves for column c of K = S^-1 B'PA and of F = -S^-1 B' (row group i writes row i)
             Ldl4<T> ldl;
@@ -813,10 +782,10 @@ __global__ void __launch_bounds__(64)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ldl.id[i] = sid[i];  // (what the workspace keeps: 1 / sqrt(d_i))
             }
-            wsync();
+            wave_sync_workgroup();
             mm_t<T, 4, LD, LD, 16, 16, 4, true>(Acm, Bm, Km, Am, pg, c16);           // Acl = A - B K
             mm_t<T, 4, LD, LD, 16, 16, 4, true>(Mm, PBm, Km, PAm, pg, c16);          // M = P Acl = PA - PB K
-            wsync();
+            wave_sync_workgroup();
             mm_t<T, LD, LD, LD, 16, 16, NXC, false>(PAm, Atm, Mm, nullptr, pg, c16);   // A' P Acl (into the PA tile)
             // factors to the workspace: the sweeps' records (A-operand order, 64 consecutive values per MFMA), and K', S^-1
             // (read at the candidate row's step)
@@ -838,7 +807,7 @@ __global__ void __launch_bounds__(64)
                     *(RecF *)(mf + g * 64 * LF) = v;
                 }
             }
-            wsync();
+            wave_sync_workgroup();
             // P_k = Q_k + sym(A' P Acl)   (x_0 is data: Q_0 = 0)
             {
                 const T qk = (k >= 1) ? wx : T(0);
@@ -848,11 +817,11 @@ __global__ void __launch_bounds__(64)
                     const int r = pg + 4 * t;
                     pn[t] = T(0.5) * (PAm[r * LD + c16] + PAm[c16 * LD + r]) + ((r == c16 && r < nx) ? qk : T(0));  // (zero padding)
                 }
-                wsync();
+                wave_sync_workgroup();
 #pragma unroll
                 for (int t = 0; t < 4; ++t) Pm[(pg + 4 * t) * LD + c16] = pn[t];
             }
-            wsync();
+            wave_sync_workgroup();
         }
     }
     tick(1);
@@ -1036,7 +1005,7 @@ __global__ void __launch_bounds__(64)
         }
     };
     auto sel_reduce = [&]() {
-        wave_argmin(selb, seli);
+        wave_argmin_dpp(selb, seli);
         selv = __shfl(selv, owner(seli < M ? seli : 0));
     };
     T myinvn = T(1);  // FUSE: 1 / |g_r| of the row this lane owns in the sweeps (r = 4 pg + c16, c16 < 4)
@@ -1241,7 +1210,7 @@ __global__ void __launch_bounds__(64)
         if constexpr (FUSE && sizeof(T) == 4) {
             int dummy = 0;
             T neg = -xm;
-            wave_argmin(neg, dummy);
+            wave_argmin_dpp(neg, dummy);
             xmax = -neg;
         }
     };
@@ -1311,7 +1280,7 @@ __global__ void __launch_bounds__(64)
         offa = false;
         forward(modec, xs, yoff, fac);
         if constexpr (!FUSE) {
-            wsync();  // (the trajectory is read by other lanes)
+            wave_sync_workgroup();  // (the trajectory is read by other lanes)
             rowpass(mode, fac);
         }
         sel_reduce();
@@ -1404,7 +1373,7 @@ __global__ void __launch_bounds__(64)
                 if (j < jstart) continue;  // (wave-uniform)
                 T v = b1;
                 int ix = i1;
-                wave_argmin(v, ix);
+                wave_argmin_dpp(v, ix);
                 rows[j] = (v < INF) ? ix : -1;
                 if (v < INF && ix == i1) {
                     b1 = b2;
@@ -1478,7 +1447,7 @@ __global__ void __launch_bounds__(64)
         }
         if constexpr (!STACK) backward(std::true_type{}, -1, pN, T(0), -1);  // (nx <= 12: done inside the recursion)
     }
-    wsync();
+    wave_sync_workgroup();
     tick(3);
     // ---- LDS of the active set (round 6): the thin QR factorisation Y_A = Q R of the active rows' whitened vectors. R (upper
     // triangular, by COLUMNS through a permutation: nothing is copied when a row leaves) sits in a WL x WL tile of LDS and
@@ -1534,10 +1503,10 @@ __global__ void __launch_bounds__(64)
                     p2 += dot4(v2, sv);
                     p3 += dot4(v3, sv);
                 }
-                p0 = wave_sum(p0);
-                p1 = wave_sum(p1);
-                p2 = wave_sum(p2);
-                p3 = wave_sum(p3);
+                p0 = wave_sum_dpp(p0);
+                p1 = wave_sum_dpp(p1);
+                p2 = wave_sum_dpp(p2);
+                p3 = wave_sum_dpp(p3);
                 if (lane == 0) {
                     co[a0] = p0;
                     if (a0 + 1 < nq) co[a0 + 1] = p1;
@@ -1561,9 +1530,9 @@ __global__ void __launch_bounds__(64)
                 ((V4 *)zq)[k] = acc;
                 part += dot4(acc, acc);
             }
-            const T prev = pass == 0 ? wave_sum(ypart) : zz;
+            const T prev = pass == 0 ? wave_sum_dpp(ypart) : zz;
             if (pass == 0) yy = prev;
-            zz = wave_sum(part);
+            zz = wave_sum_dpp(part);
             if (pass == 1) {
                 for (int a = lane; a < nq; a += 64) cv[a] += ev[a];
                 lsync();
@@ -1589,7 +1558,7 @@ __global__ void __launch_bounds__(64)
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const T g = wave_sum(p[u]);
+                const T g = wave_sum_dpp(p[u]);
                 if (lane == 0 && j0 + u < R) cg[j0 + u] = g;
             }
         }
@@ -1677,8 +1646,8 @@ __global__ void __launch_bounds__(64)
             yy = lane_get(r1, QF);
         } else {  // (three / two wavefronts per SIMD hide a wave_sum's chain, and the multi-reduction's registers spill there)
 #pragma unroll
-            for (int u = 0; u < QF; ++u) dd[u] = u < nq ? wave_sum(p1[u]) : T(0);
-            yy = wave_sum(p1[QF]);
+            for (int u = 0; u < QF; ++u) dd[u] = u < nq ? wave_sum_dpp(p1[u]) : T(0);
+            yy = wave_sum_dpp(p1[QF]);
         }
         V4 zv = yv;
 #pragma unroll
@@ -1722,10 +1691,10 @@ __global__ void __launch_bounds__(64)
                 zz = lane_get(r2, 7);
                 cgmine = r2;  // (lane j < R: y_j . z)
             } else {  // a wave_sum per cached row (their vectors were requested with Q's: one round trip for the iteration)
-                zz = wave_sum(dot4(zv, zv));
+                zz = wave_sum_dpp(dot4(zv, zv));
 #pragma unroll
                 for (int j = 0; j < R; ++j) {
-                    const T g = wave_sum(dot4(ycu[j], zv));
+                    const T g = wave_sum_dpp(dot4(ycu[j], zv));
                     cgmine = lane == j ? g : cgmine;
                 }
             }
@@ -1734,7 +1703,7 @@ __global__ void __launch_bounds__(64)
             // cancellation (rare): once more on z
 #pragma unroll
             for (int u = 0; u < QF; ++u) {
-                const T e2 = u < nq ? wave_sum(dot4(qv[u], zv)) : T(0);
+                const T e2 = u < nq ? wave_sum_dpp(dot4(qv[u], zv)) : T(0);
                 dd[u] += e2;
                 zv -= e2 * qv[u];
             }
@@ -1788,7 +1757,7 @@ __global__ void __launch_bounds__(64)
             const T *col = Rp + (int64_t)colp[b] * ld;
             T part = T(0);
             for (int j = lane; j < b; j += 64) part += col[j] * ev[j];
-            const T wb = (cv[b] - wave_sum(part)) / col[b];
+            const T wb = (cv[b] - wave_sum_dpp(part)) / col[b];
             if (lane == 0) ev[b] = wb;
             lsync();
         }
@@ -1905,7 +1874,7 @@ __global__ void __launch_bounds__(64)
             int myrow, mykq, kmax;
             MV st;
             T ffs;
-            wsync();  // (the sweeps' rows are read by other lanes)
+            wave_sync_workgroup();  // (the sweeps' rows are read by other lanes)
             if (stamp && lane == 0) stamp[15] += 1;
             candidates(bi, myrow, mykq, kmax, st, ffs);
             backward(std::false_type{}, kmax, st, ffs, mykq);
@@ -1919,7 +1888,7 @@ __global__ void __launch_bounds__(64)
                 c_act = false;
             }
             if (lane < R) crow[lane] = c_row;
-            wsync();
+            wave_sync_workgroup();
             stage_cached();
             lsync();
         }
@@ -1928,7 +1897,7 @@ __global__ void __launch_bounds__(64)
             // ---- the most violated cached row
             int hit = lane;
             T sc = (c_row >= 0 && !c_act && c_s < -c_th) ? c_s * c_iv : INF;
-            wave_argmin(sc, hit);
+            wave_argmin_dpp(sc, hit);
             if (!(sc < INF)) break;  // none: the point is evaluated from scratch
             tacc(8);
             bi = lane_get(c_row, hit);
@@ -1980,7 +1949,7 @@ __global__ void __launch_bounds__(64)
                     }
                 }
                 const bool can_move = (nq < nvar) && (zz > DEP * yy) && (zz > T(0));
-                wave_argmin(t1, l);
+                wave_argmin_dpp(t1, l);
                 const T t2 = can_move ? -sp / zz : INF;
                 const T t = t1 < t2 ? t1 : t2;
                 if (!(t < INF)) {
@@ -2055,7 +2024,7 @@ __global__ void __launch_bounds__(64)
                     }
                 }
                 if (wglob)
-                    wsync();
+                    wave_sync_workgroup();
                 else
                     lsync();
                 tacc(13);
@@ -2073,7 +2042,7 @@ __global__ void __launch_bounds__(64)
         for (;;) {
             const T fac = polish < VPASS - 1 ? T(sizeof(T) == 4 ? STAGEW_VTRIG32 : 10)
                                              : (sizeof(T) == 4 ? T(STAGEW_VACC32) : (T(100) > T(1e-7) / tol ? T(100) : T(1e-7) / tol));
-            wsync();  // (v is read by the sweep's lanes)
+            wave_sync_workgroup();  // (v is read by the sweep's lanes)
             fsweep(FwEval{}, gx0, (unsigned)wl.vpt, fac);
             if (stamp && lane == 0) stamp[15] += 256;
             if (selb < INF || !offa) break;
@@ -2082,9 +2051,9 @@ __global__ void __launch_bounds__(64)
                 fail = true;
                 break;
             }
-            wsync();
+            wave_sync_workgroup();
             fsweep(FwEvalR{}, gx0, (unsigned)wl.vpt, fac);  // (rare: the same evaluation once more, leaving every row's residual in s0)
-            wsync();  // (the rows' residuals are read by other lanes)
+            wave_sync_workgroup();  // (the rows' residuals are read by other lanes)
             for (int a = lane; a < nq; a += 64) cv[a] = s0[actrow[a]];
             lsync();
             if (wglob) {
@@ -2121,7 +2090,7 @@ __global__ void __launch_bounds__(64)
     if (fail && status == MPCQP_SOLVED) status = MPCQP_MAX_ITER;
     if (slotsfull) status = MPCQP_SLOTS_FULL;
     const bool ok = status == MPCQP_SOLVED;
-    wsync();
+    wave_sync_workgroup();
     {   // the inputs of the latest evaluation (rows of 4), or zeros when there is no plan
         const T *ust = ws + wl.ust;
         for (int i = lane; i < nv4; i += 64)
@@ -2130,7 +2099,7 @@ __global__ void __launch_bounds__(64)
     if (ka.lam) {
         T *ol = (T *)ka.lam + prob * (int64_t)M;
         for (int i = lane; i < M; i += 64) ol[i] = T(0);
-        wsync();
+        wave_sync_workgroup();
         if (ok)
             for (int a = lane; a < nq; a += 64) ol[actrow[a]] = lamv[a];
     }

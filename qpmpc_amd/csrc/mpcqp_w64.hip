@@ -44,76 +44,23 @@
 
 #include "mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_lane.h"
 
 namespace mpcqp {
 
 namespace w64 {
 
-constexpr int NV = 16;  // padded number of variables / slots
+constexpr int NV = kRowLanes;  // padded number of variables / slots
 
 // ------------------------------------------------------------ lane primitives
-__device__ __forceinline__ double bcast(double x, int lane)  // lane must be wave-uniform
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float bcast(float x, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
-}
-__device__ __forceinline__ int bcast(int x, int lane) { return __builtin_amdgcn_readlane(x, lane); }
-
-template <int CTRL> __device__ __forceinline__ int dpp(int x)
-{
-    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL> __device__ __forceinline__ unsigned dpp(unsigned x) { return (unsigned)dpp<CTRL>((int)x); }
-template <int CTRL> __device__ __forceinline__ float dpp(float x) { return __int_as_float(dpp<CTRL>(__float_as_int(x))); }
-template <int CTRL> __device__ __forceinline__ double dpp(double x)
-{
-    return __hiloint2double(dpp<CTRL>(__double2hiint(x)), dpp<CTRL>(__double2loint(x)));
-}
-constexpr int ROR8 = 0x128, ROR4 = 0x124, ROR2 = 0x122, ROR1 = 0x121;  // rotate within a row of 16
-
-template <typename T> __device__ __forceinline__ T row_sum(T v)  // all-reduce inside each row of 16
-{
-    v += dpp<ROR8>(v);
-    v += dpp<ROR4>(v);
-    v += dpp<ROR2>(v);
-    v += dpp<ROR1>(v);
-    return v;
-}
-__device__ __forceinline__ unsigned row_min(unsigned v)
-{
-    v = min(v, dpp<ROR8>(v));
-    v = min(v, dpp<ROR4>(v));
-    v = min(v, dpp<ROR2>(v));
-    v = min(v, dpp<ROR1>(v));
-    return v;
-}
 __device__ __forceinline__ unsigned wave_min(unsigned v)  // uniform result
 {
     v = row_min(v);
-    const unsigned a = (unsigned)bcast((int)v, 0), b = (unsigned)bcast((int)v, 16);
-    const unsigned c = (unsigned)bcast((int)v, 32), d = (unsigned)bcast((int)v, 48);
+    const unsigned a = (unsigned)lane_get((int)v, 0), b = (unsigned)lane_get((int)v, 16);
+    const unsigned c = (unsigned)lane_get((int)v, 32), d = (unsigned)lane_get((int)v, 48);
     return min(min(a, b), min(c, d));
 }
 
-// order-preserving map of a floating-point value onto unsigned integers
-__device__ __forceinline__ void ordered(double x, unsigned &hi, unsigned &lo)
-{
-    const unsigned h = (unsigned)__double2hiint(x), l = (unsigned)__double2loint(x);
-    const bool neg = h & 0x80000000u;
-    hi = neg ? ~h : (h | 0x80000000u);
-    lo = neg ? ~l : l;
-}
-__device__ __forceinline__ void ordered(float x, unsigned &hi, unsigned &lo)
-{
-    const unsigned h = __float_as_uint(x);
-    hi = (h & 0x80000000u) ? ~h : (h | 0x80000000u);
-    lo = 0;
-}
 // arg-min over row 0 (lanes 0..15) with take==true; ties -> lowest lane; 64 if none.
 // Exact except for the 6 low mantissa bits replaced by the lane id.
 template <typename T> __device__ __forceinline__ int argmin_row0(T x, bool take, int lane)
@@ -121,11 +68,11 @@ template <typename T> __device__ __forceinline__ int argmin_row0(T x, bool take,
     unsigned hi, lo;
     ordered(x, hi, lo);
     hi = take ? hi : 0xffffffffu;
-    const unsigned mhi = (unsigned)bcast((int)row_min(hi), 0);
+    const unsigned mhi = (unsigned)lane_get((int)row_min(hi), 0);
     if (mhi == 0xffffffffu) return 64;
     const unsigned low = (sizeof(T) == 8) ? ((lo & ~63u) | (unsigned)lane) : (unsigned)lane;
     const unsigned k2 = (take && hi == mhi) ? low : 0xffffffffu;
-    return (int)((unsigned)bcast((int)row_min(k2), 0) & 63u);
+    return (int)((unsigned)lane_get((int)row_min(k2), 0) & 63u);
 }
 // cheap selection over the wavefront (heuristic quality is enough): one reduction
 template <typename T> __device__ __forceinline__ int argmin_coarse(T x, bool take, int lane)
@@ -138,54 +85,6 @@ template <typename T> __device__ __forceinline__ int argmin_coarse(T x, bool tak
 }
 
 // ------------------------------------------------------------ 16-vectors in LDS
-template <typename T> struct Vec;
-template <> struct Vec<double> {
-    using type = double2;
-    static constexpr int W = 2;
-    static constexpr int LDW = 18;  // W row stride: 144 B, 16 lanes hit 16 distinct 16-B slots
-};
-template <> struct Vec<float> {
-    using type = float4;
-    static constexpr int W = 4;
-    static constexpr int LDW = 20;  // 80 B rows, same property
-};
-template <typename T> __device__ __forceinline__ void ld16(T (&d)[NV], const T *src)
-{
-    using V = typename Vec<T>::type;
-    const V *p = reinterpret_cast<const V *>(src);
-#pragma unroll
-    for (int i = 0; i < NV / Vec<T>::W; ++i) {
-        const V t = p[i];
-        if constexpr (Vec<T>::W == 2) {
-            d[2 * i] = t.x;
-            d[2 * i + 1] = t.y;
-        } else {
-            d[4 * i] = t.x;
-            d[4 * i + 1] = t.y;
-            d[4 * i + 2] = t.z;
-            d[4 * i + 3] = t.w;
-        }
-    }
-}
-template <typename T> __device__ __forceinline__ void st16(T *dst, const T (&s)[NV])
-{
-    using V = typename Vec<T>::type;
-    V *p = reinterpret_cast<V *>(dst);
-#pragma unroll
-    for (int i = 0; i < NV / Vec<T>::W; ++i) {
-        V t;
-        if constexpr (Vec<T>::W == 2) {
-            t.x = s[2 * i];
-            t.y = s[2 * i + 1];
-        } else {
-            t.x = s[4 * i];
-            t.y = s[4 * i + 1];
-            t.z = s[4 * i + 2];
-            t.w = s[4 * i + 3];
-        }
-        p[i] = t;
-    }
-}
 // Register pressure is what decides occupancy here (4 wavefronts per SIMD need
 // <= 128 VGPRs), so 16-vectors coming from LDS are consumed in two halves of 8 and
 // a scheduling barrier keeps the second half's loads from being hoisted.
@@ -209,13 +108,6 @@ template <typename T> __device__ __forceinline__ void ld8(T (&d)[HV], const T *s
     }
 }
 __device__ __forceinline__ void half_fence() { __builtin_amdgcn_sched_barrier(0); }
-// Make a value opaque at this point: the compiler can neither sink the
-// computation that produced it below here nor keep its operands alive instead
-// (without this the trailing updates of the factorisation are deferred and every
-// exchanged column stays live -> hundreds of bytes of scratch).
-__device__ __forceinline__ void pin(double &x) { asm volatile("" : "+v"(x)); }
-__device__ __forceinline__ void pin(float &x) { asm volatile("" : "+v"(x)); }
-
 // sum_k a[k] * v[k] with a in registers and v a 16-vector in LDS (broadcast reads)
 template <typename T> __device__ __forceinline__ T dot_reg_lds(const T (&a)[NV], const T *v)
 {
@@ -298,33 +190,6 @@ template <int STRIDE, typename T> __device__ __forceinline__ T dot_vec_col(const
     }
     return acc + acc1;
 }
-// 1/x from the hardware estimate plus Newton steps (a full IEEE division costs ~3x
-// the instructions; the operands here are never subnormal or zero when the result is used)
-__device__ __forceinline__ double fast_rcp(double x)
-{
-    double y = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    e = fma(-x, y, 1.0);
-    return fma(y, e, y);
-}
-__device__ __forceinline__ float fast_rcp(float x)
-{
-    float y = __builtin_amdgcn_rcpf(x);
-    const float e = fmaf(-x, y, 1.0f);
-    return fmaf(y, e, y);
-}
-// wavefront-level ordering of LDS traffic (a 64-thread workgroup needs no s_barrier)
-__device__ __forceinline__ void wsync()
-{
-    // One wavefront per workgroup: LDS operations of a wavefront complete in order, so what one lane
-    // wrote is what another lane reads next without any wait. Only the COMPILER has to keep the order
-    // (wavefront-scope fence); __syncthreads() would also drain the LDS queue (s_waitcnt lgkmcnt(0)) at
-    // every exchange, six times per active-set iteration.
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <typename T> struct Cst;
 template <> struct Cst<double> {
     static __device__ __forceinline__ double inf() { return HUGE_VAL; }
@@ -425,7 +290,7 @@ __global__ void __launch_bounds__(64, 4)
             invn_model = model[L.mo_invn + cid];
         }
         hv[lane] = hh;
-        wsync();
+        wave_sync();
         if (low) {  // w = L^-1 q = Wx x0 - Wg goal - Wt targets (lane k: component k)
             T wk = T(0);
             for (int c = 0; c < nx; ++c) wk += model[L.mo_Wx + lane * nx + c] * x0[c];
@@ -436,7 +301,7 @@ __global__ void __launch_bounds__(64, 4)
             y0v[lane] = wk;
         }
         for (int i = lane; i < (NV + 1) * NV; i += 64) MAl[i] = T(0);
-        wsync();
+        wave_sync();
     } else if constexpr (MODE == MODE_SOLVE) {
         const T *P = gA + prob * (int64_t)n * n;
         const T *G = gC + prob * (int64_t)m * n;
@@ -451,7 +316,7 @@ __global__ void __launch_bounds__(64, 4)
             const int row = i / NV, b = i - row * NV;
             Gimg[b * GS + row] = (b < n) ? (row < m ? G[row * n + b] : q[b]) : T(0);
         }
-        wsync();
+        wave_sync();
     } else {
         // ---------------------------------------------------------------- build
         // nx == NX here (the host dispatches on it), so the small loops are exact.
@@ -494,7 +359,7 @@ __global__ void __launch_bounds__(64, 4)
 #pragma unroll
         for (int b = 0; b < NV; ++b) Pr[b] = (lane == b) ? (col ? wu : T(1)) : T(0);
         T qa = T(0);
-        wsync();
+        wave_sync();
         T bcol[NX];  // this lane's column of B_j (enters the chain at step j)
 #pragma unroll
         for (int r = 0; r < NX; ++r) bcol[r] = col ? ((MK > 0) ? B[j * sB + r * nu + ii] : Bs[j * sB + r * nu + ii]) : T(0);
@@ -503,12 +368,12 @@ __global__ void __launch_bounds__(64, 4)
         // ref[] is this lane's reference (non-zero only in lane 16).
         auto gram = [&](T w, bool useP, bool useQ, const T (&ref)[NX]) {
             if (!useP && !useQ) return;
-            wsync();
+            wave_sync();
             if (lane < 32) {
 #pragma unroll
                 for (int s = 0; s < NX; ++s) ex[s * 32 + lane] = v[s] - ref[s];
             }
-            wsync();
+            wave_sync();
 #pragma unroll
             for (int s = 0; s < NX; ++s) {
                 const T t = w * v[s];
@@ -626,12 +491,12 @@ __global__ void __launch_bounds__(64, 4)
             }
         }
         gram((T)ka.wt, termP, termQ, gref);  // v = Psi_N
-        wsync();
+        wave_sync();
         if (low) Gimg[lane * GS + m] = col ? qa : T(0);  // the q row
-        wsync();
+        wave_sync();
         // h_i = e_i - C_k Phi_k x0 goes to LDS; the rows of G stay in the LDS image for now
         hv[lane] = (isc && L.nC) ? eval - hp[cid] : eval;
-        wsync();
+        wave_sync();
     }
 
     tick(1);
@@ -712,7 +577,7 @@ __global__ void __launch_bounds__(64, 4)
             st16(Ll + lane * LDM, Pr);
             Ll[lane * LDM + NV] = myinv;
         }
-        wsync();
+        wave_sync();
         {
             using V = typename Vec<T>::type;
             constexpr int W = Vec<T>::W;
@@ -737,7 +602,7 @@ __global__ void __launch_bounds__(64, 4)
                 pin(R[j]);
             }
         }
-        wsync();  // the M image below reuses the L image
+        wave_sync();  // the M image below reuses the L image
         tick(3);
         if (lane == 0) st16(y0v, R);           // w = L^-1 q ; y0 = -w
         if (isc) st16(Ml + cid * LDM, R);      // image of M for the row-p broadcasts
@@ -746,7 +611,7 @@ __global__ void __launch_bounds__(64, 4)
 #pragma unroll
             for (int k = 0; k < NV; ++k) R[k] = T(0);  // T = N* starts empty
         }
-        wsync();
+        wave_sync();
         }
         // rows of M for the row-p broadcasts: the LDS image, or the shared model itself
         // (4 KB read by every wavefront of the launch: it stays in L1/L2)
@@ -787,7 +652,7 @@ __global__ void __launch_bounds__(64, 4)
                     break;
                 }
                 const T *mprow = Mbase + (p - CB) * mstride;  // row p of M, read as broadcast
-                const T ip = bcast(invn, p);          // 1 / |M_p|
+                const T ip = lane_get(invn, p);       // 1 / |M_p|
                 T up = T(0);
                 bool added = false;
                 // Each trip of this loop makes exactly ONE pass "R += c * vec" over the row
@@ -811,19 +676,19 @@ __global__ void __launch_bounds__(64, 4)
                         r = dot_reg_lds(R, mprow);
                         r = occ ? r : T(0);
                         rv[vofs] = r;
-                        wsync();
+                        wave_sync();
                         // z = -M_p + M_A' r (lane k < 16)
                         T z = dot_vec_col<NV>(rv, MAl + l15, -mprow[l15]);
                         z = low ? z : T(0);
                         zv[vofs] = z;
-                        const T d2 = bcast(row_sum(z * z), 0);
+                        const T d2 = lane_get(row_sum_ror(z * z), 0);
                         // ratio test on the multipliers
                         const bool cand = occ && (r > T(0));
                         const T ratio = cand ? lam * fast_rcp(r) : INF;
                         const int l = argmin_row0<T>(ratio, cand, lane);
-                        const T t1 = (l < 64) ? bcast(ratio, l) : INF;
+                        const T t1 = (l < 64) ? lane_get(ratio, l) : INF;
                         const bool can_move = (nq < n) && (d2 * ip * ip > Cst<T>::dep()) && (d2 > T(0));
-                        const T sp = bcast(s, p);
+                        const T sp = lane_get(s, p);
                         const T inv = can_move ? fast_rcp(d2) : T(0);
                         const T t2 = can_move ? -sp * inv : INF;
                         t = t1 < t2 ? t1 : t2;
@@ -842,11 +707,11 @@ __global__ void __launch_bounds__(64, 4)
                         // slot ldrop leaves (its row T_l was copied to kAv). With W = T T' implicit,
                         // T_a -= (T_a . T_l / T_l . T_l) T_l ; row l becomes exactly zero (f = 1).
                         const T tl = dot_reg_lds(R, kAv);
-                        const T f = tl * fast_rcp(bcast(tl, ldrop));
+                        const T f = tl * fast_rcp(lane_get(tl, ldrop));
                         c = (lane == ldrop) ? T(-1) : (occ ? -f : T(0));
                         vec = kAv;
                     }
-                    wsync();
+                    wave_sync();
                     // the single pass over vec: m_i = R_i . vec (before the update), R += c vec
                     T mz0 = T(0), mz1 = T(0);
 #pragma unroll
@@ -888,8 +753,8 @@ __global__ void __launch_bounds__(64, 4)
                             added = true;
                         } else {
                             // partial step: the next trip removes slot ldrop from T
-                            const int cl = bcast(myact, ldrop);
-                            wsync();
+                            const int cl = lane_get(myact, ldrop);
+                            wave_sync();
                             if (lane == ldrop) st16(kAv, R);
                             if (lane == cl) pos = -1;
                             dropping = true;
@@ -903,7 +768,7 @@ __global__ void __launch_bounds__(64, 4)
                         --nq;
                         dropping = false;
                     }
-                    wsync();
+                    wave_sync();
                 }
                 if (fail) break;
             }
@@ -911,13 +776,13 @@ __global__ void __launch_bounds__(64, 4)
             tick(5);
             // ================================== refine multipliers, verify slacks
             // y = y0 - M_A' lam (lane k < 16)
-            wsync();
+            wave_sync();
             rv[vofs] = lam;
-            wsync();
+            wave_sync();
             T y = dot_vec_col<NV>(rv, MAl + l15, T(0));
             y = -y0v[l15] - y;  // y0 = -L^-1 q
             zv[vofs] = y;
-            wsync();
+            wave_sync();
             T fresh = hv[lane] - dot_reg_lds(R, zv);
             fresh = isc ? fresh : INF;
             if (nq > 0) {
@@ -925,24 +790,24 @@ __global__ void __launch_bounds__(64, 4)
                 // dlam = -W rho_A = -T (T' rho_A)
                 T rho = __shfl(fresh, myact);
                 rho = occ ? rho : T(0);
-                wsync();
+                wave_sync();
                 kAv[vofs] = rho;
                 if (low) st16(Timg + lane * NV, R);  // T by columns is only needed here
-                wsync();
+                wave_sync();
                 const T uk = dot_vec_col<NV>(kAv, Timg + l15, T(0));  // (T' rho)_k, lane k < 16
                 rv[vofs] = low ? uk : T(0);
-                wsync();
+                wave_sync();
                 T dl = -dot_reg_lds(R, rv);
                 dl = occ ? dl : T(0);
                 lam += dl;
                 lam = (occ && lam < T(0)) ? T(0) : lam;
-                wsync();
+                wave_sync();
                 rv[vofs] = dl;
-                wsync();
+                wave_sync();
                 y -= dot_vec_col<NV>(rv, MAl + l15, T(0));
-                wsync();
+                wave_sync();
                 zv[vofs] = y;
-                wsync();
+                wave_sync();
                 fresh = hv[lane] - dot_reg_lds(R, zv);
                 fresh = isc ? fresh : INF;
             }

@@ -265,7 +265,7 @@ def test_wip_model_constants_match_reference():
 
 
 def test_hand_written_dpp_instructions_keep_their_wait_states():
-    """The v_fmac_f64_dpp of mpcqp_pair.hip and mpcqp_quad.hip (+ its second unit, mpcqp_quadw.hip) and mpcqp_quadg.hip (+ mpcqp_quadgw.hip; the instruction itself is in mpcqp_quad_common.h) are inline asm: the compiler cannot insert the two wait states a DPP read needs
+    """The v_fmac_f64_dpp of mpcqp_pair.hip and mpcqp_quad.hip (+ its second unit, mpcqp_quadw.hip) and mpcqp_quadg.hip (+ mpcqp_quadgw.hip; the instruction itself is fmac_bcast of mpcqp_lane.h, with its hazard contract) are inline asm: the compiler cannot insert the two wait states a DPP read needs
     after a VALU write of the same register, the source does (dpp_ready). tools/check_dpp_hazards.py verifies it on the
     gfx950 assembly of every instantiation (hipcc cross-compiles without a GPU), and flags a made-up violation."""
     import os, sys

@@ -2,8 +2,8 @@
 """Static check of the gfx950 assembly of a .hip file: every DPP instruction (v_*_dpp) must read its DPP operand (src0)
 at least two wait states after the last VALU instruction that wrote that register ("VALU writes VGPR -> VALU DPP reads
 that VGPR" data hazard of the CDNA ISA). The compiler guarantees this for the DPP instructions it emits itself; the
-hand-written v_fmac_f64_dpp of mpcqp_pair.hip sit in inline asm, which it cannot see into, and rely on an s_nop placed
-by the source (dpp_ready). usage: check_dpp_hazards.py file.hip [more.hip ...]   (exit status 1 on a violation)"""
+hand-written v_fmac_f64_dpp (fmac_bcast of qpmpc_amd/csrc/mpcqp_lane.h, used by the pair and quad kernels) sit in inline
+asm, which it cannot see into, and rely on an s_nop placed by the source (dpp_ready, next to it). usage: check_dpp_hazards.py file.hip [more.hip ...]   (exit status 1 on a violation)"""
 import os, re, shutil, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
