@@ -87,9 +87,14 @@ extern "C" {
                                 kernel, float64 arithmetic, takes what the MFMA stage-wise kernels (nx <= 16, nu <= 4) and
                                 the dense path (n <= 256) do not: qpmpc/solve_mpc.py:42-44 accepts any dimension) */
 #define MPCQP_EDTYPE (-3)    /* dtype not MPCQP_F64 / MPCQP_F32               */
-#define MPCQP_ELAYOUT (-4)   /* step stride is neither 0 nor the block size, or a batch stride smaller than a problem's block
-                                (a float32 launch that is solved in float64 -- at most 160 variables -- takes any larger batch
-                                stride since ABI 11: the conversion packs the operands) */
+#define MPCQP_ELAYOUT (-4)   /* an operand of MpcqpProblem with a non-NULL pointer has a negative batch or step stride, a step
+                                stride that is neither 0 nor the block size, or a non-zero batch stride smaller than what one
+                                problem occupies (N blocks with a step stride, else one block; nx for x0 and goal, N nx for
+                                targets). Every export that takes an MpcqpProblem checks this before anything is launched
+                                (mpcqp_update_vectors_batch, which needs no A and B, for the operands it is given); any
+                                larger batch stride is taken, in both dtypes (a float32 launch that is solved in float64 -- at
+                                most 160 variables -- packs the operands on conversion). The fused WIP periods keep a stricter
+                                check of their own: x0, goal and targets packed, else MPCQP_EUNSUPPORTED */
 #define MPCQP_EWORKSPACE (-5) /* workspace missing or too small (see *_workspace_bytes) */
 #define MPCQP_EUNSUPPORTED (-6) /* option not available for these dimensions / this dtype    */
 

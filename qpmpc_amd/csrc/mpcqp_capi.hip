@@ -23,9 +23,32 @@ int check_dims(const MpcqpDims *d)
     return 0;
 }
 
-int check_step(const MpcqpOperand &op, int64_t block)
+// One operand against the addressing contract of include/mpcqp.h: no negative stride, a step stride of 0 or the block, and a
+// batch stride of 0 or at least what one problem occupies (`steps` = N; 0 for x0, goal and targets, whose step stride no
+// kernel reads)
+int check_operand(const MpcqpOperand &op, int64_t block, int64_t steps)
 {
-    if (op.ptr && op.step_stride != 0 && op.step_stride != block) return MPCQP_ELAYOUT;
+    if (!op.ptr) return 0;
+    if (op.step_stride < 0 || op.batch_stride < 0) return MPCQP_ELAYOUT;
+    if (steps && op.step_stride != 0 && op.step_stride != block) return MPCQP_ELAYOUT;
+    const int64_t extent = (steps && op.step_stride) ? steps * block : block;
+    if (op.batch_stride != 0 && op.batch_stride < extent) return MPCQP_ELAYOUT;
+    return 0;
+}
+
+// the strides of every operand that is there (mpcqp_update_vectors_batch, which needs no A and B, stops at this)
+int check_layout(const MpcqpDims *d, const MpcqpProblem *p)
+{
+    int rc;
+    const int64_t nx = d->nx, nu = d->nu, mk = d->mk, N = d->N;
+    if ((rc = check_operand(p->A, nx * nx, N))) return rc;
+    if ((rc = check_operand(p->B, nx * nu, N))) return rc;
+    if ((rc = check_operand(p->C, mk * nx, N))) return rc;
+    if ((rc = check_operand(p->D, mk * nu, N))) return rc;
+    if ((rc = check_operand(p->e, mk, N))) return rc;
+    if ((rc = check_operand(p->x0, nx, 0))) return rc;
+    if ((rc = check_operand(p->goal, nx, 0))) return rc;
+    if ((rc = check_operand(p->targets, N * nx, 0))) return rc;
     return 0;
 }
 
@@ -35,13 +58,7 @@ int check_problem(const MpcqpDims *d, const MpcqpProblem *p)
     if (d->mk > 0 && !p->e.ptr) return MPCQP_EINVAL;
     if ((d->flags & MPCQP_Q_TERMINAL) && !p->goal.ptr) return MPCQP_EINVAL;
     if ((d->flags & MPCQP_Q_STAGE) && !p->targets.ptr) return MPCQP_EINVAL;
-    int rc;
-    if ((rc = check_step(p->A, (int64_t)d->nx * d->nx))) return rc;
-    if ((rc = check_step(p->B, (int64_t)d->nx * d->nu))) return rc;
-    if ((rc = check_step(p->C, (int64_t)d->mk * d->nx))) return rc;
-    if ((rc = check_step(p->D, (int64_t)d->mk * d->nu))) return rc;
-    if ((rc = check_step(p->e, (int64_t)d->mk))) return rc;
-    return 0;
+    return check_layout(d, p);
 }
 
 void fill_args(KernelArgs &ka, const MpcqpDims *d, const MpcqpProblem *p)
@@ -558,7 +575,7 @@ const char *mpcqp_error_string(int code)
     case MPCQP_EINVAL: return "invalid argument";
     case MPCQP_ETOOLARGE: return "no kernel for these dimensions (the stage-wise kernels serve nx <= 32, nu <= 8 at any horizon; the dense HBM-resident path any system with n <= 256)";
     case MPCQP_EDTYPE: return "dtype must be MPCQP_F64 or MPCQP_F32";
-    case MPCQP_ELAYOUT: return "step stride must be 0 or the block size (float32 launches solved in float64: batch stride 0 or the packed size)";
+    case MPCQP_ELAYOUT: return "step stride must be 0 or the block size, batch stride 0 or at least a problem's extent, neither negative (the fused WIP periods take packed x0 / goal / targets only: MPCQP_EUNSUPPORTED)";
     case MPCQP_EWORKSPACE: return "workspace missing or too small (see mpcqp_workspace_bytes)";
     case MPCQP_EUNSUPPORTED: return "option not available for these dimensions / this dtype (warm start: n <= 16, m <= 32, float64)";
     default: break;
@@ -691,6 +708,7 @@ int mpcqp_update_vectors_batch(const MpcqpDims *dims, const MpcqpProblem *proble
     if (h && dims->mk > 0 && !problem->e.ptr) return MPCQP_EINVAL;
     if ((dims->flags & MPCQP_Q_TERMINAL) && q && !problem->goal.ptr) return MPCQP_EINVAL;
     if ((dims->flags & MPCQP_Q_STAGE) && q && !problem->targets.ptr) return MPCQP_EINVAL;
+    if ((rc = check_layout(dims, problem))) return rc;
     if (batch == 0 || (!q && !h)) return 0;
     KernelArgs ka;
     fill_args(ka, dims, problem);

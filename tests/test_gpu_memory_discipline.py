@@ -38,6 +38,7 @@ for _p in (HERE, os.path.join(os.path.dirname(HERE), "tools")):
 import adjoint_np as AN  # noqa: E402
 import adjoint_stagewise_np as AS  # noqa: E402
 import arena as AR  # noqa: E402
+from operand_layouts import f32_view  # noqa: E402
 import tangent_model_np as TM  # noqa: E402
 import tangent_np as TN  # noqa: E402
 
@@ -128,6 +129,11 @@ class Launch:
         return {s["name"]: a.view(s["name"]).clone().cpu().numpy() for s in live if s["role"] != "in"}
 
 
+def pad_of(pad, name):
+    """elements of batch-stride padding of operand `name`: `pad` is one int for every operand or a dict name -> elements"""
+    return int(pad.get(name, 0)) if isinstance(pad, dict) else int(pad)
+
+
 def add_problem(L, bp, pad=0, inout=()):
     """the operands of `bp`, read-only but for those named in `inout` (a fused period writes the next problem over them)"""
     for name, attr in OPS:
@@ -135,11 +141,12 @@ def add_problem(L, bp, pad=0, inout=()):
         if t is not None:
             rows = t.reshape(t.shape[0], -1)
             L.add("op_" + name, "inout" if name in inout else "in", bp.dtype, data=rows,
-                  stride=rows.shape[1] + (pad if rows.shape[0] > 1 else 0))
+                  stride=rows.shape[1] + (pad_of(pad, name) if rows.shape[0] > 1 else 0))
 
 
 def arena_problem(L, bp, pad=0):
-    """MpcqpProblem of `bp` with every operand pointing into the arena (batch strides `pad` elements past the packed ones)."""
+    """MpcqpProblem of `bp` with every operand pointing into the arena (batch strides `pad` elements past the packed ones; `pad`
+    as in pad_of)."""
     _capi = _api()[0]
     ops = []
     for name, attr in OPS:
@@ -148,7 +155,7 @@ def arena_problem(L, bp, pad=0):
             ops.append(_capi.Operand(None, 0, 0))
             continue
         o = bp._operand(t)
-        bs = 0 if t.shape[0] == 1 else t.reshape(t.shape[0], -1).shape[1] + pad
+        bs = 0 if t.shape[0] == 1 else t.reshape(t.shape[0], -1).shape[1] + pad_of(pad, name)
         ops.append(_capi.Operand(L.ptr("op_" + name), bs, o.step_stride))
     return _capi.Problem(*ops)
 
@@ -168,11 +175,6 @@ def ltv(seed, B, nx, nu, N, mk, tight=1.0, rows="cd", stage=True):
     if not stage:
         w["wx"] = w["targets"] = None
     return w
-
-
-def f32_view(w):
-    """the operands a float32 launch sees (float32 storage), as float64 arrays for the references"""
-    return {k: (np.asarray(v, dtype=np.float32).astype(np.float64) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
 
 
 _ORACLE = {}
