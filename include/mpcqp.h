@@ -209,7 +209,11 @@ typedef struct MpcqpProblem {
                                    now: warm_shift = mk. Small-problem fused kernel only (MPCQP_EUNSUPPORTED elsewhere).   */
 
 typedef struct MpcqpSolveOpts {
-    int32_t max_iter; /* active-set iterations per problem; <=0 -> 10*(n+m)     */
+    int32_t max_iter; /* active-set iterations per problem; <=0 -> 10*(n+m)+10. One iteration is one step of the dual method (a row
+                         admitted, or a blocking row dropped), counted per problem: a problem that takes `it` iterations is
+                         solved under max_iter >= it and is MPCQP_MAX_ITER with iters[b] = max_iter below it (the narrow
+                         stage-wise kernel's MPCQP_MAX_ITER items are solved again by the wide kernel under the same limit, and
+                         iters[b] is then its count). */
     int32_t flags;    /* MPCQP_OPT_* (0 = automatic dispatch)                    */
     double feas_tol;  /* a row is violated when (h_i-G_i u)/(1+|h_i|) < -tol;
                          <=0 -> 1e-12 (f64) / 1e-5 (f32)                         */
