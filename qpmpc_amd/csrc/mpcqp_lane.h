@@ -223,7 +223,9 @@ template <int N> __device__ __forceinline__ double row_bcast(double x) { return 
 // HAZARD CONTRACT: a VGPR written by a VALU instruction needs TWO wait states before a DPP instruction reads it as its DPP
 // operand (src0, here x). The compiler keeps that for the DPP instructions it emits, but it cannot see inside the asm: the
 // caller puts dpp_ready(x) -- an s_nop 1 tied to x, so that x is written before it and read after it -- in front of every
-// batch of fmac_bcast on one broadcast source. tools/check_dpp_hazards.py checks it on the assembly of every unit.
+// batch of fmac_bcast on one broadcast source. tools/check_dpp_hazards.py checks it on the assembly of every unit. The scan follows
+// branches (the worst predecessor of every basic block, back edges included), holds a VALU write of EXEC to its five wait states in
+// front of a DPP instruction too, and tests/test_gpu_dpp_instantiations.py launches every instantiation that carries the instruction.
 template <int N> __device__ __forceinline__ void fmac_bcast(double &acc, double x, double m)
 {
     asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(m), "n"(N));

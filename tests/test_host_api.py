@@ -267,30 +267,81 @@ def test_wip_model_constants_match_reference():
 def test_hand_written_dpp_instructions_keep_their_wait_states():
     """The v_fmac_f64_dpp of mpcqp_pair.hip and mpcqp_quad.hip (+ its second unit, mpcqp_quadw.hip) and mpcqp_quadg.hip (+ mpcqp_quadgw.hip; the instruction itself is fmac_bcast of mpcqp_lane.h, with its hazard contract) are inline asm: the compiler cannot insert the two wait states a DPP read needs
     after a VALU write of the same register, the source does (dpp_ready). tools/check_dpp_hazards.py verifies it on the
-    gfx950 assembly of every instantiation (hipcc cross-compiles without a GPU), and flags a made-up violation."""
+    gfx950 assembly of every instantiation (hipcc cross-compiles without a GPU), and flags a made-up violation. The scan follows the
+    control flow (worst predecessor of every basic block, to a fixpoint), holds EXEC written by a VALU instruction to its five wait
+    states, and holds the compiler's own DPP instructions to the same rules: each synthetic case below as a hazard and as its padded
+    twin."""
     import os, sys
 
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
+    tests = os.path.dirname(os.path.abspath(__file__))
+    tools = os.path.join(os.path.dirname(tests), "tools")
+    for p in (tools, tests):
+        if p not in sys.path:
+            sys.path.insert(0, p)
     import check_dpp_hazards as chk
 
     bad, ndpp, _ = chk.check("f:\n\tv_add_f64 v[0:1], v[2:3], v[4:5]\n\tv_fmac_f64_dpp v[6:7], v[0:1], v[8:9] row_newbcast:3 row_mask:0xf bank_mask:0xf\n")
     assert ndpp == 1 and len(bad) == 1
     bad, _, _ = chk.check("f:\n\tv_add_f64 v[0:1], v[2:3], v[4:5]\n\ts_nop 1\n\tv_fmac_f64_dpp v[6:7], v[0:1], v[8:9] row_newbcast:3 row_mask:0xf bank_mask:0xf\n")
     assert not bad
+
+    DPP = "v_fmac_f64_dpp v[6:7], v[0:1], v[8:9] row_newbcast:3 row_mask:0xf bank_mask:0xf"
+    ADD = "v_add_f64 v[0:1], v[2:3], v[4:5]"
+
+    def scan(*lines):
+        text = "".join(l + "\n" if l.endswith(":") else "\t" + l + "\n" for l in lines)
+        return [(h.kind, h.waited, h.writer) for h in chk.check(text)[0]]
+
+    # a source written at the bottom of a loop body, read by the DPP instruction at the top of the next trip
+    loop = lambda pad: scan("f:", "s_nop 1", ".LBB0_1:", DPP, "s_add_u32 s0, s0, 1", "s_cmp_lt_u32 s0, 4", ADD, *pad, "s_cbranch_scc1 .LBB0_1", "s_endpgm")
+    assert loop([]) == [("vgpr", 1, "v_add_f64")] and loop(["s_nop 0"]) == []
+    # a join: the taken predecessor writes the source right in front of its branch, the fall-through is clean
+    join = lambda pad: scan("f:", "s_cbranch_scc1 .LBB0_2", "s_nop 1", "s_branch .LBB0_3", ".LBB0_2:", ADD, *pad, "s_cbranch_vccnz .LBB0_3",
+                            "s_endpgm", ".LBB0_3:", DPP, "s_endpgm")
+    assert join([]) == [("vgpr", 1, "v_add_f64")] and join(["s_nop 0"]) == []
+    # a write, then s_branch over a block to the read (the block in between must not count)
+    jump = lambda pad: scan("f:", ADD, *pad, "s_branch .LBB0_2", ".LBB0_1:", "s_nop 7", "s_endpgm", ".LBB0_2:", DPP, "s_endpgm")
+    assert jump([]) == [("vgpr", 1, "v_add_f64")] and jump(["s_nop 0"]) == []
+    # s_nop 0 is ONE wait state
+    assert scan("f:", ADD, "s_nop 0", DPP) == [("vgpr", 1, "v_add_f64")] and scan("f:", ADD, "s_nop 0", "s_nop 0", DPP) == []
+    # the historic writer: an operand fetched from an accumulation register right in front of the DPP FMA
+    acc = lambda pad: scan("f:", "v_accvgpr_read_b32 v0, a3", *pad, DPP)
+    assert acc([]) == [("vgpr", 0, "v_accvgpr_read_b32")] and acc(["s_nop 1"]) == []
+    # a 64-bit source written in one half only
+    half = lambda pad: scan("f:", "v_mov_b32_e32 v1, v9", *pad, DPP)
+    assert half([]) == [("vgpr", 0, "v_mov_b32_e32")] and half(["s_nop 1"]) == []
+    assert scan("f:", "v_mov_b32_e32 v2, v9", DPP) == []  # (another register)
+    assert scan("f:", "v_swap_b32 v9, v0", DPP) == [("vgpr", 0, "v_swap_b32")]  # (a swap writes both operands)
+    assert scan("f:", "v_cmp_lt_f64_e32 vcc, v[0:1], v[2:3]", DPP) == []  # (a compare writes no VGPR)
+    # VALU writes EXEC: five wait states in front of a DPP instruction
+    cmpx = lambda n: scan("f:", "s_nop 1", "v_cmpx_lt_f64_e32 v[2:3], v[4:5]", *["s_mov_b32 s0, s1"] * n, DPP)
+    assert cmpx(4) == [("exec", 4, "v_cmpx_lt_f64_e32")] and cmpx(5) == [] and cmpx(0) == [("exec", 0, "v_cmpx_lt_f64_e32")]
+    assert scan("f:", "v_readfirstlane_b32 exec_lo, v3", "s_nop 3", DPP) == [("exec", 4, "v_readfirstlane_b32")]
+    assert scan("f:", "s_mov_b64 exec, s[0:1]", DPP) == []  # (a scalar write of EXEC is not this hazard)
+    # a function label resets the state
+    assert scan("f:", ADD, "g:", DPP) == [] and scan("f:", ADD, ".LBB0_1:", DPP) == [("vgpr", 0, "v_add_f64")]
+    # control flow the scan cannot follow, in a function that holds a DPP instruction
+    assert scan("f:", "s_nop 1", DPP, "s_setpc_b64 s[30:31]") == [("flow", None, None)]
+    assert scan("f:", "s_nop 1", DPP, "s_endpgm", "g:", "s_setpc_b64 s[30:31]") == []
+    assert scan("f:", "s_nop 1", DPP, "s_cbranch_scc0 .LBB9_9", "s_endpgm") == [("flow", None, None)]
+    # the compiler's own DPP moves are held to the same rules
+    assert scan("f:", "v_mov_b32_e32 v2, v9", "v_mov_b32_dpp v1, v2 row_shr:1 row_mask:0xf bank_mask:0xf") == [("vgpr", 0, "v_mov_b32_e32")]
+    bad = chk.check("f:\n\t" + ADD + "\n\t" + DPP + "\n")[0][0]
+    assert bad.func == "f" and bad.line == DPP and bad.lineno == 3 and "v_add_f64" in chk.describe(bad)
+
     # (mpcqp_stage.hip used the same instruction in round 4; its sweeps and recursion run on v_mfma_f64_4x4x4 since round 5, whose
     # wait states the compiler inserts itself)
-    # (the units are compiled to assembly side by side: mpcqp_quadw.hip -- the wide instantiations of mpcqp_quad.hip -- and
-    # mpcqp_quadg.hip -- the general build with four rows per lane -- take two to three minutes each)
-    from concurrent.futures import ThreadPoolExecutor
+    # (the units are compiled to assembly side by side, once per session -- tests/dpp_instantiations.py, whose census reads the same
+    # text: mpcqp_quadw.hip -- the wide instantiations of mpcqp_quad.hip -- and mpcqp_quadg.hip -- the general build with four rows
+    # per lane -- take two to three minutes each)
+    import dpp_instantiations as DI
 
     units = ("mpcqp_pair.hip", "mpcqp_quad.hip", "mpcqp_quadw.hip", "mpcqp_quadg.hip", "mpcqp_quadgw.hip")
-    with ThreadPoolExecutor(max_workers=5) as pool:
-        asms = list(pool.map(lambda u: chk.device_asm(os.path.join(os.path.dirname(tools), "qpmpc_amd", "csrc", u)), units))
-    for unit, asm in zip(units, asms):
-        bad, ndpp, nasm = chk.check(asm)
-        assert nasm > 1000 and not bad, (unit, bad[:3])
+    asms = DI.all_asm()
+    for unit in units:
+        bad, ndpp, nasm = chk.check(asms[unit])
+        assert nasm > 1000 and not bad, (unit, [chk.describe(h) for h in bad[:3]])
+        assert ndpp > nasm  # (the compiler's own v_mov_*_dpp were scanned too, and came out clean)
 
 
 def test_integration_md_shows_the_build_command_of_the_build_script():
