@@ -30,9 +30,9 @@
 //   * Cholesky and forward substitution are ONE right-looking pass: step j scales column j of L and immediately applies it
 //     to the trailing columns of P, of the two rows of G, of the identity row (-> L^-T) -- four independent FMA streams on
 //     the same DPP broadcasts -- and to q (-> w = L^-1 q, component k in lane k).
-//   * One loop serves every kind of trip. The update vector (z for a new row, T_l for a leaving slot) always sits in a
-//     register with component k in lane k and is applied by DPP row broadcasts at the top of the next trip; the rare
-//     parts (|K_p|^2 near dependence, ratio test on the multipliers, drop pass) sit behind wavefront-uniform ballots.
+//   * Plain trips (nearly all) run in a steady loop of one basic block (mpcqp_quad_steady.h) in front of the general loop, which serves
+//     every kind of trip. The update vector (z, or T_l of a leaving slot: component k in lane k) is applied by DPP row broadcasts at the
+//     top of the next trip; the rare parts (|K_p|^2 near dependence, ratio test, drop pass) sit behind wavefront-uniform ballots.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -592,8 +592,8 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     wave_sync();
     tick(4);
     for (;;) {
-        // ===================================================== active-set loop
-        for (;;) {
+#include "mpcqp_quad_steady.h"  // (a fragment of this body) the steady loop: plain trips in one basic block; defines `general`
+        if (general) for (;;) {  // ===== active-set loop: every kind of trip
             // ---- the previous trip's rank-one update  T_a += (r_a/d2) z, T_new = -z/d2 ; H -= z z'/d2  (or the same with a
             //      leaving slot's T_l), wrapped around this trip's selection and row fetch, which only read the slacks
             dpp_ready(zn);
