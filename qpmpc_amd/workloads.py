@@ -3,7 +3,9 @@
 Pure NumPy data generators (seeded); nothing here computes a solution. Each
 function returns a dict of float64 arrays laid out as ``BatchMPCProblem``
 expects plus the scalar weights, so the same inputs can be handed to the HIP
-path and to the CPU oracle.
+path and to the CPU oracle. The random families (``random_ltv``, ``tight_ltv``)
+come with ``row_residuals``, the roll-out that says how far a given plan is
+from each of their rows: the tests and tools/stress_tight.py check with it.
 """
 from __future__ import annotations
 
@@ -134,6 +136,67 @@ def synthetic_ltv_batch_slice(lo: int, hi: int, nx: int = 12, nu: int = 4, N: in
         C[12 + r, r] = -1.0
     e = np.concatenate([np.ones(8), 5.0 * np.ones(8)])
     return _pack(A, B, C, D, e, N, 10.0, 1.0, 1e-2, x0, np.zeros(nx), np.zeros(N * nx), name=f"synthetic_ltv_nx{nx}_nu{nu}_N{N}")
+
+
+def random_ltv(rng, B, nx, nu, N, mk, tight):
+    """Random LTV problems of any shape: dynamics near the identity, dense random B, C, D, and bounds ``tight`` wide around the
+    free response (smaller: more rows active). The family the tests of every kernel and of the adjoint / tangent paths draw
+    from, bench.py's accuracy samples, the stress campaigns of tools/stress_*.py and the generators of the golden fixtures.
+    The draws stay in this order: the fixtures under tests/golden/ and every seeded test depend on it."""
+    A = np.eye(nx) + 0.08 * rng.standard_normal((B, N, nx, nx))
+    Bm = rng.standard_normal((B, N, nx, nu))
+    Cm = rng.standard_normal((B, N, mk, nx))
+    D = rng.standard_normal((B, N, mk, nu))
+    x0 = 0.1 * rng.standard_normal((B, nx))
+    e = np.zeros((B, N, mk))
+    for b in range(B):
+        x = x0[b].copy()
+        for k in range(N):
+            e[b, k] = Cm[b, k] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
+            x = A[b, k] @ x
+    return dict(A=A, B=Bm, C=Cm, D=D, e=e, N=N, wt=2.0, wx=0.5, wu=1e-2, x0=x0,
+                goal=rng.standard_normal((B, nx)), targets=rng.standard_normal((B, N * nx)))
+
+
+def tight_ltv(kind, rng, batch, tight):
+    """One round of a NEARLY FULLY ACTIVE family (many tight rows per step: most of the variables end up pinned) at tightness
+    ``tight``: the dimensions, then random_ltv's problems. ``kind`` picks the system widths of the narrow (nx <= 4), wide
+    (nx <= 16; widef: constraint matrices fixed along the horizon) and general stage-wise kernels. The campaign of
+    tools/stress_tight.py, the verdict tests (tests/verdict_cases.py, tests/test_gpu_stress.py) and the oracle's certificate
+    (tests/kkt_certificate.py) are defined on these; the draws stay in this order."""
+    if kind == "narrow":
+        nx, nu = int(rng.integers(2, 5)), int(rng.integers(1, 3))
+    elif kind in ("wide", "widef"):
+        nx, nu = int(rng.integers(5, 17)), int(rng.integers(1, 5))
+    else:
+        nx, nu = int(rng.integers(17, 33)), int(rng.integers(1, 9))
+    N = int(rng.integers(20, 41)); mk = int(rng.integers(4, 7))
+    if kind == "widef":  # constraint matrices FIXED along the horizon, 4 / 8 / 12 / 16 rows per step: the wide kernel's layout in
+        mk = 4 * int(rng.integers(1, 5))  # which the forward sweep forms the rows itself (config 5's)
+    w = random_ltv(rng, batch, nx, nu, N, mk, tight)  # (smaller: tighter rows, more of them active)
+    w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
+    if kind == "widef":
+        w["C"], w["D"] = w["C"][:, :1].copy(), w["D"][:, :1].copy()
+        for b in range(batch):  # bounds around the free response, as random_ltv makes them (with the fixed C)
+            x = w["x0"][b].copy()
+            for k in range(N):
+                w["e"][b, k] = w["C"][b, 0] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
+                x = w["A"][b, k] @ x
+    return w
+
+
+def row_residuals(w, b, U):
+    """G u - h of problem b of a random_ltv / tight_ltv workload at the inputs U (<= 0: feasible, 0: on the bound), by a roll-out
+    in extended precision: a check that needs no solver and no condensing. tools/stress_tight.py weighs flagged rounds with it and
+    tests/kkt_certificate.py cross-checks the condensed residual against it."""
+    LD = np.longdouble
+    A, B, C, D, e, x0 = (np.asarray(w[k]) for k in ("A", "B", "C", "D", "e", "x0"))
+    N, nu = A.shape[1], B.shape[-1]
+    x, u, out = x0[b].astype(LD), np.asarray(U).reshape(N, nu).astype(LD), []
+    for k in range(N):
+        out.append(C[b, k].astype(LD) @ x + D[b, k].astype(LD) @ u[k] - e[b, k].astype(LD))
+        x = A[b, k].astype(LD) @ x + B[b, k].astype(LD) @ u[k]
+    return np.concatenate(out)
 
 
 def problem_from_workload(w: dict, b: int):

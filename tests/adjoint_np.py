@@ -116,3 +116,15 @@ def fd_gradients(w1: dict, gU, gX=None, step: float = 1e-6) -> dict:
 
 def strictly_complementary(lam, slack, margin: float = 1e-4) -> bool:
     return bool(np.all((np.asarray(lam) > margin) | (np.asarray(slack) > margin)))
+
+
+def complementary(w, count):
+    """Indices of the first ``count`` strictly complementary problems of a workload (by the C oracle)."""
+    picked = []
+    for b in range(np.asarray(w["x0"]).shape[0]):
+        U, lam, slack, st = solve(single(w, b))
+        if st == 0 and strictly_complementary(lam, slack):
+            picked.append(b)
+        if len(picked) == count:
+            return picked
+    raise AssertionError(f"only {len(picked)} strictly complementary problems")

@@ -15,15 +15,11 @@ from __future__ import annotations
 import functools
 import os
 import re
-import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-for _p in (HERE, os.path.join(ROOT, "tools")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
 
 UNITS = ("mpcqp_pair.hip", "mpcqp_quad.hip", "mpcqp_quadw.hip", "mpcqp_quadg.hip", "mpcqp_quadgw.hip")
 
@@ -32,7 +28,7 @@ UNITS = ("mpcqp_pair.hip", "mpcqp_quad.hip", "mpcqp_quadw.hip", "mpcqp_quadg.hip
 @functools.lru_cache(maxsize=None)
 def unit_asm(unit: str) -> str:
     """gfx950 assembly of qpmpc_amd/csrc/<unit>, compiled once per process"""
-    import check_dpp_hazards as chk
+    import tools.check_dpp_hazards as chk
 
     return chk.device_asm(os.path.join(ROOT, "qpmpc_amd", "csrc", unit))
 
@@ -206,7 +202,7 @@ REACHABLE = [k for k, r in MANIFEST.items() if not r.get("unreachable")]
 def _general_family(rng, batch, nx, nu, N, tight, rows, stage, mk):
     """tests/test_gpu_quad.py::_general_family (with rows "c" and no stage cost: its _lean_family without the time-invariant
     option), restated here so that the CPU tests do not import a GPU module"""
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     w = random_ltv(rng, batch, nx, nu, N, mk, tight)
     if rows == "c":

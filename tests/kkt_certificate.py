@@ -8,18 +8,16 @@ restatement of the reference build (oracle/condense_np.py) and the four KKT cond
 are evaluated in extended precision (np.longdouble) at the returned plan U and multipliers lam. Each quantity is scaled the
 way the oracle's acceptance rule scales it (mpc_oracle.c, end of oracle_gi_solve): rows by 1 + |h_i|, multipliers by
 1 + max(lam). The primal half can also be formed without condensing, by the long-double roll-out of
-tools/stress_tight.py:row_residuals -- ``certify(..., rollout=True)`` cross-checks the two.
+qpmpc_amd/workloads.py:row_residuals -- ``certify(..., rollout=True)`` cross-checks the two.
 """
 from __future__ import annotations
 
-import os
-import sys
 from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOLS = os.path.join(ROOT, "tools")
+from oracle.condense_np import condense
+from qpmpc_amd.workloads import problem_from_workload, row_residuals, tight_ltv
 
 # Acceptance bounds. PRIMAL is the oracle's bound on its active rows (1e-9 (1 + |h_i|)); DUAL its clamp of a weakly active row's
 # multiplier (-1e-12 (1 + umax)), with room for a kernel that reports multipliers after one fewer refinement; COMPLEMENTARITY
@@ -40,15 +38,6 @@ class Certificate(NamedTuple):
                 f"stationarity {self.stationarity:.2e} -> {'pass' if self.ok else 'FAIL'}")
 
 
-def row_residuals(w: Dict, b: int, U) -> np.ndarray:
-    """G u - h of item ``b`` by the long-double roll-out of tools/stress_tight.py (no condensing)."""
-    if TOOLS not in sys.path:
-        sys.path.insert(0, TOOLS)
-    from stress_tight import row_residuals as rr
-
-    return rr(w, b, U)
-
-
 _CACHE: Dict[tuple, tuple] = {}
 
 
@@ -58,9 +47,6 @@ def condensed(w: Dict, b: int):
     hit = _CACHE.get(key)
     if hit is not None and hit[0] is w:
         return hit[1]
-    from oracle.condense_np import condense
-    from qpmpc_amd.workloads import problem_from_workload
-
     cq = condense(problem_from_workload(w, b))
     LD = np.longdouble
     out = (cq.P.astype(LD), cq.q.astype(LD), cq.G.astype(LD), cq.h.astype(LD))
@@ -113,10 +99,6 @@ def worst(certs) -> Certificate:
 
 
 def tight_narrow(seed: int, tight: float, rounds: int, batch: int):
-    """The ``stress_tight narrow`` family (tools/stress_tight.py: draw): ``rounds`` workload dicts of ``batch`` problems."""
-    if TOOLS not in sys.path:
-        sys.path.insert(0, TOOLS)
-    from stress_tight import draw
-
+    """The ``stress_tight narrow`` family (qpmpc_amd/workloads.py: tight_ltv): ``rounds`` workload dicts of ``batch`` problems."""
     rng = np.random.default_rng(seed)
-    return [draw("narrow", rng, batch, tight) for _ in range(rounds)]
+    return [tight_ltv("narrow", rng, batch, tight) for _ in range(rounds)]

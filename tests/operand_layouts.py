@@ -17,15 +17,7 @@ lockstep; the per-cycle shifts t_X (none in the first cycle) make the twelve dis
 than four joint forms, while each block of four still gives every operand every form once (every form three times in all)."""
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, os.path.join(os.path.dirname(HERE), "tools")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
 
 OPTS = ("bn", "b1", "1n", "11")
 MATS = ("A", "B", "C", "D", "e")
@@ -88,14 +80,14 @@ def _reduce(a, form, how="slice"):
 
 
 def make(shape, rows, stage, layout, seed, margin, contractive=False):
-    """(w, full): BATCH problems of tools/stress_stagewise.random_ltv in layout `layout` (an index into LAYOUTS or a dict). `w` is
+    """(w, full): BATCH problems of qpmpc_amd.workloads.random_ltv in layout `layout` (an index into LAYOUTS or a dict). `w` is
     the workload dict with every operand in its stored shape [1|B, 1|N, ...] (goal, targets [1|B, ...]); `full` states the same
     problems with every operand materialised to [B, N, ...] and [B, ...]. rows "c" / "d" / "cd": state rows, an input box or both;
     stage: with a stage cost. e is recomputed on the materialised operands so that u = 0 stays feasible for every problem:
     e[b, k] = C[b, k] x_free[b, k] + margin (0.05 + 0.5 |N(0, 1)|), reduced by max over the axes the layout shares for e.
     contractive: every drawn A block is replaced by 0.98 times its orthogonal QR factor and B is divided by sqrt(nx), the
     dynamics of BASELINE config 5 (qpmpc_amd.workloads.synthetic_ltv_batch) -- see LONG below."""
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     nx, nu, N, mk = shape
     lay = LAYOUTS[layout] if isinstance(layout, int) else layout

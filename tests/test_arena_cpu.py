@@ -1,14 +1,11 @@
 """The guarded arena of tests/arena.py can fail: a write one byte past a buffer and one byte in front of it are reported with the
 buffer's name and the distance, a write inside a buffer is not, and a snapshot sees a single flipped bit. CPU tensors only."""
-import os
-import sys
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import arena as AR  # noqa: E402
+import arena as AR
 
 
 def make():

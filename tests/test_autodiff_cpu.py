@@ -1,19 +1,12 @@
 """Gradients through plans, without a GPU: the NumPy restatement of the vector-Jacobian product (tests/adjoint_np.py)
 against central finite differences of the C oracle's solve, on strictly complementary problems (every row has a
 multiplier or a slack above 1e-4, so a small step keeps the active set); and the public surface of the feature."""
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_np as AN  # noqa: E402
-from qpmpc_amd import _capi  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_np as AN
+from qpmpc_amd import _capi
+from qpmpc_amd import workloads as W
 
 
 def _check_against_fd(w, batch, rng, need):
@@ -43,7 +36,7 @@ def test_adjoint_np_matches_finite_differences_triple_integrator():
 
 
 def test_adjoint_np_matches_finite_differences_random_ltv():
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     rng = np.random.default_rng(11)
     w = random_ltv(rng, 10, 3, 2, 5, 2, 1.0)  # input rows (D), state rows (C), stage and terminal cost

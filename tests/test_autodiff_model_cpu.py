@@ -2,24 +2,17 @@
 finite differences of the C oracle's solve for every entry of A, B, C, D and the three weights, on strictly complementary
 problems; and the C exports and Python surface of the feature."""
 import inspect
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_model_np as AM  # noqa: E402
-import adjoint_np as AN  # noqa: E402
-from qpmpc_amd import _capi  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_model_np as AM
+import adjoint_np as AN
+from qpmpc_amd import _capi
+from qpmpc_amd import workloads as W
 
 
 def _ltv(seed, B, nx=3, nu=2, N=5, mk=2):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, 1.0)
 

@@ -4,16 +4,14 @@ mpcqp_warm_state_bytes, mpcqp_warm_state_kind, mpcqp_lds_bytes and mpcqp_solve_w
 every branch of the launch dispatch. A difference is a change in what callers are told to allocate. Only the queries are
 called: no launch entry point, so nothing here touches a device."""
 import os
-import sys
 
 import numpy as np
 
 from golden_util import GOLDEN
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-import gen_golden_dispatch as gen  # noqa: E402
+import tools.gen_golden_dispatch as gen
 
-from qpmpc_amd import _capi  # noqa: E402
+from qpmpc_amd import _capi
 
 
 def _mismatches(name, got, want, dims):

@@ -146,11 +146,6 @@ def test_bench_rank_logic_two_ranks_gloo(tmp_path, config, batch):
 def test_bench_plain_run_is_only_the_headline():
     """Without --full, run_bench launches the solver only for construction, warm-up and the timed steps, and the record
     carries none of the measurements --full adds (on CPU the strong configurations' all_gather is the one that shows)."""
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
     import bench
 
     runs = []
@@ -204,11 +199,6 @@ def test_bench_main_spawns_its_own_ranks(config, batch):
 def test_bench_main_in_process_goes_through_respawn(monkeypatch):
     """bench.main(["--gpus", "2", ...]) with no WORLD_SIZE in the environment re-executes through
     torch.distributed.run (the command line is the driver's) instead of exiting with a usage error."""
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
     import subprocess
 
     import bench
@@ -238,11 +228,6 @@ def test_bench_config5_slices_are_one_global_problem_set():
 def test_bench_dump_outputs(tmp_path, monkeypatch):
     """--dump-outputs DIR: after exactly --steps timed steps the last step's plans, statuses and iteration counts land in
     DIR/<name>.npy as float arrays, identical from run to run; above the size limit a fixed, seeded sample is written."""
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if root not in sys.path:
-        sys.path.insert(0, root)
     import bench
 
     runs = []

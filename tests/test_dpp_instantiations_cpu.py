@@ -6,16 +6,11 @@ instantiation must not ship without a launch that reaches it, and a retired one 
 the gfx950 assembly (hipcc cross-compiles without a GPU); the inputs are held to their conditions by the C oracle alone."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import dpp_instantiations as DI  # noqa: E402
+import dpp_instantiations as DI
 
 SIMDS = 1024  # an MI355X: 256 compute units of four SIMDs (the GPU tests read it from the device)
 

@@ -1,21 +1,14 @@
 """Gradients through batched plans on the MI355X: mpcqp_plan_vjp_batch (qpmpc_amd/csrc/mpcqp_adjoint.hip) against the
 NumPy restatement of tests/adjoint_np.py on every forward path, torch.autograd.gradcheck of solve_mpc_batch_diff,
 unsolved problems, shared operands, float32 storage and the envelope."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_np as AN  # noqa: E402
-from oracle.condense_np import condense  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
-from qpmpc_amd.workloads import problem_from_workload  # noqa: E402
+import adjoint_np as AN
+from oracle.condense_np import condense
+from qpmpc_amd import workloads as W
+from qpmpc_amd.workloads import problem_from_workload
 
 pytestmark = pytest.mark.gpu
 KEYS = ("x0", "goal", "targets", "e")
@@ -28,7 +21,7 @@ def _torch():
 
 
 def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
@@ -117,18 +110,6 @@ def test_vjp_n128_workspace_carve():
     _check_path(w, 16, 4)
 
 
-def _complementary(w, count):
-    """Indices of the first ``count`` strictly complementary problems of a workload (by the C oracle)."""
-    picked = []
-    for b in range(np.asarray(w["x0"]).shape[0]):
-        U, lam, slack, st = AN.solve(AN.single(w, b))
-        if st == 0 and AN.strictly_complementary(lam, slack):
-            picked.append(b)
-        if len(picked) == count:
-            return picked
-    raise AssertionError(f"only {len(picked)} strictly complementary problems")
-
-
 def _subset(w, idx):
     B = np.asarray(w["x0"]).shape[0]
     out = dict(w)
@@ -144,7 +125,7 @@ def test_gradcheck(states):
     from qpmpc_amd import solve_mpc_batch_diff
 
     w = _random_ltv(5, 40, 3, 2, 5, 2)
-    w = _subset(w, _complementary(w, 4))
+    w = _subset(w, AN.complementary(w, 4))
     bp = W.to_batch_problem(w)
     x0 = torch.as_tensor(w["x0"], device=bp.device).clone().requires_grad_()
     goal = torch.as_tensor(w["goal"], device=bp.device).clone().requires_grad_()
@@ -208,7 +189,7 @@ def test_float32_storage_gradients():
     from qpmpc_amd import solve_mpc_batch_diff
 
     w = _random_ltv(9, 60, 3, 2, 6, 2)
-    w = _subset(w, _complementary(w, 16))
+    w = _subset(w, AN.complementary(w, 16))
     grads = {}
     for dt in (torch.float64, torch.float32):
         bp = W.to_batch_problem(w, dtype=dt)

@@ -4,21 +4,15 @@ restatements (tests/adjoint_stagewise_np.py, tests/adjoint_np.py, tests/adjoint_
 the condensed adjoint where both apply, gradcheck, and the export's edge cases."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_model_np as AM  # noqa: E402
-import adjoint_np as AN  # noqa: E402
-import adjoint_stagewise_np as AS  # noqa: E402
-from golden_util import GOLDEN  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_model_np as AM
+import adjoint_np as AN
+import adjoint_stagewise_np as AS
+from golden_util import GOLDEN
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 KEYS = ("x0", "goal", "targets", "e")
@@ -33,7 +27,7 @@ def _torch():
 
 
 def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 

@@ -19,21 +19,15 @@ Every bound is one an older test of the same launch shape holds:
            the cold ones and of the oracle (tests/test_gpu_warm_start.py)
   warm     MPCQP_WARM_OPERATOR after the cold launch: statuses equal, plans within 1e-9 of the cold ones, 1e-8 of the oracle (same)
 The inputs are held to their conditions (binding rows, drops, all solved) by tests/test_dpp_instantiations_cpu.py."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
+import dpp_instantiations as DI
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import dpp_instantiations as DI  # noqa: E402
 
 
 def _simds():

@@ -18,7 +18,6 @@ sizes, 512-byte aligned, 64 KiB of guard on either side. Each launch runs under 
 The exports are called through ctypes directly. No launch ever gets a buffer smaller than the contract says."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -26,21 +25,19 @@ import pytest
 import oracle
 from oracle import condense_np
 
+import adjoint_np as AN
+import adjoint_stagewise_np as AS
+import arena as AR
+from operand_layouts import f32_view
+import tangent_model_np as TM
+import tangent_np as TN
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, os.path.join(os.path.dirname(HERE), "tools")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
 
-import adjoint_np as AN  # noqa: E402
-import adjoint_stagewise_np as AS  # noqa: E402
-import arena as AR  # noqa: E402
-from operand_layouts import f32_view  # noqa: E402
-import tangent_model_np as TM  # noqa: E402
-import tangent_np as TN  # noqa: E402
 
 Z, F = 0x00, 0xFF
 I32, U8, F64, F32 = torch.int32, torch.uint8, torch.float64, torch.float32
@@ -162,8 +159,8 @@ def arena_problem(L, bp, pad=0):
 
 # ---------------------------------------------------------------------------------------------- workloads
 def ltv(seed, B, nx, nu, N, mk, tight=1.0, rows="cd", stage=True):
-    """tools/stress_stagewise.random_ltv; rows "c" / "d" / "cd": state rows, an input box or both; stage: with a stage cost"""
-    from stress_stagewise import random_ltv
+    """qpmpc_amd.workloads.random_ltv; rows "c" / "d" / "cd": state rows, an input box or both; stage: with a stage cost"""
+    from qpmpc_amd.workloads import random_ltv
 
     rng = np.random.default_rng(seed)
     w = random_ltv(rng, B, nx, nu, N, mk, tight)

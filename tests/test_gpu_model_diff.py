@@ -4,20 +4,17 @@ which each of the two kernels can go wrong; against mpcqp_plan_vjp_batch / mpcqp
 plan; and the Python surface (SharedModel.solve_diff, .plan_jvp, .plan_jacobian)."""
 import os
 import re
-import sys
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import adjoint_np as AN
+import model_adjoint_np as MN
+from qpmpc_amd import workloads as W
 
-import adjoint_np as AN  # noqa: E402
-import model_adjoint_np as MN  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-8

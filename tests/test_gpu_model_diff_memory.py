@@ -4,20 +4,13 @@ guards (the model at mpcqp_model_bytes), the outputs poisoned; afterwards the gu
 output of a solved problem, the read-only buffers (the model included) are bitwise unchanged and NULL outputs are
 respected. One small-kernel and one general-kernel shape, each with an odd batch."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import arena as AR  # noqa: E402
-import model_adjoint_np as MN  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import arena as AR
+import model_adjoint_np as MN
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 

@@ -26,27 +26,22 @@ builds hoist, and the fused constraint layout of mpcqp_stagew.hip on the layouts
 (OL.coverage()). A layout that a route did refuse would be skipped with the code that refuses it (SKIPS); none is today."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
+
+import adjoint_np as AN
+import adjoint_stagewise_np as AS
+import operand_layouts as OL
+import tangent_model_np as TM
+import tangent_np as TN
+import test_gpu_memory_discipline as MD
+from test_gpu_memory_discipline import Forward, Launch, against_oracle, close
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, os.path.join(os.path.dirname(HERE), "tools")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
-import adjoint_np as AN  # noqa: E402
-import adjoint_stagewise_np as AS  # noqa: E402
-import operand_layouts as OL  # noqa: E402
-import tangent_model_np as TM  # noqa: E402
-import tangent_np as TN  # noqa: E402
-import test_gpu_memory_discipline as MD  # noqa: E402
-from test_gpu_memory_discipline import Forward, Launch, against_oracle, close  # noqa: E402
 
 F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
 ELAYOUT = -4

@@ -483,14 +483,8 @@ def test_large_condense_long_horizons(nx, nu, N, mk):
     """The dense large-problem condensing on LONG horizons of narrow-input systems (n = N nu up to 256 with N up to 256: the
     Gram's chunk staging, its weighted-residual table in dynamic LDS and the causality bounds at their extremes) against the
     float64 oracle (mpc_qp.py:53-122)."""
-    import sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from stress_stagewise import random_ltv
     from qpmpc_amd import BatchMPCQP
-    from qpmpc_amd.workloads import problem_from_workload, to_batch_problem
+    from qpmpc_amd.workloads import problem_from_workload, random_ltv, to_batch_problem
 
     rng = np.random.default_rng(4)
     w = random_ltv(rng, 2, nx, nu, N, mk, 1.0)
@@ -1141,12 +1135,7 @@ def test_pair_kernel_random_shapes_with_drops_vs_oracle_and_other_kernels():
     coefficients of the projector rows and the fast loop all run): statuses equal to the C oracle's and to the
     one-per-wavefront and workgroup kernels', plans within 1e-7 relative. Replaces qpsolvers.solve_problem at
     qpmpc/solve_mpc.py:43 like every solver kernel."""
-    import os, sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from stress_pair import run
+    from tools.stress_pair import run
 
     worst, flagged, drops = run(16, 96, seed=20260929, verbose=False)
     assert flagged == 0, (worst, flagged)
@@ -1160,14 +1149,8 @@ def test_inconsistent_problems_are_never_reported_solved():
     are solvable, and a plan reported solved must satisfy its rows. (Round 2: the workgroup kernel's dependence test sat
     at rounding-noise level and returned |u| ~ 1e13 'solutions' for a few such problems; qpsolvers reports found=False
     there, plan.py:35-40.)"""
-    import os, sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from stress_stagewise import random_ltv
     from qpmpc_amd import _capi, solve_mpc_batch
-    from qpmpc_amd.workloads import to_batch_problem
+    from qpmpc_amd.workloads import random_ltv, to_batch_problem
 
     rng = np.random.default_rng(99)
     unsolved = 0
@@ -1209,14 +1192,8 @@ def test_lean_instantiations_of_the_pair_kernel(nx, lti):
     registers (element e of [A_k | C_k] in lane e, and e + 16 for nx = 4) and reach the chain as DPP row broadcasts;
     time-varying and time-invariant operands (stride 0 along the horizon), odd and even horizons, against the C oracle and
     the one-per-wavefront kernel (equal iteration counts). qpmpc/mpc_qp.py:53-114 + qpmpc/solve_mpc.py:43."""
-    import os, sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from stress_stagewise import random_ltv
     from qpmpc_amd import _capi, solve_mpc_batch
-    from qpmpc_amd.workloads import to_batch_problem
+    from qpmpc_amd.workloads import random_ltv, to_batch_problem
 
     rng = np.random.default_rng(1000 + 10 * nx + int(lti))
     for N in (16, 13, 7, 2):

@@ -2,20 +2,13 @@
 qpmpc_amd/csrc/mpcqp_adjoint.hip) against the NumPy restatement of tests/tangent_np.py on every forward path, its duality
 with mpcqp_plan_vjp_batch, plan_jacobian against the LQR gain, shared tangents, unsolved problems, float32 storage and
 forward-mode AD through solve_mpc_batch_diff."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_np as AN  # noqa: E402
-import tangent_np as TN  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_np as AN
+import tangent_np as TN
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 NAMES = dict(x0="initial_state", goal="goal_state", targets="target_states", e="ineq_vector")
@@ -28,7 +21,7 @@ def _torch():
 
 
 def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
@@ -228,17 +221,6 @@ def test_float32_storage():
     assert (err[same] <= 1e-3 * scale[same]).all()
 
 
-def _complementary(w, count):
-    picked = []
-    for b in range(np.asarray(w["x0"]).shape[0]):
-        U, lam, slack, st = AN.solve(AN.single(w, b))
-        if st == 0 and AN.strictly_complementary(lam, slack):
-            picked.append(b)
-        if len(picked) == count:
-            return picked
-    raise AssertionError(f"only {len(picked)} strictly complementary problems")
-
-
 def _subset(w, idx):
     B = np.asarray(w["x0"]).shape[0]
     out = dict(w)
@@ -255,7 +237,7 @@ def test_forward_ad_through_solve_mpc_batch_diff():
     from qpmpc_amd import plan_jvp, solve_mpc_batch_diff
 
     w = _random_ltv(11, 40, 3, 2, 5, 2)
-    w = _subset(w, _complementary(w, 8))
+    w = _subset(w, AN.complementary(w, 8))
     bp = W.to_batch_problem(w)
     dev = bp.device
     rng = np.random.default_rng(11)

@@ -6,20 +6,13 @@ state-only call (bitwise mpcqp_plan_jvp_batch) and plan_jacobian(wrt="cost_weigh
 
 The helpers take ``formulation``: tests/test_gpu_plan_jvp_model_stagewise.py runs them on the stage-wise export."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_np as AN  # noqa: E402
-import tangent_model_np as TM  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_np as AN
+import tangent_model_np as TM
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 NAMES = dict(x0="initial_state", goal="goal_state", targets="target_states", e="ineq_vector",
@@ -36,7 +29,7 @@ def _torch():
 
 
 def random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv as make
+    from qpmpc_amd.workloads import random_ltv as make
 
     return make(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
@@ -351,17 +344,6 @@ def test_state_tangents_only_are_bitwise_the_old_export():
     check_state_only_is_bitwise_the_old_export(random_ltv(8, 48, 3, 2, 8, 2), "condensed")
 
 
-def complementary(w, count):
-    picked = []
-    for b in range(np.asarray(w["x0"]).shape[0]):
-        U, lam, slack, st = AN.solve(AN.single(w, b))
-        if st == 0 and AN.strictly_complementary(lam, slack):
-            picked.append(b)
-        if len(picked) == count:
-            return picked
-    raise AssertionError(f"only {len(picked)} strictly complementary problems")
-
-
 def subset(w, idx):
     B = np.asarray(w["x0"]).shape[0]
     out = dict(w)
@@ -379,7 +361,7 @@ def check_weight_jacobian(formulation):
     from qpmpc_amd import plan_jacobian, solve_mpc_batch
 
     w = random_ltv(11, 40, 3, 2, 5, 2)
-    w = subset(w, complementary(w, 8))
+    w = subset(w, AN.complementary(w, 8))
     bp = W.to_batch_problem(w)
     plan = solve_mpc_batch(bp, return_multipliers=True)
     JU, JX = plan_jacobian(bp, plan, wrt="cost_weights", states=True, formulation=formulation)

@@ -5,19 +5,12 @@ the config-5 shape (float32 storage too), beyond the wide forward kernel and wit
 independence of its slot, pass and T; and, through the helpers of tests/test_gpu_plan_jvp_model.py, the duality with
 mpcqp_plan_vjp_stagewise_batch, shared and time-invariant tangents, unsolved problems, the state-only call and the
 weight Jacobian."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import test_gpu_plan_jvp_model as M  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import test_gpu_plan_jvp_model as M
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 SW = dict(formulation="stagewise")

@@ -5,20 +5,14 @@ solve_mpc_batch_diff(tangent="stagewise"), beyond the condensed tangent's 128 va
 duality with the stage-wise adjoint, and the export's edge cases."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import adjoint_np as AN  # noqa: E402
-import tangent_stagewise_np as TS  # noqa: E402
-from golden_util import GOLDEN  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+import adjoint_np as AN
+import tangent_stagewise_np as TS
+from golden_util import GOLDEN
+from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
 NAMES = dict(x0="initial_state", goal="goal_state", targets="target_states", e="ineq_vector")
@@ -31,7 +25,7 @@ def _torch():
 
 
 def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 

@@ -7,8 +7,6 @@ forces it, MPCQP_OPT_TWO_PER_WAVE keeps the other.
 
 Tolerances (float64): plans |u - u_ref|_inf <= 1e-7 max(1, |u_ref|_inf) against the C oracle (BASELINE.json: 1e-6), observed
 ~1e-12; statuses equal; iteration counts equal to the two-per-wavefront kernel's (same method, same pivots)."""
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -19,13 +17,9 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-TOOLS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-if TOOLS not in sys.path:
-    sys.path.insert(0, TOOLS)
-
 
 def _lean_family(rng, batch, nx, nu, N, tight, lti):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     w = random_ltv(rng, batch, nx, nu, N, 2, tight)
     w["wx"] = w["targets"] = w["D"] = None
@@ -278,7 +272,7 @@ def test_forcing_the_kernel_where_it_does_not_apply_is_refused():
     dimensions: MPCQP_EUNSUPPORTED before any launch."""
     from qpmpc_amd import BackendError, WarmState, _capi, solve_mpc_batch
     from qpmpc_amd import workloads as W
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     rng = np.random.default_rng(1)
     w = random_ltv(rng, 8, 3, 1, 6, 9, 1.0)  # nine rows per step
@@ -297,7 +291,7 @@ def test_forcing_the_kernel_where_it_does_not_apply_is_refused():
 
 def _general_family(rng, batch, nx, nu, N, tight, rows, stage, mk=2):
     """random LTV problems with mk rows per step: state rows, input rows or both; with or without a stage cost"""
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     w = random_ltv(rng, batch, nx, nu, N, mk, tight)
     if rows == "c":
@@ -426,7 +420,7 @@ def test_default_dispatch_of_the_general_layouts_and_of_double_integrators():
 def test_stress_campaign_with_drops():
     """tools/stress_pair.py's lean rounds forced through this kernel: statuses equal to the C oracle's and to the one-per-wavefront
     and workgroup kernels', plans within 1e-7 relative."""
-    from stress_pair import run
+    from tools.stress_pair import run
 
     worst, flagged, drops = run(24, 96, seed=20260930, verbose=False, lean_only=True, flags_lean=4096)
     assert flagged == 0, (worst, flagged)
@@ -436,7 +430,7 @@ def test_stress_campaign_with_drops():
 def test_stress_campaign_through_the_general_build():
     """... and tools/stress_pair.py's other rounds (stage costs, input rows, one to four rows per step, nx = 3, 4; tight enough for
     partial steps and drops) forced through the kernel's general build: the same checks."""
-    from stress_pair import run
+    from tools.stress_pair import run
 
     worst, flagged, drops = run(32, 96, seed=20261001, verbose=False, flags_lean=4096, flags_other=4096)
     assert flagged == 0, (worst, flagged)
@@ -447,7 +441,7 @@ def test_random_campaign_over_the_whole_envelope_of_the_general_build():
     """tools/stress_quad_general.py: nx 2..4, nu 1..4, every horizon with n <= 16, one to four rows per step, state / input rows or both,
     with and without a stage cost, per-step or time-invariant operands, loose to very tight bounds -- 80 rounds of 64 problems forced
     through the kernel against the C oracle (six seeds of 150 x 96 ran clean when the build was written: worst 2.5e-11)."""
-    from stress_quad_general import run
+    from tools.stress_quad_general import run
 
     worst, flagged, solved, drops = run(80, 64, seed=7, verbose=False)
     assert flagged == 0 and worst <= 1e-7, (worst, flagged)

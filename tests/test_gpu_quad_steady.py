@@ -11,21 +11,16 @@ the shared-model mode on the humanoid model. The 64 problems mix tight, loose an
 that leave the steady loop at different trips and for different reasons: test_the_fixture_mixes_the_wavefronts re-asserts that from
 the stored arrays (no GPU)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-
-TOOLS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-if TOOLS not in sys.path:
-    sys.path.insert(0, TOOLS)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "quad_steady_parent.npz")
 _CACHE = {}
 
 
 def _fixture():
-    import gen_golden_quad_steady as G
+    import tools.gen_golden_quad_steady as G
 
     if not _CACHE:
         _CACHE["sets"], _CACHE["results"] = G.unpack(np.load(GOLDEN))

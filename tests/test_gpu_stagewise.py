@@ -418,13 +418,8 @@ def test_slot_overflow_is_retried_with_more_slots():
     """N = 4096 (n = 4096, m = 16384): with the default 128 slots a few problems want more rows active at once and the kernel
     reports MPCQP_SLOTS_FULL (4) for them; solve_mpc_batch solves those again with 256, 512, ... slots: 100 % solved, and the
     re-solved ones equal a solve that had enough slots from the start."""
-    import os, sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from bench_stagewise import long_batch
     from qpmpc_amd import _capi, solve_mpc_batch
+    from tools.bench_stagewise import long_batch
 
     bp = long_batch(192, 4096, 1.0 / 128)
     raw = solve_mpc_batch(bp, retry_slots=False)
@@ -501,13 +496,8 @@ def test_wide_systems_any_horizon_against_the_oracle(nx, nu, N, mk, dtype, tol):
     back MPCQP_ETOOLARGE; the general stage-wise kernel serves them (nx <= 32, nu <= 8, float64 arithmetic; float32
     launches are converted). Plans against the float64 C oracle through the default dispatch."""
     import os
-    import sys
-
     from qpmpc_amd import _capi, solve_mpc_batch
-    from qpmpc_amd.workloads import to_batch_problem
-
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv, to_batch_problem
 
     rng = np.random.default_rng(1000 * nx + N)
     w = random_ltv(rng, 8, nx, nu, N, mk, 3.0)
@@ -541,14 +531,8 @@ def test_factor_options_of_the_narrow_kernel_for_every_dimension(nx, nu, N, mk):
     wavefront of the pipelined instantiation (operands padded and transposed into LDS, round 4) must give the plans of the
     plain launch -- same recursion, same sweeps: bitwise. Replaces qpmpc/solve_mpc.py:42-44 / mpc_qp.py:129-163 (build once,
     update, re-solve) like the closed loops."""
-    import os, sys
-
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    if tools not in sys.path:
-        sys.path.insert(0, tools)
-    from stress_stagewise import random_ltv
     from qpmpc_amd import PreparedSolve, _capi
-    from qpmpc_amd.workloads import to_batch_problem
+    from qpmpc_amd.workloads import random_ltv, to_batch_problem
 
     rng = np.random.default_rng(1000 * nx + 100 * nu + N)
     # (nx = 3: a batch that is no multiple of four -- the pipelined instantiation packs four problems per workgroup and ONE

@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TIGHT = (0.5, 0.3, 0.15, 0.05)
 BATCH = 64
-# one round of BATCH problems per seed (tools/stress_tight.py: draw("narrow", default_rng(seed), BATCH, tight)). A campaign of 150
+# one round of BATCH problems per seed (qpmpc_amd/workloads.py: tight_ltv("narrow", default_rng(seed), BATCH, tight)). A campaign of 150
 # such rounds per tightness found the narrow kernel alone (a KEEP_FACTOR launch without the second opinion) ending unsolved where the
 # oracle solves on three items, all at 0.05: seed 4012 item 41 (MPCQP_MAX_ITER), 4114 item 29 (MPCQP_INFEASIBLE), 4146 item 51
 # (MPCQP_MAX_ITER); none at 0.5 / 0.3 / 0.15, and the plain one-shot launch agreed with the oracle everywhere.

@@ -122,20 +122,15 @@ def test_solve_mpc_delivers_what_an_exact_backend_would_on_known_hard_problems()
     import numpy as np
     import torch
 
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
     import oracle
     from qpmpc_amd import solve_mpc, solve_mpc_batch
     from qpmpc_amd import workloads as W
-    from stress_stagewise import random_ltv
 
     checked = 0
     for seed in (1, 5):
         rng = np.random.default_rng(seed)
-        for it in range(8):  # (the generator of tools/stress_tight.py, wide family)
-            nx, nu = int(rng.integers(5, 17)), int(rng.integers(1, 5))
-            N, mk = int(rng.integers(20, 41)), int(rng.integers(4, 7))
-            w = random_ltv(rng, 8, nx, nu, N, mk, 0.3)
-            w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
+        for it in range(8):  # (the rounds of tools/stress_tight.py wide at STRESS_TIGHT=0.3)
+            w = W.tight_ltv("wide", rng, 8, 0.3)
             raw = solve_mpc_batch(W.to_batch_problem(w))
             torch.cuda.synchronize()
             st = raw.status.cpu().numpy()

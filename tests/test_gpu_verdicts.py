@@ -16,26 +16,21 @@ No kernel's multipliers are read: every expectation comes from the oracle or fro
 With MPCQP_VERDICT_REPORT=<path> a complete run writes the per-route table of profiles/verdicts.txt."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 
+import operand_layouts as OL
+import test_gpu_memory_discipline as MD
+import verdict_cases as VC
+from test_gpu_memory_discipline import Forward, Launch, against_oracle, equal_outputs
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _p in (HERE, os.path.join(os.path.dirname(HERE), "tools")):
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
-
-import operand_layouts as OL  # noqa: E402
-import test_gpu_memory_discipline as MD  # noqa: E402
-import verdict_cases as VC  # noqa: E402
-from test_gpu_memory_discipline import Forward, Launch, against_oracle, equal_outputs  # noqa: E402
 
 F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
 MAX_ITER, INFEASIBLE, NOT_PD = 1, 2, 3

@@ -446,9 +446,7 @@ def test_seeded_start_gives_the_plain_iterations_minimiser(family):
     from qpmpc_amd import workloads as W
 
     if family == "random":
-        import sys, os
-        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-        from stress_stagewise import random_ltv
+        from qpmpc_amd.workloads import random_ltv
 
         rng = np.random.default_rng(77)
         w = random_ltv(rng, 384, 4, 2, 8, 2, 0.2)

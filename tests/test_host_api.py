@@ -271,14 +271,7 @@ def test_hand_written_dpp_instructions_keep_their_wait_states():
     control flow (worst predecessor of every basic block, to a fixpoint), holds EXEC written by a VALU instruction to its five wait
     states, and holds the compiler's own DPP instructions to the same rules: each synthetic case below as a hazard and as its padded
     twin."""
-    import os, sys
-
-    tests = os.path.dirname(os.path.abspath(__file__))
-    tools = os.path.join(os.path.dirname(tests), "tools")
-    for p in (tools, tests):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import check_dpp_hazards as chk
+    import tools.check_dpp_hazards as chk
 
     bad, ndpp, _ = chk.check("f:\n\tv_add_f64 v[0:1], v[2:3], v[4:5]\n\tv_fmac_f64_dpp v[6:7], v[0:1], v[8:9] row_newbcast:3 row_mask:0xf bank_mask:0xf\n")
     assert ndpp == 1 and len(bad) == 1

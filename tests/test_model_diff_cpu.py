@@ -5,19 +5,16 @@ library, host-side checks in their order)."""
 import ctypes as C
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import adjoint_np as AN
+import model_adjoint_np as MN
+import tangent_np as TN
 
-import adjoint_np as AN  # noqa: E402
-import model_adjoint_np as MN  # noqa: E402
-import tangent_np as TN  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 FAMILIES = ("triple", "humanoid", "wip", "mixed")
 _CACHE = {}

@@ -12,19 +12,13 @@
 the same for the inputs of the derivative, shared-model and condensing tests; and the layout list has the coverage its docstring
 claims. The refusals of check_problem() (MPCQP_ELAYOUT) are reached here too: they come before any launch."""
 import itertools
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import operand_layouts as OL  # noqa: E402
+import operand_layouts as OL
 
 
 def test_layout_list_coverage():

@@ -238,10 +238,6 @@ def test_thin_qr_stagewise_restatement_equals_the_certified_fixtures_and_the_lon
 def test_thin_qr_stagewise_restatement_on_nearly_fully_active_problems():
     """Random LTV problems with 4-6 tight rows per step (most of the ~40 variables pinned; the family of tools/stress_tight.py,
     where the explicit-inverse operator of rounds 2-5 lost problems): statuses and plans equal to the dense C oracle's."""
-    import os
-    import sys
-
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     from oracle import stagewise_qr_np as SQ
     from oracle.stagewise_np import StageProblem
 

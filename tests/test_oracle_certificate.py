@@ -14,7 +14,7 @@ from kkt_certificate import certify, tight_narrow, worst
 def test_oracle_solutions_pass_the_kkt_certificate_on_tight_narrow_families(tight):
     """24 rounds of 32 problems per tightness (3072 in all): every item the oracle reports SOLVED passes the certificate -- primal
     feasibility, dual feasibility, complementarity and stationarity in long double, on the NumPy restatement of the build -- and its
-    primal residual agrees with the roll-out of tools/stress_tight.py:row_residuals."""
+    primal residual agrees with the roll-out of qpmpc_amd/workloads.py:row_residuals."""
     certs, solved = [], 0
     for w in tight_narrow(int(100 * tight) + 11, tight, 24, 32):
         U, lam, st, _ = oracle.solve_workload(w)

@@ -6,23 +6,20 @@ import ctypes as C
 import inspect
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import adjoint_model_np as AM
+import adjoint_np as AN
+import tangent_model_np as TM
+import tangent_model_stagewise_np as TMS
+import tangent_np as TN
+from qpmpc_amd import _capi
+from qpmpc_amd import workloads as W
 
-import adjoint_model_np as AM  # noqa: E402
-import adjoint_np as AN  # noqa: E402
-import tangent_model_np as TM  # noqa: E402
-import tangent_model_stagewise_np as TMS  # noqa: E402
-import tangent_np as TN  # noqa: E402
-from qpmpc_amd import _capi  # noqa: E402
-from qpmpc_amd import workloads as W  # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 EXPORTS = ("mpcqp_plan_jvp_model_workspace_bytes", "mpcqp_plan_jvp_model_batch",
            "mpcqp_plan_jvp_model_stagewise_workspace_bytes", "mpcqp_plan_jvp_model_stagewise_batch")
@@ -30,7 +27,7 @@ EINVAL, EDTYPE, EWORKSPACE, EUNSUPPORTED = -1, -3, _capi.EWORKSPACE, -6
 
 
 def _ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 

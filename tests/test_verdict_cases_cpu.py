@@ -12,20 +12,14 @@ routes of tests/operand_layouts.py, on the C oracle:
     under max_iter >= it and MPCQP_MAX_ITER below;
 
 and the shared-model and dense-QP batches: the six good items solved, the three bad ones MPCQP_INFEASIBLE."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import oracle
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import operand_layouts as OL  # noqa: E402
-import verdict_cases as VC  # noqa: E402
+import operand_layouts as OL
+import verdict_cases as VC
 
 CASES = [routes[0] for routes in VC.distinct_cases().values()]
 _INTERIOR = {}

@@ -17,16 +17,9 @@ tests/test_verdict_cases_cpu.py shows on the C oracle that the inputs are what t
 tests/test_gpu_verdicts.py launches them through every forward route."""
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-import operand_layouts as OL  # noqa: E402
+import operand_layouts as OL
 
 INFEASIBLE = (1, 6, 7)
 GOOD = tuple(b for b in range(OL.BATCH) if b not in INFEASIBLE)

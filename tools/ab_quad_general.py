@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))));
 import numpy as np, torch
 from qpmpc_amd import PreparedSolve, workloads as W, _capi
 from ab_quad import time_it
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 
 def one(name, w, batch):
     bp = W.to_batch_problem(w)

@@ -4,10 +4,10 @@ nx = 8, nu = 1, N = 37, mk = 3, rows nearly conflicting, 150+ active-set iterati
 verification rounds end unsolved while the other formulations and the oracle solve them, with the oracle's plans."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, ROOT)
 import numpy as np
 import oracle
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 rng = np.random.default_rng(777)
 for it in range(120):
     nx, nu = int(rng.integers(1, 9)), int(rng.integers(1, 4))

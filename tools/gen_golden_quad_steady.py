@@ -13,7 +13,7 @@ Sets (every launch forced through MPCQP_OPT_FOUR_PER_WAVE):
   lean9        lean build, N = 9 (m = 18: the lanes' second register row is partly populated), 32 problems
   gen12        general build, (4, 1, 12) with state and input rows and a stage cost, 32 problems
   model        shared-model mode, the humanoid model, 32 initial states
-Families: random LTV problems (tools/stress_stagewise.py) with A and C taken from the first step -- bounds generated along that
+Families: random LTV problems (qpmpc_amd/workloads.py: random_ltv) with A and C taken from the first step -- bounds generated along that
 time-invariant system (consistent; tightness 0.05 / 0.2 / 3.0) or along the per-step one (rows no longer consistent with e: the
 inconsistent family of tests/test_gpu_quad.py) --, interleaved so that the four rows of a wavefront differ in kind.
 The generator draws seeds until the recorded outputs of lean16 satisfy conditions() below; the test asserts them again."""
@@ -22,7 +22,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
 
 PATH = os.path.join(ROOT, "tests", "golden", "quad_steady_parent.npz")
@@ -35,7 +34,7 @@ SETS = ("lean16", "lean16_cut5", "lean16_mi5", "lean16_slim", "lean9", "gen12", 
 
 def mixed_family(rng, batch, nx, nu, N, mk, general):
     """`batch` problems, row i of kind i % 4: tight (0.05), loose (3.0), inconsistent and tight (0.05), inconsistent (0.2)"""
-    from stress_stagewise import random_ltv
+    from qpmpc_amd.workloads import random_ltv
 
     w = random_ltv(rng, batch, nx, nu, N, mk, 1.0)
     tight = np.array([0.05, 3.0, 0.05, 0.2])[np.arange(batch) % 4]

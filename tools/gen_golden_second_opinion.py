@@ -2,20 +2,20 @@
 """Writes tests/golden/second_opinion_narrow.npz: one nearly fully active problem (nx <= 4, nu <= 2, n = N nu in 17..128) on which
 the narrow stage-wise kernel alone ends unsolved although the oracle solves it, so mpcqp_build_solve_batch answers SOLVED only through
 its second opinion (the wide kernel behind the narrow one). The problem is item 41 of the stress_tight narrow family at STRESS_TIGHT
-0.05, seed 4012 (tools/stress_tight.py: draw("narrow", default_rng(4012), 64, 0.05)); the narrow kernel alone (a KEEP_FACTOR launch
+0.05, seed 4012 (qpmpc_amd/workloads.py: tight_ltv("narrow", default_rng(4012), 64, 0.05)); the narrow kernel alone (a KEEP_FACTOR launch
 before the second opinion applied to it) ended it MPCQP_MAX_ITER after 796 iterations. Stored with the oracle's plan, multipliers and
 status. CPU only: usage: gen_golden_second_opinion.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 import oracle
-from stress_tight import draw
+from qpmpc_amd.workloads import tight_ltv
 
 SEED, BATCH, TIGHT, ITEM = 4012, 64, 0.05, 41
 
 if __name__ == "__main__":
-    w = draw("narrow", np.random.default_rng(SEED), BATCH, TIGHT)
+    w = tight_ltv("narrow", np.random.default_rng(SEED), BATCH, TIGHT)
     one = {k: (v[ITEM:ITEM + 1].copy() if isinstance(v, np.ndarray) else v) for k, v in w.items()}
     U, lam, st, it = oracle.solve_workload(one)
     assert st[0] == 0, st

@@ -15,7 +15,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)  # (dpp_instantiations imports tools.check_dpp_hazards)
 
 
 def trace_name(name: str) -> str:

@@ -2,10 +2,10 @@
 """Dev probe: a wide system that fits the dense path (nx > 16 or nu > 4, n = N nu <= 256): default dispatch (dense
 large-problem path) against the general stage-wise kernel. usage: probe_dense_vs_general.py nx nu N mk [batch]"""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from qpmpc_amd import solve_mpc_batch, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 nx, nu, N, mk = (int(a) for a in sys.argv[1:5])
 batch = int(sys.argv[5]) if len(sys.argv) > 5 else 512
 dt = torch.float32 if (len(sys.argv) > 6 and sys.argv[6] == "f32") else torch.float64

@@ -2,11 +2,11 @@
 """Dev probe (argument f64 for float64): float32 mid-size problems through the default dispatch (on-chip condensed kernels) and through the stage-wise
 kernel: error vs the float64 oracle and time."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import PreparedSolve, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 rng = np.random.default_rng(5)
 dt = torch.float64 if (len(sys.argv) > 1 and sys.argv[1] == 'f64') else torch.float32
 for (nx, nu, N, mk) in ((3, 4, 32, 2), (2, 3, 46, 3), (4, 4, 39, 3), (3, 3, 43, 8), (8, 2, 20, 4), (6, 1, 40, 2), (12, 4, 16, 4), (8, 1, 37, 3), (5, 2, 8, 2), (3, 1, 16, 2), (6, 3, 5, 3)):

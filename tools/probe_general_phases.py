@@ -2,10 +2,10 @@
 """Dev probe: where a problem of the general stage-wise kernel spends its cycles (MpcqpSolveOpts.probe, csrc/mpcqp_stageg.hip).
 usage: probe_general_phases.py nx nu N mk [batch]"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from qpmpc_amd import solve_mpc_batch, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 nx, nu, N, mk = (int(a) for a in sys.argv[1:5])
 batch = int(sys.argv[5]) if len(sys.argv) > 5 else 512
 rng = np.random.default_rng(7)

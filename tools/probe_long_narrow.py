@@ -1,8 +1,8 @@
 import sys, os
-sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tools"))
+sys.path.insert(0, os.getcwd())
 import numpy as np, torch
 from qpmpc_amd import PreparedSolve, _capi, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 rng = np.random.default_rng(2)
 for (nx, nu, N, mk) in ((4, 1, 160, 1), (3, 1, 200, 2), (4, 2, 100, 2), (2, 1, 256, 2)):
     w = random_ltv(rng, 1024, nx, nu, N, mk, 1.0)

@@ -7,8 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import solve_mpc_batch, workloads as W
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stress_stagewise import random_ltv  # noqa
+from qpmpc_amd.workloads import random_ltv
 
 if __name__ == "__main__":
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 40

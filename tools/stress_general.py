@@ -2,11 +2,11 @@
 """Dev stress run: random wide LTV systems (17 <= nx <= 32 or 5 <= nu <= 8) through the default dispatch -- the general stage-wise
 kernel for every nx > 16 -- against the C oracle: statuses must agree, plans within 1e-7 relative. usage: stress_general.py [rounds] [batch]"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import solve_mpc_batch, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 
 def run(rounds, batch, seed, verbose=True):
     rng = np.random.default_rng(seed)

@@ -10,8 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import solve_mpc_batch, _capi, workloads as W
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from stress_stagewise import random_ltv  # noqa
+from qpmpc_amd.workloads import random_ltv
 
 
 def run(rounds, batch, seed=4242, verbose=True, lean_only=False, flags_lean=0, flags_other=0):

@@ -6,11 +6,11 @@ without a stage cost, time-invariant or per-step operands, loose to very tight b
 usage: stress_quad_general.py [rounds] [batch]   (STRESS_SEED; STRESS_ROWS64=1: also problems of 33 .. 64 rows, the four-rows-per-lane
 copy of the kernel in csrc/mpcqp_quadg.hip)"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import solve_mpc_batch, _capi, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import random_ltv
 
 
 def run(rounds, batch, seed, verbose=True):

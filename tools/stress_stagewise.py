@@ -5,21 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from qpmpc_amd import solve_mpc_batch, _capi, workloads as W
-
-def random_ltv(rng, B, nx, nu, N, mk, tight):
-    A = np.eye(nx) + 0.08 * rng.standard_normal((B, N, nx, nx))
-    Bm = rng.standard_normal((B, N, nx, nu))
-    Cm = rng.standard_normal((B, N, mk, nx))
-    D = rng.standard_normal((B, N, mk, nu))
-    x0 = 0.1 * rng.standard_normal((B, nx))
-    e = np.zeros((B, N, mk))
-    for b in range(B):
-        x = x0[b].copy()
-        for k in range(N):
-            e[b, k] = Cm[b, k] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
-            x = A[b, k] @ x
-    return dict(A=A, B=Bm, C=Cm, D=D, e=e, N=N, wt=2.0, wx=0.5, wu=1e-2, x0=x0,
-                goal=rng.standard_normal((B, nx)), targets=rng.standard_normal((B, N * nx)))
+from qpmpc_amd.workloads import random_ltv  # bench.py imports the family from this module by this name
 
 if __name__ == "__main__":
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20

@@ -5,55 +5,20 @@ kernels. usage: stress_tight.py [narrow|wide|widef|general] [rounds] [batch] (wi
 MPCQP_MAX_ITER go through the other formulations of the solver, retry_unsolved=True); STRESS_FORMULATION=stagewise: through
 mpcqp_stagewise_solve_batch (the narrow kernel where it applies, the wide one behind it) instead of the default entry point"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
 from qpmpc_amd import solve_mpc_batch, workloads as W
-from stress_stagewise import random_ltv
+from qpmpc_amd.workloads import row_residuals
 
-
-def row_residuals(w, b, U):
-    """G u - h of problem b of a random_ltv workload at the inputs U (<= 0: feasible, 0: on the bound), by a roll-out in extended
-    precision: a check that needs no solver."""
-    LD = np.longdouble
-    A, B, C, D, e, x0 = (np.asarray(w[k]) for k in ("A", "B", "C", "D", "e", "x0"))
-    N, nu = A.shape[1], B.shape[-1]
-    x, u, out = x0[b].astype(LD), np.asarray(U).reshape(N, nu).astype(LD), []
-    for k in range(N):
-        out.append(C[b, k].astype(LD) @ x + D[b, k].astype(LD) @ u[k] - e[b, k].astype(LD))
-        x = A[b, k].astype(LD) @ x + B[b, k].astype(LD) @ u[k]
-    return np.concatenate(out)
-
-
-def draw(kind, rng, batch, tight):
-    """One round's workload of family ``kind`` at tightness ``tight`` (STRESS_TIGHT): the dimensions, then random_ltv's problems
-    (shared by run() and the tests that replay these families through other launch modes; the draws stay in this order)."""
-    if kind == "narrow":
-        nx, nu = int(rng.integers(2, 5)), int(rng.integers(1, 3))
-    elif kind in ("wide", "widef"):
-        nx, nu = int(rng.integers(5, 17)), int(rng.integers(1, 5))
-    else:
-        nx, nu = int(rng.integers(17, 33)), int(rng.integers(1, 9))
-    N = int(rng.integers(20, 41)); mk = int(rng.integers(4, 7))
-    if kind == "widef":  # constraint matrices FIXED along the horizon, 4 / 8 / 12 / 16 rows per step: the wide kernel's layout in
-        mk = 4 * int(rng.integers(1, 5))  # which the forward sweep forms the rows itself (config 5's)
-    w = random_ltv(rng, batch, nx, nu, N, mk, tight)  # (smaller: tighter rows, more of them active)
-    w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
-    if kind == "widef":
-        w["C"], w["D"] = w["C"][:, :1].copy(), w["D"][:, :1].copy()
-        for b in range(batch):  # bounds around the free response, as random_ltv makes them (with the fixed C)
-            x = w["x0"][b].copy()
-            for k in range(N):
-                w["e"][b, k] = w["C"][b, 0] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
-                x = w["A"][b, k] @ x
-    return w
+draw = W.tight_ltv  # the name this family had here: callers that import it from this module keep working
 
 
 def run(kind, rounds, batch, seed, verbose=True):
     rng = np.random.default_rng(seed)
     worst, bad = 0.0, 0
     for it in range(rounds):
-        w = draw(kind, rng, batch, float(os.environ.get("STRESS_TIGHT", "0.5")))
+        w = W.tight_ltv(kind, rng, batch, float(os.environ.get("STRESS_TIGHT", "0.5")))
         nx, nu, N, mk = w["A"].shape[-1], w["B"].shape[-1], int(w["N"]), w["e"].shape[-1]
         kw = {}
         if os.environ.get("STRESS_FORMULATION") == "stagewise":  # (mpcqp_stagewise_solve_batch instead of the default entry point)
