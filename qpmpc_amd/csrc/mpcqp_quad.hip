@@ -31,8 +31,11 @@
 //     to the trailing columns of P, of the two rows of G, of the identity row (-> L^-T) -- four independent FMA streams on
 //     the same DPP broadcasts -- and to q (-> w = L^-1 q, component k in lane k).
 //   * Plain trips (nearly all) run in a steady loop of one basic block (mpcqp_quad_steady.h) in front of the general loop, which serves
-//     every kind of trip. The update vector (z, or T_l of a leaving slot: component k in lane k) is applied by DPP row broadcasts at the
-//     top of the next trip; the rare parts (|K_p|^2 near dependence, ratio test, drop pass) sit behind wavefront-uniform ballots.
+//     every kind of trip. A trip that is not plain is made ONCE: the steady loop leaves with what it computed of it, the general loop
+//     finishes it. A partial step removes its blocking slot in the same trip (the removal is that trip's rank-one update), and the
+//     wavefront is back in the steady loop as soon as none of its live rows holds a constraint it still has to add.
+//     The update vector (z, or T_l of a leaving slot: component k in lane k) is applied by DPP row broadcasts at the
+//     top of the next trip; the rare parts (|K_p|^2 near dependence, ratio test, drop) sit behind wavefront-uniform ballots.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -99,7 +102,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     constexpr int GS = 33;  // the G image is stored by COLUMN with an odd stride
     T *Gimg = sm + CV::OFF_M, *Ml = sm + CV::OFF_M;
     T *LTp = sm + CV::OFF_LT + (l * (31 - l)) / 2 - (l + 1);  // slim: LTp[k] = entry (l, k) of L^-T, k > l
-    T *LTimg = sm + CV::OFF_LT, *Timg = sm + CV::OFF_T, *kAv = sm + CV::OFF_KA;  // roomy
+    T *LTimg = sm + CV::OFF_LT, *Timg = sm + CV::OFF_T;  // roomy (OFF_KA, the row of a leaving slot, is no longer used by this kernel)
     int *actv = reinterpret_cast<int *>(sm + CV::OFF_ACT);
 
     // optional phase timestamps (developer probe, MpcqpSolveOpts.probe): long long[16] per problem, slots as mpcqp_pair.hip
@@ -548,9 +551,9 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     bool e0 = sel0, e1 = sel1;  // this lane's constraints may be selected: they have a bound and are not active (the slack of an
                                 // active row is never read: it stays whatever the steps make of it, zero up to rounding)
     // row-uniform state
-    int nq = 0, p = 0, ldrop = 0;
+    int nq = 0, p = 0;
     unsigned mask = 0;  // occupied slots
-    bool needp = true, dropping = false;
+    bool needp = true;
     T up = T(0);
     int fails = 0;
     // ---- selection, for the rows that start a new constraint (straight-line selects: no divergent branches), and the
@@ -560,7 +563,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     auto select = [&]() {
         // a violated row's scaled slack is negative: the order of the magnitudes is the order of the high words, so
         // the most violated row has the smallest complement
-        const bool want = needp & !done & !dropping;
+        const bool want = needp & !done;
         const unsigned h0 = ~(unsigned)__double2hiint(s0 * invn0), h1 = ~(unsigned)__double2hiint(s1 * invn1);
         const bool v0 = want & e0 & (s0 < -tolh0), v1 = want & e1 & (s1 < -tolh1);
         const unsigned k0 = v0 ? ((h0 & ~31u) | (unsigned)row0) : 0xffffffffu;
@@ -589,41 +592,19 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
     // pending rank-one update R += c v, applied at the top of the next trip -- the ONE site that writes the register rows,
     // selects and fetches
     T zn = T(0), cT = T(0), cH = T(0);
+    T hd, kd0, kd1, inv, t2, rd;  // the general loop's trip in flight (-z_l, -M_i . z, 1/|z|^2, t2, r_a): handed over by the steady loop
     wave_sync();
     tick(4);
     for (;;) {
 #include "mpcqp_quad_steady.h"  // (a fragment of this body) the steady loop: plain trips in one basic block; defines `general`
-        if (general) for (;;) {  // ===== active-set loop: every kind of trip
-            // ---- the previous trip's rank-one update  T_a += (r_a/d2) z, T_new = -z/d2 ; H -= z z'/d2  (or the same with a
-            //      leaving slot's T_l), wrapped around this trip's selection and row fetch, which only read the slacks
-            dpp_ready(zn);
-            update(ic<0>{}, ic<USPLIT>{}, zn, cT, cH);
-            select();
-            ld16(mp, Ml + p * LDM);
-            update(ic<USPLIT>{}, ic<NV>{}, zn, cT, cH);
-            cT = cH = T(0);
-            if (__ballot(!done) == 0ull) break;
-            const bool st = !done & !dropping;  // this row steps
-            const bool drp = !done & dropping;  // ... or drops a slot
-            const bool phi = p >= NV;           // (row-uniform)
+        // (the two loops alternate inside one pass of this outer loop: `resume` sends the wavefront back to the steady loop's entry;
+        // the refinement and the acceptance test below are reached only when every row is done)
+        bool resume = false;
+        if (general) for (;;) {  // ===== general loop: every kind of trip. Entered, and re-entered from its own tail, with a trip that is
+            //                         updated, selected and measured: hd = -z_l, kd = -M_i . z, inv = 1/|z|^2, t2, rd = r_a
+            const bool st = !done;     // this row steps
+            const bool phi = p >= NV;  // (row-uniform)
             const int pl = p & 15;
-            // ---- r_a = T_a . M_p ; -z_l = H_l . M_p ; then -M_i . z = sum_k M_i[k] (-z_k) for this lane's two rows, with -z
-            //      spread over the row: the projected rows K_i = H M_i of mpcqp_pair.hip are NOT maintained (32 FMAs of update
-            //      and 32 of dot products per trip against the 32 of these two)
-            const T hd = dot16(RH, mp);
-            const T kd0 = dot_bcast(hd, RM0, T(0)), kd1 = dot_bcast(hd, RM1, T(0));
-            // ---- step length, by lane p from its own row: |z|^2 = -M_p . z (trusted well away from dependence, DEP_FAST),
-            //      1/|z|^2, t2 = -s_p/|z|^2; the two results go to the row (inv = -1: too close to dependence)
-            T inv, t2;
-            {
-                const T kp = phi ? kd1 : kd0, sq = phi ? s1 : s0, iq = phi ? invn1 : invn0;
-                const bool okf = kp * iq * iq > T(DEP_FAST);
-                const T iv = fast_rcp(kp);
-                inv = row_get(okf ? iv : T(-1), rb, pl);
-                t2 = row_get(-sq * iv, rb, pl);
-            }
-            T rd = dot16(RT, mp);  // (while the exchange is in flight)
-            pin(rd);
             if (__ballot(st & !(inv > T(0))) != 0ull) {  // rare: |z|^2 as a sum of squares, robust near dependence
                 T z2 = hd * hd;
                 z2 += dpp_mov<ROR8>(z2);
@@ -645,7 +626,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
             const T r = (occ & st) ? rd : T(0);
             // a blocking multiplier exists iff lam_a / r_a < t2 for some slot
             const bool blk = (r > T(0)) & (lam < t2 * r);
-            if (__ballot(drp | (st & (!can_move | (iters >= max_iter) | blk))) == 0ull) {
+            if (__ballot(st & (!can_move | (iters >= max_iter) | blk)) == 0ull) {
                 // ---- PLAIN TRIP: every row still in the loop takes a full step. Coefficients of the (deferred) update with
                 //      -z: slot sl takes -z/d2, the occupied slots r_a/d2, H row l -z_l/d2
                 const T tt = st ? t2 : T(0);
@@ -666,123 +647,142 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                 mask |= st ? (1u << sl) : 0u;
                 nq += st ? 1 : 0;
                 needp = needp | st;
-                continue;
-            }
-            // ---- GENERAL TRIP: limits, partial steps, drops
-            bool stepping = st;
-            {
-                const bool lim = stepping & (iters >= max_iter);
-                done = done | lim;
-                finished = finished | lim;
-                status = lim ? (int)MPCQP_MAX_ITER : status;
-                stepping = stepping & !lim;
-            }
-            iters += stepping ? 1 : 0;
-            const bool cand = occ & stepping & (r > T(0));
-            T t1 = INF;
-            int lq = 0;
-            const unsigned long long bl = __ballot(stepping & blk);
-            if (bl != 0ull) {  // ratio test on the multipliers
-                const T ratio = cand ? lam * fast_rcp(r) : INF;
-                unsigned hi, lo;
-                ordered(ratio, hi, lo);
-                hi = cand ? hi : 0xffffffffu;
-                const unsigned mhi = row_min(hi);
-                const unsigned k2 = (cand && hi == mhi) ? ((lo & ~31u) | (unsigned)l) : 0xffffffffu;
-                const unsigned ml = row_min(k2);
-                lq = (int)(ml & 15u);
-                const T tl1 = row_get(ratio, rb, lq);
-                // (only for the rows that are blocked: a row's result must not depend on what its wavefront's other rows need)
-                const bool blocked = ((unsigned)(bl >> rb) & 0xffffu) != 0u;
-                t1 = (blocked && mhi != 0xffffffffu) ? tl1 : INF;
-            }
-            T t = t1 < t2 ? t1 : t2;
-            {
-                const bool inf = stepping & !(t < INF);  // no step possible: the constraints are inconsistent
-                done = done | inf;
-                finished = finished | inf;
-                status = inf ? (int)MPCQP_INFEASIBLE : status;
-                stepping = stepping & !inf;
-            }
-            t = stepping ? t : T(0);
-            const bool full = stepping & (t2 <= t1);
-            zn = hd;
-            cT = full ? ((l == sl) ? inv : -(r * inv)) : T(0);
-            cH = full ? -(hd * inv) : T(0);
-            if (__ballot(drp) != 0ull) {
-                // slot ldrop leaves (its row T_l still sits in lane ldrop -- a partial step has no update of its own --, roomy: and in kAv).
-                // With W = T T' implicit, T_a -= (T_a . T_l / T_l . T_l) T_l
-                // (row l becomes exactly zero); the null space of the active rows gains the direction T_l:
-                // H += T_l T_l' / T_l . T_l.
-                T vv[NV];
-                T vl = T(0);
-                if constexpr (SLIM) {
+            } else {
+                // ---- GENERAL TRIP: limits, partial steps, drops
+                bool stepping = st;
+                {
+                    const bool lim = stepping & (iters >= max_iter);
+                    done = done | lim;
+                    finished = finished | lim;
+                    status = lim ? (int)MPCQP_MAX_ITER : status;
+                    stepping = stepping & !lim;
+                }
+                iters += stepping ? 1 : 0;
+                const bool cand = occ & stepping & (r > T(0));
+                T t1 = INF;
+                int lq = 0;
+                const unsigned long long bl = __ballot(stepping & blk);
+                if (bl != 0ull) {  // ratio test on the multipliers
+                    const T ratio = cand ? lam * fast_rcp(r) : INF;
+                    unsigned hi, lo;
+                    ordered(ratio, hi, lo);
+                    hi = cand ? hi : 0xffffffffu;
+                    const unsigned mhi = row_min(hi);
+                    const unsigned k2 = (cand && hi == mhi) ? ((lo & ~31u) | (unsigned)l) : 0xffffffffu;
+                    const unsigned ml = row_min(k2);
+                    lq = (int)(ml & 15u);
+                    const T tl1 = row_get(ratio, rb, lq);
+                    // (only for the rows that are blocked: a row's result must not depend on what its wavefront's other rows need)
+                    const bool blocked = ((unsigned)(bl >> rb) & 0xffffu) != 0u;
+                    t1 = (blocked && mhi != 0xffffffffu) ? tl1 : INF;
+                }
+                T t = t1 < t2 ? t1 : t2;
+                {
+                    const bool inf = stepping & !(t < INF);  // no step possible: the constraints are inconsistent
+                    done = done | inf;
+                    finished = finished | inf;
+                    status = inf ? (int)MPCQP_INFEASIBLE : status;
+                    stepping = stepping & !inf;
+                }
+                t = stepping ? t : T(0);
+                const bool full = stepping & (t2 <= t1);
+                zn = hd;
+                cT = full ? ((l == sl) ? inv : -(r * inv)) : T(0);
+                cH = full ? -(hd * inv) : T(0);
+                // ---- bookkeeping: the implied primal point moved by t z: s_i -= t M_i . z
+                if (stepping) {
+                    s0 = fma(t, kd0, s0);
+                    s1 = fma(t, kd1, s1);
+                    lam -= t * r;
+                    lam = (occ && lam < T(0)) ? T(0) : lam;
+                    up += t;
+                }
+                if (full) {  // p takes slot sl
+                    if (l == sl) {
+                        lam = up;
+                        myact = p;
+                        occ = true;
+                    }
+                    if (l == pl) {
+                        e0 = e0 & phi;
+                        e1 = e1 & !phi;
+                    }
+                    mask |= 1u << sl;
+                    ++nq;
+                    needp = true;
+                }
+                const bool partial = stepping & !full;
+                if (__ballot(partial) != 0ull) {
+                    // partial step: slot lq leaves in this very trip. Its row T_l sits in lane lq and is current -- a row that takes a
+                    // partial step has no update pending, and none of its own: the slot's removal IS this trip's update. With W = T T'
+                    // implicit, T_a -= (T_a . T_l / T_l . T_l) T_l (row l becomes exactly zero); the null space of the active rows
+                    // gains the direction T_l: H += T_l T_l' / T_l . T_l. The row keeps its p and steps again in the next trip.
+                    const int cl = row_get(myact, rb, lq);
+                    // T_a . T_l as dot16 sums it (four chains, column k in chain k % 4), four columns of T_l at a time, each fetched from
+                    // lane lq: the row is never held as a whole -- 32 registers this loop does not have (nor an image of it in LDS: the
+                    // masked stores of lane lq cost the roomy instantiations their budget of 256 registers)
+                    T vl = T(0), ac[4] = {T(0), T(0), T(0), T(0)};
+                    static_for<0, NV / 4>([&](auto cc) {
+                        constexpr int k = 4 * decltype(cc)::value;
+                        T v[4];
 #pragma unroll
-                    for (int k = 0; k < NV; ++k) {  // (fetched from its lane: a rare trip, and LDS has no room for the row)
-                        vv[k] = row_get(RT[k], rb, ldrop);
-                        vl = (l == k) ? vv[k] : vl;
-                    }
-                } else {
-                    ld16(vv, kAv);
-                    vl = kAv[l];
-                }
-                const T tl = dot16(RT, vv);
-                const T tld = row_get(tl, rb, ldrop);
-                const T itl = fast_rcp(tld);
-                if (drp) {
-                    zn = vl;
-                    cT = (l == ldrop) ? T(-1) : (occ ? -tl * itl : T(0));
-                    cH = vl * itl;
-                    if (l == ldrop) {
-                        lam = T(0);
-                        occ = false;
-                    }
-                    mask &= ~(1u << ldrop);
-                    --nq;
-                    dropping = false;
-                }
-            }
-            // ---- bookkeeping: the implied primal point moved by t z: s_i -= t M_i . z
-            if (stepping) {
-                s0 = fma(t, kd0, s0);
-                s1 = fma(t, kd1, s1);
-                lam -= t * r;
-                lam = (occ && lam < T(0)) ? T(0) : lam;
-                up += t;
-            }
-            if (full) {  // p takes slot sl
-                if (l == sl) {
-                    lam = up;
-                    myact = p;
-                    occ = true;
-                }
-                if (l == pl) {
-                    e0 = e0 & phi;
-                    e1 = e1 & !phi;
-                }
-                mask |= 1u << sl;
-                ++nq;
-                needp = true;
-            }
-            const bool partial = stepping & !full;
-            if (__ballot(partial) != 0ull) {
-                // partial step: the next trip removes slot lq from T (no update is pending for this row: RT is current)
-                const int cl = row_get(myact, rb, lq);
-                if constexpr (!SLIM) {
-                    wave_sync();
-                    if (partial && l == lq) st16(kAv, RT);
-                }
-                if (partial) {
-                    if (l == (cl & 15)) {  // the row that leaves may be selected again
+                        for (int j = 0; j < 4; ++j) {
+                            v[j] = row_get(RT[k + j], rb, lq);
+                            vl = (l == k + j) ? v[j] : vl;
+                        }
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) ac[j] = fma(RT[k + j], v[j], ac[j]);
+                        pin(ac[3]);
+                    });
+                    const T tl = (ac[0] + ac[1]) + (ac[2] + ac[3]);
+                    const T tld = row_get(tl, rb, lq);
+                    const T itl = fast_rcp(tld);
+                    if (partial && l == (cl & 15)) {  // the row that leaves may be selected again
                         e0 = (cl < NV) ? sel0 : e0;
                         e1 = (cl < NV) ? e1 : sel1;
                     }
-                    dropping = true;
-                    ldrop = lq;
+                    zn = partial ? vl : zn;
+                    cT = partial ? ((l == lq) ? T(-1) : (occ ? -tl * itl : T(0))) : cT;
+                    cH = partial ? vl * itl : cH;
+                    lam = (partial & (l == lq)) ? T(0) : lam;
+                    occ = occ & !(partial & (l == lq));
+                    mask &= partial ? ~(1u << lq) : ~0u;
+                    nq -= partial ? 1 : 0;
                 }
-                if constexpr (!SLIM) wave_sync();
             }
+            // ---- back to the steady loop when no live row holds a p (its entry state; its first update applies zn, cT, cH) -- also
+            //      when every row is done: it ends at once and skips this loop
+            if (__ballot(!done & !needp) == 0ull) {
+                resume = true;
+                break;
+            }
+            // ---- the next trip. The rank-one update  T_a += (r_a/d2) z, T_new = -z/d2 ; H -= z z'/d2  (or the same with a leaving
+            //      slot's T_l), wrapped around the selection and row fetch, which only read the slacks
+            dpp_ready(zn);
+            update(ic<0>{}, ic<USPLIT>{}, zn, cT, cH);
+            select();
+            ld16(mp, Ml + p * LDM);
+            update(ic<USPLIT>{}, ic<NV>{}, zn, cT, cH);
+            cT = cH = T(0);
+            // ---- r_a = T_a . M_p ; -z_l = H_l . M_p ; then -M_i . z = sum_k M_i[k] (-z_k) for this lane's two rows, with -z
+            //      spread over the row: the projected rows K_i = H M_i of mpcqp_pair.hip are NOT maintained (32 FMAs of update
+            //      and 32 of dot products per trip against the 32 of these two)
+            hd = dot16(RH, mp);
+            kd0 = dot_bcast(hd, RM0, T(0)), kd1 = dot_bcast(hd, RM1, T(0));
+            // ---- step length, by lane p from its own row: |z|^2 = -M_p . z (trusted well away from dependence, DEP_FAST),
+            //      1/|z|^2, t2 = -s_p/|z|^2; the two results go to the row (inv = -1: too close to dependence)
+            {
+                const bool hi = p >= NV;
+                const T kp = hi ? kd1 : kd0, sq = hi ? s1 : s0, iq = hi ? invn1 : invn0;
+                const bool okf = kp * iq * iq > T(DEP_FAST);
+                const T iv = fast_rcp(kp);
+                inv = row_get(okf ? iv : T(-1), rb, p & 15);
+                t2 = row_get(-sq * iv, rb, p & 15);
+            }
+            rd = dot16(RT, mp);  // (while the exchange is in flight)
+            pin(rd);
         }
+        if (resume) continue;
         tick(5);
         if (__ballot(!finished) == 0ull) break;
         // ================================== multipliers by refinement, slacks re-evaluated

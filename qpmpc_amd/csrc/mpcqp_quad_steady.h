@@ -1,16 +1,17 @@
 // mpcqp_quad_steady.h -- the STEADY LOOP of mpcqp_quad_kernel (mpcqp_quad.hip): a fragment of that kernel's body, included once at the
 // top of its outer loop, in front of the general active-set loop. It is no header in the usual sense: it reads and writes the kernel's
-// local state (RT, RH, RM0, RM1, s0, s1, lam, myact, occ, e0, e1, mask, nq, iters, zn, cT, cH, done, status, p, up, needp) and defines
-// `general`, false when every row finished here and the general loop has nothing to do. It sits in a file of its own so that the
-// kernel file keeps its line numbers (tests/dpp_instantiations.py names the launch lines of every instantiation).
+// local state (RT, RH, RM0, RM1, s0, s1, lam, myact, occ, e0, e1, mask, nq, iters, zn, cT, cH, done, status, p, up, needp; hd, kd0, kd1,
+// inv, t2, rd of the trip it leaves with) and defines `general`, false when every row finished here and the general loop has nothing to
+// do. It sits in a file of its own so that the kernel file keeps its line numbers (tests/dpp_instantiations.py names the launch lines
+// of every instantiation).
 //
 // Nearly every trip is a plain one -- every row still in the loop selects a constraint and takes the full step, no multiplier
 // blocks (config 2: 10.75 iterations per problem, 10.75 rows active at the optimum). Those trips run here, in a loop of one
-// basic block that carries only what a plain trip changes; the flags stay lane masks. Here no row is dropping and every row
-// that is not done needs a new constraint (true at the kernel's start and after a failed acceptance; kept by every plain trip).
+// basic block that carries only what a plain trip changes; the flags stay lane masks. Here every row that is not done needs a new
+// constraint (true at the kernel's start, after a failed acceptance and whenever the general loop hands back; kept by every plain trip).
 // The first trip that is not plain -- near dependence, a step that cannot be taken, the iteration limit, a blocking multiplier --
-// leaves WITHOUT its bookkeeping: the general loop behind this one makes the same trip again (its entry update has zero coefficients, its
-// selection keeps p) and stays in charge until every row is done. Same operations in the same order as its plain arm.
+// leaves WITHOUT its bookkeeping: the general loop behind this one FINISHES that trip from hd, kd0, kd1, inv, t2, rd, which are what it
+// would compute itself, and comes back here as soon as no live row holds a p. Same operations in the same order as its plain arm.
 bool general = true;
 {
     const int iters_in = iters;
@@ -42,8 +43,7 @@ bool general = true;
         }
         const bool phi = p >= NV;  // (row-uniform)
         const int pl = p & 15;
-        T hd = dot16(RH, mp);
-        T kd0, kd1;
+        hd = dot16(RH, mp);
         {  // dot_bcast(hd, RM0, 0), dot_bcast(hd, RM1, 0) on ONE pinned copy of hd: each sum's chains in their own order
             T a0 = T(0), a1 = T(0), b0 = T(0), b1 = T(0);
             dpp_ready(hd);
@@ -57,7 +57,6 @@ bool general = true;
             kd0 = a0 + a1;
             kd1 = b0 + b1;
         }
-        T inv, t2;
         {
             const T kp = phi ? kd1 : kd0, sq = phi ? s1 : s0, iq = phi ? invn1 : invn0;
             const bool okf = kp * iq * iq > T(DEP_FAST);
@@ -65,13 +64,13 @@ bool general = true;
             inv = row_get(okf ? iv : T(-1), rb, pl);
             t2 = row_get(-sq * iv, rb, pl);
         }
-        T rd = dot16(RT, mp);  // (while the exchange is in flight)
+        rd = dot16(RT, mp);  // (while the exchange is in flight)
         pin(rd);
         const bool can_move = (nq < n) & (inv > T(0));  // (inv <= 0: near dependence, the general loop's sum of squares)
         const int sl = (int)__builtin_ctz(~mask);  // lowest free slot
         const T r = (occ & st) ? rd : T(0);
         const bool blk = (r > T(0)) & (lam < t2 * r);
-        if (maskof(st & (!can_move | (iters >= max_iter) | blk)) != 0ull) break;
+        if (maskof(st & (!can_move | (iters >= max_iter) | blk)) != 0ull) break;  // not plain: the general loop finishes THIS trip
         // ---- the plain trip's bookkeeping (a row that is done: zero coefficients, nothing changes)
         inv = st ? inv : T(0);
         const T tt = st ? t2 : T(0);

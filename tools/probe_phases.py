@@ -40,3 +40,15 @@ if not one:
     print(f"  real time (100 MHz): first start -> last end {(en.max()-st.min()).item()/100:.2f} us ; wavefront mean {(en-st).mean().item()/100:.2f} us max {(en-st).max().item()/100:.2f} us")
     print("    starts after the first (50/90/99/100 %, us):", [round(v / 100, 2) for v in torch.quantile(st - st.min(), q).tolist()],
           "; ends before the last:", [round(v / 100, 2) for v in torch.quantile(en.max() - en, q).tolist()])
+if not one and "--wavefronts" in sys.argv:
+    # the slowest wavefronts by active-set cycles: wavefront, its active-set cycles, its total, when it ended after the launch's first
+    # start and how long before the launch's last end (100 MHz clock), the iterations of its four rows
+    top = int(sys.argv[sys.argv.index("--wavefronts") + 1])
+    wf = torch.arange(0, batch, 4)
+    act, tot, endt = d[wf, 4], (t[wf, 6] - t[wf, 0]), en[wf]
+    print(f"  slowest {top} wavefronts by active-set cycles (of {len(wf)}; wavefront, active set, total, end after first start us, before last end us, iterations):")
+    for i in torch.argsort(act, descending=True)[:top].tolist():
+        print(f"    {i:5d} {act[i].item():8.0f} {tot[i].item():8.0f} {(endt[i] - st.min()).item() / 100:7.2f} {(en.max() - endt[i]).item() / 100:6.2f}  "
+              f"{[int(v) for v in it[4 * i:4 * i + 4].tolist()]}")
+    hist = torch.bincount((act / 500).round().long())
+    print("  active-set cycles per wavefront, histogram in bins of 500:", {int(500 * k): int(c) for k, c in enumerate(hist.tolist()) if c})
