@@ -216,7 +216,9 @@ typedef struct MpcqpSolveOpts {
                          iters[b] is then its count). */
     int32_t flags;    /* MPCQP_OPT_* (0 = automatic dispatch)                    */
     double feas_tol;  /* a row is violated when (h_i-G_i u)/(1+|h_i|) < -tol;
-                         <=0 -> 1e-12 (f64) / 1e-5 (f32)                         */
+                         <=0 -> 1e-12 (f64) / 1e-5 (f32). The float32 dense condensed
+                         kernels divide by |G_i|+|h_i| instead (Euclidean row norm):
+                         the same verdict whatever units the row is stated in      */
     /* Warm start for receding-horizon loops (the reference reaches its backends' warm start through
      * **kwargs -> qpsolvers' initvals, qpmpc/solve_mpc.py:20,43; loops at
      * examples/wheeled_inverted_pendulum.py:99-118, examples/lipm_walking_controller.py:307-335).

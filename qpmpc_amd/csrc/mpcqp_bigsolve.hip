@@ -644,7 +644,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
     const int npad = MID ? ((n + 15) & ~15) : n;  // mid-size kind: triangle padded to 16-row blocks (identity rows)
     T *sv = Li + npad * (npad + 1) / 2;  // slacks            [m]
     T *gin = sv + m;                    // 1 / |G_i|          [m]
-    T *tolv = gin + m;                  // tol (1 + |h_i|)    [m]
+    T *tolv = gin + m;                  // row_tol: tol (1 + |h_i|), float32 dense / structured kind tol (|G_i| + |h_i|)  [m]
     T *y0 = tolv + m;                   // -L^-1 q            [n]
     T *mp = y0 + n;                     // M_p                [n]
     T *zv = mp + n;                     // z (y coordinates)  [n]
@@ -1149,7 +1149,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                     const T hi = h[i];
                     sv[i] = hi - struct_row(j);
                     gin[i] = nrm[i];
-                    tolv[i] = (hi < T(1e29)) ? tol + tol * fabs(hi) : INF;
+                    tolv[i] = (hi < T(1e29)) ? row_tol(tol, T(1) / gin[i], hi) : INF;
                     pos[i] = -1;
                 }
             }
@@ -1170,7 +1170,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                         const T hi = h[i];
                         sv[i] = hi - a[c];
                         gin[i] = (nn[c] > T(0)) ? T(1) / sqrt(nn[c]) : T(1);
-                        tolv[i] = (hi < T(1e29)) ? tol + tol * fabs(hi) : INF;  // padded rows are never selected
+                        tolv[i] = (hi < T(1e29)) ? row_tol(tol, T(1) / gin[i], hi) : INF;  // padded rows are never selected
                         pos[i] = -1;
                     }
                 }
@@ -1185,7 +1185,7 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                     const T hi = h[i];
                     sv[i] = hi - a;
                     gin[i] = (nn > T(0)) ? T(1) / sqrt(nn) : T(1);
-                    tolv[i] = (hi < T(1e29)) ? tol + tol * fabs(hi) : INF;
+                    tolv[i] = (hi < T(1e29)) ? row_tol(tol, T(1) / gin[i], hi) : INF;
                     pos[i] = -1;
                 }
             }
@@ -1528,7 +1528,8 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
             // back 'solved' with |u| ~ 2e6 and rows violated by 6e6 -- and then the active rows are far off.
             if (status == MPCQP_SOLVED) {
                 // |residual| <= (1 + |h_i|) max(1e3 tol, 1e-6): the contract's 1e-6 in float64 (no refinement step here: an
-                // ill-conditioned but legitimate plan leaves ~1e-8), 1e-2 in float32
+                // ill-conditioned but legitimate plan leaves ~1e-8); float32: 1e-2 (|G_i| + |h_i|), relative to the row like
+                // its admission (row_tol, mpcqp_internal.h)
                 const T kacc = T(1000) > T(1e-6) / tol ? T(1000) : T(1e-6) / tol;
                 bool bad = false;
                 if constexpr (MID) {

@@ -13,6 +13,21 @@ enum { MODE_FUSED = 0, MODE_CONDENSE = 1, MODE_SOLVE = 2, MODE_MODEL = 3 };
 
 constexpr size_t kLdsBytesPerCU = 160 * 1024;  // gfx950: 160 KiB per CU
 
+// Feasibility tolerance of row i of the dense condensed kernels (mpcqp_bigsolve.hip dense and structured kinds, mpcqp_lds.hip
+// without a prefactored model): the row counts as violated below -row_tol, its refinement and acceptance bounds are multiples
+// of it. float64: tol (1 + |h_i|) with tol = 1e-12 -- the absolute term is far below every bound in any units. float32
+// (tol = 1e-5): tol (|G_i| + |h_i|), which scales with the row, so a row stated in other units (r G_i u <= r h_i) is admitted,
+// refined and accepted at the same distance |G_i u - h_i| / |G_i| from its hyperplane; with the absolute term a row stated
+// 2^-10 times smaller stayed violated by 1e-2 in the caller's units and plans came back 'solved' 4.6e-3 off.
+template <typename T>
+__device__ __forceinline__ T row_tol(T tol, T gnorm, T hi)
+{
+    if constexpr (sizeof(T) == 4)
+        return tol * (gnorm + (T)fabs(hi));
+    else
+        return tol + tol * (T)fabs(hi);
+}
+
 // SIMDs of the device that is current for this call (4 per compute unit). Asked per call: the library keeps no state between
 // calls (include/mpcqp.h), and a process may drive several devices. 0 when the runtime cannot tell.
 inline int device_simds_now()

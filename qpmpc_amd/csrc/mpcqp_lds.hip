@@ -240,6 +240,15 @@ __device__ __forceinline__ void solve_phase(const Layout &L, T *sm, int n, int m
     T *redv = sm + L.off_red;
     int *act = (int *)(sm + L.off_int), *where = act + (n + 2), *redi = where + m;
     const T INF = Lim<T>::inf();
+    // float32 without a prefactored model: the feasibility tolerance is relative to the row, tol (|G_i| + |h_i|) (row_tol,
+    // mpcqp_internal.h), taken before G_i becomes M_i and kept in the padding column of the row; otherwise tol (1 + |h_i|)
+    constexpr bool ROWTOL = (sizeof(T) == 4) && !PREFAC;
+    auto rtol = [&](int i) __attribute__((always_inline)) -> T {
+        if constexpr (ROWTOL)
+            return Mm[i * ld + n];
+        else
+            return tol + tol * fabs(hv[i]);
+    };
 
     status = MPCQP_MAX_ITER;
     iters = 0;
@@ -266,6 +275,13 @@ __device__ __forceinline__ void solve_phase(const Layout &L, T *sm, int n, int m
     // M = G L^-T and w = L^-1 q: one row per lane, forward substitution
     for (int i = tid; i <= m; i += BS) {
         T *row = Mm + i * ld;
+        if constexpr (ROWTOL) {  // |G_i| while the row still holds G_i; the tolerance goes to the row's padding column (ld > n)
+            if (i < m) {
+                T nn = T(0);
+                for (int k = 0; k < n; ++k) nn += row[k] * row[k];
+                row[n] = row_tol(tol, (T)sqrt(nn), hv[i]);
+            }
+        }
         for (int j = 0; j < n; ++j) {
             T v = row[j];
             for (int k = 0; k < j; ++k) v -= row[k] * Pm[j * ld + k];
@@ -306,7 +322,7 @@ __device__ __forceinline__ void solve_phase(const Layout &L, T *sm, int n, int m
             T s = hv[i];
             for (int k = 0; k < n; ++k) s -= row[k] * y[k];
             sv[i] = s;
-            const bool violated = (where[i] < 0) && (s < -(tol + tol * fabs(hv[i])));
+            const bool violated = (where[i] < 0) && (s < -rtol(i));
             const T key = violated ? s * hs[i] : INF;
             if (key < best) {
                 best = key;
@@ -326,7 +342,7 @@ __device__ __forceinline__ void solve_phase(const Layout &L, T *sm, int n, int m
                     const int a = act[i];
                     const T rho = sv[a];
                     r[i] = rho;
-                    if (!(fabs(rho) <= T(64) * (tol + tol * fabs(hv[a])))) flag = T(1);
+                    if (!(fabs(rho) <= T(64) * rtol(a))) flag = T(1);
                 }
                 if (block_sum<T, WAVES>(flag, redv, tid) > T(0)) {
                     ++refined;
