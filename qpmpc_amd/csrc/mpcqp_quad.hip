@@ -51,6 +51,13 @@ namespace quad {
 
 constexpr int MMAX = 32;  // constraints a problem can hold (two per lane)
 constexpr int MK = 2;     // inequality rows per step
+// Placement of the steady loop (profiles/quad_prologue.md: faster with its header 4 bytes past a multiple of 8): padding in the probe's
+#ifndef QUAD_STEADY_PAD  // tick(4) block of the headline instantiation, which a launch without probe skips
+#define QUAD_STEADY_PAD "s_nop 0"
+#endif
+#ifndef QUAD_PROBE_REFINE  // 1: slot 14 of the probe also marks a pass through the refinement arm (tools/gen_golden_quad_prologue.py);
+#define QUAD_PROBE_REFINE 0  // not in the shipped build: the mark costs the slim instantiations 8 B of scratch
+#endif
 
 }  // namespace quad
 
@@ -111,6 +118,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         if (stamp && l == 0 && valid) {
             stamp[slot] = (long long)__builtin_readcyclecounter();
             if (slot == 0 || slot == 6) stamp[slot ? 13 : 12] = (long long)__builtin_amdgcn_s_memrealtime();
+            if (slot == 4 && NX == 3 && !ORD && !SLIM && !MODEL && !GEN) asm volatile(QUAD_STEADY_PAD);
         }
     };
     tick(0);
@@ -173,27 +181,32 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         const int mk = GEN ? ka.mk : MK;
         auto stepof = [&](int row) { return mk == 2 ? row >> 1 : (mk == 1 ? row : (mk == 4 ? row >> 2 : row / 3)); };
         const T *A = gA + prob * ka.A.batch_stride;
-        const T *B = gB + prob * ka.B.batch_stride;
         const bool hasC = !GEN || gC != nullptr;
         const T *Cm = hasC ? gC + prob * ka.C.batch_stride : A;  // (no state rows: the lanes load valid addresses, the products are dropped)
+        const int sA = ka.A.step_stride ? nx * nx : 0, sB = ka.B.step_stride ? nx * nu : 0, sC = (hasC && ka.C.step_stride) ? mk * nx : 0;
+        constexpr int NAe = NX * NX, NEe = NAe + MKG * NX;  // elements of [A_k | C_k]
+        const int NEr = hasC ? NAe + mk * NX : NAe;          // ... that exist
+        constexpr int NOP = WIDE ? 1 : (NEe + 15) / 16;  // operand registers per step: two up to nx = 4, three / four for nx = 5 / 6
+        T op[NOP][NV];
+#include "mpcqp_quad_operands.h"  // (a fragment of this body) the sixteen [A_k | C_k] loads, requested in front of everything else
+        const T *B = gB + prob * ka.B.batch_stride;
         const T *x0 = gx0 + prob * ka.x0.batch_stride;
         const T *goal = ggoal ? ggoal + prob * ka.goal.batch_stride : nullptr;
-        const int sA = ka.A.step_stride ? nx * nx : 0, sB = ka.B.step_stride ? nx * nu : 0, sC = (hasC && ka.C.step_stride) ? mk * nx : 0;
         const bool termP = ka.flags & MPCQP_P_TERMINAL, termQ = (ka.flags & MPCQP_Q_TERMINAL) && goal;
         // (GEN) input rows and the stage cost
         const T *Dm = (GEN && ka.D.ptr) ? (const T *)ka.D.ptr + prob * ka.D.batch_stride : nullptr;
         const T *tgt = (GEN && gtgt) ? gtgt + prob * ka.targets.batch_stride : nullptr;
         const int sD = (GEN && ka.D.step_stride) ? mk * nu : 0;
         const bool stageP = GEN && (ka.flags & MPCQP_P_STAGE), stageQ = GEN && (ka.flags & MPCQP_Q_STAGE) && tgt;
-        constexpr int NAe = NX * NX, NEe = NAe + MKG * NX;  // elements of [A_k | C_k]
-        const int NEr = hasC ? NAe + mk * NX : NAe;          // ... that exist
         const bool col = (l < n);
         const int j = col ? (nu == 1 ? l : l / nu) : -1, ii = col ? l - j * nu : 0;  // (nu == 1: no division before the loads)
-        // every load is issued before the first use: the whole build costs ONE HBM latency
+        // every load is issued before the first use: the whole build costs ONE HBM latency. A lane without an element loads a valid
+        // address of its problem and drops the value: no load sits behind an exec-mask branch
         const int64_t eb = prob * ka.e.batch_stride;
         const int kq0 = stepof(row0), kq1 = stepof(row1);
-        const T eval0 = isc0 ? ge[eb + kq0 * ka.e.step_stride + (row0 - kq0 * mk)] : INF;
-        const T eval1 = isc1 ? ge[eb + kq1 * ka.e.step_stride + (row1 - kq1 * mk)] : INF;
+        const T elo0 = ge[eb + (isc0 ? kq0 * ka.e.step_stride + (row0 - kq0 * mk) : 0)];
+        const T elo1 = ge[eb + (isc1 ? kq1 * ka.e.step_stride + (row1 - kq1 * mk) : 0)];
+        const T eval0 = isc0 ? elo0 : INF, eval1 = isc1 ? elo1 : INF;
         // The free response Phi_k x0 rides in LANE 15 of the row: that lane's own column belongs to the horizon's last step (or to
         // no variable at all), so it is zero in every G_k and enters Psi_N only as B's column itself -- its registers are idle for the
         // whole chain. The lane starts from x0 instead of zero, the chain's FMAs propagate it with everyone else's columns, and a row's
@@ -201,13 +214,19 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         // in every lane).
         const bool xl15 = (l == NV - 1);
         T v[NX], gref[NX], bcol[NX];
+        const T *gsrc = termQ ? goal : x0;  // (every lane of the row loads x0 and the goal from the address lane 15 uses, and selects)
 #pragma unroll
         for (int s = 0; s < NX; ++s) {
-            v[s] = (xl15 && s < nx) ? x0[s < nx ? s : 0] : T(0);
-            gref[s] = (termQ && s < nx) ? goal[s < nx ? s : 0] : T(0);
+            const T xs = x0[s < nx ? s : 0], gs = gsrc[s < nx ? s : 0];
+            v[s] = (xl15 && s < nx) ? xs : T(0);
+            gref[s] = (termQ && s < nx) ? gs : T(0);
         }
+        const int jB = col ? j * sB + ii : 0;
 #pragma unroll
-        for (int r = 0; r < NX; ++r) bcol[r] = (col && r < nx) ? B[j * sB + (r < nx ? r : 0) * nu + ii] : T(0);
+        for (int r = 0; r < NX; ++r) {
+            const T bs = B[jB + (r < nx ? r : 0) * nu];
+            bcol[r] = (col && r < nx) ? bs : T(0);
+        }
         // (GEN) this lane's column of D_j: the G entries of its variable, rows (j, 0) and (j, 1). Lane 15's cells of the image carry
         // the free response through the chain: when it owns a variable (n = 16: an input of the LAST step) the two rows of that step
         // fetch its entries of D straight from memory, behind the chain. Targets: lane e keeps xref element e, e + 16, e + 32, e + 48
@@ -233,22 +252,6 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
             }
         }
         if constexpr (!WIDE) {
-        // lane e of the row keeps element e (and e + 16) of [A_k | C_k] for every step k, straight from HBM; the chain
-        // fetches an operand as a DPP row broadcast (lanes without an element load a valid address and are never read)
-        constexpr int NOP = (NEe + 15) / 16;  // operand registers per step: two up to nx = 4, three / four for nx = 5 / 6
-        T op[NOP][NV];
-        static_for<0, NOP>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            const int e = l + 16 * r;
-            const bool ok = e < NEr;
-            const T *p = (e < NAe) ? A + e : Cm + (ok ? e - NAe : 0);
-            const int st = (e < NAe) ? sA : sC;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) {
-                const int kc = (k < N) ? k : N - 1;
-                op[r][k] = p[kc * st];
-            }
-        });
         tick(8);
         const T wu = (T)ka.wu;
         qa = T(0);
@@ -264,37 +267,6 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
         static_for<0, NV>([&](auto kk) {
             constexpr int k = decltype(kk)::value;
             if (k < N) {
-                // (lane 15 stores C_k Phi_k x0 into column 15 of the image -- zero in G by construction --: the rows read their
-                // entry of it behind the chain)
-                if constexpr (!GEN) {
-                    T g[MK];
-                    static_for<0, MK>([&](auto i2c) {
-                        constexpr int i2 = decltype(i2c)::value;
-                        T acc = T(0);
-                        static_for<0, NX>([&](auto sc) {
-                            constexpr int s2 = decltype(sc)::value;
-                            mac(ic<NAe + i2 * NX + s2>{}, kk, acc, v[s2]);
-                        });
-                        g[i2] = acc;
-                    });
-#pragma unroll
-                    for (int i2 = 0; i2 < MK; ++i2) Gimg[l * GS + k * MK + i2] = g[i2];
-                } else {
-                    static_for<0, MKG>([&](auto i2c) {
-                        constexpr int i2 = decltype(i2c)::value;
-                        if (i2 < mk) {  // (wavefront-uniform)
-                            T acc = T(0);
-                            if (hasC) {
-                                static_for<0, NX>([&](auto sc) {
-                                    constexpr int s2 = decltype(sc)::value;
-                                    mac(ic<NAe + i2 * NX + s2>{}, kk, acc, v[s2]);
-                                });
-                            }
-                            acc += (j == k) ? dcol[i2] : T(0);
-                            Gimg[l * GS + k * mk + i2] = acc;
-                        }
-                    });
-                }
                 if constexpr (GEN && k >= 1) {
                     // stage cost on x_k: P += w_x Psi_k' Psi_k, q += w_x Psi_k' (Phi_k x0 - xref_k)  (mpc_qp.py:99-105, 129-149; lane 15's
                     // own column is zero in every Psi_k of the chain, its registers hold the free response)
@@ -313,19 +285,48 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
                         });
                     }
                 }
-                // column j of Psi_k is zero up to step j, so B_j's column enters as the start value of lane j's sums (lane 15 carries
-                // the free response: its own column is put in place behind the chain)
+                // A step has mk + NX independent sums of NX products; fmac_bcast is asm volatile, so the source order is the issue order. The
+                // loop over the products is the OUTER one and the sums take their turn inside it; each keeps its start value and the order of its
+                // terms: the same bits. Lane 15 stores C_k Phi_k x0 into column 15 of the image (zero in G); B_j's column starts lane j's sums.
                 const T hk = (j == k && !xl15) ? T(1) : T(0);
-                T w[NX];
-                static_for<0, NX>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
-                    T acc = hk * bcol[r];
+                T g[MKG], w[NX];
+#pragma unroll
+                for (int i2 = 0; i2 < MKG; ++i2) g[i2] = T(0);
+#pragma unroll
+                for (int r = 0; r < NX; ++r) w[r] = hk * bcol[r];
+                if constexpr (!GEN) {
                     static_for<0, NX>([&](auto sc) {
                         constexpr int s2 = decltype(sc)::value;
-                        mac(ic<r * NX + s2>{}, kk, acc, v[s2]);
+                        static_for<0, MK>([&](auto i2c) { mac(ic<NAe + decltype(i2c)::value * NX + s2>{}, kk, g[decltype(i2c)::value], v[s2]); });
+                        static_for<0, NX>([&](auto rc) { mac(ic<decltype(rc)::value * NX + s2>{}, kk, w[decltype(rc)::value], v[s2]); });
                     });
-                    w[r] = acc;
-                });
+#pragma unroll
+                    for (int i2 = 0; i2 < MK; ++i2) Gimg[l * GS + k * MK + i2] = g[i2];
+                } else {
+                    // (one to four rows per step, wavefront-uniform tests. nx = 6: the G rows first, as a group: ten sums do not fit 256 registers)
+                    auto psi = [&](auto sc) {
+                        constexpr int s2 = decltype(sc)::value;
+                        static_for<0, NX>([&](auto rc) { mac(ic<decltype(rc)::value * NX + s2>{}, kk, w[decltype(rc)::value], v[s2]); });
+                    };
+                    auto grows = [&](auto sc) {
+                        constexpr int s2 = decltype(sc)::value;
+                        if (!hasC) return;
+                        mac(ic<NAe + s2>{}, kk, g[0], v[s2]);
+                        if (mk > 1) mac(ic<NAe + NX + s2>{}, kk, g[1], v[s2]);
+                        if (mk > 2) mac(ic<NAe + 2 * NX + s2>{}, kk, g[2], v[s2]);
+                        if (mk > 3) mac(ic<NAe + 3 * NX + s2>{}, kk, g[3], v[s2]);
+                    };
+                    if constexpr (NX > 5) static_for<0, NX>(grows);
+                    else static_for<0, NX>([&](auto sc) { psi(sc); grows(sc); });
+                    static_for<0, MKG>([&](auto i2c) {
+                        constexpr int i2 = decltype(i2c)::value;
+                        if (i2 < mk) {  // (wavefront-uniform)
+                            g[i2] += (j == k) ? dcol[i2] : T(0);
+                            Gimg[l * GS + k * mk + i2] = g[i2];
+                        }
+                    });
+                    if constexpr (NX > 5) static_for<0, NX>(psi);
+                }
 #pragma unroll
                 for (int r = 0; r < NX; ++r) v[r] = w[r];
             }
@@ -878,9 +879,8 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
             const bool off = row_any(occ && !(fabs(ra) <= T(1e3) * ta), rb);
             const bool neg = row_any(occ && !(lam >= T(0)), rb);
             if (stamp && l == 0 && valid && !finished && done) {  // developer probe: why the last acceptance test failed
-                T worst = T(0);
                 stamp[14] = (long long)(dirty ? 1 : 0) | (off ? 2 : 0) | (neg ? 4 : 0) | ((long long)fails << 8) | ((long long)nq << 16);
-                (void)worst;
+                if (QUAD_PROBE_REFINE && ((unsigned)(nr >> rb) & 0xffffu) != 0u) stamp[14] |= 1ll << 24;  // (this pass refined)
             }
             dirty = dirty || off || neg;
         }
