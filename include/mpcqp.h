@@ -201,6 +201,21 @@ typedef struct MpcqpProblem {
                                  starts, seed steps, a pairing order together with input rows / a stage cost). The shared-model solves (mpcqp_solve_model_batch / _bounds_batch) take
                                  it too, with the same batch-size rule, for every model with n <= 16, m <= 32. */
 
+#define MPCQP_OPT_ON_CHIP_32 16384 /* mpcqp_build_solve_batch only: solve problems of 17 .. 32 variables on chip, TWO per wavefront
+                                 (mpcqp_duo.hip: the dual active-set method of the small-problem kernels on 32-wide rows), instead of
+                                 the stage-wise kernels the dispatch takes one step past n = 16. Replaces the same reference code as
+                                 its siblings (qpmpc/mpc_qp.py:53-149 for the build, qpsolvers.solve_problem at qpmpc/solve_mpc.py:43
+                                 for the solve). Envelope: cold fused build+solve, float64 (a float32 launch is converted and solved
+                                 in float64 like every small problem), 17 <= n = N nu <= 32, m = N mk <= 64, 1 <= mk <= 4,
+                                 2 <= nx <= 4; every operand layout of MpcqpProblem; lam and iters may be NULL; NO workspace (NULL is
+                                 accepted whatever mpcqp_workspace_bytes reports -- the queries see no flags and answer as before).
+                                 MPCQP_EUNSUPPORTED outside the envelope, with warm_state, order, MPCQP_OPT_SEED_VIOLATED, the
+                                 FORCE_* / ONE_ / TWO_ / FOUR_PER_WAVE overrides and the *_FACTOR options. Additive in ABI 12.
+                                 Where it is faster (MI355X, us per launch, flagged / default route on the same problems,
+                                 profiles/onchip32.md): 4096 problems of (nx, nu, N, mk) = (3,1,17,2) 135 / 366,
+                                 (3,1,20,2) 152 / 453, (3,1,24,2) 178 / 583, (3,1,32,2) 218 / 879, (4,2,12,2) 165 / 362,
+                                 (4,2,16,2) 196 / 511, (3,1,20,3) 288 / 925; 1.9-4.0 x at 256, 4096 and 16384 problems alike. */
+
 /* MpcqpSolveOpts.warm_start */
 #define MPCQP_WARM_OPERATOR 1   /* begin from the stored active set AND operator N* (contract: matrices unchanged)          */
 #define MPCQP_WARM_ACTIVE_SET 2 /* begin from the stored active set's ROW IDS only, moved by warm_shift rows: the rows enter

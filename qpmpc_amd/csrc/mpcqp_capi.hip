@@ -272,6 +272,8 @@ int run_gws_solve(KernelArgs ka, int dtype, int64_t batch, void *ws, size_t ws_b
 template <int MODE>
 int run_solver(const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, hipStream_t st)
 {
+    // on request, inside its envelope (mpcqp_build_solve_batch has checked both): 17 .. 32 variables, two problems per wavefront
+    if (MODE == MODE_FUSED && (ka.opt_flags & MPCQP_OPT_ON_CHIP_32)) return dtype == MPCQP_F64 && duo_applies(ka) ? launch_duo(ka, batch, st) : MPCQP_EUNSUPPORTED;
     if (!force_lds(ka.opt_flags)) {
         // (nx = 2 and nx > 4 have no two-per-wavefront instantiation: the four-per-wavefront kernel takes them where it pays -- the general
         // layouts and nx > 4 at every batch size, the lean layout of nx = 2 from more than two problems per SIMD --, on its own)
@@ -451,6 +453,8 @@ Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
         r.bytes = (size_t)(per * 8 * batch + 10 * 256) + r.inner;
         return r;
     }
+    // MPCQP_OPT_ON_CHIP_32: the on-chip kernel for 17 .. 32 variables, no workspace (the size queries carry no flags and never get here)
+    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) return (dtype == MPCQP_F64 && duo_applies(ka)) ? take(Path::OnChip, 0, 0) : refuse(MPCQP_EUNSUPPORTED);
     if (use_stage_auto(ka, dtype)) return narrow(stage_default_maxq(ka), stagew_auto_maxq(ka));
     if (use_stagew_auto(ka, dtype)) return wide(stagew_auto_maxq(ka));
     if (!e.bulky && use_mid(ka, dtype)) return take(Path::Mid, 0, bigsolve_ws_elems(ka.n) * esz);
@@ -798,6 +802,14 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     if ((ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) &&
         ((ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE)) ||
          (!pair_eligible(ka, MODE_FUSED, MPCQP_F64) && ka.nx != 2 && ka.nx <= 4 && !quad4_applies(ka)) || (!quad_applies(ka) && !quad4_applies(ka))))
+        return MPCQP_EUNSUPPORTED;
+    // 17 .. 32 variables on chip on request: cold launches inside the kernel's envelope, with no other choice of kernel or factor
+    // (a float32 launch is converted below, promote_f32, and arrives here again in float64 with the flag)
+    if ((ka.opt_flags & MPCQP_OPT_ON_CHIP_32) &&
+        (!duo_applies(ka) || ka.warm_state || ka.order ||
+         (ka.opt_flags & (kOverrideFlags | MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_FOUR_PER_WAVE | MPCQP_OPT_KEEP_FACTOR |
+                          MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR)) ||
+         (dims->dtype != MPCQP_F64 && !promote_f32(ka, dims->dtype))))
         return MPCQP_EUNSUPPORTED;
     const bool stepA = problem->A.step_stride != 0, stepB = problem->B.step_stride != 0;
     hipStream_t st = (hipStream_t)stream;

@@ -227,6 +227,10 @@ int launch_quad(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // ... and its general build with four rows per lane for 33 .. 64 rows (mpcqp_quadg.hip): cold launches, any batch size
 bool quad4_applies(const KernelArgs &ka);
 int launch_quad4(const KernelArgs &ka, int64_t batch, hipStream_t st);
+// problems of 17 .. 32 variables on chip (mpcqp_duo.hip): two problems per wavefront, cold fused build+solve, no workspace;
+// taken on request only (MPCQP_OPT_ON_CHIP_32)
+bool duo_applies(const KernelArgs &ka);
+int launch_duo(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // small-problem kernel (mpcqp_w64.hip): one problem per wavefront
 bool w64_eligible(const KernelArgs &ka, int mode, int dtype);
 int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStream_t st);
