@@ -201,7 +201,8 @@ typedef struct MpcqpProblem {
                                  starts, seed steps, a pairing order together with input rows / a stage cost). The shared-model solves (mpcqp_solve_model_batch / _bounds_batch) take
                                  it too, with the same batch-size rule, for every model with n <= 16, m <= 32. */
 
-#define MPCQP_OPT_ON_CHIP_32 16384 /* mpcqp_build_solve_batch only: solve problems of 17 .. 32 variables on chip, TWO per wavefront
+#define MPCQP_OPT_ON_CHIP_32 16384 /* mpcqp_build_solve_batch and the shared-model solves (below, after the fused launch's part):
+                                 solve problems of 17 .. 32 variables on chip, TWO per wavefront
                                  (mpcqp_duo.hip: the dual active-set method of the small-problem kernels on 32-wide rows), instead of
                                  the stage-wise kernels the dispatch takes one step past n = 16. Replaces the same reference code as
                                  its siblings (qpmpc/mpc_qp.py:53-149 for the build, qpsolvers.solve_problem at qpmpc/solve_mpc.py:43
@@ -214,7 +215,19 @@ typedef struct MpcqpProblem {
                                  Where it is faster (MI355X, us per launch, flagged / default route on the same problems,
                                  profiles/onchip32.md): 4096 problems of (nx, nu, N, mk) = (3,1,17,2) 135 / 366,
                                  (3,1,20,2) 152 / 453, (3,1,24,2) 178 / 583, (3,1,32,2) 218 / 879, (4,2,12,2) 165 / 362,
-                                 (4,2,16,2) 196 / 511, (3,1,20,3) 288 / 925; 1.9-4.0 x at 256, 4096 and 16384 problems alike. */
+                                 (4,2,16,2) 196 / 511, (3,1,20,3) 288 / 925; 1.9-4.0 x at 256, 4096 and 16384 problems alike.
+                                 Shared-model solves (the kernel's MODEL mode: the rows of M and L^-T are read from what
+                                 mpcqp_factor_model wrote, h and L^-1 q come from its linear maps; replaces update_cost_vector /
+                                 update_constraint_vector + the solver call, mpc_qp.py:129-163). Envelope: float64,
+                                 17 <= n <= 32, 1 <= m <= 64, ANY nx and ANY number of rows per step (the operands' layout no
+                                 longer matters), cold. mpcqp_solve_model_bounds_batch with bounds per problem takes this kernel
+                                 inside the envelope WITH OR WITHOUT the flag (nothing else serves those launches; at n <= 16 the
+                                 small-problem kernels serve them as before and the flag changes nothing).
+                                 mpcqp_solve_model_batch, and _bounds_batch with e == NULL, take it only with the flag: without
+                                 it the launch goes where it always went (the workgroup kernel at these sizes); with it,
+                                 MPCQP_EUNSUPPORTED outside the envelope (n <= 16 included), in float32, with warm_state or
+                                 order, and next to MPCQP_OPT_FORCE_LDS, ONE_ / TWO_ / FOUR_PER_WAVE or SEED_VIOLATED.
+                                 Figures: profiles/onchip32_model.md. */
 
 /* MpcqpSolveOpts.warm_start */
 #define MPCQP_WARM_OPERATOR 1   /* begin from the stored active set AND operator N* (contract: matrices unchanged)          */
@@ -437,7 +450,10 @@ int mpcqp_factor_model(const MpcqpDims *dims, const void *P, const void *G,
  * differ (batch_stride 0 = shared; goal/targets may be NULL when their cost term is
  * not flagged). Replaces update_cost_vector + update_constraint_vector + the solver
  * call for every problem. Outputs as mpcqp_build_solve_batch: U[b] = zeros, status and iters for a problem with status[b] != 0,
- * its lam[b] undefined; lam and iters may be NULL. `model` is only read; there is no workspace. */
+ * its lam[b] undefined; lam and iters may be NULL. `model` is only read; there is no workspace.
+ * MPCQP_OPT_ON_CHIP_32 in opts->flags sends a float64 launch of 17 <= n <= 32, 1 <= m <= 64 to the on-chip kernel of
+ * mpcqp_duo.hip (two problems per wavefront) instead of the workgroup kernel, and is MPCQP_EUNSUPPORTED for every other
+ * launch (see the flag); without the flag nothing changes. */
 int mpcqp_solve_model_batch(const MpcqpDims *dims, const void *model,
                             const MpcqpOperand *x0, const MpcqpOperand *goal,
                             const MpcqpOperand *targets, int64_t batch,
@@ -448,8 +464,11 @@ int mpcqp_solve_model_batch(const MpcqpDims *dims, const void *model,
  * instead of taken from the model: the matrices are shared and constant, the bounds move -- the per-step ZMP bounds
  * that examples/lipm_walking_controller.py:179-213 (update_goal_and_constraints) rewrites every control period while
  * A, B, C stay, i.e. update_constraint_vector (mpc_qp.py:151-163) with a new e. h = e - (C Phi) x0 uses the model's map.
- * e == NULL or e->ptr == NULL is mpcqp_solve_model_batch. Served by the pair kernel (n <= 16, m <= 32, float64);
- * MPCQP_EUNSUPPORTED elsewhere. Outputs for unsolved problems as mpcqp_solve_model_batch. */
+ * e == NULL or e->ptr == NULL is mpcqp_solve_model_batch. Served by the small-problem kernels (n <= 16, m <= 32, float64)
+ * and, for float64 models of 17 <= n <= 32 with 1 <= m <= 64 (any nx, any number of rows per step), by the MODEL mode of
+ * mpcqp_duo.hip -- with or without MPCQP_OPT_ON_CHIP_32, cold, with no order and none of MPCQP_OPT_FORCE_LDS, ONE_ / TWO_ /
+ * FOUR_PER_WAVE, SEED_VIOLATED; MPCQP_EUNSUPPORTED elsewhere (float32 past sixteen variables, n > 32, m > 64). Outputs
+ * for unsolved problems as mpcqp_solve_model_batch. */
 int mpcqp_solve_model_bounds_batch(const MpcqpDims *dims, const void *model, const MpcqpOperand *e,
                                    const MpcqpOperand *x0, const MpcqpOperand *goal,
                                    const MpcqpOperand *targets, int64_t batch,

@@ -19,7 +19,7 @@ OPT_FORCE_LDS, OPT_FORCE_GWS, OPT_FORCE_DENSE_G, OPT_ONE_PER_WAVE, OPT_FORCE_CON
 OPT_KEEP_FACTOR, OPT_REUSE_FACTOR, OPT_PIPELINE_FACTOR, OPT_SEED_VIOLATED, OPT_EXACT_SELECTION = 64, 128, 256, 512, 1024
 OPT_TWO_PER_WAVE, OPT_FOUR_PER_WAVE = 2048, 4096
 OPT_STAGE_GENERAL = 8192
-OPT_ON_CHIP_32 = 16384  # mpcqp_build_solve_batch: 17 .. 32 variables on chip, two problems per wavefront (csrc/mpcqp_duo.hip)
+OPT_ON_CHIP_32 = 16384  # mpcqp_build_solve_batch and the shared-model solves: 17 .. 32 variables on chip, two problems per wavefront (csrc/mpcqp_duo.hip)
 WARM_OPERATOR, WARM_ACTIVE_SET = 1, 2
 
 # MPCQP_LIB (dev only) points at another build of the same sources for A/B timing.

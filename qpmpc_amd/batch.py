@@ -836,8 +836,17 @@ class SharedModel:
         return PreparedModelSolve(self, problem, return_multipliers, max_iter, feas_tol, **opt_kw)
 
     def solve(self, x0, goal=None, targets=None, return_multipliers: bool = False,
-              max_iter: Optional[int] = None, feas_tol: Optional[float] = None, **opt_kw) -> BatchPlan:
-        run = self.prepare(self.problem_for(x0, goal, targets), return_multipliers, max_iter, feas_tol, **opt_kw)
+              max_iter: Optional[int] = None, feas_tol: Optional[float] = None, *, ineq_vector=None, **opt_kw) -> BatchPlan:
+        """One launch for the given states. ``ineq_vector`` (``[B|1, N|1, mk]``, ``[N|1, mk]`` or ``[mk]``, as
+        :meth:`solve_diff` takes it) gives every problem bounds of its own (``mpcqp_solve_model_bounds_batch``: n <= 16, and
+        float64 models of 17 <= n <= 32 with at most 64 rows); otherwise the model's are used. ``flags=_capi.OPT_ON_CHIP_32``
+        sends a solve with the model's bounds at 17 <= n <= 32 to the on-chip kernel instead of the workgroup kernel."""
+        e = None
+        if ineq_vector is not None:
+            from . import model_diff
+
+            e = model_diff.per_problem_bounds(self, x0, ineq_vector)[1]
+        run = self.prepare(self.problem_for(x0, goal, targets, e), return_multipliers, max_iter, feas_tol, **opt_kw)
         run.launch()
         return run.plan
 
@@ -855,7 +864,10 @@ class SharedModel:
         backward ``plan.vjp_status`` holds their status (``MPCQP_NOT_PD`` where the active rows' Gram matrix is
         singular). A float32 model factors a float64 twin on the first derivative call and casts the results back.
         Envelope: n = N * nu <= 64 (``BackendError`` before anything is launched; ``solve_mpc_batch_diff`` serves
-        larger problems, and gradients with respect to the model matrices and weights). With nothing requiring grad
+        larger problems, and gradients with respect to the model matrices and weights). A per-problem ``ineq_vector`` is
+        served for n <= 32 (17 .. 32: float64 models with at most 64 rows, the on-chip kernel of ``MPCQP_OPT_ON_CHIP_32``);
+        at 33 <= n <= 64 the forward with per-problem bounds is still refused, by a ``BackendError`` that says so before
+        anything is launched. With nothing requiring grad
         and nothing dual this is :meth:`solve`."""
         from . import model_diff
 
@@ -866,7 +878,8 @@ class SharedModel:
         """Jacobian-vector products of a plan of this model, ``(dU [B, T, N, nu], dX [B, T, N+1, nx] or None)``: the
         module-level ``plan_jvp`` (tangent shapes ``[B|1, T, ...]``, a leading 1 shares one set with the batch, T <=
         256) by one ``mpcqp_model_jvp_batch`` call. ``plan`` was solved with ``return_multipliers=True``; after the call
-        ``plan.jvp_status`` holds the per-problem outcome. Envelope: n <= 64."""
+        ``plan.jvp_status`` holds the per-problem outcome. Envelope: n <= 64 (a plan solved with per-problem bounds exists
+        for n <= 32 only: see :meth:`solve_diff`)."""
         from . import model_diff
 
         return model_diff.plan_jvp(self, plan, initial_state, goal_state, target_states, ineq_vector, states)

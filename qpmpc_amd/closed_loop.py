@@ -235,13 +235,15 @@ class LIPMWalkingLoop:
                  state=None, com_height: float = 0.84, dsp_duration: float = 0.1, ssp_duration: float = 0.7,
                  gravity: float = 9.81, init_support_foot_pos: float = 0.09, nb_timesteps: int = 16,
                  sampling_period: float = 0.1, substeps: int = 15, max_iter: Optional[int] = None,
-                 warm_start=False, shared_model: bool = False):
+                 warm_start=False, shared_model: bool = False, flags: int = 0):
         import torch
 
         _capi.require_gpu()
         dev, f64 = torch.device("cuda", torch.cuda.current_device()), torch.float64
         T, N = float(sampling_period), int(nb_timesteps)
         self.nb_timesteps, self.sampling_period, self.substeps = N, T, int(substeps)
+        # flags: MpcqpSolveOpts.flags of every period's solve (_capi.OPT_*), e.g. OPT_ON_CHIP_32 at 17 <= nb_timesteps <= 32
+        opt_kw = {"flags": int(flags)} if flags else {}
         self.nb_dsp, self.nb_ssp = int(round(dsp_duration / T)), int(round(ssp_duration / T))
         if 2 * (self.nb_dsp + self.nb_ssp) < N:  # PhaseStepper.__init__, :107-110
             from .exceptions import ProblemDefinitionError
@@ -281,16 +283,17 @@ class LIPMWalkingLoop:
         if shared_model:
             # The matrices never change here, only e / x0 / goal do: factor them ONCE (the reference's own usage of
             # MPCQP, mpc_qp.py:129-163: build, then update_cost_vector / update_constraint_vector per period) and give
-            # every period's solve its bounds (mpcqp_solve_model_bounds_batch). Same plans as the rebuilding loop.
+            # every period's solve its bounds (mpcqp_solve_model_bounds_batch: up to 32 timesteps). Same plans as the
+            # rebuilding loop.
             from .batch import SharedModel
 
             if warm_start:
                 raise ValueError("LIPMWalkingLoop: warm_start and shared_model are exclusive")
             self.model = SharedModel(self.problem)
-            self.solver = self.model.prepare(self.problem, max_iter=max_iter)
+            self.solver = self.model.prepare(self.problem, max_iter=max_iter, **opt_kw)
         else:
-            self.solver = (PreparedSolve(self.problem, max_iter=max_iter, warm_state=self.warm_state) if warm_start
-                           else PreparedSolve(self.problem, max_iter=max_iter))
+            self.solver = (PreparedSolve(self.problem, max_iter=max_iter, warm_state=self.warm_state, **opt_kw) if warm_start
+                           else PreparedSolve(self.problem, max_iter=max_iter, **opt_kw))
         self._k = torch.arange(N, device=dev)
         self._problem_written = False  # e / goal / x0 of the CURRENT phase are in the problem buffers
         self.mpc_steps = 0

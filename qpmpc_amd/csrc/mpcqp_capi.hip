@@ -1003,13 +1003,21 @@ int mpcqp_solve_model_bounds_batch(const MpcqpDims *dims, const void *model, con
         ((ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)) || !small))
         return MPCQP_EUNSUPPORTED;  // (the four-per-wavefront kernel has no seed steps: asked for by name, it is refused by name)
     hipStream_t st = (hipStream_t)stream;
-    const bool own_e = e && e->ptr;  // per-problem bounds: the small-problem kernels' model mode only
+    // 17 .. 32 variables on chip (mpcqp_duo.hip, its shared-model mode): float64 inside the kernel's envelope, cold (a warm state
+    // was refused above), with no pairing order and no other choice of kernel or start
+    const bool on_chip_32 = dims->dtype == MPCQP_F64 && duo_model_applies(ka) && !ka.order &&
+                            !(ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE |
+                                              MPCQP_OPT_FOUR_PER_WAVE | MPCQP_OPT_SEED_VIOLATED));
+    const bool own_e = e && e->ptr;  // per-problem bounds: the model modes of the small-problem kernels and of the on-chip-32 kernel
     if (own_e) {
         if (ka.m < 1) return MPCQP_EINVAL;
         ka.e = *e;
-        if (!small) return MPCQP_EUNSUPPORTED;
+        // (past sixteen variables nothing else serves them: the kernel is taken with or without MPCQP_OPT_ON_CHIP_32)
+        if (!small) return on_chip_32 ? launch_duo_model(ka, batch, st) : MPCQP_EUNSUPPORTED;
         return quad_model_eligible(ka, batch) ? launch_quad_model(ka, batch, st) : launch_pair_model(ka, batch, st);
     }
+    // the model's own bounds: on request only (the default route of these sizes, the workgroup kernel below, stays)
+    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) return on_chip_32 ? launch_duo_model(ka, batch, st) : MPCQP_EUNSUPPORTED;
     if (!force_lds(ka.opt_flags) && !(ka.opt_flags & MPCQP_OPT_ONE_PER_WAVE) && small)
         return quad_model_eligible(ka, batch) ? launch_quad_model(ka, batch, st) : launch_pair_model(ka, batch, st);
     if (!force_lds(ka.opt_flags) && w64_eligible(ka, MODE_MODEL, dims->dtype)) return launch_w64(ka, MODE_MODEL, dims->dtype, batch, st);

@@ -34,6 +34,13 @@
 // and the rows of L^-T come out of ONE right-looking elimination: column j of the trailing matrix is broadcast through LDS and
 // both rows a lane holds (P_l, e_l) take the same update; M = G L^-T is then a triangular product against the broadcast rows
 // of L^-T.
+//
+// Shared model (MODEL = true; mpcqp_solve_model_bounds_batch, and mpcqp_solve_model_batch with MPCQP_OPT_ON_CHIP_32): the
+// reference's build-once usage (mpc_qp.py:129-163, update_cost_vector / update_constraint_vector). Build, elimination and
+// triangular product are replaced by loads from what mpcqp_factor_model wrote and a few short products with its linear maps
+// (h = e - Hx x0, w = Wx x0 - Wg goal - Wt targets); nx and the number of rows per step are run-time numbers there (NX is not
+// read), and the bounds e come per problem or from the model. From `int status = MPCQP_MAX_ITER` on both modes run the same
+// statements.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -140,7 +147,7 @@ __device__ __forceinline__ double half_colsum(const double (&x)[NV], double *W, 
 
 using namespace duo;
 
-template <int NX>
+template <int NX, bool MODEL>
 __global__ void __launch_bounds__(64, 1)
     mpcqp_duo_kernel(const double *__restrict__ gA, const double *__restrict__ gB, const double *__restrict__ gC,
                      const double *__restrict__ gD, const double *__restrict__ ge, const double *__restrict__ gx0,
@@ -169,8 +176,99 @@ __global__ void __launch_bounds__(64, 1)
     T Pr[NV];  // row hl of P
     T qa = T(0);
     T h0, h1;
+    bool notpd = false;
+    T y0m = T(0);  // MODEL: y0 = -w of this lane
+    // ---------------------------------------------------------------- shared model (mpc_qp.py:129-163 on a factored model)
+    // What mpcqp_factor_model wrote replaces the build, the elimination and the triangular product: the rows of M and of L^-T
+    // are loaded (row stride n, which may be odd: no 16-byte loads), h = e - Hx x0 and w = Wx x0 - Wg goal - Wt targets come from
+    // the model's linear maps against the problem's x0, goal and targets, staged once per half in the scratch image.
+    if constexpr (MODEL) {
+        const T *model = gA;
+        const int nxr = ka.nx, nT = ka.N * ka.nx, mk = ka.mk;
+        const ModelLayout ml = make_model_layout(nxr, ka.N, n, m);
+        const T *x0 = gx0 + prob * ka.x0.batch_stride;
+        const T *goal = ggoal ? ggoal + prob * ka.goal.batch_stride : nullptr;
+        const T *tgt = gtgt ? gtgt + prob * ka.targets.batch_stride : nullptr;
+        const bool termQ = (ka.flags & MPCQP_Q_TERMINAL) && goal, stageQ = (ka.flags & MPCQP_Q_STAGE) && tgt;
+        notpd = model[ml.total] != T(0);
+        auto al4 = [](int c) { return (c + 3) & ~3; };  // as make_lay
+        T *xs = Wimg, *gs = xs + al4(nxr), *ts = gs + al4(nxr);
+        for (int i = hl; i < nxr; i += NV) {
+            xs[i] = x0[i];
+            gs[i] = termQ ? goal[i] : T(0);
+        }
+        if (stageQ)
+            for (int i = hl; i < nT; i += NV) ts[i] = tgt[i];
+        const bool col = hl < n;
+        const int c1 = hl + 32;
+        // rows hl and 32 + hl of M: a lane without a row reads row 0 and keeps zeros, a column beyond n repeats column n - 1
+        // and keeps a zero (no load leaves the model, no branch on the lane)
+        {
+            const T *p0 = model + ml.off_M + (size_t)(isc0 ? hl : 0) * n;
+            const T *p1 = model + ml.off_M + (size_t)(isc1 ? c1 : 0) * n;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const int kc = k < n ? k : n - 1;
+                const T a = p0[kc], b = p1[kc];
+                RM0[k] = (isc0 && k < n) ? a : T(0);
+                RM1[k] = (isc1 && k < n) ? b : T(0);
+            }
+        }
+        // row hl of L^-T into its image; rows and columns beyond n are the identity (a lane without a variable keeps u = 0)
+        {
+            const T *pl = model + ml.off_LinvT + (size_t)(col ? hl : 0) * n;
+            T lt[NV];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const int kc = k < n ? k : n - 1;
+                const T a = pl[kc];
+                lt[k] = (col && k < n) ? a : ((hl == k) ? T(1) : T(0));
+            }
+            st32(LTimg + hl * LDG, lt);
+        }
+        const T e0 = !isc0 ? INF : ge ? ge[prob * ka.e.batch_stride + (hl / mk) * ka.e.step_stride + (hl % mk)] : model[ml.off_e + hl];
+        const T e1 = !isc1 ? INF : ge ? ge[prob * ka.e.batch_stride + (c1 / mk) * ka.e.step_stride + (c1 % mk)] : model[ml.off_e + c1];
+        wave_sync();  // (x0, goal and targets are staged)
+        // h_i = e_i - Hx_i . x0
+        {
+            const T *hx0 = model + ml.off_Hx + (size_t)(isc0 ? hl : 0) * nxr;
+            const T *hx1 = model + ml.off_Hx + (size_t)(isc1 ? c1 : 0) * nxr;
+            T a0 = T(0), a1 = T(0);
+            for (int c = 0; c < nxr; ++c) {
+                const T xc = xs[c];
+                a0 += hx0[c] * xc;
+                a1 += hx1[c] * xc;
+            }
+            h0 = isc0 ? e0 - a0 : INF;
+            h1 = isc1 ? e1 - a1 : INF;
+        }
+        // w_k = Wx_k . x0 - Wg_k . goal - Wt_k . targets, lane k walking its own rows (the staged vectors are broadcast reads);
+        // the long product over the targets runs in four chains
+        {
+            const size_t row = col ? hl : 0;
+            const T *wx = model + ml.off_Wx + row * nxr, *wg = model + ml.off_Wg + row * nxr, *wt = model + ml.off_Wt + row * nT;
+            T wk = T(0);
+            for (int c = 0; c < nxr; ++c) wk += wx[c] * xs[c];
+            if (termQ)
+                for (int c = 0; c < nxr; ++c) wk -= wg[c] * gs[c];
+            if (stageQ) {
+                T t0 = T(0), t1 = T(0), t2 = T(0), t3 = T(0);
+                int j = 0;
+                for (; j + 4 <= nT; j += 4) {
+                    t0 += wt[j] * ts[j];
+                    t1 += wt[j + 1] * ts[j + 1];
+                    t2 += wt[j + 2] * ts[j + 2];
+                    t3 += wt[j + 3] * ts[j + 3];
+                }
+                for (; j < nT; ++j) t0 += wt[j] * ts[j];
+                wk -= (t0 + t1) + (t2 + t3);
+            }
+            y0m = col ? -wk : T(0);  // y0 = -w
+        }
+        wave_sync();  // (the staged vectors are read: the scratch image is free again; the L^-T image is written)
+    }
     // ---------------------------------------------------------------- build (mpc_qp.py:53-114)
-    {
+    if constexpr (!MODEL) {
         constexpr int nx = NX;
         const int nu = ka.nu, N = ka.N, mk = ka.mk;
         const T *A = gA + prob * ka.A.batch_stride;
@@ -320,8 +418,7 @@ __global__ void __launch_bounds__(64, 1)
     // Right-looking: in step j, column j of the trailing matrix (lane k: P[k][j] = L[k][j] L[j][j]) is broadcast through a
     // double-buffered LDS vector, and a row x becomes x_j / L[j][j], x_k -= (x_j / piv) P[k][j] for k > j -- the Cholesky
     // update for the rows of P, the forward substitution x L^-T for the rows of the identity.
-    bool notpd = false;
-    {
+    if constexpr (!MODEL) {
         T LT[NV];  // row hl of the identity -> of L^-T
 #pragma unroll
         for (int k = 0; k < NV; ++k) LT[k] = (hl == k) ? T(1) : T(0);
@@ -359,7 +456,7 @@ __global__ void __launch_bounds__(64, 1)
     }
     wave_sync();
     // M_i = G_i L^-T: row l of L^-T (zero before column l) is broadcast from its image, once for both rows of a lane
-    {
+    if constexpr (!MODEL) {
         T g0[NV], g1[NV];
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
@@ -393,7 +490,9 @@ __global__ void __launch_bounds__(64, 1)
     wave_sync();
     // y0 = -w, w = L^-1 q: w_k = sum_l q_l (L^-T)[l][k]
     T y0k;
-    {
+    if constexpr (MODEL) {
+        y0k = y0m;
+    } else {
         T qq[NV];
         ld32(qq, rv);
         T a0 = T(0), a1 = T(0);
@@ -705,17 +804,21 @@ __global__ void __launch_bounds__(64, 1)
 }
 
 // ------------------------------------------------------------ host side
-static Lay make_lay(const KernelArgs &ka)
+// model: the carve of a shared-model launch -- no staged operands; x0, goal and the targets (N nx of them) share the scratch image
+static Lay make_lay(const KernelArgs &ka, bool model = false)
 {
     Lay L{};
     auto al = [](int c) { return (c + 3) & ~3; };
     L.off_X = 0;
     L.off_W = NV * LDG;
-    L.nA = (ka.A.step_stride ? ka.N : 1) * ka.nx * ka.nx;
-    L.nB = (ka.B.step_stride ? ka.N : 1) * ka.nx * ka.nu;
-    L.nC = ka.C.ptr ? (ka.C.step_stride ? ka.N : 1) * ka.mk * ka.nx : 0;
-    L.nD = ka.D.ptr ? (ka.D.step_stride ? ka.N : 1) * ka.mk * ka.nu : 0;
-    const int w_build = al(L.nA) + al(L.nB) + al(L.nC) + al(L.nD) + ka.nx * NV, w_main = NV * LDW;
+    if (!model) {
+        L.nA = (ka.A.step_stride ? ka.N : 1) * ka.nx * ka.nx;
+        L.nB = (ka.B.step_stride ? ka.N : 1) * ka.nx * ka.nu;
+        L.nC = ka.C.ptr ? (ka.C.step_stride ? ka.N : 1) * ka.mk * ka.nx : 0;
+        L.nD = ka.D.ptr ? (ka.D.step_stride ? ka.N : 1) * ka.mk * ka.nu : 0;
+    }
+    const int w_build = model ? 2 * al(ka.nx) + al(ka.N * ka.nx) : al(L.nA) + al(L.nB) + al(L.nC) + al(L.nD) + ka.nx * NV;
+    const int w_main = NV * LDW;
     L.off_v = L.off_W + al(w_build > w_main ? w_build : w_main);
     L.per = al(L.off_v + MMAX + 4 * NV + NV + 4);
     return L;
@@ -726,13 +829,15 @@ bool duo_applies(const KernelArgs &ka)
 {
     return ka.n >= 17 && ka.n <= NV && ka.m >= 1 && ka.m <= MMAX && ka.mk >= 1 && ka.mk <= 4 && ka.nx >= 2 && ka.nx <= 4;
 }
+// ... and of its shared-model mode: the operands' layout no longer matters (any nx, any number of rows per step)
+bool duo_model_applies(const KernelArgs &ka) { return ka.n >= 17 && ka.n <= NV && ka.m >= 1 && ka.m <= MMAX && ka.mk >= 1; }
 
 template <int NX> static int launch_duo_t(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
     const Lay L = make_lay(ka);
     const size_t bytes = (size_t)L.per * 2 * sizeof(double);
     const int64_t waves = (batch + 1) / 2;  // one wavefront per workgroup, whatever the batch: they share nothing
-    hipLaunchKernelGGL(mpcqp_duo_kernel<NX>, dim3((unsigned)waves), dim3(64), bytes, st, (const double *)ka.A.ptr,
+    hipLaunchKernelGGL((mpcqp_duo_kernel<NX, false>), dim3((unsigned)waves), dim3(64), bytes, st, (const double *)ka.A.ptr,
                        (const double *)ka.B.ptr, (const double *)ka.C.ptr, (const double *)ka.D.ptr, (const double *)ka.e.ptr,
                        (const double *)ka.x0.ptr, (const double *)ka.goal.ptr, (const double *)ka.targets.ptr, (double *)ka.U,
                        (double *)ka.lam, ka.status, ka.iters, ka, L, batch);
@@ -746,6 +851,22 @@ int launch_duo(const KernelArgs &ka, int64_t batch, hipStream_t st)
     case 3: return launch_duo_t<3>(ka, batch, st);
     default: return launch_duo_t<4>(ka, batch, st);
     }
+}
+
+// shared model (ka.model, in the first argument as in the pair and quad kernels; ka.e.ptr: bounds per problem, or null)
+int launch_duo_model(const KernelArgs &ka, int64_t batch, hipStream_t st)
+{
+    const Lay L = make_lay(ka, true);
+    const size_t bytes = (size_t)L.per * 2 * sizeof(double);  // (38 KB until N nx exceeds 1000: then the targets set the carve)
+    if (bytes > kLdsBytesPerCU) return MPCQP_ETOOLARGE;
+    auto kern = mpcqp_duo_kernel<0, true>;
+    if (bytes > 48 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    const int64_t waves = (batch + 1) / 2;
+    hipLaunchKernelGGL(kern, dim3((unsigned)waves), dim3(64), bytes, st, (const double *)ka.model, (const double *)nullptr,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)ka.e.ptr, (const double *)ka.x0.ptr,
+                       (const double *)ka.goal.ptr, (const double *)ka.targets.ptr, (double *)ka.U, (double *)ka.lam, ka.status,
+                       ka.iters, ka, L, batch);
+    return (int)hipGetLastError();
 }
 
 }  // namespace mpcqp

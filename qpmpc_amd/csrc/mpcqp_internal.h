@@ -231,6 +231,10 @@ int launch_quad4(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // taken on request only (MPCQP_OPT_ON_CHIP_32)
 bool duo_applies(const KernelArgs &ka);
 int launch_duo(const KernelArgs &ka, int64_t batch, hipStream_t st);
+// ... and its shared-model mode (ka.model; ka.e.ptr: bounds per problem, or null for the model's): 17 <= n <= 32, 1 <= m <= 64,
+// any nx and any number of rows per step, float64, cold
+bool duo_model_applies(const KernelArgs &ka);
+int launch_duo_model(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // small-problem kernel (mpcqp_w64.hip): one problem per wavefront
 bool w64_eligible(const KernelArgs &ka, int mode, int dtype);
 int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStream_t st);

@@ -35,6 +35,31 @@ def check_envelope(model) -> None:
                            f"not {n}; solve_mpc_batch_diff differentiates larger problems")
 
 
+MAX_VARIABLES_OWN_BOUNDS = 32  # envelope of mpcqp_solve_model_bounds_batch: n <= 16 (any dtype), float64 17 <= n <= 32 with m <= 64
+MAX_ROWS_OWN_BOUNDS = 64
+
+
+def per_problem_bounds(model, x0, ineq_vector):
+    """``(e_canon [B|1, N|1, mk], e [B, N, mk])`` of an ``ineq_vector`` that gives every problem of a shared-model solve bounds
+    of its own (the forward is then ``mpcqp_solve_model_bounds_batch``). Raises ``BackendError`` before anything is
+    launched where that export refuses the model's size."""
+    torch = _torch()
+    t = model.template
+    e_canon = _canon(_as_tensor(_detached(ineq_vector), t.dtype, t.device), (t.ineq_dim,), "ineq_vector")
+    Bn = _as_tensor(_detached(x0), t.dtype, t.device).reshape(-1, t.state_dim).shape[0]
+    if e_canon.shape[1] not in (1, t.nb_timesteps) or e_canon.shape[0] not in (1, Bn):
+        raise ProblemDefinitionError(
+            f"ineq_vector: shape {tuple(e_canon.shape)} is not [B|1, N|1, {t.ineq_dim}]")
+    n, m = t.nb_variables, t.nb_constraints
+    served = n <= 16 or (n <= MAX_VARIABLES_OWN_BOUNDS and m <= MAX_ROWS_OWN_BOUNDS and t.dtype == torch.float64)
+    if Bn > 1 and not served:
+        raise BackendError(
+            f"a shared-model solve that gives every problem bounds of its own (ineq_vector) is served for n = N * nu <= 16 "
+            f"variables and, in float64, for n <= {MAX_VARIABLES_OWN_BOUNDS} with at most {MAX_ROWS_OWN_BOUNDS} rows, not for "
+            f"n = {n}, m = {m}; solve_mpc_batch and solve_mpc_batch_diff serve larger problems with per-problem bounds")
+    return e_canon, e_canon.expand(Bn, -1, -1).contiguous()
+
+
 def _float64_model(model):
     """The model the derivative exports read: ``model`` itself when it is float64, else a float64 twin factored on the
     first derivative call and kept (float32 problems are converted for the backward)."""
@@ -213,16 +238,9 @@ def solve_diff(model, x0, goal=None, targets=None, ineq_vector=None, states: boo
     global _FUNCTION
     torch = _torch()
     passed = (x0, goal, targets, ineq_vector)
-    t = model.template
     e_canon = e = None
     if ineq_vector is not None:
-        e_canon = _canon(_as_tensor(_detached(ineq_vector), t.dtype, t.device), (t.ineq_dim,), "ineq_vector")
-        Bn = _as_tensor(_detached(x0), t.dtype, t.device).reshape(-1, t.state_dim).shape[0]
-        if e_canon.shape[1] not in (1, t.nb_timesteps) or e_canon.shape[0] not in (1, Bn):
-            raise ProblemDefinitionError(
-                f"ineq_vector: shape {tuple(e_canon.shape)} is not [B|1, N|1, {t.ineq_dim}]")
-        # bounds of its own for every problem: the forward is then mpcqp_solve_model_bounds_batch
-        e = e_canon.expand(Bn, -1, -1).contiguous()
+        e_canon, e = per_problem_bounds(model, x0, ineq_vector)
     work = model.problem_for(_detached(x0), _detached(goal), _detached(targets), e)
     dual = [_is_dual(v) for v in passed]
     need = any(dual) or (torch.is_grad_enabled()
