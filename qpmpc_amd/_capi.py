@@ -13,7 +13,7 @@ from .exceptions import BackendError
 F64, F32 = 0, 1
 P_TERMINAL, P_STAGE, Q_TERMINAL, Q_STAGE = 1, 2, 4, 8
 SOLVED, MAX_ITER, INFEASIBLE, NOT_PD, SLOTS_FULL = 0, 1, 2, 3, 4
-EINVAL, EDTYPE, EWORKSPACE, EUNSUPPORTED = -1, -3, -5, -6
+EINVAL, ETOOLARGE, EDTYPE, ELAYOUT, EWORKSPACE, EUNSUPPORTED = -1, -2, -3, -4, -5, -6
 ABI_VERSION = 12
 OPT_FORCE_LDS, OPT_FORCE_GWS, OPT_FORCE_DENSE_G, OPT_ONE_PER_WAVE, OPT_FORCE_CONDENSED, OPT_STAGE_WIDE = 1, 2, 4, 8, 16, 32
 OPT_KEEP_FACTOR, OPT_REUSE_FACTOR, OPT_PIPELINE_FACTOR, OPT_SEED_VIOLATED, OPT_EXACT_SELECTION = 64, 128, 256, 512, 1024
@@ -259,10 +259,10 @@ def check(code: int, what: str) -> None:
     """Turn a non-zero return code of the C ABI into ``BackendError``."""
     if code != 0:
         msg = load().mpcqp_error_string(code).decode()
-        if code == -2:  # MPCQP_ETOOLARGE: name the envelope instead of leaving the caller guessing
+        if code == ETOOLARGE:  # name the envelope instead of leaving the caller guessing
             msg += (". Served: everything that fits 160 KiB of LDS; beyond that any horizon for systems with nx <= 32, "
                     "nu <= 8 (stage-wise kernels)")
-        raise BackendError(f"{what} failed with code {code}: {msg}")
+        raise BackendError(f"{what} failed with code {code}: {msg}", code=code)
 
 
 def require_gpu():

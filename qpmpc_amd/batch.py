@@ -327,22 +327,34 @@ def _require_on_gpu(*tensors) -> None:
             raise BackendError(f"operand on {t.device}: the HIP path needs device-resident tensors (no CPU fallback)")
 
 
-def _workspace(problem: "BatchMPCProblem", for_solve: bool):
-    """Caller-owned scratch for problems that do not fit the on-chip path (None when
-    they do): a uint8 tensor of exactly ``mpcqp_workspace_bytes`` bytes."""
-    torch = _torch()
-    lib = _capi.load()
-    dims = problem.dims()
+def _workspace(problem: "BatchMPCProblem", dims, for_solve: bool, stagewise: bool = False, max_active: int = 0, flags: int = 0):
+    """Caller-owned scratch of a launch on ``problem`` (``dims``: its ``problem.dims()``), a uint8 tensor of exactly the
+    bytes the library asks for, or None where it needs none (the on-chip path): ``mpcqp_workspace_bytes`` for
+    ``mpcqp_condense_batch`` and, ``for_solve``, for ``mpcqp_build_solve_batch``; ``stagewise``:
+    ``mpcqp_stagewise_workspace_bytes`` for ``mpcqp_stagewise_solve_batch`` with ``max_active`` slots and the launch's ``flags``."""
+    if stagewise:
+        # (MPCQP_OPT_STAGE_GENERAL: the general kernel's workspace is asked for with a negative slot count, include/mpcqp.h)
+        query, ask = "mpcqp_stagewise_workspace_bytes", (-max(max_active, 1) if flags & _capi.OPT_STAGE_GENERAL else max_active)
+    else:
+        query, ask = "mpcqp_workspace_bytes", 1 if for_solve else 0
     nbytes = C.c_size_t(0)
-    rc = lib.mpcqp_workspace_bytes(C.byref(dims), problem.batch_size, 1 if for_solve else 0, C.byref(nbytes))
-    _capi.check(rc, "mpcqp_workspace_bytes")
+    _capi.check(getattr(_capi.load(), query)(C.byref(dims), problem.batch_size, ask, C.byref(nbytes)), query)
     if nbytes.value == 0:
         return None
+    torch = _torch()
     return torch.empty((nbytes.value,), dtype=torch.uint8, device=problem.device)
 
 
 def _ws_args(ws):
     return (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+def _outputs(Bn: int, n: int, m: int, dtype, device, return_multipliers: bool):
+    """``(U [B, n], lam [B, m] | None, status [B], iters [B])`` of one launch, uninitialised."""
+    torch = _torch()
+    return (torch.empty((Bn, n), dtype=dtype, device=device),
+            torch.empty((Bn, m), dtype=dtype, device=device) if return_multipliers else None,
+            torch.empty((Bn,), dtype=torch.int32, device=device), torch.empty((Bn,), dtype=torch.int32, device=device))
 
 
 def _warm_mode(warm_start) -> int:
@@ -398,6 +410,13 @@ def pairing_order(counts, out=None):
     return order
 
 
+def _warm_bytes(problem: "BatchMPCProblem") -> int:
+    """``mpcqp_warm_state_bytes``: bytes per problem of the warm record for these dimensions (0: none is offered)."""
+    dims, nbytes = problem.dims(), C.c_size_t(0)
+    _capi.check(_capi.load().mpcqp_warm_state_bytes(C.byref(dims), C.byref(nbytes)), "mpcqp_warm_state_bytes")
+    return int(nbytes.value)
+
+
 class WarmState:
     """Per-problem active set and active-set operator kept in HBM between the periods of
     receding-horizon loops (``MpcqpSolveOpts.warm_state``). Valid while the problems' matrices and
@@ -406,18 +425,14 @@ class WarmState:
 
     def __init__(self, problem: "BatchMPCProblem"):
         torch = _torch()
-        lib = _capi.load()
-        dims = problem.dims()
-        nbytes = C.c_size_t(0)
-        _capi.check(lib.mpcqp_warm_state_bytes(C.byref(dims), C.byref(nbytes)), "mpcqp_warm_state_bytes")
-        if nbytes.value == 0:
+        self.bytes_per_problem = _warm_bytes(problem)
+        if self.bytes_per_problem == 0:
             raise BackendError(
                 "warm start is available for problems with n = N*nu <= 16 variables and m <= 32 rows (the active-set "
                 "operator persists; float32 launches of that size are solved in float64), for small systems (nx <= 4, nu <= 2) with "
                 "16 < n <= 128 (the active rows' vectors "
                 "persist in the solver's workspace) and for what the wide stage-wise kernel takes (nx <= 16, nu <= 4: the active "
                 f"rows' ids); got n={problem.nb_variables}, m={problem.nb_constraints}, {problem.dtype}")
-        self.bytes_per_problem = int(nbytes.value)
         self.batch_size = problem.batch_size
         self.device = problem.device
         # "pair": the operator T (16 x 16 doubles) first, then the slots' constraint ids (int32); "stage": int32 record
@@ -427,8 +442,8 @@ class WarmState:
         # warm_start="active_set" only (the rows' vectors ride along with the first sweeps)
         # (asked of the library: the dispatch is its business -- a float32 problem of at most 160 variables is solved by the
         # float64 kernels and keeps their record)
-        kind = C.c_int32(0)
-        _capi.check(lib.mpcqp_warm_state_kind(C.byref(dims), C.byref(kind)), "mpcqp_warm_state_kind")
+        dims, kind = problem.dims(), C.c_int32(0)
+        _capi.check(_capi.load().mpcqp_warm_state_kind(C.byref(dims), C.byref(kind)), "mpcqp_warm_state_kind")
         self.kind = {1: "pair", 2: "stage", 3: "stagew"}[kind.value]
         self._mk = problem.ineq_dim
         self._ids_at = 16 * 16 * 8 if self.kind == "pair" else 0
@@ -439,13 +454,11 @@ class WarmState:
     def check(self, problem: "BatchMPCProblem") -> None:
         """Raise ``BackendError`` unless this state was allocated for ``problem``'s batch, dimensions and device
         (the kernel indexes it by problem: a smaller buffer would be read and written out of bounds)."""
-        lib = _capi.load()
-        dims, nbytes = problem.dims(), C.c_size_t(0)
-        _capi.check(lib.mpcqp_warm_state_bytes(C.byref(dims), C.byref(nbytes)), "mpcqp_warm_state_bytes")
-        if nbytes.value != self.bytes_per_problem or problem.batch_size != self.batch_size:
+        nbytes = _warm_bytes(problem)
+        if nbytes != self.bytes_per_problem or problem.batch_size != self.batch_size:
             raise BackendError(
                 f"WarmState holds {self.batch_size} problems of {self.bytes_per_problem} bytes; this launch needs "
-                f"{problem.batch_size} of {nbytes.value}: allocate WarmState(problem) for the batch it is used with")
+                f"{problem.batch_size} of {nbytes}: allocate WarmState(problem) for the batch it is used with")
         if problem.device != self.device:
             raise BackendError(f"WarmState lives on {self.device}, the problem on {problem.device}")
 
@@ -485,13 +498,11 @@ def _check_warm(problem: "BatchMPCProblem", opt_kw) -> None:
     if isinstance(ws, WarmState):
         ws.check(problem)
         return
-    lib = _capi.load()
-    dims, nbytes = problem.dims(), C.c_size_t(0)
-    _capi.check(lib.mpcqp_warm_state_bytes(C.byref(dims), C.byref(nbytes)), "mpcqp_warm_state_bytes")
-    need = nbytes.value * problem.batch_size
-    if ws.device != problem.device or ws.numel() * ws.element_size() < need or nbytes.value == 0:
+    nbytes = _warm_bytes(problem)
+    need = nbytes * problem.batch_size
+    if ws.device != problem.device or ws.numel() * ws.element_size() < need or nbytes == 0:
         raise BackendError(f"warm_state tensor: {ws.numel() * ws.element_size()} bytes on {ws.device}; this launch needs "
-                           f"{need} bytes on {problem.device} (mpcqp_warm_state_bytes per problem: {nbytes.value})")
+                           f"{need} bytes on {problem.device} (mpcqp_warm_state_bytes per problem: {nbytes})")
 
 
 class BatchPlan:
@@ -557,57 +568,49 @@ def solve_mpc_batch(problem: BatchMPCProblem, solver: str = "hip_gi", return_mul
     to begin from it, ``flags`` (``_capi.OPT_*`` dispatch overrides for cross-checks), ``probe``."""
     if solver not in HIP_SOLVERS:
         raise BackendError(f"solver '{solver}' is not a batched backend; available: {HIP_SOLVERS}")
-    torch = _torch()
-    lib = _capi.load()
-    _require_on_gpu(problem.initial_state)
-    Bn, n, m = problem.batch_size, problem.nb_variables, problem.nb_constraints
-    U = torch.empty((Bn, n), dtype=problem.dtype, device=problem.device)
-    lam = torch.empty((Bn, m), dtype=problem.dtype, device=problem.device) if return_multipliers else None
-    status = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
-    iters = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
-    _check_warm(problem, opt_kw)
-    _check_order(problem, opt_kw)
     ws_ = opt_kw.get("warm_state")
     if isinstance(ws_, WarmState) and ws_.kind == "stage" and opt_kw.get("warm_start"):
         # the stage-wise kernel's warm start continues from the vectors its previous launch left in the SAME workspace;
         # this function allocates a fresh one per call, so the request could only ever be a silent cold start
         raise BackendError("a stage-kind WarmState warm-starts through PreparedSolve (one workspace kept across launches), "
                            "not through solve_mpc_batch(warm_start=True)")
-    dims, cp, opts = problem.dims(), problem.c_problem(), _opts(max_iter, feas_tol, **opt_kw)
+    # (keep_warm_factor=False: nothing launches from this workspace again, so no factor is kept in it)
+    run = PreparedSolve(problem, return_multipliers, max_iter, feas_tol, formulation, max_active, keep_warm_factor=False,
+                        **opt_kw)
+    run.launch()
+    plan = run.plan
+    plan._launch = run  # keep the scratch (and the opts' tensors) alive until the stream has consumed them
+    flags = opt_kw.get("flags") or 0
     if formulation == "stagewise":
-        nbytes = C.c_size_t(0)
-        # (MPCQP_OPT_STAGE_GENERAL: the general kernel's workspace is asked for with a negative slot count, include/mpcqp.h)
-        general = bool((opt_kw.get("flags") or 0) & _capi.OPT_STAGE_GENERAL)
-        ask = (-max(int(max_active or 0), 1)) if general else int(max_active or 0)
-        _capi.check(lib.mpcqp_stagewise_workspace_bytes(C.byref(dims), Bn, ask, C.byref(nbytes)),
-                    "mpcqp_stagewise_workspace_bytes")
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=problem.device)
-        rc = lib.mpcqp_stagewise_solve_batch(
-            C.byref(dims), C.byref(cp), Bn, C.byref(opts), int(max_active or 0), U.data_ptr(),
-            None if lam is None else lam.data_ptr(), status.data_ptr(), iters.data_ptr(), ws.data_ptr(), ws.numel(),
-            _stream_ptr())
-        _capi.check(rc, "mpcqp_stagewise_solve_batch")
-        plan = BatchPlan(problem, U, status, iters, lam)
-        plan._workspace = (ws, opt_kw)
         if retry_slots:
-            _retry_slots_full(plan, int(max_active or (256 if general else 128)), max_iter, feas_tol, opt_kw)
+            _retry_slots_full(plan, int(max_active or (256 if flags & _capi.OPT_STAGE_GENERAL else 128)), max_iter, feas_tol,
+                              opt_kw)
         return plan
-    if formulation != "condensed":
-        raise ProblemDefinitionError(f"formulation must be 'condensed' or 'stagewise', not {formulation!r}")
-    ws = _workspace(problem, True)
-    rc = lib.mpcqp_build_solve_batch(
-        C.byref(dims), C.byref(cp), Bn, C.byref(opts), U.data_ptr(),
-        None if lam is None else lam.data_ptr(), status.data_ptr(), iters.data_ptr(), *_ws_args(ws), _stream_ptr())
-    _capi.check(rc, "mpcqp_build_solve_batch")
-    plan = BatchPlan(problem, U, status, iters, lam)
-    plan._workspace = (ws, opt_kw)  # keep the scratch (and the opts' tensors) alive until the stream has consumed them
-    if retry_slots and min(n, m) > 256:
+    if retry_slots and min(problem.nb_variables, problem.nb_constraints) > 256:
         # (the automatic dispatch sends what can have more than 128 active rows to the wide stage-wise kernel, which holds
         # min(n, m, 256) of them -- mpcqp_capi.hip)
         _retry_slots_full(plan, 256, max_iter, feas_tol, opt_kw)
-    if retry_unsolved and not (opt_kw.get("flags") or 0):
+    if retry_unsolved and not flags:
         _retry_unsolved(plan, max_iter, feas_tol, opt_kw)
     return plan
+
+
+# the codes with which route() and the entry points (csrc/mpcqp_capi.hip) refuse a launch for its dimensions, dtype or options.
+# (MPCQP_EDTYPE is not among them: check_dims answers it to a dtype that is neither float64 nor float32 only, and a
+# BatchMPCProblem holds no other.) Every other failure of a re-solve -- workspace, layout, arguments, a HIP error, an error
+# raised in Python -- is a fault and leaves the retry as the exception it is.
+_NOT_SERVED = (_capi.ETOOLARGE, _capi.EUNSUPPORTED)
+
+
+def _merge_back(plan: "BatchPlan", index, again: "BatchPlan", only=None) -> None:
+    """Write the re-solve ``again`` of the items ``index`` of ``plan`` back into it (``only``: just these items of ``again``)."""
+    if only is not None:
+        index = index.index_select(0, only)
+    for name in ("U", "status", "iters", "multipliers"):
+        dst, src = getattr(plan, name), getattr(again, name)
+        if dst is not None:  # (multipliers: only where the plan has them)
+            dst.index_copy_(0, index, src if only is None else src.index_select(0, only))
+    plan._states = None
 
 
 def _retry_unsolved(plan: "BatchPlan", max_iter, feas_tol, opt_kw) -> None:
@@ -636,19 +639,13 @@ def _retry_unsolved(plan: "BatchPlan", max_iter, feas_tol, opt_kw) -> None:
         try:
             again = solve_mpc_batch(problem.select(index), return_multipliers=plan.multipliers is not None, max_iter=max_iter,
                                     feas_tol=feas_tol, retry_unsolved=False, **attempt, **kw)
-        except BackendError:  # (this formulation does not serve these dimensions)
-            continue
+        except BackendError as exn:
+            if exn.code not in _NOT_SERVED:
+                raise
+            continue  # (this formulation does not serve these dimensions)
         better = again.status == _capi.SOLVED
-        if not bool(better.any().item()):
-            continue
-        sub = better.nonzero().flatten()
-        dst = index.index_select(0, sub)
-        plan.U.index_copy_(0, dst, again.U.index_select(0, sub))
-        plan.status.index_copy_(0, dst, again.status.index_select(0, sub))
-        plan.iters.index_copy_(0, dst, again.iters.index_select(0, sub))
-        if plan.multipliers is not None:
-            plan.multipliers.index_copy_(0, dst, again.multipliers.index_select(0, sub))
-        plan._states = None
+        if bool(better.any().item()):
+            _merge_back(plan, index, again, better.nonzero().flatten())
 
 
 def _retry_slots_full(plan: "BatchPlan", held: int, max_iter, feas_tol, opt_kw) -> None:
@@ -656,7 +653,6 @@ def _retry_slots_full(plan: "BatchPlan", held: int, max_iter, feas_tol, opt_kw) 
     solved again through the stage-wise entry point with twice the slots, until they fit (at most min(n, m) rows can
     be active) -- the reference's backends have no such cap (solve_mpc.py:42-44). Reading the statuses synchronises;
     this is only reached for problems with more than 128 variables and rows, where the cap exists."""
-    torch = _torch()
     problem = plan.problem
     cap = min(problem.nb_variables, problem.nb_constraints)
     kw = {k: v for k, v in opt_kw.items() if k not in ("warm_state", "warm_start", "probe")}
@@ -669,64 +665,95 @@ def _retry_slots_full(plan: "BatchPlan", held: int, max_iter, feas_tol, opt_kw) 
         try:
             again = solve_mpc_batch(problem.select(index), return_multipliers=plan.multipliers is not None, max_iter=max_iter,
                                     feas_tol=feas_tol, formulation="stagewise", max_active=held, retry_slots=False, **kw)
-        except BackendError:  # (more slots than the kernel of these dimensions holds -- the general one stops at 1024: the items keep
-            return            # their MPCQP_SLOTS_FULL status, an empty plan, instead of an exception out of a batch call)
-        plan.U.index_copy_(0, index, again.U)
-        plan.status.index_copy_(0, index, again.status)
-        plan.iters.index_copy_(0, index, again.iters)
-        if plan.multipliers is not None:
-            plan.multipliers.index_copy_(0, index, again.multipliers)
-        plan._states = None
+        except BackendError as exn:
+            if exn.code not in _NOT_SERVED:
+                raise
+            # (more slots than the kernel of these dimensions holds -- the general one stops at 1024: the items keep
+            # their MPCQP_SLOTS_FULL status, an empty plan, instead of an exception out of a batch call)
+            return
+        _merge_back(plan, index, again)
 
 
-class PreparedSolve:
+class _PreparedLaunch:
+    """What :class:`PreparedSolve` and :class:`PreparedModelSolve` share: the output tensors, the opts struct (and the
+    tensors it points at), and the launch -- one call of ``self._entry`` with the arguments ``rebind()`` marshalled."""
+
+    _stage_warm_pending = False  # (PreparedSolve: a stage-kind warm start asked for before the first launch)
+
+    def __init__(self, problem: BatchMPCProblem, return_multipliers, max_iter, feas_tol, opt_kw):
+        self._lib = _capi.load()
+        self.problem = problem
+        self._opt_kw = opt_kw  # tensors referenced by the opts struct stay alive with the object
+        self.U, self.lam, self.status, self.iters = _outputs(
+            problem.batch_size, problem.nb_variables, problem.nb_constraints, problem.dtype, problem.device,
+            return_multipliers)
+        self._opts = _opts(max_iter, feas_tol, **opt_kw)
+
+    def set_order(self, order) -> None:
+        """Pairing order of the next launches (:func:`pairing_order`; ``None``: natural). The tensor is kept alive here."""
+        _check_order(self.problem, {"order": order})
+        probe = _opts(order=order)  # (dtype / device / layout checks)
+        self._opt_kw["order"] = order
+        self._opts.order = probe.order
+
+    def launch(self, stream=None) -> None:
+        """Enqueue one solve of the whole batch on ``stream`` (default: torch's current stream). Asynchronous."""
+        sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+        rc = self._entry(*self._args, sp)
+        if rc != 0:
+            _capi.check(rc, self._entry.__name__)
+        if self._stage_warm_pending:
+            self._stage_warm_pending = False
+            self.set_warm_start(True)
+
+    @property
+    def plan(self) -> BatchPlan:
+        return BatchPlan(self.problem, self.U, self.status, self.iters, self.lam)
+
+
+class PreparedSolve(_PreparedLaunch):
     """A fused build+solve bound to fixed device buffers: ``launch()`` costs one
     C call (no allocation, no struct marshalling), so a receding-horizon loop or a
     benchmark can enqueue steps back-to-back or capture them in a HIP graph.
 
     Update problem data IN PLACE (``problem.initial_state.copy_(x)``) between
     launches; if a tensor of the problem is replaced, call ``rebind()``.
+
+    ``keep_warm_factor``: with a stage-kind ``warm_state``, keep the Riccati factor and the active rows' vectors in this
+    object's workspace so that later launches can start from them (``set_warm_start``). ``solve_mpc_batch``, whose
+    workspace serves one launch, passes ``False``.
     """
 
     def __init__(self, problem: BatchMPCProblem, return_multipliers: bool = False,
                  max_iter: Optional[int] = None, feas_tol: Optional[float] = None, formulation: str = "condensed",
-                 max_active: Optional[int] = None, **opt_kw):
-        torch = _torch()
-        self._lib = _capi.load()
+                 max_active: Optional[int] = None, *, keep_warm_factor: bool = True, **opt_kw):
         _require_on_gpu(problem.initial_state)
         if formulation not in ("condensed", "stagewise"):
             raise ProblemDefinitionError(f"formulation must be 'condensed' or 'stagewise', not {formulation!r}")
-        self.problem = problem
-        self._stagewise, self._max_active = formulation == "stagewise", int(max_active or 0)
-        self._opt_kw = opt_kw  # tensors referenced by the opts struct stay alive with the object
-        Bn, n, m = problem.batch_size, problem.nb_variables, problem.nb_constraints
-        self.U = torch.empty((Bn, n), dtype=problem.dtype, device=problem.device)
-        self.lam = torch.empty((Bn, m), dtype=problem.dtype, device=problem.device) if return_multipliers else None
-        self.status = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
-        self.iters = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
         _check_warm(problem, opt_kw)
         _check_order(problem, opt_kw)
-        self._opts = _opts(max_iter, feas_tol, **opt_kw)
+        super().__init__(problem, return_multipliers, max_iter, feas_tol, opt_kw)
+        self._stagewise, self._max_active = formulation == "stagewise", int(max_active or 0)
         ws_ = opt_kw.get("warm_state")
         # the stage-wise kernel's warm start continues from the vectors its previous launch left in THIS object's
         # workspace: the first launch keeps the Riccati factor, set_warm_start(True) switches to re-using it
-        self._stage_warm = isinstance(ws_, WarmState) and ws_.kind == "stage"
+        self._stage_warm = keep_warm_factor and isinstance(ws_, WarmState) and ws_.kind == "stage"
         # (warm_start=True at construction: the first launch has nothing to continue from -- it factors, keeps the factor
         # and starts cold; launch() switches to the re-used factor + warm start right after it)
         self._stage_warm_pending = self._stage_warm and bool(self._opts.warm_start)
         if self._stage_warm:
             self._opts.flags |= _capi.OPT_KEEP_FACTOR
-        if self._stagewise:
-            dims, nbytes = problem.dims(), C.c_size_t(0)
-            _capi.check(self._lib.mpcqp_stagewise_workspace_bytes(C.byref(dims), Bn, self._max_active, C.byref(nbytes)),
-                        "mpcqp_stagewise_workspace_bytes")
-            self._ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=problem.device)
-        else:
-            self._ws = _workspace(problem, True)
-        self.rebind()
+        self._dims = problem.dims()
+        self._ws = _workspace(problem, self._dims, True, self._stagewise, self._max_active, self._opts.flags)
+        self._marshal()
 
     def rebind(self) -> None:
-        self._dims, self._cp = self.problem.dims(), self.problem.c_problem()
+        self._dims = self.problem.dims()
+        self._marshal()
+
+    def _marshal(self) -> None:
+        """The entry point and its argument tuple, from ``self._dims`` and the problem's tensors as they are now."""
+        self._cp = self.problem.c_problem()
         head = (C.byref(self._dims), C.byref(self._cp), self.problem.batch_size, C.byref(self._opts))
         if self._stagewise:
             head = head + (self._max_active,)
@@ -748,28 +775,6 @@ class PreparedSolve:
         if self._stage_warm:  # (contract of both: A, B, C, D and the weights are those of the launch before)
             keep, reuse = _capi.OPT_KEEP_FACTOR, _capi.OPT_REUSE_FACTOR
             self._opts.flags = (self._opts.flags & ~(keep | reuse)) | (reuse if on else keep)
-
-    def set_order(self, order) -> None:
-        """Pairing order of the next launches (:func:`pairing_order`; ``None``: natural). The tensor is kept alive here."""
-        _check_order(self.problem, {"order": order})
-        probe = _opts(order=order)  # (dtype / device / layout checks)
-        self._opt_kw["order"] = order
-        self._opts.order = probe.order
-
-    def launch(self, stream=None) -> None:
-        """Enqueue one fused build+solve of the whole batch on ``stream``
-        (default: torch's current stream). Asynchronous."""
-        sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
-        rc = self._entry(*self._args, sp)
-        if rc != 0:
-            _capi.check(rc, "mpcqp_stagewise_solve_batch" if self._stagewise else "mpcqp_build_solve_batch")
-        if self._stage_warm_pending:
-            self._stage_warm_pending = False
-            self.set_warm_start(True)
-
-    @property
-    def plan(self) -> BatchPlan:
-        return BatchPlan(self.problem, self.U, self.status, self.iters, self.lam)
 
 
 class SharedModel:
@@ -893,27 +898,19 @@ class SharedModel:
         return model_diff.plan_jacobian(self, plan, wrt, states)
 
 
-class PreparedModelSolve:
+class PreparedModelSolve(_PreparedLaunch):
     """``PreparedSolve`` for a ``SharedModel``: one C call per launch; update the problem's
     states IN PLACE between launches."""
 
     def __init__(self, model: SharedModel, problem: BatchMPCProblem, return_multipliers: bool = False,
                  max_iter: Optional[int] = None, feas_tol: Optional[float] = None, **opt_kw):
-        torch = _torch()
-        self._lib = _capi.load()
-        self.model, self.problem = model, problem
-        self._opt_kw = opt_kw
+        self.model = model
         flags = model.dims.flags
         if (flags & _capi.Q_TERMINAL) and problem.goal_state is None:
             raise ProblemDefinitionError("MPC problem has terminal cost but the goal state is undefined")
         if (flags & _capi.Q_STAGE) and problem.target_states is None:
             raise ProblemDefinitionError("MPC problem has a stage state cost but the reference trajectory is undefined")
-        Bn, n, m = problem.batch_size, problem.nb_variables, problem.nb_constraints
-        self.U = torch.empty((Bn, n), dtype=problem.dtype, device=problem.device)
-        self.lam = torch.empty((Bn, m), dtype=problem.dtype, device=problem.device) if return_multipliers else None
-        self.status = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
-        self.iters = torch.empty((Bn,), dtype=torch.int32, device=problem.device)
-        self._opts = _opts(max_iter, feas_tol, **opt_kw)
+        super().__init__(problem, return_multipliers, max_iter, feas_tol, opt_kw)
         self.rebind()
 
     def rebind(self) -> None:
@@ -926,26 +923,7 @@ class PreparedModelSolve:
                 self.iters.data_ptr())
         head = (C.byref(self.model.dims), self.model.model.data_ptr())
         self._args = head + ((C.byref(self._ops[3]),) if self._own_e else ()) + tail
-
-    def set_order(self, order) -> None:
-        """Pairing order of the next launches (:func:`pairing_order`; ``None``: natural), as ``PreparedSolve.set_order``."""
-        _check_order(self.problem, {"order": order})
-        probe = _opts(order=order)
-        self._opt_kw["order"] = order
-        self._opts.order = probe.order
-
-    def launch(self, stream=None) -> None:
-        sp = _stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
-        if self._own_e:
-            rc = self._lib.mpcqp_solve_model_bounds_batch(*self._args, sp)
-        else:
-            rc = self._lib.mpcqp_solve_model_batch(*self._args, sp)
-        if rc != 0:
-            _capi.check(rc, "mpcqp_solve_model_batch")
-
-    @property
-    def plan(self) -> BatchPlan:
-        return BatchPlan(self.problem, self.U, self.status, self.iters, self.lam)
+        self._entry = self._lib.mpcqp_solve_model_bounds_batch if self._own_e else self._lib.mpcqp_solve_model_batch
 
 
 class BatchMPCQP:
@@ -962,7 +940,7 @@ class BatchMPCQP:
         self.Phi_all = mk(Bn, (N + 1) * nx, nx) if keep_propagators else None
         self.Psi_all = mk(Bn, (N + 1) * nx, n) if keep_propagators else None
         dims, cp = problem.dims(), problem.c_problem()
-        self._ws = _workspace(problem, False)
+        self._ws = _workspace(problem, dims, False)
         rc = lib.mpcqp_condense_batch(
             C.byref(dims), C.byref(cp), Bn, self.P.data_ptr(), self.q.data_ptr(), self.G.data_ptr(),
             self.h.data_ptr(), None if self.Phi_all is None else self.Phi_all.data_ptr(),
@@ -1005,10 +983,7 @@ def solve_qp_batch(P, q, G, h, return_multipliers: bool = False, max_iter=None, 
     m = 0 if G is None else int(G.shape[1])
     G = None if G is None else G.contiguous()
     h = None if h is None else h.contiguous()
-    x = torch.empty((Bn, n), dtype=P.dtype, device=P.device)
-    lam = torch.empty((Bn, m), dtype=P.dtype, device=P.device) if return_multipliers else None
-    status = torch.empty((Bn,), dtype=torch.int32, device=P.device)
-    iters = torch.empty((Bn,), dtype=torch.int32, device=P.device)
+    x, lam, status, iters = _outputs(Bn, n, m, P.dtype, P.device, return_multipliers)
     opts = _opts(max_iter, feas_tol, **opt_kw)
     nbytes = C.c_size_t(0)
     _capi.check(lib.mpcqp_solve_workspace_bytes(n, m, _dtype_code(P.dtype), Bn, C.byref(nbytes)),

@@ -25,4 +25,11 @@ class BackendError(QPMPCException):
     """The HIP library is missing, failed to load, or a launch returned an error.
 
     There is no CPU fallback: the product path fails loudly instead.
+
+    ``code``: the C ABI's return code (``MPCQP_E*`` < 0, a HIP error > 0) when a call of the library failed, ``None``
+    when the error was raised on the Python side.
     """
+
+    def __init__(self, *args, code=None):
+        super().__init__(*args)
+        self.code = code

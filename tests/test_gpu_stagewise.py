@@ -556,3 +556,72 @@ def test_factor_options_of_the_narrow_kernel_for_every_dimension(nx, nu, N, mk):
         torch.cuda.synchronize()
         assert torch.equal(run.status, st0), (flags, slot)
         assert torch.equal(run.U, U0), (flags, slot, float((run.U - U0).abs().max()))
+
+
+def _through_both_doors(bp, **kw):
+    """One request through ``solve_mpc_batch`` and through ``PreparedSolve(...).launch()``: the same launch, hence the same
+    bits in every output. Returns the plan."""
+    from qpmpc_amd import PreparedSolve, solve_mpc_batch
+
+    plan = solve_mpc_batch(bp, return_multipliers=True, **kw)
+    run = PreparedSolve(bp, return_multipliers=True, **kw)
+    run.launch()
+    torch.cuda.synchronize()
+    assert torch.equal(plan.status, run.status) and torch.equal(plan.iters, run.iters), kw
+    assert torch.equal(plan.U, run.U) and torch.equal(plan.multipliers, run.lam), kw
+    return plan
+
+
+@pytest.mark.gpu
+def test_solve_mpc_batch_and_prepared_solve_launch_the_same_bits():
+    """``solve_mpc_batch`` is a ``PreparedSolve`` launched once: bit-identical U, status, iters and multipliers on the
+    small-problem route (triple integrator, N = 16), on the narrow stage-wise kernel with its second opinion ((3, 1, 24, 2) by
+    the default dispatch) and through the stage-wise entry point."""
+    from qpmpc_amd import workloads as W
+
+    plan = _through_both_doors(W.to_batch_problem(W.triple_integrator_batch(8)))
+    assert int((plan.status == 0).sum()) >= 6
+    bp = W.to_batch_problem(W.random_ltv(np.random.default_rng(3124), 8, 3, 1, 24, 2, 1.0))
+    plan = _through_both_doors(bp)
+    assert int((plan.status == 0).sum()) >= 4
+    _through_both_doors(bp, formulation="stagewise")
+
+
+@pytest.mark.gpu
+def test_general_kernel_through_both_doors():
+    """``formulation="stagewise", flags=OPT_STAGE_GENERAL`` at (5, 2, 6, 2): both doors size the general kernel's workspace
+    (the query with a negative slot count: 57344 bytes for these 8 problems), run, agree bit for bit and give the oracle's
+    verdicts. Before the two doors shared one workspace query, ``PreparedSolve`` asked with a slot count of 0 and got the wide
+    kernel's size here (204800 bytes): the launch ran, all 8 solved, in a buffer sized for another kernel -- it would have
+    come back MPCQP_EWORKSPACE wherever the general kernel needs more than the kernel the query priced."""
+    from qpmpc_amd import _capi
+    from qpmpc_amd import workloads as W
+
+    w = W.random_ltv(np.random.default_rng(5262), 8, 5, 2, 6, 2, 1.0)
+    plan = _through_both_doors(W.to_batch_problem(w), formulation="stagewise", flags=_capi.OPT_STAGE_GENERAL)
+    Uo, _, sto, _ = oracle.solve_workload(w)
+    st = plan.status.cpu().numpy()
+    assert np.array_equal(st, sto), (st, sto)
+    ok = sto == 0
+    assert ok.sum() >= 2
+    scale = np.maximum(1.0, np.abs(Uo[ok]).max(axis=1, keepdims=True))
+    assert (np.abs(plan.U.cpu().numpy()[ok] - Uo[ok]) / scale).max() <= 1e-7
+
+
+@pytest.mark.gpu
+def test_a_refused_model_launch_names_the_entry_it_called():
+    """Bounds per problem on a float32 model of 20 variables (include/mpcqp.h: float32 past sixteen variables is
+    MPCQP_EUNSUPPORTED): the error names ``mpcqp_solve_model_bounds_batch``, the entry that was called, and carries the code."""
+    from qpmpc_amd import BackendError, SharedModel, _capi
+    from qpmpc_amd import workloads as W
+
+    w = W.random_ltv(np.random.default_rng(42102), 8, 4, 2, 10, 2, 1.0)
+    for key in ("A", "B", "C", "D"):
+        w[key] = w[key][:1]
+    bp = W.to_batch_problem(w, dtype=torch.float32)
+    run = SharedModel(bp).prepare(bp)
+    run.status.fill_(-7)
+    with pytest.raises(BackendError, match="^mpcqp_solve_model_bounds_batch failed with code -6") as caught:
+        run.launch()
+    torch.cuda.synchronize()
+    assert caught.value.code == _capi.EUNSUPPORTED and bool((run.status == -7).all())
