@@ -40,6 +40,25 @@
  *    `order` leaves out keeps its old outputs; the elements between two rows of a strided argument (u_stride) are not touched;
  *  - read-only arguments (everything declared const, the operands, the model of the solve_model exports) are never written;
  *  - mpcqp_model_vjp_batch / mpcqp_model_jvp_batch touch nothing outside the named extents and the model (mpcqp_model_bytes).
+ *
+ * Stream contract (tests/test_gpu_streams.py holds every forward route, the stateful sequences and the Python layer to it)
+ *  - every kernel of a call is enqueued on the stream the call is given, in order, and on no other: a call that launches several
+ *    kernels (the float32 conversion around a float64 solve; propagate, Gram, transpose and solve on the dense path; the narrow
+ *    stage-wise kernel and the wide kernel's second opinion; the three kernels of mpcqp_order_by_count) is one item of that
+ *    stream's order -- it sees what was enqueued on the stream before it and is seen by what is enqueued behind it;
+ *  - no call synchronises with the host or reads a device value on the host: the return code says what was enqueued, never what
+ *    a kernel found (that is status[b]);
+ *  - a call can be captured into a HIP graph (hipStreamBeginCapture on its stream) after one eager launch of the same
+ *    dimensions, and the graph replayed on new operand VALUES at the captured addresses; this includes the
+ *    MPCQP_OPT_KEEP_FACTOR / _REUSE_FACTOR and cold / warm pairs captured as one graph of two launches. The launchers of the
+ *    kernels that can need more than 48 KiB of dynamic LDS set the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to the
+ *    launch's own size in front of the launch: most of them only when that size exceeds 48 KiB, the dense solver's and the
+ *    general stage-wise kernel's on every launch; a refusal by the runtime is the call's return code, except in the
+ *    model-factoring and the on-chip 17 .. 32-variable launchers, which ignore the result (a launch the runtime then cannot
+ *    make is reported by the launch itself). The runtime takes the attribute call while a stream is capturing, and one graph
+ *    may hold launches of one kernel at several sizes: the value last set does not bind a replay;
+ *  - concurrent calls on distinct streams, or from distinct host threads, with distinct outputs and workspaces (and warm
+ *    states) are independent: each gives the bits of the same call made alone. Operands and a factored model may be shared.
  */
 #ifndef MPCQP_H_
 #define MPCQP_H_

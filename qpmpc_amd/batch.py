@@ -714,7 +714,9 @@ class _PreparedLaunch:
 class PreparedSolve(_PreparedLaunch):
     """A fused build+solve bound to fixed device buffers: ``launch()`` costs one
     C call (no allocation, no struct marshalling), so a receding-horizon loop or a
-    benchmark can enqueue steps back-to-back or capture them in a HIP graph.
+    benchmark can enqueue steps back-to-back or capture them in a HIP graph
+    (after one eager launch; ``launch(stream=...)`` and capture and replay are held to the
+    header's stream contract by tests/test_gpu_streams.py).
 
     Update problem data IN PLACE (``problem.initial_state.copy_(x)``) between
     launches; if a tensor of the problem is replaced, call ``rebind()``.

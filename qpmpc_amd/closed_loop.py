@@ -58,7 +58,14 @@ class WIPClosedLoop:
         not offer it. ``periods_per_launch``: with the fused period, ``step(n)`` runs up to that many consecutive periods
         per launch (``mpcqp_wip_periods_batch``: the wavefront that solved period t carries on with period t + 1; the
         loops never interact, so nothing has to meet at a period's end) -- same trajectories bit for bit, without the
-        dispatch gap between the periods. The first period of an episode is always a launch of its own."""
+        dispatch gap between the periods. The first period of an episode is always a launch of its own.
+
+        HIP graphs: with ``reuse_factor`` and ``pipeline_factor`` off and ``periods_per_launch=1`` the steady-state
+        ``step(1)`` makes the same call(s) every period and can be captured once (after the first periods ran eagerly) and
+        replayed: tests/test_gpu_streams.py does so with the fused one-launch period (24 timesteps) and with the two
+        launches per period the loop falls back to where the fused one is not offered (12 timesteps).
+        ``reuse_factor`` switches its flags after the first period and ``pipeline_factor`` alternates ``factor_slot`` with the host-side period count: their periods differ from one
+        another in host-side state, so a captured period is not replayable by construction."""
         import torch
 
         self.pendulum = WheeledInvertedPendulum(nb_timesteps=nb_timesteps, sampling_period=sampling_period)
@@ -229,6 +236,10 @@ class LIPMWalkingLoop:
     sub-steps (:216-236, :311-312) and (4) advances its phase (:329-332). Walkers differ by initial
     phase, support foot, stride lengths and foot size; the model (A, B, C) is shared (stride 0).
     Everything stays on the device; the host only enqueues work.
+
+    HIP graphs: ``step`` is not a call to capture once and replay. The host decides per period what it enqueues -- the
+    first period also writes the problem of the current phase, a warm start is switched on after it --, and with
+    ``fused=False`` the phase and the states are NEW tensors every period, which a captured period would not follow.
     """
 
     def __init__(self, batch: int, strides=None, foot_size=None, index=None, stride_index=None, support=None,

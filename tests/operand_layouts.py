@@ -126,14 +126,34 @@ def make(shape, rows, stage, layout, seed, margin, contractive=False):
     return w, full
 
 
+def ltv(seed, B, nx, nu, N, mk, tight=1.0, rows="cd", stage=True):
+    """qpmpc_amd.workloads.random_ltv; rows "c" / "d" / "cd": state rows, an input box or both; stage: with a stage cost (the
+    workloads of tests/test_gpu_memory_discipline.py, here so that a CPU test can state the same problems)"""
+    from qpmpc_amd.workloads import random_ltv
+
+    rng = np.random.default_rng(seed)
+    w = random_ltv(rng, B, nx, nu, N, mk, tight)
+    if rows == "c":
+        w["D"] = None
+    elif rows == "d":
+        w["C"] = None
+        w["e"] = tight * (0.05 + 0.5 * np.abs(rng.standard_normal(w["e"].shape)))
+    if not stage:
+        w["wx"] = w["targets"] = None
+    return w
+
+
 # ---------------------------------------------------------------------------------------------- the forward launches
 # name -> (shape (nx, nu, N, mk), rows, stage cost, MpcqpSolveOpts flag names, float32, stage-wise entry point, margin, seed base):
 # the routes, flags and smallest shapes of tests/test_gpu_memory_discipline.py, whose docstrings say why each is the smallest
 # that reaches its kernel. Layout i of a route is make(shape, rows, stage, i, seed base + i, margin); margin and seed base are
 # tuned on the CPU oracle (tests/test_operand_layouts_cpu.py: every problem solved, at least 6 of 9 with a binding row).
-def _route(shape, rows="cd", stage=True, flags=(), f32=False, stagewise=False, margin=0.2, seed=1000, contractive=False):
+def route(shape, rows="cd", stage=True, flags=(), f32=False, stagewise=False, margin=0.2, seed=1000, contractive=False):
     return dict(shape=shape, rows=rows, stage=stage, flags=tuple(flags), f32=f32, stagewise=stagewise, margin=margin, seed=seed,
                 contractive=contractive)
+
+
+_route = route
 
 
 # The long horizons (the float32 wide stage-wise kernel at n > 160 and the dense HBM path at BASELINE config 5's shape, that of

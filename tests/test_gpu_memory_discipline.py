@@ -28,7 +28,7 @@ from oracle import condense_np
 import adjoint_np as AN
 import adjoint_stagewise_np as AS
 import arena as AR
-from operand_layouts import f32_view
+from operand_layouts import f32_view, ltv  # noqa: F401  (ltv: the random workloads of this file, NumPy only)
 import tangent_model_np as TM
 import tangent_np as TN
 
@@ -158,22 +158,6 @@ def arena_problem(L, bp, pad=0):
 
 
 # ---------------------------------------------------------------------------------------------- workloads
-def ltv(seed, B, nx, nu, N, mk, tight=1.0, rows="cd", stage=True):
-    """qpmpc_amd.workloads.random_ltv; rows "c" / "d" / "cd": state rows, an input box or both; stage: with a stage cost"""
-    from qpmpc_amd.workloads import random_ltv
-
-    rng = np.random.default_rng(seed)
-    w = random_ltv(rng, B, nx, nu, N, mk, tight)
-    if rows == "c":
-        w["D"] = None
-    elif rows == "d":
-        w["C"] = None
-        w["e"] = tight * (0.05 + 0.5 * np.abs(rng.standard_normal(w["e"].shape)))
-    if not stage:
-        w["wx"] = w["targets"] = None
-    return w
-
-
 _ORACLE = {}
 
 
@@ -188,7 +172,7 @@ def oracle_of(key, w):
 class Forward:
     """mpcqp_build_solve_batch (or mpcqp_stagewise_solve_batch) of a workload with everything in an arena."""
 
-    def __init__(self, w, dtype=None, stagewise=False, max_active=0, query=None, pad=0, order=None, warm=False):
+    def __init__(self, w, dtype=None, stagewise=False, max_active=0, query=None, pad=0, order=None, warm=False, inout=()):
         from qpmpc_amd import workloads as W
 
         _capi, lib, _ = _api()
@@ -204,7 +188,7 @@ class Forward:
         assert rc == 0, rc
         self.ws_bytes = nbytes.value
         L = self.L = Launch()
-        add_problem(L, bp, pad)
+        add_problem(L, bp, pad, inout)  # (inout: operands a call rewrites itself, tests/test_gpu_streams.py)
         L.add("U", "out", bp.dtype, self.B * self.n)
         L.add("lam", "out", bp.dtype, self.B * self.m)
         L.add("status", "out", I32, self.B)

@@ -46,9 +46,10 @@ class ModelCase:
     """A factored model and the per-problem operands of one shared-model workload `w` (A, B, C, D shared; x0, goal, targets, e
     with 1 or B rows, `pad` elements past the packed batch stride) in a guarded arena. The model is factored once, outside the
     arena, from the pseudo-problems of include/mpcqp.h (bounds: w["e_model"], else the first problem's) and copied in as a
-    read-only buffer."""
+    read-only buffer. The operands named in `inout` are reloaded before every run and may be rewritten inside a call
+    (tests/test_gpu_streams.py)."""
 
-    def __init__(self, w, pad=None, dtype=F64, order=None, warm=False, wt=None):
+    def __init__(self, w, pad=None, dtype=F64, order=None, warm=False, wt=None, inout=()):
         from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
 
         _, lib, stream = MD._api()
@@ -81,7 +82,7 @@ class ModelCase:
             rows = np.asarray(w[key]).reshape(w[key].shape[0], -1)
             assert rows.shape[1] == width and rows.shape[0] in (1, B)
             stride = width + int(pad.get(key, 0)) if rows.shape[0] > 1 else 0
-            L.add(key, "in", dtype, data=rows, stride=stride or None)
+            L.add(key, "inout" if key in inout else "in", dtype, data=rows, stride=stride or None)
             ops[key] = (stride, mk if key == "e" else 0)
         L.add("U", "out", dtype, B * self.n)
         L.add("lam", "out", dtype, B * self.m)
