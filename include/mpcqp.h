@@ -246,7 +246,24 @@ typedef struct MpcqpProblem {
                                  it the launch goes where it always went (the workgroup kernel at these sizes); with it,
                                  MPCQP_EUNSUPPORTED outside the envelope (n <= 16 included), in float32, with warm_state or
                                  order, and next to MPCQP_OPT_FORCE_LDS, ONE_ / TWO_ / FOUR_PER_WAVE or SEED_VIOLATED.
-                                 Figures: profiles/onchip32_model.md. */
+                                 Figures: profiles/onchip32_model.md.
+                                 QP given (mpcqp_solve_batch, the kernel's QP mode: packed P, q, G, h come through the LDS image to
+                                 the lanes that own them, then the fused mode's elimination and iteration; replaces
+                                 qpsolvers.solve_problem at qpmpc/solve_mpc.py:43). Envelope: float64, 1 <= n <= 32,
+                                 1 <= m <= 64, cold; P is read in full and taken as symmetric; lam, status and iters may be
+                                 NULL; NO workspace (NULL is accepted whatever mpcqp_solve_workspace_bytes reports). Taken only
+                                 with the flag: without it the launch goes where it always went; with it, MPCQP_EUNSUPPORTED
+                                 and nothing written for n > 32, m > 64, m == 0, float32, an order, a warm_state, and next to
+                                 MPCQP_OPT_FORCE_LDS / _CONDENSED / _GWS / _DENSE_G, ONE_ / TWO_ / FOUR_PER_WAVE, SEED_VIOLATED
+                                 or a *_FACTOR option. With mpcqp_condense_batch in front it is the on-chip route, in two
+                                 launches, for problems of 17 .. 32 variables that the fused mode refuses (nx >= 5, more than
+                                 four rows per step). Where it is faster (MI355X, us per launch, flagged / default route of
+                                 mpcqp_solve_batch on the same problems, profiles/onchip32_qp.md): from seventeen variables up,
+                                 where the default route is the workgroup kernel -- 4096 problems of (n, m) = (17, 33) 212 / 334,
+                                 (24, 48) 309 / 948, (32, 64) 373 / 2362; 1.4-6.9 x at 256, 4096 and 16384 problems. At n <= 16
+                                 it is SLOWER than the one-per-wavefront kernel the default route takes there ((16, 32):
+                                 212 / 86 at 4096 problems, 0.35-0.46 x): the envelope starts at n = 1 so that one route serves
+                                 whatever size a condensed problem has, not because it pays there. */
 
 /* MpcqpSolveOpts.warm_start */
 #define MPCQP_WARM_OPERATOR 1   /* begin from the stored active set AND operator N* (contract: matrices unchanged)          */
@@ -394,7 +411,11 @@ int mpcqp_update_vectors_batch(const MpcqpDims *dims, const MpcqpProblem *proble
  * x[batch*n], lam[batch*m] (multipliers of G u <= h, nullable),
  * status[batch], iters[batch] (nullable). Dual active-set method.
  * A problem with status[b] != 0 gets x[b] = zeros and its status and iters; its lam[b] is undefined. The workspace's initial
- * content is never read. */
+ * content is never read.
+ * MPCQP_OPT_ON_CHIP_32 in opts->flags sends a float64 launch of 1 <= n <= 32, 1 <= m <= 64 to the on-chip kernel of
+ * mpcqp_duo.hip (two problems per wavefront; workspace may be NULL, status may be NULL too) instead of the one-per-wavefront
+ * (n <= 16) and workgroup kernels, and is MPCQP_EUNSUPPORTED, with nothing written, for every other launch (see the flag);
+ * without the flag nothing changes. */
 int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P,
                       const void *q, const void *G, const void *h, int64_t batch,
                       const MpcqpSolveOpts *opts, void *x, void *lam,

@@ -929,7 +929,11 @@ class PreparedModelSolve(_PreparedLaunch):
 
 
 class BatchMPCQP:
-    """Condensed QPs of a batch, kept in HBM (batched ``MPCQP``, mpc_qp.py:21-163)."""
+    """Condensed QPs of a batch, kept in HBM (batched ``MPCQP``, mpc_qp.py:21-163).
+
+    ``BatchMPCQP(problem).solve(flags=_capi.OPT_ON_CHIP_32)`` is the on-chip route (csrc/mpcqp_duo.hip, two problems per
+    wavefront) for float64 problems of 17 .. 32 variables and at most 64 rows that ``solve_mpc_batch`` refuses with the same
+    flag -- ``nx >= 5``, more than four rows per step --: condensed here they are plain dense QPs, solved in a second launch."""
 
     def __init__(self, problem: BatchMPCProblem, keep_propagators: bool = True):
         torch = _torch()
@@ -970,13 +974,18 @@ class BatchMPCQP:
         self._update(problem, False, True)
 
     def solve(self, return_multipliers: bool = False, max_iter=None, feas_tol=None, **opt_kw):
+        """``solve_qp_batch`` on the kept P, q, G, h; ``flags`` as there."""
         return solve_qp_batch(self.P, self.q, self.G, self.h, return_multipliers, max_iter, feas_tol, **opt_kw)
 
 
 def solve_qp_batch(P, q, G, h, return_multipliers: bool = False, max_iter=None, feas_tol=None, **opt_kw):
     """Batched dense QP solve, ``min 1/2 x'Px + q'x s.t. Gx <= h`` per item
     (replaces ``qpsolvers.solve_problem`` at solve_mpc.py:43).
-    Returns (x [B,n], lam [B,m] | None, status [B], iters [B])."""
+    Returns (x [B,n], lam [B,m] | None, status [B], iters [B]).
+
+    ``flags=_capi.OPT_ON_CHIP_32`` solves float64 QPs of ``1 <= n <= 32``, ``1 <= m <= 64`` on chip, two problems per wavefront
+    (csrc/mpcqp_duo.hip), without a workspace; every other launch with the flag -- larger, float32, ``m = 0``, an ``order`` or
+    another dispatch override next to it -- raises ``BackendError``. ``P`` is read in full and taken as symmetric."""
     torch = _torch()
     lib = _capi.load()
     _require_on_gpu(P, q, G, h)
@@ -988,8 +997,9 @@ def solve_qp_batch(P, q, G, h, return_multipliers: bool = False, max_iter=None, 
     x, lam, status, iters = _outputs(Bn, n, m, P.dtype, P.device, return_multipliers)
     opts = _opts(max_iter, feas_tol, **opt_kw)
     nbytes = C.c_size_t(0)
-    _capi.check(lib.mpcqp_solve_workspace_bytes(n, m, _dtype_code(P.dtype), Bn, C.byref(nbytes)),
-                "mpcqp_solve_workspace_bytes")
+    if not (opts.flags & _capi.OPT_ON_CHIP_32):  # (the on-chip kernel takes no workspace, whatever the query -- which sees no flags -- says)
+        _capi.check(lib.mpcqp_solve_workspace_bytes(n, m, _dtype_code(P.dtype), Bn, C.byref(nbytes)),
+                    "mpcqp_solve_workspace_bytes")
     ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=P.device) if nbytes.value else None
     rc = lib.mpcqp_solve_batch(
         n, m, _dtype_code(P.dtype), P.data_ptr(), q.data_ptr(), None if m == 0 else G.data_ptr(),

@@ -773,6 +773,14 @@ int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P, const 
     ka.iters = iters;
     if (int rc = fill_opts(ka, opts, dtype)) return rc;
     if (ka.warm_state) return MPCQP_EUNSUPPORTED;
+    // MPCQP_OPT_ON_CHIP_32: the QP-given mode of the on-chip kernel (mpcqp_duo.hip), float64 inside its envelope, no workspace,
+    // with no other choice of kernel, start or factor next to it (an order and a warm state were refused above)
+    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) {
+        constexpr int kOthers = kOverrideFlags | MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_FOUR_PER_WAVE |
+                                MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR;
+        if (dtype != MPCQP_F64 || !duo_qp_applies(ka) || (ka.opt_flags & kOthers)) return MPCQP_EUNSUPPORTED;
+        return launch_duo_qp(ka, batch, (hipStream_t)stream);
+    }
     if (fits_on_chip(ka, false, false, MODE_SOLVE, dtype))
         return run_solver<MODE_SOLVE>(ka, false, false, dtype, batch, (hipStream_t)stream);
     return run_gws_solve(ka, dtype, batch, workspace, workspace_bytes, (hipStream_t)stream);

@@ -41,6 +41,12 @@
 // (h = e - Hx x0, w = Wx x0 - Wg goal - Wt targets); nx and the number of rows per step are run-time numbers there (NX is not
 // read), and the bounds e come per problem or from the model. From `int status = MPCQP_MAX_ITER` on both modes run the same
 // statements.
+//
+// QP given (NX = 0, MODEL = false; mpcqp_solve_batch with MPCQP_OPT_ON_CHIP_32): the dense strictly convex QPs that replace
+// qpsolvers.solve_problem at qpmpc/solve_mpc.py:43, 1 <= n <= 32 and 1 <= m <= 64, packed per problem. The build is replaced by
+// loads: P, then the rows of G, come through the 32-row image to the lanes that own them, padded as the fused build pads
+// (identity rows and columns of P beyond n, zero rows and columns of G); elimination, triangular product and everything after
+// them are the fused mode's statements. P is read in full and taken as symmetric. Figures: profiles/onchip32_qp.md.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -178,6 +184,7 @@ __global__ void __launch_bounds__(64, 1)
     T h0, h1;
     bool notpd = false;
     T y0m = T(0);  // MODEL: y0 = -w of this lane
+    constexpr bool QP = !MODEL && NX == 0;  // the QP is given: P, q, G, h in the first four operand slots
     // ---------------------------------------------------------------- shared model (mpc_qp.py:129-163 on a factored model)
     // What mpcqp_factor_model wrote replaces the build, the elimination and the triangular product: the rows of M and of L^-T
     // are loaded (row stride n, which may be odd: no 16-byte loads), h = e - Hx x0 and w = Wx x0 - Wg goal - Wt targets come from
@@ -267,8 +274,55 @@ __global__ void __launch_bounds__(64, 1)
         }
         wave_sync();  // (the staged vectors are read: the scratch image is free again; the L^-T image is written)
     }
+    // ---------------------------------------------------------------- QP given (the call at solve_mpc.py:43)
+    // Packed P [n n], q [n], G [m n], h [m] of this problem. The 32 lanes of the half read 32 consecutive elements of a row
+    // (n may be odd: 8-byte loads), row after row with no index to divide, into the 32-row image; then every lane takes its own
+    // row from there: P, G rows 0 .. 31, G rows 32 .. 63 (the fused build's flush). A lane without a column repeats column n - 1, a
+    // row beyond the last one repeats the last one, and both keep the padding value: no load leaves the problem's arrays.
+    if constexpr (QP) {
+        const T *Pg = gA + prob * (int64_t)(n * n), *qg = gB + prob * (int64_t)n;
+        const T *Gg = gC + prob * (int64_t)(m * n), *hg = gD + prob * (int64_t)m;
+        const bool col = hl < n;
+        const int cc = col ? hl : n - 1;
+        const int c1 = hl + 32;
+        // (all the loads of a stage are issued before its first store to the image)
+        auto stage = [&](const T *src, int rows, int first, bool ident) {
+            T t[NV];
+#pragma unroll
+            for (int r = 0; r < NV; ++r) {
+                const int rr = first + r < rows ? first + r : rows - 1;
+                t[r] = src[(size_t)rr * n + cc];
+            }
+#pragma unroll
+            for (int r = 0; r < NV; ++r) {
+                const T pad = (ident && hl == r) ? T(1) : T(0);
+                Gimg[r * LDG + hl] = (col && first + r < rows) ? t[r] : pad;
+            }
+        };
+        auto take = [&](T (&dst)[NV]) {
+            wave_sync();
+            ld32(dst, Gimg + hl * LDG);
+            wave_sync();
+        };
+        stage(Pg, n, 0, true);
+        const T qv = qg[cc];
+        const T hv0 = hg[isc0 ? hl : m - 1], hv1 = hg[isc1 ? c1 : m - 1];
+        take(Pr);
+        stage(Gg, m, 0, false);
+        take(RM0);
+        if (m > 32) {
+            stage(Gg, m, 32, false);
+            take(RM1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) RM1[k] = T(0);
+        }
+        qa = col ? qv : T(0);
+        h0 = isc0 ? hv0 : INF;
+        h1 = isc1 ? hv1 : INF;
+    }
     // ---------------------------------------------------------------- build (mpc_qp.py:53-114)
-    if constexpr (!MODEL) {
+    if constexpr (!MODEL && !QP) {
         constexpr int nx = NX;
         const int nu = ka.nu, N = ka.N, mk = ka.mk;
         const T *A = gA + prob * ka.A.batch_stride;
@@ -422,6 +476,7 @@ __global__ void __launch_bounds__(64, 1)
         T LT[NV];  // row hl of the identity -> of L^-T
 #pragma unroll
         for (int k = 0; k < NV; ++k) LT[k] = (hl == k) ? T(1) : T(0);
+        T pmin = T(1);  // QP: the smallest pivot so far, -1 behind one that is not positive
         cb[hl] = Pr[0];
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -435,7 +490,10 @@ __global__ void __launch_bounds__(64, 1)
                 cv[2 * g + 1] = t.y;
             }
             const T piv = cv[j];
-            if (!(piv > T(0))) notpd = true;
+            if constexpr (QP)  // (one running minimum instead of 32 pivots kept for 32 comparisons behind the triangular product)
+                pmin = fmin(pmin, piv > T(0) ? piv : T(-1));
+            else if (!(piv > T(0)))
+                notpd = true;
             const T rinv = rsqrt(piv);
             const T ri2 = rinv * rinv;
             const T tP = Pr[j] * ri2, tL = LT[j] * ri2;
@@ -453,6 +511,7 @@ __global__ void __launch_bounds__(64, 1)
             LTimg[hl * LDG + j] = LT[j] * rinv;
             __builtin_amdgcn_sched_barrier(0);  // (a step's updates finish before the next column arrives: register pressure)
         }
+        if constexpr (QP) notpd = !(pmin > T(0));
     }
     wave_sync();
     // M_i = G_i L^-T: row l of L^-T (zero before column l) is broadcast from its image, once for both rows of a lane
@@ -805,19 +864,20 @@ __global__ void __launch_bounds__(64, 1)
 
 // ------------------------------------------------------------ host side
 // model: the carve of a shared-model launch -- no staged operands; x0, goal and the targets (N nx of them) share the scratch image
-static Lay make_lay(const KernelArgs &ka, bool model = false)
+// qp: the carve of a QP-given launch -- nothing is staged beside the image: the image, the column-sum scratch, the vectors
+static Lay make_lay(const KernelArgs &ka, bool model = false, bool qp = false)
 {
     Lay L{};
     auto al = [](int c) { return (c + 3) & ~3; };
     L.off_X = 0;
     L.off_W = NV * LDG;
-    if (!model) {
+    if (!model && !qp) {
         L.nA = (ka.A.step_stride ? ka.N : 1) * ka.nx * ka.nx;
         L.nB = (ka.B.step_stride ? ka.N : 1) * ka.nx * ka.nu;
         L.nC = ka.C.ptr ? (ka.C.step_stride ? ka.N : 1) * ka.mk * ka.nx : 0;
         L.nD = ka.D.ptr ? (ka.D.step_stride ? ka.N : 1) * ka.mk * ka.nu : 0;
     }
-    const int w_build = model ? 2 * al(ka.nx) + al(ka.N * ka.nx) : al(L.nA) + al(L.nB) + al(L.nC) + al(L.nD) + ka.nx * NV;
+    const int w_build = qp ? 0 : model ? 2 * al(ka.nx) + al(ka.N * ka.nx) : al(L.nA) + al(L.nB) + al(L.nC) + al(L.nD) + ka.nx * NV;
     const int w_main = NV * LDW;
     L.off_v = L.off_W + al(w_build > w_main ? w_build : w_main);
     L.per = al(L.off_v + MMAX + 4 * NV + NV + 4);
@@ -831,6 +891,8 @@ bool duo_applies(const KernelArgs &ka)
 }
 // ... and of its shared-model mode: the operands' layout no longer matters (any nx, any number of rows per step)
 bool duo_model_applies(const KernelArgs &ka) { return ka.n >= 17 && ka.n <= NV && ka.m >= 1 && ka.m <= MMAX && ka.mk >= 1; }
+// ... and of its QP-given mode: dense QPs from one variable up (below seventeen they are padded like the last lanes of n = 17)
+bool duo_qp_applies(const KernelArgs &ka) { return ka.n >= 1 && ka.n <= NV && ka.m >= 1 && ka.m <= MMAX; }
 
 template <int NX> static int launch_duo_t(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
@@ -866,6 +928,21 @@ int launch_duo_model(const KernelArgs &ka, int64_t batch, hipStream_t st)
                        (const double *)nullptr, (const double *)nullptr, (const double *)ka.e.ptr, (const double *)ka.x0.ptr,
                        (const double *)ka.goal.ptr, (const double *)ka.targets.ptr, (double *)ka.U, (double *)ka.lam, ka.status,
                        ka.iters, ka, L, batch);
+    return (int)hipGetLastError();
+}
+
+// QP given (ka.P, ka.q, ka.G, ka.h, packed per problem, in the first four arguments). The carve is the shared-model one without
+// its staged vectors (37.1 KB per wavefront): below the 48 KB a launch may ask for without setting a function attribute.
+int launch_duo_qp(const KernelArgs &ka, int64_t batch, hipStream_t st)
+{
+    const Lay L = make_lay(ka, false, true);
+    const size_t bytes = (size_t)L.per * 2 * sizeof(double);
+    static_assert((size_t)(NV * LDG + NV * LDW + MMAX + 5 * NV + 4 + 3) * 2 * sizeof(double) <= 48 * 1024, "the QP carve needs no attribute");
+    const int64_t waves = (batch + 1) / 2;
+    hipLaunchKernelGGL((mpcqp_duo_kernel<0, false>), dim3((unsigned)waves), dim3(64), bytes, st, (const double *)ka.P,
+                       (const double *)ka.q, (const double *)ka.G, (const double *)ka.h, (const double *)nullptr,
+                       (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, (double *)ka.U, (double *)ka.lam,
+                       ka.status, ka.iters, ka, L, batch);
     return (int)hipGetLastError();
 }
 

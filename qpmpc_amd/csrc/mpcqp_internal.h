@@ -235,6 +235,10 @@ int launch_duo(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // any nx and any number of rows per step, float64, cold
 bool duo_model_applies(const KernelArgs &ka);
 int launch_duo_model(const KernelArgs &ka, int64_t batch, hipStream_t st);
+// ... and its QP-given mode (ka.P, ka.q, ka.G, ka.h, packed per problem; mpcqp_solve_batch with the flag): 1 <= n <= 32,
+// 1 <= m <= 64, float64, cold, no workspace
+bool duo_qp_applies(const KernelArgs &ka);
+int launch_duo_qp(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // small-problem kernel (mpcqp_w64.hip): one problem per wavefront
 bool w64_eligible(const KernelArgs &ka, int mode, int dtype);
 int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStream_t st);
