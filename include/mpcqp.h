@@ -120,7 +120,9 @@ extern "C" {
 /* Problem dimensions and cost weights (mpc_problem.py:88-139).
  * n = N*nu decision variables, m = N*mk inequality rows. Problems whose
  * per-step row count varies are padded by the host to mk rows with C=D=0 and
- * e=+1e30 (an inequality that can never be active). */
+ * e=+1e30 (an inequality that can never be active). Held, route by route, against the
+ * problem with those rows deleted by tests/test_gpu_padded_rows.py (forward kernels, shared-model
+ * solves, warm starts, derivative exports: lam = 0 and zero gradients on such rows). */
 typedef struct MpcqpDims {
     int32_t nx;    /* state_dim                                   */
     int32_t nu;    /* input_dim                                   */
@@ -318,7 +320,9 @@ typedef struct MpcqpSolveOpts {
      * dimensions) is refused with MPCQP_EWORKSPACE before anything is launched. Ignored when warm_state is NULL. */
     size_t warm_state_bytes;
     /* MPCQP_WARM_ACTIVE_SET (ABI 8): stored row id r is taken as row r - warm_shift of this launch's problem; ids that
-     * fall off the horizon's start (or name a padded row) are dropped. 0: the rows kept their places. */
+     * fall off the horizon's start (or name a padded row) are dropped. 0: the rows kept their places.
+     * (tests/test_gpu_padded_rows.py::test_small_kernel_warm_active_set_shifted_onto_padding and
+     * ::test_wide_stagewise_active_set_record_shifted_onto_padding: stored ids that land on padded rows.) */
     int32_t warm_shift;
     int32_t reserved_;
     /* Pairing order (ABI 9), NULL = natural: DEVICE array of `batch` int32, a permutation of 0 .. batch-1. The small-problem

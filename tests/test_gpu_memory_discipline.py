@@ -204,7 +204,7 @@ class Forward:
         self.cp = arena_problem(L, bp, pad)
         print(f"    batch {self.B} n {self.n} m {self.m}: workspace {self.ws_bytes} bytes")
 
-    def run(self, byte, flags=0, lam=True, iters=True, warm_start=0, keep=(), max_iter=0, factor_slot=0):
+    def run(self, byte, flags=0, lam=True, iters=True, warm_start=0, keep=(), max_iter=0, factor_slot=0, warm_shift=0):
         _capi, lib, stream = _api()
         L = self.L
         o = _capi.SolveOpts()
@@ -213,6 +213,7 @@ class Forward:
             o.order = L.ptr("order")
         if L.has("warm"):
             o.warm_state, o.warm_state_bytes, o.warm_start = L.ptr("warm"), L.nbytes("warm"), int(warm_start)
+            o.warm_shift = int(warm_shift)
         tail = (L.ptr("U"), L.ptr("lam") if lam else None, L.ptr("status"), L.ptr("iters") if iters else None, L.ptr("ws"),
                 self.ws_bytes, stream())
 

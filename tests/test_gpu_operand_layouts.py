@@ -216,12 +216,19 @@ def test_plan_vjp_layouts(kind, shape, layout):
     """mpcqp_plan_vjp_batch / _vjp_model_batch / _vjp_stagewise_batch as tests/test_gpu_memory_discipline.py::test_plan_vjp_exports
     sets them up, the operands in the stored, padded layout; every gradient per problem against the NumPy restatement on the
     materialised problem (the sum over a shared operand is the caller's)."""
+    plan_vjp(kind, shape, _diff_case(shape, layout), OL.pads_of(layout), layout)
+
+
+def plan_vjp(kind, shape, case, pad, layout):
+    """the launch and the comparisons of test_plan_vjp_layouts on `case` = (w, full, U, lam, status) with batch-stride padding
+    `pad` (`layout` names the case in a failure); returns the gradients {operand: [B, size]} and the statuses
+    (tests/test_gpu_padded_rows.py runs its own cases through this)"""
     from qpmpc_amd import _capi, autodiff
     from qpmpc_amd import workloads as W
 
     _, lib, stream = MD._api()
     nx, nu, N, mk = shape
-    w, full, U, lam, status = _diff_case(shape, layout)
+    w, full, U, lam, status = case
     bp = W.to_batch_problem(w)
     B, n = OL.BATCH, N * nu
     assert bp.batch_size == B and (status == 0).sum() * 2 >= B, status
@@ -238,7 +245,6 @@ def test_plan_vjp_layouts(kind, shape, layout):
     assert rc == 0
     sizes = SIZES(*shape)
     outs = list(sizes)[:4] if kind == "condensed" else list(sizes)
-    pad = OL.pads_of(layout)
     L = Launch()
     MD.add_problem(L, bp, pad)
     for key, a in (("lam", lam), ("U", U), ("gU", gU), ("gX", gX)):
@@ -276,6 +282,7 @@ def test_plan_vjp_layouts(kind, shape, layout):
         ref = AN.vjp(w1, lam[b], gU[b], gX[b]) if kind == "condensed" else AS.stagewise_vjp(w1, lam[b], gU[b], gX[b], U[b])
         for k in outs:
             close(got[k], ref[k], (kind, layout, b, k))
+    return {k: f["g_" + k].reshape(B, -1) for k in outs}, vst
 
 
 JVP = [(model, sw, shape, i) for i in DIFF_LAYOUTS for model, sw, shape in
@@ -288,16 +295,23 @@ def test_plan_jvp_layouts(model, stagewise, shape, layout):
     """mpcqp_plan_jvp_batch / _jvp_stagewise_batch / _jvp_model_batch / _jvp_model_stagewise_batch as
     tests/test_gpu_memory_discipline.py::test_plan_jvp_exports sets them up, three tangents, the operands in the stored, padded
     layout; dU and dX per problem against the NumPy restatement on the materialised problem."""
+    plan_jvp(model, stagewise, shape, _diff_case(shape, layout), OL.pads_of(layout), layout)
+
+
+def plan_jvp(model, stagewise, shape, case, pad, layout, tan=None):
+    """the launch and the comparisons of test_plan_jvp_layouts on `case` = (w, full, U, lam, status), with its three random
+    tangents or with `tan` ({operand: [B, 3, ...]}); returns dU, dX [B, 3, -1] and the statuses (tests/test_gpu_padded_rows.py
+    runs its own cases through this)"""
     from qpmpc_amd import _capi, autodiff
     from qpmpc_amd import workloads as W
 
     _, lib, stream = MD._api()
     nx, nu, N, mk = shape
-    w, full, U, lam, status = _diff_case(shape, layout)
+    w, full, U, lam, status = case
     bp = W.to_batch_problem(w)
     B, n, T = OL.BATCH, N * nu, 3
     assert bp.batch_size == B and (status == 0).sum() * 2 >= B, status
-    tan = MD._tangents(full, B, T, np.random.default_rng(4), model)
+    tan = MD._tangents(full, B, T, np.random.default_rng(4), model) if tan is None else tan
     dims, nbytes = autodiff._vjp_dims(bp), C.c_size_t(0)
     ka = MD.max_active_of(lam, status, n)
     query = {(False, False): lib.mpcqp_plan_jvp_workspace_bytes, (True, False): lib.mpcqp_plan_jvp_model_workspace_bytes,
@@ -305,7 +319,6 @@ def test_plan_jvp_layouts(model, stagewise, shape, layout):
              (True, True): lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes}[(model, stagewise)]
     extra = (ka, T) if stagewise else (T,)
     assert query(C.byref(dims), B, *extra, C.byref(nbytes)) == 0
-    pad = OL.pads_of(layout)
     L = Launch()
     MD.add_problem(L, bp, pad)
     L.add("lam", "in", F64, data=lam)
@@ -347,6 +360,7 @@ def test_plan_jvp_layouts(model, stagewise, shape, layout):
             ref = TM.jvp_model(w1, U[b], lam[b], one) if model else TN.jvp(w1, lam[b], one)
             close(dU[b, t], ref["U"], (layout, b, t, "dU"))
             close(dX[b, t], ref["X"], (layout, b, t, "dX"))
+    return dU, dX, vst
 
 
 # ---------------------------------------------------------------------------------------------- condensing, vectors, roll-out
