@@ -86,7 +86,8 @@ void fill_args(KernelArgs &ka, const MpcqpDims *d, const MpcqpProblem *p)
     }
 }
 
-int fill_opts(KernelArgs &ka, const MpcqpSolveOpts *o, int dtype, bool order_ok = false)
+// (what a launch may not combine is refused by refusal(), which every export calls right after this)
+int fill_opts(KernelArgs &ka, const MpcqpSolveOpts *o, int dtype)
 {
     ka.max_iter = (o && o->max_iter > 0) ? o->max_iter : 10 * (ka.n + ka.m) + 10;
     ka.tol = (o && o->feas_tol > 0.0) ? o->feas_tol : (dtype == MPCQP_F64 ? 1e-12 : 1e-5);
@@ -99,7 +100,6 @@ int fill_opts(KernelArgs &ka, const MpcqpSolveOpts *o, int dtype, bool order_ok 
     if (ka.warm_start < 0 || ka.warm_start > MPCQP_WARM_ACTIVE_SET) return MPCQP_EINVAL;
     ka.warm_state_bytes = o->warm_state ? o->warm_state_bytes : 0;
     ka.factor_slot = o->factor_slot & 1;
-    if (o->order && !order_ok) return MPCQP_EUNSUPPORTED;  // (only mpcqp_build_solve_batch's small-problem kernel takes one)
     ka.order = o->order;
     return 0;
 }
@@ -122,6 +122,14 @@ bool force_dense_g(int fl) { return fl & MPCQP_OPT_FORCE_DENSE_G; }
 // the overrides that take a launch off the automatic choice of kernel (the cross-check tests of the kernels)
 constexpr int kOverrideFlags =
     MPCQP_OPT_FORCE_LDS | MPCQP_OPT_FORCE_GWS | MPCQP_OPT_FORCE_DENSE_G | MPCQP_OPT_FORCE_CONDENSED | MPCQP_OPT_ONE_PER_WAVE;
+// the flags by which a launch names its small-problem kernel or its start itself
+constexpr int kChoiceFlags =
+    MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_FOUR_PER_WAVE | MPCQP_OPT_SEED_VIOLATED;
+// what a launch keeps of, or takes from, the stage-wise kernels' factor
+constexpr int kFactorFlags = MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR;
+// MPCQP_OPT_ON_CHIP_32 in the fused and the QP-given export: no other choice of kernel, start or factor next to it (the
+// shared-model exports hold it to kChoiceFlags only: the other flags have no meaning there and are ignored as ever)
+constexpr int kOnChip32Alone = kOverrideFlags | kChoiceFlags | kFactorFlags;
 // every combination of overrides a launch may carry: the workspace queries, which see no opts, report the
 // largest amount any of them needs
 const int kFlagVariants[] = {0, MPCQP_OPT_FORCE_LDS, MPCQP_OPT_FORCE_GWS, MPCQP_OPT_FORCE_DENSE_G, MPCQP_OPT_FORCE_CONDENSED};
@@ -181,7 +189,7 @@ int64_t al256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 KernelArgs second_opinion_args(const KernelArgs &ka)
 {
     KernelArgs kb = ka;
-    kb.opt_flags = (ka.opt_flags | kOptSecondOpinion) & ~(MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR);
+    kb.opt_flags = (ka.opt_flags | kOptSecondOpinion) & ~kFactorFlags;
     kb.warm_state = nullptr;
     kb.warm_state_bytes = 0;
     kb.warm_start = 0;
@@ -250,12 +258,10 @@ bool fits_on_chip(const KernelArgs &ka, bool stepA, bool stepB, int mode, int dt
     return layout_for(ka, stepA, stepB, mode, dtype, L) == 0;
 }
 
-// Solve QPs given in HBM (ka.P/q/G/h) with the solver arrays in the workspace.
-int run_gws_solve(KernelArgs ka, int dtype, int64_t batch, void *ws, size_t ws_bytes, hipStream_t st)
+// Solve QPs given in HBM (ka.P/q/G/h) with the solver arrays in the workspace (n <= 256 and the workspace's size: route()).
+int run_gws_solve(KernelArgs ka, int dtype, int64_t batch, void *ws, hipStream_t st)
 {
-    if (ka.n > 256) return MPCQP_ETOOLARGE;
     const size_t esz = elem_size(dtype);
-    if (!ws || ws_bytes < solver_ws_elems(ka.n, ka.m, dtype, ka.opt_flags) * esz * (size_t)batch) return MPCQP_EWORKSPACE;
     if (use_bigsolve(ka.n, ka.m, dtype, ka.opt_flags)) {
         // L^-1 packed in LDS, lazy rows of M; needs G transposed (coalesced slack updates)
         void *GT = ws;
@@ -269,26 +275,12 @@ int run_gws_solve(KernelArgs ka, int dtype, int64_t batch, void *ws, size_t ws_b
     return dispatch_gws_solve(ka, L, dtype, batch, st);
 }
 
+// the workgroup kernel with everything in LDS (the shared-model mode carves like the solver: the model stays in HBM)
 template <int MODE>
-int run_solver(const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, hipStream_t st)
+int run_lds(const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, hipStream_t st)
 {
-    // on request, inside its envelope (mpcqp_build_solve_batch has checked both): 17 .. 32 variables, two problems per wavefront
-    if (MODE == MODE_FUSED && (ka.opt_flags & MPCQP_OPT_ON_CHIP_32)) return dtype == MPCQP_F64 && duo_applies(ka) ? launch_duo(ka, batch, st) : MPCQP_EUNSUPPORTED;
-    if (!force_lds(ka.opt_flags)) {
-        // (nx = 2 and nx > 4 have no two-per-wavefront instantiation: the four-per-wavefront kernel takes them where it pays -- the general
-        // layouts and nx > 4 at every batch size, the lean layout of nx = 2 from more than two problems per SIMD --, on its own)
-        // (more than 32 rows at n <= 16: the four-rows-per-lane copy of that kernel, at every batch size -- the workgroup / one-per-wavefront
-        // kernels it replaces there are 5-9 x slower)
-        if (MODE == MODE_FUSED && dtype == MPCQP_F64 && !(ka.opt_flags & MPCQP_OPT_ONE_PER_WAVE) && quad4_applies(ka)) return launch_quad4(ka, batch, st);
-        if (MODE == MODE_FUSED && dtype == MPCQP_F64 && !(ka.opt_flags & MPCQP_OPT_ONE_PER_WAVE) && (ka.nx == 2 || ka.nx > 4) && quad_eligible(ka, batch))
-            return launch_quad(ka, batch, st);
-        if (!(ka.opt_flags & MPCQP_OPT_ONE_PER_WAVE) && pair_eligible(ka, MODE, dtype)) return launch_pair(ka, batch, st);
-        if (ka.warm_state) return MPCQP_EUNSUPPORTED;
-        if (w64_eligible(ka, MODE, dtype)) return launch_w64(ka, MODE, dtype, batch, st);
-    }
-    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
     Layout L;
-    int rc = layout_for(ka, stepA, stepB, MODE, dtype, L);
+    int rc = layout_for(ka, stepA, stepB, MODE == MODE_MODEL ? MODE_SOLVE : MODE, dtype, L);
     if (rc) return rc;
     return dispatch_lds<MODE>(ka, L, dtype, batch, st);
 }
@@ -355,22 +347,30 @@ int64_t operand_elems(const MpcqpOperand &op, int64_t block, int N, int64_t batc
 
 // ---- The dispatch table. route() decides, for one launch, which path runs, with how many slots, and the workspace that
 // path needs, laid out. The launch entry points follow it, and the size queries report the largest route over what they
-// cannot see (the override flags, the operands' bulk). A new path is one entry here. The choice among the on-chip kernels (quad4 / quad / pair / w64 / LDS) needs no
-// workspace and depends on the batch size and the device: it stays in run_solver.
-// Paths: Refused (Route::rc), OnChip (the condensed on-chip kernels, run_solver), Narrow (narrow stage-wise kernel, then the wide
-// one as its second opinion where that applies), Wide, Mid (mid-size condensed kernel), General (general stage-wise kernel), the
-// dense HBM-resident path with G applied through the roll-out (DenseStruct) or formed (DenseGws), and Promote (promote_f32).
+// cannot see (the override flags, the operands' bulk). A new path or kernel is one entry here. What a launch may not combine is
+// refused by refusal(), before the route is made (and, for the rules that read the route, after).
+// Paths: Refused (Route::rc), OnChip (no workspace: Route::kernel names the launcher), Narrow (narrow stage-wise kernel, then the
+// wide one as its second opinion where that applies), Wide, Mid (mid-size condensed kernel), General (general stage-wise kernel),
+// the dense HBM-resident path with G applied through the roll-out (DenseStruct) or formed (DenseGws; for a QP that is given:
+// Kernel::GwsSolve alone), and Promote (promote_f32).
 enum class Path { Refused, OnChip, Narrow, Wide, Mid, General, DenseStruct, DenseGws, Promote };
+// The launchers behind Path::OnChip, one value each: launch_quad4, launch_quad, launch_pair, launch_w64 and the workgroup kernel
+// (run_lds) in their modes, launch_duo and its shared-model and QP-given modes, launch_quad_model, launch_pair_model; and
+// run_gws_solve for a given QP that does not fit on chip. None: the path is the launcher.
+enum class Kernel { None, Quad4, Quad, Pair, W64Fused, W64Solve, W64Model, LdsFused, LdsSolve, LdsModel, Duo, DuoModel, DuoQp, QuadModel, PairModel, GwsSolve };
 
 struct Entry {
-    enum Kind { BUILD_SOLVE, STAGEWISE, WIP_PERIODS } kind = BUILD_SOLVE;
+    // mpcqp_build_solve_batch, mpcqp_stagewise_solve_batch, mpcqp_wip_periods_batch, the shared-model solves, mpcqp_solve_batch
+    enum Kind { BUILD_SOLVE, STAGEWISE, WIP_PERIODS, MODEL, QP_GIVEN } kind = BUILD_SOLVE;
     int max_active = 0;                  // STAGEWISE: slots asked for (<= 0: the kernel's default)
     bool general = false, wide = false;  // STAGEWISE: MPCQP_OPT_STAGE_GENERAL / MPCQP_OPT_STAGE_WIDE
     bool bulky = false;                  // BUILD_SOLVE size queries: operands too bulky for the mid-size kernel's LDS
+    bool own_e = false;                  // MODEL: bounds per problem (mpcqp_solve_model_bounds_batch with e)
 };
 
 struct Route {
     Path path = Path::Refused;
+    Kernel kernel = Kernel::None;
     int rc = 0;         // Refused: the launch's return code; Promote: that of the float64 size query
     int maxq = 0;       // slots of the stage-wise kernel
     int maxq2 = 0;      // Narrow: slots of the second opinion (0: no second opinion)
@@ -379,7 +379,9 @@ struct Route {
     size_t inner = 0;   // Promote: workspace of the float64 launch, after the copies
 };
 
-Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e);
+// (simds: for the batch-size rule of the four-per-wavefront kernels. A launch hands over SimdCount{}, which asks the device on first
+// use; the size queries a constant, since no on-chip route needs a workspace)
+Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e, SimdCount simds = SimdCount{0});
 
 bool promote_f32(const KernelArgs &ka, int dtype)
 {
@@ -403,10 +405,77 @@ bool promote_f32(const KernelArgs &ka, int dtype)
     return p == Path::Narrow || p == Path::Wide || p == Path::Mid || fits_on_chip(ka, true, true, MODE_FUSED, MPCQP_F64);
 }
 
-Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
+// Every refusal that reads the options: flag, order and warm-state combinations, the envelope of MPCQP_OPT_ON_CHIP_32, a kernel
+// asked for by name where it does not apply. Without a route: the rules that need none (right after fill_opts); with the launch's
+// route: the rules that read it. Where two rules refuse one launch the code tells which came first, so each kind keeps the order
+// its export always had (tests/test_refusal_codes.py).
+int warm_kind(const Route &r);
+int refusal(const KernelArgs &ka, int dtype, const Entry &e, const Route *r = nullptr)
+{
+    const int fl = ka.opt_flags;
+    if (r) {
+        if (e.kind != Entry::BUILD_SOLVE) return 0;
+        // a warm state: on a kernel that keeps a record, and row ids (MPCQP_WARM_ACTIVE_SET) not on the narrow stage-wise kernel, whose
+        // record is of its own kind. FORCE_LDS / ONE_PER_WAVE at the pair kernel's sizes is left to the export, which refuses it after
+        // the record's size (kept apart: refused here, a short record would answer EUNSUPPORTED instead of EWORKSPACE)
+        if (ka.warm_state && !(r->path == Path::OnChip && pair_eligible(ka, MODE_FUSED, dtype))) {
+            const int kind = warm_kind(*r);
+            if (kind == MPCQP_WARM_KIND_NONE || (ka.warm_start == MPCQP_WARM_ACTIVE_SET && kind == MPCQP_WARM_KIND_STAGE)) return MPCQP_EUNSUPPORTED;
+        }
+        if ((fl & MPCQP_OPT_PIPELINE_FACTOR) && !(r->path == Path::Narrow && stage_pipeline_supported(ka, dtype))) return MPCQP_EUNSUPPORTED;
+        return 0;
+    }
+    switch (e.kind) {
+    case Entry::BUILD_SOLVE: {
+        // (MPCQP_F64: float32 launches of the small-problem kernels' size arrive here converted)
+        auto pairs = [&] { return pair_eligible(ka, MODE_FUSED, MPCQP_F64); };
+        // a pairing order: cold launches of the small-problem fused kernel
+        if (ka.order && (ka.warm_state || (fl & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)) || !pairs())) return MPCQP_EUNSUPPORTED;
+        // four problems per wavefront by name: no other kernel named, and one of those kernels applies (nx = 3, 4 reach the one with
+        // two rows per lane from the pair kernel's sizes only)
+        if ((fl & MPCQP_OPT_FOUR_PER_WAVE) &&
+            ((fl & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE)) ||
+             !(quad4_applies(ka) || (quad_applies(ka) && (ka.nx == 2 || ka.nx > 4 || pairs())))))
+            return MPCQP_EUNSUPPORTED;
+        // 17 .. 32 variables on chip by name: cold launches inside the kernel's envelope, float64 (a float32 launch is converted,
+        // promote_f32, and arrives here again in float64 with the flag)
+        if ((fl & MPCQP_OPT_ON_CHIP_32) && (!duo_applies(ka) || ka.warm_state || ka.order || (fl & kOnChip32Alone) ||
+                                           (dtype != MPCQP_F64 && !promote_f32(ka, dtype))))
+            return MPCQP_EUNSUPPORTED;
+        return 0;
+    }
+    case Entry::STAGEWISE: return (ka.order || ka.warm_state) ? MPCQP_EUNSUPPORTED : 0;
+    case Entry::WIP_PERIODS: return ka.order ? MPCQP_EUNSUPPORTED : 0;
+    case Entry::MODEL: {
+        if (ka.warm_state) return MPCQP_EUNSUPPORTED;
+        const bool small = pair_eligible(ka, MODE_MODEL, dtype);
+        // (a pairing order: the pair kernel's model mode only)
+        if (ka.order && ((fl & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE)) || !small)) return MPCQP_EUNSUPPORTED;
+        // (the four-per-wavefront kernel has no seed steps: asked for by name, it is refused by name)
+        if ((fl & MPCQP_OPT_FOUR_PER_WAVE) && ((fl & kChoiceFlags & ~MPCQP_OPT_FOUR_PER_WAVE) || !small)) return MPCQP_EUNSUPPORTED;
+        // (an argument check, kept at its place between the rules: next to an order or FOUR_PER_WAVE such a launch is EUNSUPPORTED)
+        if (e.own_e && ka.m < 1) return MPCQP_EINVAL;
+        // 17 .. 32 variables on chip (mpcqp_duo.hip, its shared-model mode): float64 inside the kernel's envelope, with no pairing order
+        // and no other choice of kernel or start. Bounds per problem past sixteen variables: nothing else serves them, with or without
+        // the flag; the model's own bounds: by name only
+        const bool on_chip_32 = dtype == MPCQP_F64 && duo_model_applies(ka) && !ka.order && !(fl & kChoiceFlags);
+        if ((e.own_e ? !small : (fl & MPCQP_OPT_ON_CHIP_32)) && !on_chip_32) return MPCQP_EUNSUPPORTED;
+        return 0;
+    }
+    case Entry::QP_GIVEN:
+        if (ka.order || ka.warm_state) return MPCQP_EUNSUPPORTED;
+        // the QP-given mode of the on-chip kernel (mpcqp_duo.hip), by name: float64 inside its envelope
+        if ((fl & MPCQP_OPT_ON_CHIP_32) && (dtype != MPCQP_F64 || !duo_qp_applies(ka) || (fl & kOnChip32Alone))) return MPCQP_EUNSUPPORTED;
+        return 0;
+    }
+    return 0;
+}
+
+Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e, SimdCount simds)
 {
     Route r;
     const size_t nb = (size_t)batch, esz = elem_size(dtype);
+    const int fl = ka.opt_flags;
     auto refuse = [&](int rc) {  // (r.path is still Path::Refused)
         r.rc = rc;
         return r;
@@ -429,7 +498,31 @@ Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
         }
         return r;
     };
+    auto on_chip = [&](Kernel k) {
+        r.kernel = k;
+        return take(Path::OnChip, 0, 0);
+    };
+    const bool per_wave_ok = !(fl & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE));  // (no flag against two or four problems per wavefront)
     switch (e.kind) {
+    case Entry::QP_GIVEN:  // (refusal() holds MPCQP_OPT_ON_CHIP_32 to the kernel's envelope, here and below)
+        if (fl & MPCQP_OPT_ON_CHIP_32) return on_chip(Kernel::DuoQp);
+        if (fits_on_chip(ka, false, false, MODE_SOLVE, dtype))
+            return on_chip(!force_lds(fl) && w64_eligible(ka, MODE_SOLVE, dtype) ? Kernel::W64Solve : Kernel::LdsSolve);
+        if (ka.n > 256) return refuse(MPCQP_ETOOLARGE);
+        r.kernel = Kernel::GwsSolve;
+        return take(Path::DenseGws, 0, solver_ws_elems(ka.n, ka.m, dtype, fl) * esz);
+    case Entry::MODEL: {
+        const bool small = pair_eligible(ka, MODE_MODEL, dtype);
+        // 17 .. 32 variables on chip: bounds per problem past the small-problem kernels, the model's own bounds by name only (the
+        // default route of these sizes, the workgroup kernel below, stays)
+        if (e.own_e ? !small : (fl & MPCQP_OPT_ON_CHIP_32)) return on_chip(Kernel::DuoModel);
+        // (bounds per problem: the model modes of the small-problem kernels, whatever the flags)
+        if (small && (e.own_e || per_wave_ok)) return on_chip(quad_model_eligible(ka, batch, simds) ? Kernel::QuadModel : Kernel::PairModel);
+        if (!force_lds(fl) && w64_eligible(ka, MODE_MODEL, dtype)) return on_chip(Kernel::W64Model);
+        Layout L;
+        if (int rc = layout_for(ka, false, false, MODE_SOLVE, dtype, L)) return refuse(rc);
+        return on_chip(Kernel::LdsModel);
+    }
     case Entry::WIP_PERIODS:  // (the closed-loop epilogue is compiled into the narrow kernel; no second opinion)
         return use_stage_auto(ka, dtype) ? narrow(stage_default_maxq(ka), 0) : refuse(MPCQP_EUNSUPPORTED);
     case Entry::STAGEWISE: {
@@ -454,12 +547,25 @@ Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
         return r;
     }
     // MPCQP_OPT_ON_CHIP_32: the on-chip kernel for 17 .. 32 variables, no workspace (the size queries carry no flags and never get here)
-    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) return (dtype == MPCQP_F64 && duo_applies(ka)) ? take(Path::OnChip, 0, 0) : refuse(MPCQP_EUNSUPPORTED);
+    if (fl & MPCQP_OPT_ON_CHIP_32) return on_chip(Kernel::Duo);
     if (use_stage_auto(ka, dtype)) return narrow(stage_default_maxq(ka), stagew_auto_maxq(ka));
     if (use_stagew_auto(ka, dtype)) return wide(stagew_auto_maxq(ka));
     if (!e.bulky && use_mid(ka, dtype)) return take(Path::Mid, 0, bigsolve_ws_elems(ka.n) * esz);
     const bool q = size_query(ka);
-    if (fits_on_chip(ka, q || ka.A.step_stride, q || ka.B.step_stride, MODE_FUSED, dtype)) return take(Path::OnChip, 0, 0);
+    if (fits_on_chip(ka, q || ka.A.step_stride, q || ka.B.step_stride, MODE_FUSED, dtype)) {
+        // The on-chip tier. Four problems per wavefront with four rows per lane (more than 32 rows, or five to eight per step, at
+        // n <= 16) at every batch size: the workgroup / one-per-wavefront kernels it replaces there are 5-9 x slower. With two rows
+        // per lane where it pays -- the general layouts and nx > 4 at every batch size, the lean layout from more than two problems
+        // per SIMD (quad_eligible) --: on its own for nx = 2 and nx > 4, which have no two-per-wavefront instantiation, and from the
+        // pair kernel's sizes for nx = 3, 4. Then two per wavefront, one per wavefront, one per workgroup. (A warm state on the last
+        // two is refused by the export.)
+        if (dtype == MPCQP_F64 && per_wave_ok) {
+            if (quad4_applies(ka)) return on_chip(Kernel::Quad4);
+            if ((ka.nx == 2 || ka.nx > 4) && quad_eligible(ka, batch, simds)) return on_chip(Kernel::Quad);
+        }
+        if (per_wave_ok && pair_eligible(ka, MODE_FUSED, dtype)) return on_chip(quad_eligible(ka, batch, simds) ? Kernel::Quad : Kernel::Pair);
+        return on_chip(!force_lds(fl) && w64_eligible(ka, MODE_FUSED, dtype) ? Kernel::W64Fused : Kernel::LdsFused);
+    }
     // wide systems on horizons the dense path cannot hold -- and every float64 problem it could hold (prefer_general): the
     // general stage-wise kernel (float64; float32 launches of these dimensions arrive here converted, promote_f32)
     if (!big_supported(ka) || ka.n > 256 || prefer_general(ka, dtype))
@@ -471,12 +577,12 @@ Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e)
 // whose warm-state record a launch on this route reads and writes (MPCQP_WARM_KIND_*): the small-problem pair kernel's
 // (operator + slot ids), the narrow stage-wise kernel's (row ids; the rows' vectors stay in its workspace) or the wide one's
 // (row ids only, MPCQP_WARM_ACTIVE_SET)
-int warm_kind(const Route &r, const KernelArgs &ka, int dtype)
+int warm_kind(const Route &r)
 {
     switch (r.path) {
     case Path::Narrow: return MPCQP_WARM_KIND_STAGE;
     case Path::Wide: return MPCQP_WARM_KIND_ROWS;
-    case Path::OnChip: return pair_eligible(ka, MODE_FUSED, dtype) ? MPCQP_WARM_KIND_OPERATOR : MPCQP_WARM_KIND_NONE;
+    case Path::OnChip: return r.kernel == Kernel::Pair ? MPCQP_WARM_KIND_OPERATOR : MPCQP_WARM_KIND_NONE;
     default: return MPCQP_WARM_KIND_NONE;
     }
 }
@@ -486,10 +592,13 @@ int warm_kind(const Route &r, const KernelArgs &ka, int dtype)
 size_t warm_bytes_per_problem(KernelArgs ka, int dtype, int *kind = nullptr)
 {
     ka.opt_flags = 0;
-    ka.warm_state = nullptr;
+    ka.warm_start = 0;
     if (dtype == MPCQP_F32 && promote_f32(ka, dtype)) dtype = MPCQP_F64;  // (the launch that is solved in float64: its kernel's record)
+    // routed as the launch that carries a record: the four-per-wavefront kernels, which keep none, step aside for the pair kernel
+    // (any pointer will do: route() reads it as a flag)
+    ka.warm_state = &ka;
     const Route r = route(ka, dtype, 1, Entry{});
-    const int k = warm_kind(r, ka, dtype);
+    const int k = warm_kind(r);
     if (kind) *kind = k;
     switch (k) {
     case MPCQP_WARM_KIND_OPERATOR: return kPairWarmDoubles * sizeof(double);
@@ -563,7 +672,40 @@ int run_dense(KernelArgs ka, int dtype, int64_t batch, void *workspace, hipStrea
     ka.q = qw;
     ka.G = Gw;
     ka.h = hw;
-    return run_gws_solve(ka, dtype, batch, w, b.solver * nb * esz, st);
+    return run_gws_solve(ka, dtype, batch, w, st);
+}
+
+// The launch of a route: its kernel's launcher, or the path's where the path is the launcher. stepA / stepB: A and B per step
+// (the workgroup kernel's carve in the fused mode).
+int run(const Route &r, const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, void *ws, hipStream_t st)
+{
+    switch (r.kernel) {
+    case Kernel::Quad4: return launch_quad4(ka, batch, st);
+    case Kernel::Quad: return launch_quad(ka, batch, st);
+    case Kernel::Pair: return launch_pair(ka, batch, st);
+    case Kernel::W64Fused: return launch_w64(ka, MODE_FUSED, dtype, batch, st);
+    case Kernel::W64Solve: return launch_w64(ka, MODE_SOLVE, dtype, batch, st);
+    case Kernel::W64Model: return launch_w64(ka, MODE_MODEL, dtype, batch, st);
+    case Kernel::LdsFused: return run_lds<MODE_FUSED>(ka, stepA, stepB, dtype, batch, st);
+    case Kernel::LdsSolve: return run_lds<MODE_SOLVE>(ka, false, false, dtype, batch, st);
+    case Kernel::LdsModel: return run_lds<MODE_MODEL>(ka, false, false, dtype, batch, st);
+    case Kernel::Duo: return launch_duo(ka, batch, st);
+    case Kernel::DuoModel: return launch_duo_model(ka, batch, st);
+    case Kernel::DuoQp: return launch_duo_qp(ka, batch, st);
+    case Kernel::QuadModel: return launch_quad_model(ka, batch, st);
+    case Kernel::PairModel: return launch_pair_model(ka, batch, st);
+    case Kernel::GwsSolve: return run_gws_solve(ka, dtype, batch, ws, st);
+    case Kernel::None: break;
+    }
+    switch (r.path) {
+    case Path::Narrow: return run_narrow(ka, dtype, r, batch, ws, st);
+    case Path::Wide: return launch_stagew(ka, dtype, r.maxq, batch, ws, st);
+    case Path::Mid: return launch_mid(ka, dtype, batch, ws, st);
+    case Path::General: return launch_stageg(ka, r.maxq, batch, ws, st);
+    case Path::DenseStruct:
+    case Path::DenseGws: return run_dense(ka, dtype, batch, ws, st);
+    default: return MPCQP_ETOOLARGE;  // (Refused and Promote are the exports' business)
+    }
 }
 
 }  // namespace
@@ -771,19 +913,13 @@ int mpcqp_solve_batch(int32_t n, int32_t m, int32_t dtype, const void *P, const 
     ka.lam = lam;
     ka.status = status;
     ka.iters = iters;
-    if (int rc = fill_opts(ka, opts, dtype)) return rc;
-    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
-    // MPCQP_OPT_ON_CHIP_32: the QP-given mode of the on-chip kernel (mpcqp_duo.hip), float64 inside its envelope, no workspace,
-    // with no other choice of kernel, start or factor next to it (an order and a warm state were refused above)
-    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) {
-        constexpr int kOthers = kOverrideFlags | MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_FOUR_PER_WAVE |
-                                MPCQP_OPT_KEEP_FACTOR | MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR;
-        if (dtype != MPCQP_F64 || !duo_qp_applies(ka) || (ka.opt_flags & kOthers)) return MPCQP_EUNSUPPORTED;
-        return launch_duo_qp(ka, batch, (hipStream_t)stream);
-    }
-    if (fits_on_chip(ka, false, false, MODE_SOLVE, dtype))
-        return run_solver<MODE_SOLVE>(ka, false, false, dtype, batch, (hipStream_t)stream);
-    return run_gws_solve(ka, dtype, batch, workspace, workspace_bytes, (hipStream_t)stream);
+    const Entry entry{Entry::QP_GIVEN};
+    int rc = fill_opts(ka, opts, dtype);
+    if (rc || (rc = refusal(ka, dtype, entry))) return rc;
+    const Route r = route(ka, dtype, batch, entry, SimdCount{});
+    if (r.path == Path::Refused) return r.rc;
+    if (r.path != Path::OnChip && (!workspace || workspace_bytes < r.bytes)) return MPCQP_EWORKSPACE;
+    return run(r, ka, false, false, dtype, batch, workspace, (hipStream_t)stream);
 }
 
 int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, int64_t batch,
@@ -801,27 +937,10 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     ka.lam = lam;
     ka.status = status;
     ka.iters = iters;
-    if ((rc = fill_opts(ka, opts, dims->dtype, true))) return rc;
-    // a pairing order: cold launches of the small-problem fused kernel (float32 launches of its size arrive here converted)
-    if (ka.order && (ka.warm_state || (ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)) ||
-                     !pair_eligible(ka, MODE_FUSED, MPCQP_F64)))
-        return MPCQP_EUNSUPPORTED;
-    // four problems per wavefront on request: only where that kernel applies (the dispatch picks it by batch size otherwise)
-    if ((ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) &&
-        ((ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE)) ||
-         (!pair_eligible(ka, MODE_FUSED, MPCQP_F64) && ka.nx != 2 && ka.nx <= 4 && !quad4_applies(ka)) || (!quad_applies(ka) && !quad4_applies(ka))))
-        return MPCQP_EUNSUPPORTED;
-    // 17 .. 32 variables on chip on request: cold launches inside the kernel's envelope, with no other choice of kernel or factor
-    // (a float32 launch is converted below, promote_f32, and arrives here again in float64 with the flag)
-    if ((ka.opt_flags & MPCQP_OPT_ON_CHIP_32) &&
-        (!duo_applies(ka) || ka.warm_state || ka.order ||
-         (ka.opt_flags & (kOverrideFlags | MPCQP_OPT_SEED_VIOLATED | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_FOUR_PER_WAVE | MPCQP_OPT_KEEP_FACTOR |
-                          MPCQP_OPT_REUSE_FACTOR | MPCQP_OPT_PIPELINE_FACTOR)) ||
-         (dims->dtype != MPCQP_F64 && !promote_f32(ka, dims->dtype))))
-        return MPCQP_EUNSUPPORTED;
-    const bool stepA = problem->A.step_stride != 0, stepB = problem->B.step_stride != 0;
+    const Entry entry{Entry::BUILD_SOLVE};
+    if ((rc = fill_opts(ka, opts, dims->dtype)) || (rc = refusal(ka, dims->dtype, entry))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const Route r = route(ka, dims->dtype, batch, Entry{});
+    const Route r = route(ka, dims->dtype, batch, entry, SimdCount{});
     if (r.path == Path::Promote) {
         // float32 at an on-chip condensed kernel's size: solved in float64 on converted copies (see promote_f32)
         const int64_t N = ka.N, nx = ka.nx, nu = ka.nu, mk = ka.mk;
@@ -875,27 +994,14 @@ int mpcqp_build_solve_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
         if (lam) out.seg[out.nseg++] = ConvSeg{w + offL, lam, batch * ka.m};
         return launch_convert(out, st);
     }
-    const int kind = ka.warm_state ? warm_kind(r, ka, dims->dtype) : MPCQP_WARM_KIND_NONE;  // (warm_start is 0 without a state)
-    if (ka.warm_state && kind == MPCQP_WARM_KIND_NONE) return MPCQP_EUNSUPPORTED;
-    // (row-id warm starts: the pair kernel and the wide stage-wise kernel; the narrow stage-wise kernel, which the dispatch
-    // prefers for small systems with 16 < n <= 128, has its own kind of record)
-    if (ka.warm_start == MPCQP_WARM_ACTIVE_SET && kind != MPCQP_WARM_KIND_OPERATOR && kind != MPCQP_WARM_KIND_ROWS) return MPCQP_EUNSUPPORTED;
-    if ((ka.opt_flags & MPCQP_OPT_PIPELINE_FACTOR) && !(r.path == Path::Narrow && stage_pipeline_supported(ka, dims->dtype)))
-        return MPCQP_EUNSUPPORTED;
+    if ((rc = refusal(ka, dims->dtype, entry, &r))) return rc;
     // the state is indexed by problem: a buffer made for a smaller batch would be read and written out of bounds
     if (ka.warm_state && ka.warm_state_bytes < (size_t)batch * warm_bytes_per_problem(ka, dims->dtype)) return MPCQP_EWORKSPACE;
     if (r.path == Path::Refused) return r.rc;
     if (r.path != Path::OnChip && (!workspace || workspace_bytes < r.bytes)) return MPCQP_EWORKSPACE;
-    switch (r.path) {
-    case Path::Narrow: return run_narrow(ka, dims->dtype, r, batch, workspace, st);
-    case Path::Wide: return launch_stagew(ka, dims->dtype, r.maxq, batch, workspace, st);
-    case Path::Mid: return launch_mid(ka, dims->dtype, batch, workspace, st);
-    case Path::OnChip: return run_solver<MODE_FUSED>(ka, stepA, stepB, dims->dtype, batch, st);
-    case Path::General: return launch_stageg(ka, r.maxq, batch, workspace, st);
-    case Path::DenseStruct:
-    case Path::DenseGws: return run_dense(ka, dims->dtype, batch, workspace, st);
-    default: return MPCQP_ETOOLARGE;  // (Refused and Promote returned above)
-    }
+    // (FORCE_LDS / ONE_PER_WAVE at the pair kernel's sizes: the one warm-state refusal that comes after the record's size, see refusal())
+    if (ka.warm_state && warm_kind(r) == MPCQP_WARM_KIND_NONE) return MPCQP_EUNSUPPORTED;
+    return run(r, ka, problem->A.step_stride != 0, problem->B.step_stride != 0, dims->dtype, batch, workspace, st);
 }
 
 int mpcqp_stagewise_workspace_bytes(const MpcqpDims *dims, int64_t batch, int32_t max_active, size_t *bytes)
@@ -934,17 +1040,13 @@ int mpcqp_stagewise_solve_batch(const MpcqpDims *dims, const MpcqpProblem *probl
     const bool general = opts && (opts->flags & MPCQP_OPT_STAGE_GENERAL), wide = opts && (opts->flags & MPCQP_OPT_STAGE_WIDE);
     // (as in mpcqp_build_solve_batch: what the narrow kernel leaves MPCQP_MAX_ITER / MPCQP_INFEASIBLE goes through the wide one, with
     // the same slots, in a region of its own after the narrow kernel's workspace -- mpcqp_stagewise_workspace_bytes reports the sum)
-    const Route r = route(ka, dims->dtype, batch, {Entry::STAGEWISE, max_active, general, wide});
+    // (this export has always routed first: a system no stage-wise kernel serves is refused as such whatever its options)
+    const Entry entry{Entry::STAGEWISE, max_active, general, wide};
+    const Route r = route(ka, dims->dtype, batch, entry, SimdCount{});
     if (r.path == Path::Refused) return r.rc;
-    if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
-    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
+    if ((rc = fill_opts(ka, opts, dims->dtype)) || (rc = refusal(ka, dims->dtype, entry))) return rc;
     if (!workspace || workspace_bytes < r.bytes) return MPCQP_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    switch (r.path) {
-    case Path::General: return launch_stageg(ka, r.maxq, batch, workspace, st);
-    case Path::Wide: return launch_stagew(ka, dims->dtype, r.maxq, batch, workspace, st);
-    default: return run_narrow(ka, dims->dtype, r, batch, workspace, st);
-    }
+    return run(r, ka, false, false, dims->dtype, batch, workspace, (hipStream_t)stream);
 }
 
 int mpcqp_model_bytes(const MpcqpDims *dims, size_t *bytes)
@@ -1001,37 +1103,14 @@ int mpcqp_solve_model_bounds_batch(const MpcqpDims *dims, const void *model, con
     ka.lam = lam;
     ka.status = status;
     ka.iters = iters;
-    if ((rc = fill_opts(ka, opts, dims->dtype, true))) return rc;
-    if (ka.warm_state) return MPCQP_EUNSUPPORTED;
-    // (a pairing order: the pair kernel's model mode only)
-    if (ka.order && ((ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE)) || !pair_eligible(ka, MODE_MODEL, dims->dtype)))
-        return MPCQP_EUNSUPPORTED;
-    const bool small = pair_eligible(ka, MODE_MODEL, dims->dtype);
-    if ((ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) &&
-        ((ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)) || !small))
-        return MPCQP_EUNSUPPORTED;  // (the four-per-wavefront kernel has no seed steps: asked for by name, it is refused by name)
-    hipStream_t st = (hipStream_t)stream;
-    // 17 .. 32 variables on chip (mpcqp_duo.hip, its shared-model mode): float64 inside the kernel's envelope, cold (a warm state
-    // was refused above), with no pairing order and no other choice of kernel or start
-    const bool on_chip_32 = dims->dtype == MPCQP_F64 && duo_model_applies(ka) && !ka.order &&
-                            !(ka.opt_flags & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_TWO_PER_WAVE |
-                                              MPCQP_OPT_FOUR_PER_WAVE | MPCQP_OPT_SEED_VIOLATED));
-    const bool own_e = e && e->ptr;  // per-problem bounds: the model modes of the small-problem kernels and of the on-chip-32 kernel
-    if (own_e) {
-        if (ka.m < 1) return MPCQP_EINVAL;
-        ka.e = *e;
-        // (past sixteen variables nothing else serves them: the kernel is taken with or without MPCQP_OPT_ON_CHIP_32)
-        if (!small) return on_chip_32 ? launch_duo_model(ka, batch, st) : MPCQP_EUNSUPPORTED;
-        return quad_model_eligible(ka, batch) ? launch_quad_model(ka, batch, st) : launch_pair_model(ka, batch, st);
-    }
-    // the model's own bounds: on request only (the default route of these sizes, the workgroup kernel below, stays)
-    if (ka.opt_flags & MPCQP_OPT_ON_CHIP_32) return on_chip_32 ? launch_duo_model(ka, batch, st) : MPCQP_EUNSUPPORTED;
-    if (!force_lds(ka.opt_flags) && !(ka.opt_flags & MPCQP_OPT_ONE_PER_WAVE) && small)
-        return quad_model_eligible(ka, batch) ? launch_quad_model(ka, batch, st) : launch_pair_model(ka, batch, st);
-    if (!force_lds(ka.opt_flags) && w64_eligible(ka, MODE_MODEL, dims->dtype)) return launch_w64(ka, MODE_MODEL, dims->dtype, batch, st);
-    Layout L;
-    if ((rc = layout_for(ka, false, false, MODE_SOLVE, dims->dtype, L))) return rc;
-    return dispatch_lds<MODE_MODEL>(ka, L, dims->dtype, batch, st);
+    // per-problem bounds: the model modes of the small-problem kernels and of the on-chip-32 kernel
+    Entry entry{Entry::MODEL};
+    entry.own_e = e && e->ptr;
+    if ((rc = fill_opts(ka, opts, dims->dtype)) || (rc = refusal(ka, dims->dtype, entry))) return rc;
+    if (entry.own_e) ka.e = *e;
+    const Route r = route(ka, dims->dtype, batch, entry, SimdCount{});
+    if (r.path == Path::Refused) return r.rc;
+    return run(r, ka, false, false, dims->dtype, batch, nullptr, (hipStream_t)stream);
 }
 
 int mpcqp_rollout_batch(const MpcqpDims *dims, const MpcqpOperand *A, const MpcqpOperand *B,
@@ -1601,10 +1680,11 @@ int mpcqp_wip_periods_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     ka.lam = lam;
     ka.status = status;
     ka.iters = iters;
-    if ((rc = fill_opts(ka, opts, dims->dtype))) return rc;
+    const Entry entry{Entry::WIP_PERIODS};
+    if ((rc = fill_opts(ka, opts, dims->dtype)) || (rc = refusal(ka, dims->dtype, entry))) return rc;
     // the plant is the 4-state, 1-input pendulum, every loop with its own x0, goal and targets; only the stage-wise
     // kernel carries the epilogue
-    const Route r = route(ka, dims->dtype, batch, {Entry::WIP_PERIODS});
+    const Route r = route(ka, dims->dtype, batch, entry, SimdCount{});
     if (ka.nx != 4 || ka.nu != 1 || !problem->x0.ptr || !problem->goal.ptr || !problem->targets.ptr ||
         problem->x0.batch_stride != 4 || problem->goal.batch_stride != 4 || problem->targets.batch_stride != (int64_t)ka.N * 4 ||
         r.path == Path::Refused)

@@ -37,6 +37,18 @@ inline int device_simds_now()
     return 4 * cus;
 }
 
+// The SIMD count as the dispatch hands it to the batch-size rule of the four-per-wavefront kernels (quad_eligible,
+// quad_model_eligible): SimdCount{} asks the device on first use, so a launch whose kernel is settled without the rule makes no
+// runtime call for it; SimdCount{n} is the constant n (the size queries, which launch nothing).
+struct SimdCount {
+    int value = -1;  // < 0: not asked yet
+    int get()
+    {
+        if (value < 0) value = device_simds_now();
+        return value;
+    }
+};
+
 // INTERNAL bit of KernelArgs.opt_flags (never taken from MpcqpSolveOpts.flags: fill_opts clears it): the wide stage-wise kernel runs as
 // the SECOND OPINION behind the narrow one -- a wavefront whose problem the first launch settled (solved, not positive definite,
 // slots full) exits at once, the others (MPCQP_MAX_ITER, MPCQP_INFEASIBLE) are solved again from scratch. Round 6: the narrow kernel
@@ -216,14 +228,17 @@ int launch_stageg(const KernelArgs &ka, int maxq, int64_t batch, void *ws, hipSt
 // small-problem kernel (mpcqp_pair.hip): two problems per wavefront, fused build+solve
 bool pair_eligible(const KernelArgs &ka, int mode, int dtype);
 constexpr size_t kPairWarmDoubles = 16 * 16 + 8;  // T (16 x 16), then 16 int32 constraint ids
-int launch_pair(const KernelArgs &ka, int64_t batch, hipStream_t st);
+int launch_pair(const KernelArgs &ka, int64_t batch, hipStream_t st);        // (pair_eligible and not quad_eligible: the dispatch)
 int launch_pair_model(const KernelArgs &ka, int64_t batch, hipStream_t st);  // shared model (ka.model)
 // small-problem kernel (mpcqp_quad.hip): four problems per wavefront, cold lean fused build+solve
 bool quad_applies(const KernelArgs &ka);                  // the kernel serves this launch's layout
-bool quad_model_eligible(const KernelArgs &ka, int64_t batch);  // shared-model launches of that layout
-int launch_quad_model(const KernelArgs &ka, int64_t batch, hipStream_t st);
-bool quad_eligible(const KernelArgs &ka, int64_t batch);  // ... and the dispatch takes it (batch size, MPCQP_OPT_TWO / FOUR_PER_WAVE)
+// ... and the dispatch takes it: no MPCQP_OPT_TWO_PER_WAVE, and MPCQP_OPT_FOUR_PER_WAVE, the general build or a batch of more than
+// two problems per SIMD (`simds` is asked only where that last rule decides)
+bool quad_eligible(const KernelArgs &ka, int64_t batch, SimdCount &simds);
 int launch_quad(const KernelArgs &ka, int64_t batch, hipStream_t st);
+// shared-model launches of the pair kernel's sizes (the caller has checked pair_eligible(ka, MODE_MODEL)): the same rule
+bool quad_model_eligible(const KernelArgs &ka, int64_t batch, SimdCount &simds);
+int launch_quad_model(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // ... and its general build with four rows per lane for 33 .. 64 rows (mpcqp_quadg.hip): cold launches, any batch size
 bool quad4_applies(const KernelArgs &ka);
 int launch_quad4(const KernelArgs &ka, int64_t batch, hipStream_t st);

@@ -1531,7 +1531,6 @@ int launch_pair(const KernelArgs &ka, int64_t batch, hipStream_t st)
 {
     // the register-pipelined chain: terminal cost only, state constraints only, two rows per step
     const bool lean = ka.mk == 2 && ka.C.ptr && !ka.D.ptr && !(ka.flags & (MPCQP_P_STAGE | MPCQP_Q_STAGE));
-    if (quad_eligible(ka, batch)) return launch_quad(ka, batch, st);  // cold lean launches that fill the machine about once: four problems per wavefront
     if (ka.nx == 3) return lean ? launch_pair_t<3, 2>(ka, batch, st) : launch_pair_t<3, 0>(ka, batch, st);
     return lean ? launch_pair_t<4, 2>(ka, batch, st) : launch_pair_t<4, 0>(ka, batch, st);
 }

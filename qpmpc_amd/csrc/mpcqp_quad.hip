@@ -951,7 +951,7 @@ __global__ void __launch_bounds__(64 * WPB, SLIM ? 2 : 1)
 // round (up to four problems per SIMD) runs the roomy carve: config 2 at 4096: 22.4 against 24.8 us; anything larger the slim one,
 // two wavefronts per SIMD: config 2 at 8192 / 16,384: 37.8 / 65.0 against 47.3 / 85.6 us; config 4 at 8192 / 16,384 / 65,536:
 // 45.5 / 74.0 / 231 against 56.9 / 90.9 / 305 us.
-[[maybe_unused]] static bool quad_pays(int64_t batch) { return batch > 2 * (int64_t)device_simds_now(); }
+[[maybe_unused]] static bool quad_pays(int64_t batch, SimdCount &simds) { return batch > 2 * (int64_t)simds.get(); }
 
 // the lean build (terminal cost only, state rows only: BASELINE configs 1, 2, 4) or the general one (GEN: input rows, stage cost)
 static bool quad_general(const KernelArgs &ka)
@@ -974,14 +974,14 @@ bool quad_applies(const KernelArgs &ka)
     return true;
 }
 
-bool quad_eligible(const KernelArgs &ka, int64_t batch)
+bool quad_eligible(const KernelArgs &ka, int64_t batch, SimdCount &simds)
 {
     if (!quad_applies(ka) || (ka.opt_flags & MPCQP_OPT_TWO_PER_WAVE)) return false;
     // (the general build at every batch size: the two-per-wavefront kernel's generic build stages its operands in LDS and is the slower
     // one from a single wavefront up -- the reference's WIP example, N = 12: 256 problems 13.2 against 19.3 us, 2048: 14.2 / 21.8,
     // 4096: 15.1 / 25.8; a random family with C + D rows and a stage cost, 12 iterations: 32.5 / 40.3, 39.5 / 49.7, 45.3 / 61.6;
     // tools/ab_quad_general.py)
-    return (ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) || quad_general(ka) || quad_pays(batch);
+    return (ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) || quad_general(ka) || quad_pays(batch, simds);
 }
 
 #endif
@@ -1047,11 +1047,11 @@ int launch_quad(const KernelArgs &ka, int64_t batch, hipStream_t st)
 
 // Shared-model launches (mpcqp_solve_model_batch / _bounds_batch): any cost and constraint layout the model was factored from, as
 // long as the condensed problem fits the rows (the caller has checked pair_eligible(ka, MODE_MODEL)).
-bool quad_model_eligible(const KernelArgs &ka, int64_t batch)
+bool quad_model_eligible(const KernelArgs &ka, int64_t batch, SimdCount &simds)
 {
     if (ka.n > NV || ka.m > MMAX || ka.m < 1 || ka.warm_state || (ka.opt_flags & (MPCQP_OPT_TWO_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)))
         return false;
-    return (ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) || quad_pays(batch);
+    return (ka.opt_flags & MPCQP_OPT_FOUR_PER_WAVE) || quad_pays(batch, simds);
 }
 
 int launch_quad_model(const KernelArgs &ka, int64_t batch, hipStream_t st)
