@@ -74,6 +74,13 @@ __device__ __forceinline__ unsigned row_min(unsigned v)
     v = min(v, dpp<ROR1>(v));
     return v;
 }
+// One step of row_min, hand-written (N = 8, 4, 2, 1 in this order make the reduction): for a caller that places the steps between its
+// own hand-written instructions, where the compiler would pad each of its own DPP steps (it counts no wait states for inline asm).
+// HAZARD CONTRACT as fmac_bcast's: v is the DPP operand, written by a VALU instruction at least two wait states earlier.
+template <int N> __device__ __forceinline__ void min_ror(unsigned &v)
+{
+    asm volatile("v_min_u32_dpp %0, %0, %0 row_ror:%1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(v) : "n"(N));
+}
 // order-preserving map of a floating-point value onto unsigned words (the key of the arg-mins built on row_min)
 __device__ __forceinline__ void ordered(double x, unsigned &hi, unsigned &lo)
 {

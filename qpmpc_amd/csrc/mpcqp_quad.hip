@@ -51,9 +51,9 @@ namespace quad {
 
 constexpr int MMAX = 32;  // constraints a problem can hold (two per lane)
 constexpr int MK = 2;     // inequality rows per step
-// Placement of the steady loop (profiles/quad_prologue.md: faster with its header 4 bytes past a multiple of 8): padding in the probe's
-#ifndef QUAD_STEADY_PAD  // tick(4) block of the headline instantiation, which a launch without probe skips
-#define QUAD_STEADY_PAD "s_nop 0"
+// Placement of the steady loop (profiles/quad_prologue.md, quad_trip_slots.md: its speed follows the header's offset): padding in the probe's
+#ifndef QUAD_STEADY_PAD  // tick(4) block of the headline instantiation, which a launch without probe skips. Six: the best of eight
+#define QUAD_STEADY_PAD "s_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0"
 #endif
 #ifndef QUAD_PROBE_REFINE  // 1: slot 14 of the probe also marks a pass through the refinement arm (tools/gen_golden_quad_prologue.py);
 #define QUAD_PROBE_REFINE 0  // not in the shipped build: the mark costs the slim instantiations 8 B of scratch

@@ -14,36 +14,66 @@
 // would compute itself, and comes back here as soon as no live row holds a p. Same operations in the same order as its plain arm.
 bool general = true;
 {
-    const int iters_in = iters;
-    // the lane flags travel as the wavefront's lane masks (every lane is active here): no 0/1 bytes in vector registers
+    const int iters_in = iters, nq_in = nq;
+    // the lane flags travel as the wavefront's lane masks (every lane is active here): no 0/1 bytes in vector registers. A new mask is
+    // the ballot of ONE compare, combined with the carried masks by scalar logic: the ballot of a combined predicate goes through a 0/1
+    // register and a second compare
     auto maskof = [](bool b) { return (unsigned long long)__builtin_amdgcn_ballot_w64(b); };
     auto lanes = [](unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); };
     unsigned long long donem = maskof(done), occm = maskof(occ), e0m = maskof(e0), e1m = maskof(e1);
-    for (;;) {
-        dpp_ready(zn);
-        update(ic<0>{}, ic<USPLIT>{}, zn, cT, cH);
-        {  // select() of a row that needs a constraint and is not dropping
-            const bool want = !lanes(donem), e0 = lanes(e0m), e1 = lanes(e1m);
+    const unsigned long long done_in = donem;
+    // iters and nq both grow by one per trip a row steps: ONE counter of those trips, against the nearer of the two limits (the
+    // iteration limit, nq = n); both are rebuilt behind the loop, where a row that finished here gets its status too
+    int ks = 0;
+    const int klim = min(max_iter - iters_in, n - nq_in);
+    static_assert(USPLIT % 4 == 0, "the four steps of the row minimum stand between the quarters of the update's first half");
+    dpp_ready(zn);  // (on the entry edge only: inside the loop zn is written in a trip's bookkeeping, many instructions in front of the
+    for (;;) {      // next trip's first FMA -- tools/check_dpp_hazards.py follows the back edge)
+        {  // select() of a row that needs a constraint and is not dropping. The four steps of its row minimum are hand-written (min_ror)
+            // and stand between the hand-written FMAs of the update's first half, four FMAs apart: the compiler pads its own DPP steps
+            // there with s_nop 1 each, because it counts no wait states for inline asm
             const unsigned h0 = ~(unsigned)__double2hiint(s0 * invn0), h1 = ~(unsigned)__double2hiint(s1 * invn1);
-            const bool v0 = want & e0 & (s0 < -tolh0), v1 = want & e1 & (s1 < -tolh1);
+            const bool v0 = lanes(~donem & e0m & maskof(s0 < -tolh0)), v1 = lanes(~donem & e1m & maskof(s1 < -tolh1));
             const unsigned k0 = v0 ? ((h0 & ~31u) | (unsigned)row0) : 0xffffffffu;
             const unsigned k1 = v1 ? ((h1 & ~31u) | (unsigned)row1) : 0xffffffffu;
-            const unsigned mkey = row_min(min(k0, k1));
-            const bool none = want & (mkey == 0xffffffffu);
-            donem |= maskof(none);
-            status = none ? (int)MPCQP_SOLVED : status;
-            p = (want & !none) ? (int)(mkey & 31u) : p;
+            unsigned mkey = min(k0, k1);
+            pin(mkey);  // (written here: four FMAs in front of its first DPP read)
+            update(ic<0>{}, ic<USPLIT / 4>{}, zn, cT, cH);
+            min_ror<8>(mkey);
+            update(ic<USPLIT / 4>{}, ic<USPLIT / 2>{}, zn, cT, cH);
+            min_ror<4>(mkey);
+            update(ic<USPLIT / 2>{}, ic<3 * USPLIT / 4>{}, zn, cT, cH);
+            min_ror<2>(mkey);
+            update(ic<3 * USPLIT / 4>{}, ic<USPLIT>{}, zn, cT, cH);
+            min_ror<1>(mkey);
+            donem |= maskof(mkey == 0xffffffffu);  // no violated row: solved (a row that is done has no key either)
+            p = lanes(donem) ? p : (int)(mkey & 31u);
         }
         ld16(mp, Ml + p * LDM);
         update(ic<USPLIT>{}, ic<NV>{}, zn, cT, cH);
-        const bool st = !lanes(donem), occ = lanes(occm);  // st: this row steps
         if (donem == ~0ull) {  // every row is done: no general trip either
             general = false;
             break;
         }
-        const bool phi = p >= NV;  // (row-uniform)
+        const unsigned long long stm = ~donem, phim = maskof(p >= NV);  // stm: this row steps; phim (row-uniform)
+        const bool st = lanes(stm), phi = lanes(phim);
         const int pl = p & 15;
-        hd = dot16(RH, mp);
+        {  // hd = dot16(RH, mp), its sums and their order, with TWO waits for row p: each half of the row is pinned as a whole in front of
+            // the eight FMAs that read it (the compiler waits once per pin; left alone, it waits once per 16-byte read, eight times)
+            asm volatile("" : "+v"(mp[0]), "+v"(mp[1]), "+v"(mp[2]), "+v"(mp[3]), "+v"(mp[4]), "+v"(mp[5]), "+v"(mp[6]), "+v"(mp[7]));
+            T c0 = T(0), c1 = T(0), c2 = T(0), c3 = T(0);
+            static_for<0, 2>([&](auto qc) {
+                constexpr int k = 4 * decltype(qc)::value;
+                c0 += RH[k] * mp[k], c1 += RH[k + 1] * mp[k + 1], c2 += RH[k + 2] * mp[k + 2], c3 += RH[k + 3] * mp[k + 3];
+            });
+            asm volatile("" : "+v"(mp[8]), "+v"(mp[9]), "+v"(mp[10]), "+v"(mp[11]), "+v"(mp[12]), "+v"(mp[13]), "+v"(mp[14]), "+v"(mp[15]),
+                         "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
+            static_for<2, 4>([&](auto qc) {
+                constexpr int k = 4 * decltype(qc)::value;
+                c0 += RH[k] * mp[k], c1 += RH[k + 1] * mp[k + 1], c2 += RH[k + 2] * mp[k + 2], c3 += RH[k + 3] * mp[k + 3];
+            });
+            hd = (c0 + c1) + (c2 + c3);
+        }
         {  // dot_bcast(hd, RM0, 0), dot_bcast(hd, RM1, 0) on ONE pinned copy of hd: each sum's chains in their own order
             T a0 = T(0), a1 = T(0), b0 = T(0), b1 = T(0);
             dpp_ready(hd);
@@ -66,38 +96,41 @@ bool general = true;
         }
         rd = dot16(RT, mp);  // (while the exchange is in flight)
         pin(rd);
-        const bool can_move = (nq < n) & (inv > T(0));  // (inv <= 0: near dependence, the general loop's sum of squares)
         const int sl = (int)__builtin_ctz(~mask);  // lowest free slot
-        const T r = (occ & st) ? rd : T(0);
-        const bool blk = (r > T(0)) & (lam < t2 * r);
-        if (maskof(st & (!can_move | (iters >= max_iter) | blk)) != 0ull) break;  // not plain: the general loop finishes THIS trip
+        const T r = lanes(occm & stm) ? rd : T(0);
+        // not plain -- inv <= 0 (near dependence, the general loop's sum of squares), a limit, a blocking multiplier --: the general
+        // loop finishes THIS trip
+        if ((stm & (maskof(!(inv > T(0))) | maskof(ks >= klim) | (maskof(r > T(0)) & maskof(lam < t2 * r)))) != 0ull) break;
         // ---- the plain trip's bookkeeping (a row that is done: zero coefficients, nothing changes)
         inv = st ? inv : T(0);
         const T tt = st ? t2 : T(0);
-        const bool isnew = st & (l == sl), isp = st & (l == pl);
-        iters += st ? 1 : 0;
+        const unsigned long long slm = maskof(l == sl), isnewm = slm & stm, ispm = maskof(l == pl) & stm;
+        const bool isnew = lanes(isnewm);
+        ks += st ? 1 : 0;
         zn = hd;
-        cT = (l == sl) ? inv : -(r * inv);
+        cT = lanes(slm) ? inv : -(r * inv);
         cH = -(hd * inv);
         s0 = fma(tt, kd0, s0);  // s_i -= t M_i . z
         s1 = fma(tt, kd1, s1);
         T ln = fma(-tt, r, lam);
-        ln = (occ & (ln < T(0))) ? T(0) : ln;
+        ln = lanes(occm & maskof(ln < T(0))) ? T(0) : ln;
         lam = isnew ? tt : ln;  // (up + tt with up = 0 since the selection; tt > 0)
         myact = isnew ? p : myact;
-        occm |= maskof(isnew);
-        e0m &= ~maskof(isp & !phi);
-        e1m &= ~maskof(isp & phi);
+        occm |= isnewm;
+        e0m &= ~(ispm & ~phim);
+        e1m &= ~(ispm & phim);
         mask |= st ? (1u << sl) : 0u;
-        nq += st ? 1 : 0;
     }
     done = lanes(donem);
     occ = lanes(occm);
     e0 = lanes(e0m);
     e1 = lanes(e1m);
+    status = lanes(donem & ~done_in) ? (int)MPCQP_SOLVED : status;  // (the one way a row finishes in this loop)
+    iters = iters_in + ks;
+    nq = nq_in + ks;
     // what select() and the plain trips leave in the state this loop does not carry: a row that selected has up = 0; one that
     // still steps holds its p (needp false), one that stepped and is done asks for a new one (never read before it is reset)
-    const bool went = iters != iters_in;
+    const bool went = ks != 0;
     up = (went | !done) ? T(0) : up;
     needp = done ? (needp | went) : false;
     cT = cH = T(0);  // (the update of the trip that left has been applied)
