@@ -769,6 +769,51 @@ int mpcqp_wip_periods_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
                             double sampling_period, double target_vel, double length, double gravity, int32_t nsub,
                             int32_t nperiods, void *stream);
 
+/* `nperiods` consecutive control periods of `batch` closed loops of ANY factored shared model in ONE launch (an additive
+ * part of ABI 12: MPCQP_ABI_VERSION is unchanged) -- what mpcqp_wip_period_batch / mpcqp_wip_periods_batch do for the
+ * wheeled inverted pendulum, with a linear plant given as data instead of compiled in. The plant may differ from the model. */
+typedef struct MpcqpLoopPlant {
+    MpcqpOperand A;  /* [B|1] nx x nx   x+ = A x + B u0 + d   (batch_stride 0 = shared; step_stride unused) */
+    MpcqpOperand B;  /* [B|1] nx x nu */
+    MpcqpOperand d;  /* [B|1, P|1] nx   additive disturbance, ptr NULL = none; step_stride = PERIOD stride (0: same every period) */
+} MpcqpLoopPlant;
+
+typedef struct MpcqpLoopOut {
+    void    *X;          /* [batch, nperiods+1, nx]  state before every period and after the last; NULL = not recorded */
+    void    *U0;         /* [batch, nperiods, nu]    the input applied in every period; NULL = not recorded */
+    int64_t *loop_stats; /* [batch, 3] accumulated (+=): periods without a plan, iterations, warm periods re-solved cold; NULL ok */
+} MpcqpLoopOut;
+
+/* Period t = 0 .. nperiods-1 of loop b, by the rules of the WIP loop's exports above:
+ *   1. mpcqp_solve_model_batch's problem at x0 = states[b], goal[b, t], targets[b, t] (step_stride of `goal` and `targets` is
+ *      the PERIOD stride, 0 = the same every period), with the model's own bounds;
+ *   2. u0 = the first nu entries of the plan, zero when the period's status is not MPCQP_SOLVED -- then loop_stats[b][0] += 1
+ *      and the loop carries on;
+ *   3. states[b] = A states[b] + B u0 + d[b, t];
+ *   4. loop_stats[b][1] += the period's iterations.
+ * U, lam, status and iters are those of the LAST period, as mpcqp_solve_model_batch leaves them (lam and iters may be NULL;
+ * status[b] != 0: U[b] = zeros, lam[b] undefined). `out` may be NULL. No workspace, no allocation, no synchronisation;
+ * `model`, the plant and the references are only read. One launch of nperiods periods leaves, with warm == 0, bitwise what
+ * nperiods launches of one period with advanced pointers leave (the property mpcqp_wip_periods_batch states).
+ * warm != 0: inside ONE launch, a period that follows a period that ended MPCQP_SOLVED starts from that period's active set
+ * and operator T = N*, kept in registers (T depends on the matrices only: the contract of MpcqpSolveOpts.warm_state). The
+ * kept set's multipliers are recomputed for the new state, rows with a negative one are dropped (one iteration each), and
+ * the period is accepted through the from-scratch verification only; a warm period that does not end verified-solved --
+ * the iteration limit, a failed verification, also an INFEASIBLE verdict -- is solved again cold in place and
+ * loop_stats[b][2] += 1: a stale state costs a cold restart, never a wrong plan. Its iterations count in full (iters,
+ * loop_stats[b][1]). The first period of a launch is always cold and nothing of the state is stored.
+ * Served: float64, n = N nu <= 16, 1 <= m = N mk <= 32, nx <= 16, opts->flags == 0, no warm_state, no order
+ * (mpcqp_w64.hip, one loop per wavefront); MPCQP_EUNSUPPORTED otherwise (float32 and every MPCQP_OPT_* flag included).
+ * nperiods < 1, batch < 0 or a NULL required pointer: MPCQP_EINVAL. The reference has no counterpart beyond the Python
+ * loops of its examples (examples/wheeled_inverted_pendulum.py:99-118 is one for one plant). */
+int mpcqp_model_periods_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant,
+                              void *states,                 /* [batch, nx], updated in place */
+                              const MpcqpOperand *goal,     /* [B|1, P|1, nx];    step_stride = period stride */
+                              const MpcqpOperand *targets,  /* [B|1, P|1, N*nx];  step_stride = period stride */
+                              int64_t batch, int32_t nperiods, int32_t warm, const MpcqpSolveOpts *opts,
+                              void *U, void *lam, int32_t *status, int32_t *iters, /* those of the LAST period */
+                              const MpcqpLoopOut *out, void *stream);
+
 /* Bookkeeping of closed loops (the reference's loops count nothing; ours report failures and iterations):
  * stats[0] += number of problems with status != 0, stats[1] += sum of iters. stats: two int64 in DEVICE memory. */
 int mpcqp_accumulate_stats(const int32_t *status, const int32_t *iters, int64_t batch, int64_t *stats, void *stream);

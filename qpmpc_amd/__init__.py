@@ -25,6 +25,7 @@ from .batch import (  # noqa: F401
     solve_mpc_batch,
     solve_qp_batch,
 )
+from .closed_loop import ModelClosedLoop  # noqa: F401
 from .autodiff import plan_jacobian, plan_jvp, solve_mpc_batch_diff  # noqa: F401
 from .exceptions import (  # noqa: F401
     BackendError,
@@ -50,6 +51,7 @@ __all__ = [
     "WarmState",
     "SharedModel",
     "PreparedModelSolve",
+    "ModelClosedLoop",
     "pairing_order",
     "solve_mpc_batch",
     "solve_qp_batch",

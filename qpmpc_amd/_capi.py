@@ -70,6 +70,7 @@ EXPORTS = (
     "mpcqp_plan_jvp_model_stagewise_batch",
     "mpcqp_model_vjp_batch",
     "mpcqp_model_jvp_batch",
+    "mpcqp_model_periods_batch",
 )
 
 
@@ -101,6 +102,14 @@ class Tangents(C.Structure):
 class ModelTangents(C.Structure):
     _fields_ = ([(name, C.c_void_p) for name in ("dA", "dB", "dC", "dD", "dw")]
                 + [(name + "_stride", C.c_int64) for name in ("dA", "dB", "dC", "dD", "dw")])
+
+
+class LoopPlant(C.Structure):
+    _fields_ = [(name, Operand) for name in ("A", "B", "d")]
+
+
+class LoopOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("X", "U0", "loop_stats")]
 
 
 class SolveOpts(C.Structure):
@@ -248,6 +257,10 @@ def load():
     lib.mpcqp_model_jvp_batch.restype = C.c_int
     lib.mpcqp_model_jvp_batch.argtypes = [C.POINTER(Dims), vp, i64, C.c_int32, vp, vp, C.POINTER(Tangents),
                                           C.POINTER(Operand), C.POINTER(Operand), vp, vp, vp, vp]
+    lib.mpcqp_model_periods_batch.restype = C.c_int
+    lib.mpcqp_model_periods_batch.argtypes = [C.POINTER(Dims), vp, C.POINTER(LoopPlant), vp, C.POINTER(Operand),
+                                              C.POINTER(Operand), i64, C.c_int32, C.c_int32, C.POINTER(SolveOpts), vp, vp,
+                                              vp, vp, C.POINTER(LoopOut), vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -19,6 +19,7 @@ import ctypes as C
 
 from . import _capi
 from .batch import BatchMPCProblem, PreparedSolve, SharedModel, WarmState, _dtype_code, _stream_ptr
+from .exceptions import BackendError
 from .systems import WheeledInvertedPendulum
 
 NB_SUBSTEPS = 15  # examples/wheeled_inverted_pendulum.py:31
@@ -430,3 +431,249 @@ class LIPMWalkingLoop:
         solves = max(self.mpc_steps * B, 1)
         return {"loops": B, "mpc_steps": self.mpc_steps, "builds_and_solves": self.mpc_steps * B,
                 "failed": int(self.failed.item()), "mean_iters": float(self.iters_total.item()) / solves}
+
+
+# ---------------------------------------------------------------------------
+# Closed loops of any shared model (mpcqp_model_periods_batch)
+# ---------------------------------------------------------------------------
+class ModelClosedLoop:
+    """``B`` independent control loops of one :class:`SharedModel` against a linear plant, advancing in lock step.
+
+    Per period every loop solves the model's problem at its state, applies the first input of the plan (zero when no plan
+    was found -- the loop carries on and the period is counted in ``failed``) and steps its plant
+    ``x+ = Ap x + Bp u0 + d``: the rules of :class:`WIPClosedLoop`, with the plant given as data. ``plant=(Ap, Bp)`` is
+    ``[nx, nx]`` / ``[nx, nu]`` shared or ``[B, nx, nx]`` / ``[B, nx, nu]`` per loop and defaults to the model's own A, B.
+    ``goal`` (``[nx]``, ``[B, nx]``), ``targets`` (``[N nx]``, ``[B, N nx]``) and ``disturbance`` (``[nx]``, ``[B, nx]``) are
+    constant, or carry a period axis in front of the last one (``[B|1, P, nx]``, ``[B|1, P, N nx]``): the loop keeps a period
+    counter and ``step`` reads on from where the last call stopped.
+
+    ``step(n, fused=True)`` runs the ``n`` periods in ONE launch (``mpcqp_model_periods_batch``: float64, N nu <= 16,
+    1 <= N mk <= 32, nx <= 16, the model's own bounds; ``BackendError`` outside that envelope). ``fused=False`` is the loop
+    written by hand -- a :class:`PreparedModelSolve` launch plus the plant step in torch per period -- and serves everything
+    ``SharedModel`` solves. ``warm=True`` (fused only: ``step(fused=False)`` then raises ``ValueError``) starts every period of a launch but the first from the active set
+    and operator of the period before, kept in registers; a warm period that does not end verified-solved is solved again
+    cold (``stats()["resolved_cold"]``), so the trajectories are those of the cold loop to rounding.
+
+    ``feas_tol`` defaults to 1e-9 here, not to the solvers' 1e-12, on purpose: a state-constrained loop whose plant is its
+    model lands exactly ON a bound, and the next period's row on x_0 -- which no input can move -- is then satisfied only to
+    rounding. With the C oracle on the triple-integrator family (e = 3, 67 loops, 7 periods) an error of 1e-11 on the
+    acceleration turned 330 of 469 periods INFEASIBLE under ``1e-12 (1 + |h|)`` and none at 1e-9, where the trajectories
+    moved by 2e-11.
+
+    Measured (profiles/model_loop.md, tools/bench_model_loop.py: triple-integrator family, 50 periods, one MI355X, us per
+    period for the whole batch, by hand / fused cold / fused warm): B = 256: 91 / 11.0 / 6.1; 1024: 87 / 11.4 / 6.7;
+    4096: 88 / 16.9 / 12.9; 65536: 174 / 159 / 131. The fused launch wins at every size measured -- by 5-8x up to 4096,
+    where the loop by hand is bound by the HOST (about 87 us per period of enqueueing, whatever B: the ratio measures that
+    cost, not one kernel against another), by 1.10x (cold) where the device is the bound.
+    The warm start took 0.40 of the cold iterations there; on loops whose active set does not carry over (input boxes
+    with a mismatched plant) it took MORE iterations than cold. Nothing is switched here by a threshold."""
+
+    def __init__(self, model: SharedModel, x0, goal=None, targets=None, plant=None, disturbance=None, warm: bool = False,
+                 feas_tol: float = 1e-9, max_iter: Optional[int] = None, record: bool = True):
+        import torch
+
+        t = model.template
+        self.model = model
+        self._dev, self._dt = t.device, t.dtype
+        self.nx, self.nu, self.N = t.state_dim, t.input_dim, t.nb_timesteps
+        self.n, self.m = t.nb_variables, t.nb_constraints
+        as_t = lambda a: None if a is None else torch.as_tensor(a, dtype=self._dt, device=self._dev).contiguous()  # noqa: E731
+        self.states = as_t(np.asarray(x0, dtype=float) if not torch.is_tensor(x0) else x0).clone()
+        if self.states.ndim != 2 or self.states.shape[1] != self.nx:
+            raise ValueError(f"x0 must be [B, {self.nx}]")
+        B = self.batch = self.states.shape[0]
+        self._goal = self._reference(as_t(goal), self.nx, "goal")
+        self._targets = self._reference(as_t(targets), self.N * self.nx, "targets")
+        self._dist = self._reference(as_t(disturbance), self.nx, "disturbance")
+        Ap, Bp = (t.A[0, 0], t.B[0, 0]) if plant is None else plant
+        self._Ap, self._Bp = as_t(Ap).clone(), as_t(Bp).clone()
+        if self._Ap.shape[-2:] != (self.nx, self.nx) or self._Bp.shape[-2:] != (self.nx, self.nu):
+            raise ValueError("plant must be (Ap [nx, nx] or [B, nx, nx], Bp [nx, nu] or [B, nx, nu])")
+        for M in (self._Ap, self._Bp):
+            if M.ndim == 3 and M.shape[0] != B:
+                raise ValueError("a per-loop plant needs one matrix per loop")
+        self.warm, self.record = bool(warm), bool(record)
+        self._feas_tol, self._max_iter = float(feas_tol), max_iter
+        self._opts = _opts_for_loop(max_iter, feas_tol)
+        self.periods = 0
+        self._loopstats = torch.zeros((B, 3), dtype=torch.int64, device=self._dev)
+        self.U = torch.zeros((B, self.n), dtype=self._dt, device=self._dev)
+        self.lam = torch.zeros((B, max(self.m, 1)), dtype=self._dt, device=self._dev)
+        self.status = torch.zeros((B,), dtype=torch.int32, device=self._dev)
+        self.iters = torch.zeros((B,), dtype=torch.int32, device=self._dev)
+        self._X, self._U0 = [self.states.clone()[:, None]], []
+        self._solver = None  # fused=False: a PreparedModelSolve on buffers of its own, built on first use
+
+    # ------------------------------------------------------------------ references
+    def _reference(self, a, width: int, what: str):
+        """(tensor, batch_stride, period_stride, periods or None) of a reference that is constant or has a period axis."""
+        if a is None:
+            return None
+        if a.shape[-1] != width or a.ndim > 3:
+            raise ValueError(f"{what}: last axis must be {width}, with at most a loop and a period axis in front")
+        if a.ndim == 3:  # [B|1, P, width]
+            if a.shape[0] not in (1, self.batch):
+                raise ValueError(f"{what}: first axis must be 1 or the number of loops")
+            return a, (a.shape[1] * width if a.shape[0] != 1 or self.batch == 1 else 0), width, a.shape[1]
+        if a.ndim == 2 and a.shape[0] not in (1, self.batch):
+            raise ValueError(f"{what}: first axis must be 1 or the number of loops")
+        return a, (width if a.ndim == 2 and (a.shape[0] != 1 or self.batch == 1) else 0), 0, None
+
+    def _operand(self, ref, t: int):
+        if ref is None:
+            return _capi.Operand(None, 0, 0)
+        a, bs, ps, _ = ref
+        return _capi.Operand(a.data_ptr() + t * ps * a.element_size(), bs, ps)
+
+    def _at(self, ref, t: int):
+        """The reference of period t as a tensor that broadcasts against [B, width]."""
+        a, _, ps, _ = ref
+        return a[:, t] if ps else a
+
+    def _check_periods(self, n: int) -> None:
+        for ref, what in ((self._goal, "goal"), (self._targets, "targets"), (self._dist, "disturbance")):
+            if ref is not None and ref[3] is not None and self.periods + n > ref[3]:
+                raise ValueError(f"{what} is laid out for {ref[3]} periods; {self.periods} have run and {n} more were asked for")
+
+    # ------------------------------------------------------------------ stepping
+    def step(self, nb_periods: int = 1, fused: bool = True):
+        """Advance every loop by ``nb_periods`` periods. Asynchronous; returns ``self.states``."""
+        n = int(nb_periods)
+        if n < 1:
+            raise ValueError("nb_periods must be at least 1")
+        self._check_periods(n)
+        if fused:
+            self._step_fused(n)
+        else:
+            if self.warm:
+                raise ValueError("warm=True is carried inside a fused launch only; step(fused=False) always starts cold")
+            for _ in range(n):
+                self._step_by_hand()
+        return self.states
+
+    def _step_fused(self, n: int) -> None:
+        import torch
+
+        if self._dt != torch.float64 or self.n > 16 or not (1 <= self.m <= 32) or self.nx > 16 or self.model.per_problem_bounds:
+            raise BackendError(
+                "ModelClosedLoop.step(fused=True) serves float64 models with N nu <= 16, 1 <= N mk <= 32, nx <= 16 and "
+                f"the model's own bounds (mpcqp_model_periods_batch); this one has N nu = {self.n}, N mk = {self.m}, "
+                f"nx = {self.nx}, {self._dt}" + (", bounds per problem" if self.model.per_problem_bounds else "")
+                + ". step(fused=False) serves everything SharedModel solves.", code=_capi.EUNSUPPORTED)
+        t = self.periods
+        B = self.batch
+        plant = _capi.LoopPlant(
+            _capi.Operand(self._Ap.data_ptr(), self.nx * self.nx if self._Ap.ndim == 3 else 0, 0),
+            _capi.Operand(self._Bp.data_ptr(), self.nx * self.nu if self._Bp.ndim == 3 else 0, 0),
+            self._operand(self._dist, t))
+        goal, targets = self._operand(self._goal, t), self._operand(self._targets, t)
+        X = U0 = None
+        if self.record:
+            X = torch.empty((B, n + 1, self.nx), dtype=self._dt, device=self._dev)
+            U0 = torch.empty((B, n, self.nu), dtype=self._dt, device=self._dev)
+        out = _capi.LoopOut(None if X is None else X.data_ptr(), None if U0 is None else U0.data_ptr(),
+                            self._loopstats.data_ptr())
+        rc = _capi.load().mpcqp_model_periods_batch(
+            C.byref(self.model.dims), self.model.model.data_ptr(), C.byref(plant), self.states.data_ptr(), C.byref(goal),
+            C.byref(targets), B, n, int(self.warm), C.byref(self._opts), self.U.data_ptr(),
+            self.lam.data_ptr() if self.m else None, self.status.data_ptr(), self.iters.data_ptr(), C.byref(out), _stream_ptr())
+        _capi.check(rc, "mpcqp_model_periods_batch")
+        self.periods += n
+        if self.record:
+            self._X.append(X[:, 1:])
+            self._U0.append(U0)
+
+    def _step_by_hand(self) -> None:
+        """One period as users wrote it before: a PreparedModelSolve launch, then the plant step in torch."""
+        import torch
+
+        t = self.periods
+        if self._solver is None:
+            B = self.batch
+            x0 = self.states.clone()
+            goal = None if self._goal is None else torch.zeros((B, self.nx), dtype=self._dt, device=self._dev)
+            tg = None if self._targets is None else torch.zeros((B, self.N * self.nx), dtype=self._dt, device=self._dev)
+            self._solver = self.model.prepare(self.model.problem_for(x0, goal, tg), return_multipliers=True,
+                                              max_iter=self._max_iter, feas_tol=self._feas_tol)
+        s = self._solver
+        p = s.problem
+        p.initial_state.copy_(self.states)
+        if self._goal is not None:
+            p.goal_state.copy_(self._at(self._goal, t).expand_as(p.goal_state))
+        if self._targets is not None:
+            p.target_states.copy_(self._at(self._targets, t).expand_as(p.target_states))
+        s.launch()
+        ok = (s.status == 0)[:, None]
+        u0 = torch.where(ok, s.U[:, :self.nu], torch.zeros((), dtype=self._dt, device=self._dev))
+        if self._Ap.ndim == 3:
+            x = torch.bmm(self._Ap, self.states[:, :, None])[:, :, 0]
+        else:
+            x = self.states @ self._Ap.T
+        if self._Bp.ndim == 3:
+            x = x + torch.bmm(self._Bp, u0[:, :, None])[:, :, 0]
+        else:
+            x = x + u0 @ self._Bp.T
+        if self._dist is not None:
+            x = x + self._at(self._dist, t)
+        self.states.copy_(x)
+        self._loopstats[:, 0] += s.status != 0
+        self._loopstats[:, 1] += s.iters
+        # (the last period's plan is the prepared solve's own output: no copies)
+        self.U, self.status, self.iters = s.U, s.status, s.iters
+        if self.m:
+            self.lam = s.lam
+        self.periods += 1
+        if self.record:
+            self._X.append(self.states.clone()[:, None])
+            self._U0.append(u0[:, None])
+
+    # ------------------------------------------------------------------ results
+    @property
+    def X(self):
+        """[B, periods + 1, nx]: the state before every period and after the last (``record=True``)."""
+        import torch
+
+        return torch.cat(self._X, dim=1)
+
+    @property
+    def U0(self):
+        """[B, periods, nu]: the input applied in every period (``record=True``)."""
+        import torch
+
+        if not self._U0:
+            return torch.empty((self.batch, 0, self.nu), dtype=self._dt, device=self._dev)
+        return torch.cat(self._U0, dim=1)
+
+    @property
+    def plan(self):
+        """The LAST period's plan (``BatchPlan``: U, status, iters, multipliers) at the state before that period."""
+        from .batch import BatchPlan
+
+        x_before = self.X[:, -2] if self.record and self.periods else self.states
+        return BatchPlan(self.model.problem_for(x_before), self.U, self.status, self.iters, self.lam if self.m else None)
+
+    @property
+    def failed(self):
+        """0-d int64 device tensor: periods of any loop without a plan (the zero input was applied)."""
+        return self._loopstats[:, 0].sum()
+
+    @property
+    def iters_total(self):
+        """0-d int64 device tensor: active-set iterations of all periods so far."""
+        return self._loopstats[:, 1].sum()
+
+    def stats(self) -> Dict[str, float]:
+        solves = max(self.periods * self.batch, 1)
+        return {
+            "loops": self.batch,
+            "periods": self.periods,
+            "failed": int(self.failed.item()),
+            "mean_iters": float(self.iters_total.item()) / solves,
+            "resolved_cold": int(self._loopstats[:, 2].sum().item()),
+        }
+
+
+def _opts_for_loop(max_iter, feas_tol):
+    from .batch import _opts
+
+    return _opts(max_iter, feas_tol)

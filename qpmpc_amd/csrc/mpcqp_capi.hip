@@ -355,13 +355,15 @@ int64_t operand_elems(const MpcqpOperand &op, int64_t block, int N, int64_t batc
 // Kernel::GwsSolve alone), and Promote (promote_f32).
 enum class Path { Refused, OnChip, Narrow, Wide, Mid, General, DenseStruct, DenseGws, Promote };
 // The launchers behind Path::OnChip, one value each: launch_quad4, launch_quad, launch_pair, launch_w64 and the workgroup kernel
-// (run_lds) in their modes, launch_duo and its shared-model and QP-given modes, launch_quad_model, launch_pair_model; and
-// run_gws_solve for a given QP that does not fit on chip. None: the path is the launcher.
-enum class Kernel { None, Quad4, Quad, Pair, W64Fused, W64Solve, W64Model, LdsFused, LdsSolve, LdsModel, Duo, DuoModel, DuoQp, QuadModel, PairModel, GwsSolve };
+// (run_lds) in their modes, launch_duo and its shared-model and QP-given modes, launch_quad_model, launch_pair_model;
+// run_gws_solve for a given QP that does not fit on chip; and launch_w64_loop (run() hands it the export's LoopArgs).
+// None: the path is the launcher.
+enum class Kernel { None, Quad4, Quad, Pair, W64Fused, W64Solve, W64Model, LdsFused, LdsSolve, LdsModel, Duo, DuoModel, DuoQp, QuadModel, PairModel, GwsSolve, W64Loop };
 
 struct Entry {
-    // mpcqp_build_solve_batch, mpcqp_stagewise_solve_batch, mpcqp_wip_periods_batch, the shared-model solves, mpcqp_solve_batch
-    enum Kind { BUILD_SOLVE, STAGEWISE, WIP_PERIODS, MODEL, QP_GIVEN } kind = BUILD_SOLVE;
+    // mpcqp_build_solve_batch, mpcqp_stagewise_solve_batch, mpcqp_wip_periods_batch, the shared-model solves, mpcqp_solve_batch,
+    // mpcqp_model_periods_batch
+    enum Kind { BUILD_SOLVE, STAGEWISE, WIP_PERIODS, MODEL, QP_GIVEN, MODEL_PERIODS } kind = BUILD_SOLVE;
     int max_active = 0;                  // STAGEWISE: slots asked for (<= 0: the kernel's default)
     bool general = false, wide = false;  // STAGEWISE: MPCQP_OPT_STAGE_GENERAL / MPCQP_OPT_STAGE_WIDE
     bool bulky = false;                  // BUILD_SOLVE size queries: operands too bulky for the mid-size kernel's LDS
@@ -446,6 +448,8 @@ int refusal(const KernelArgs &ka, int dtype, const Entry &e, const Route *r = nu
     }
     case Entry::STAGEWISE: return (ka.order || ka.warm_state) ? MPCQP_EUNSUPPORTED : 0;
     case Entry::WIP_PERIODS: return ka.order ? MPCQP_EUNSUPPORTED : 0;
+    // the closed loop of a shared model: the automatic kernel, cold or with the warm start it carries itself
+    case Entry::MODEL_PERIODS: return (fl || ka.order || ka.warm_state) ? MPCQP_EUNSUPPORTED : 0;
     case Entry::MODEL: {
         if (ka.warm_state) return MPCQP_EUNSUPPORTED;
         const bool small = pair_eligible(ka, MODE_MODEL, dtype);
@@ -523,6 +527,8 @@ Route route(const KernelArgs &ka, int dtype, int64_t batch, const Entry &e, Simd
         if (int rc = layout_for(ka, false, false, MODE_SOLVE, dtype, L)) return refuse(rc);
         return on_chip(Kernel::LdsModel);
     }
+    case Entry::MODEL_PERIODS:  // (one loop per wavefront: the period loop is compiled into the one-per-wavefront kernel's MODEL mode)
+        return w64_loop_eligible(ka, dtype) ? on_chip(Kernel::W64Loop) : refuse(MPCQP_EUNSUPPORTED);
     case Entry::WIP_PERIODS:  // (the closed-loop epilogue is compiled into the narrow kernel; no second opinion)
         return use_stage_auto(ka, dtype) ? narrow(stage_default_maxq(ka), 0) : refuse(MPCQP_EUNSUPPORTED);
     case Entry::STAGEWISE: {
@@ -677,7 +683,8 @@ int run_dense(KernelArgs ka, int dtype, int64_t batch, void *workspace, hipStrea
 
 // The launch of a route: its kernel's launcher, or the path's where the path is the launcher. stepA / stepB: A and B per step
 // (the workgroup kernel's carve in the fused mode).
-int run(const Route &r, const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, void *ws, hipStream_t st)
+int run(const Route &r, const KernelArgs &ka, bool stepA, bool stepB, int dtype, int64_t batch, void *ws, hipStream_t st,
+        const LoopArgs *loop = nullptr)  // (loop: what Kernel::W64Loop takes next to KernelArgs)
 {
     switch (r.kernel) {
     case Kernel::Quad4: return launch_quad4(ka, batch, st);
@@ -695,6 +702,7 @@ int run(const Route &r, const KernelArgs &ka, bool stepA, bool stepB, int dtype,
     case Kernel::QuadModel: return launch_quad_model(ka, batch, st);
     case Kernel::PairModel: return launch_pair_model(ka, batch, st);
     case Kernel::GwsSolve: return run_gws_solve(ka, dtype, batch, ws, st);
+    case Kernel::W64Loop: return loop ? launch_w64_loop(ka, *loop, batch, st) : MPCQP_EINVAL;
     case Kernel::None: break;
     }
     switch (r.path) {
@@ -1707,6 +1715,47 @@ int mpcqp_wip_periods_batch(const MpcqpDims *dims, const MpcqpProblem *problem, 
     ka.ep_states = states;
     ka.ep_loopstats = (long long *)loop_stats;
     return run_narrow(ka, dims->dtype, r, batch, workspace, (hipStream_t)stream);
+}
+
+int mpcqp_model_periods_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant, void *states,
+                              const MpcqpOperand *goal, const MpcqpOperand *targets, int64_t batch, int32_t nperiods, int32_t warm,
+                              const MpcqpSolveOpts *opts, void *U, void *lam, int32_t *status, int32_t *iters,
+                              const MpcqpLoopOut *out, void *stream)
+{
+    if (nperiods < 1) return MPCQP_EINVAL;
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    if (!model || !plant || !plant->A.ptr || !plant->B.ptr || !states || !U || !status || batch < 0) return MPCQP_EINVAL;
+    if ((dims->flags & MPCQP_Q_TERMINAL) && !(goal && goal->ptr)) return MPCQP_EINVAL;
+    if ((dims->flags & MPCQP_Q_STAGE) && !(targets && targets->ptr)) return MPCQP_EINVAL;
+    KernelArgs ka;
+    fill_args(ka, dims, nullptr);
+    if (goal) ka.goal = *goal;
+    if (targets) ka.targets = *targets;
+    ka.model = model;
+    ka.U = U;
+    ka.lam = lam;
+    ka.status = status;
+    ka.iters = iters;
+    const Entry entry{Entry::MODEL_PERIODS};
+    if ((rc = fill_opts(ka, opts, dims->dtype)) || (rc = refusal(ka, dims->dtype, entry))) return rc;
+    ka.probe = nullptr;
+    const Route r = route(ka, dims->dtype, batch, entry, SimdCount{});
+    if (r.path == Path::Refused) return r.rc;
+    if (batch == 0) return 0;
+    LoopArgs lp{};
+    lp.A = plant->A;
+    lp.B = plant->B;
+    lp.d = plant->d;
+    lp.states = states;
+    if (out) {
+        lp.X = out->X;
+        lp.U0 = out->U0;
+        lp.stats = (long long *)out->loop_stats;
+    }
+    lp.nperiods = nperiods;
+    lp.warm = warm != 0;
+    return run(r, ka, false, false, dims->dtype, batch, nullptr, (hipStream_t)stream, &lp);
 }
 
 int mpcqp_wip_advance_stats_batch(int32_t dtype, void *states, const void *U, int64_t u_stride, const int32_t *status,

@@ -9,7 +9,7 @@
 
 namespace mpcqp {
 
-enum { MODE_FUSED = 0, MODE_CONDENSE = 1, MODE_SOLVE = 2, MODE_MODEL = 3 };
+enum { MODE_FUSED = 0, MODE_CONDENSE = 1, MODE_SOLVE = 2, MODE_MODEL = 3, MODE_LOOP = 4 };
 
 constexpr size_t kLdsBytesPerCU = 160 * 1024;  // gfx950: 160 KiB per CU
 
@@ -257,6 +257,20 @@ int launch_duo_qp(const KernelArgs &ka, int64_t batch, hipStream_t st);
 // small-problem kernel (mpcqp_w64.hip): one problem per wavefront
 bool w64_eligible(const KernelArgs &ka, int mode, int dtype);
 int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStream_t st);
+// ... and its closed loop (MODE_LOOP, mpcqp_model_periods_batch): `nperiods` control periods of a shared model per launch, the
+// wavefront that solved period t stepping its plant and carrying on with period t + 1. What the loop adds to KernelArgs is a
+// kernel argument of its own, so the other kernels' argument layouts stay what they were. ka.goal / ka.targets: step_stride is
+// the PERIOD stride here.
+struct LoopArgs {
+    MpcqpOperand A, B, d;  // the plant x+ = A x + B u0 + d (d.ptr null: none; d.step_stride: period stride)
+    void *states;          // [batch, nx], updated in place
+    void *X, *U0;          // recorded trajectories, or null
+    long long *stats;      // [batch, 3] += (periods without a plan, iterations, warm periods re-solved cold), or null
+    int nperiods, warm;
+    int off_xs;            // LDS: the state (16) and the applied input (16), behind the kernel's own carve
+};
+bool w64_loop_eligible(const KernelArgs &ka, int dtype);  // float64, n <= 16, 1 <= m <= 32, nx <= 16
+int launch_w64_loop(const KernelArgs &ka, const LoopArgs &lp, int64_t batch, hipStream_t st);
 int launch_phi(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);
 int launch_update(const KernelArgs &ka, int dtype, int64_t phi_bs, int64_t psi_bs, int64_t batch, hipStream_t st);
 int launch_rollout(const KernelArgs &ka, int dtype, int64_t batch, hipStream_t st);

@@ -227,14 +227,44 @@ using namespace w64;
 // MODE_FUSED: build from the MPC problem (A..targets). MODE_SOLVE: gA=P, gB=q, gC=G, ge=h.
 // MK > 0: compile-time number of inequality rows per step for the software-pipelined
 // chain (terminal cost only, state constraints only); MK == 0: generic chain.
-template <typename T, int NX, int MODE, int MK>
+// MODE_LOOP (mpcqp_model_periods_batch): MODE_MODEL's lane roles with a PERIOD LOOP around the active-set loop. The rows of M
+// and of L^-T are loaded once per launch: the only pass that writes R adds c * vec with c == 0 on every lane that is no slot, so
+// they survive a solve untouched. Per period the wavefront forms h and w = L^-1 q from the state it keeps in LDS, solves, applies
+// the first input to the plant (lane r < nx: row r of A_p, B_p) and carries on. With lp.warm the slots, M_A, T, mask, nq and pos of
+// a period that ended solved are KEPT (T = N* depends on the matrices only: MpcqpSolveOpts.warm_state's contract): the multipliers
+// of the equality-constrained problem on the kept set come from the refinement block's formulas started at lam = 0, negative ones
+// leave through the drop pass below, the slacks are evaluated from scratch and the active-set loop carries on from there. Such a
+// period is accepted through the from-scratch verification only; one that does not end solved is solved again cold, in place.
+// MODE_LOOP keeps nothing in registers across the active-set loop that it can read again: per period the kernel's arguments come
+// from the kernel-argument segment (explicit arguments in order from offset 0, each at its natural alignment; twelve pointers,
+// then KernelArgs, Lay, LoopArgs) through a pointer the compiler cannot see through, so neither they nor the addresses
+// derived from them are hoisted out of the period loop and held -- or spilled -- while the solver runs.
+#define MPCQP_KERNARG __attribute__((address_space(4)))
+constexpr size_t karg_up(size_t o, size_t a) { return (o + a - 1) / a * a; }
+constexpr size_t kArgKa = karg_up(12 * sizeof(void *), alignof(KernelArgs));
+constexpr size_t kArgLay = karg_up(kArgKa + sizeof(KernelArgs), alignof(Lay));
+constexpr size_t kArgLoop = karg_up(kArgLay + sizeof(Lay), alignof(LoopArgs));
+template <typename S> __device__ __forceinline__ const S MPCQP_KERNARG *kernarg_now(size_t off)
+{
+    const char MPCQP_KERNARG *p = (const char MPCQP_KERNARG *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (const S MPCQP_KERNARG *)(p + off);
+}
+// What the loop adds to the kernel's arguments is a trailing pack, empty in every other mode: their signatures stay what they were.
+struct NoLoop {};
+__device__ __forceinline__ NoLoop loop_of() { return {}; }
+__device__ __forceinline__ const LoopArgs &loop_of(const LoopArgs &l) { return l; }
+template <typename T, int NX, int MODE, int MK, typename... LP>
 __global__ void __launch_bounds__(64, 4)
     mpcqp_w64_kernel(const T *__restrict__ gA, const T *__restrict__ gB, const T *__restrict__ gC,
                      const T *__restrict__ gD, const T *__restrict__ ge, const T *__restrict__ gx0,
                      const T *__restrict__ ggoal, const T *__restrict__ gtgt, T *__restrict__ oU,
                      T *__restrict__ olam, int32_t *__restrict__ ostatus, int32_t *__restrict__ oiters,
-                     const KernelArgs ka, const Lay L)
+                     const KernelArgs ka, const Lay L, const LP... lpk)
 {
+    const auto &lp = loop_of(lpk...);  // (MODE_LOOP: LoopArgs)
+    constexpr bool kLoop = (MODE == MODE_LOOP);
+    constexpr bool kFactored = (MODE == MODE_MODEL) || kLoop;  // M, L^-T and the maps from the states come from the shared model
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sm = (T *)smem_raw;
     const int lane = threadIdx.x;
@@ -266,7 +296,39 @@ __global__ void __launch_bounds__(64, 4)
 
     T invn_model = T(1);
     bool notpd = false;
-    if constexpr (MODE == MODE_MODEL) {
+    if constexpr (kLoop) {
+        // what does not depend on the state, once per launch: this lane's row of M or of L^-T, the model's flag
+        const T *model = gA;
+        {
+            // The segment offsets above are tied to this kernel's signature by hand: once per launch, what they read is held against
+            // the arguments as the compiler passes them. A signature that moved away from kArgKa / kArgLay / kArgLoop ends the launch
+            // here with status MPCQP_EINVAL on every loop and nothing else written (tests compare every status).
+            const auto *kq = kernarg_now<KernelArgs>(kArgKa);
+            const auto *Lq = kernarg_now<Lay>(kArgLay);
+            const auto *lq = kernarg_now<LoopArgs>(kArgLoop);
+            if (kq->n != ka.n || kq->m != ka.m || kq->model != ka.model || kq->max_iter != ka.max_iter || Lq->off_hv != L.off_hv ||
+                Lq->mo_flag != L.mo_flag || lq->off_xs != lp.off_xs || lq->nperiods != lp.nperiods || lq->states != lp.states ||
+                lq->stats != lp.stats) {
+                if (lane == 0 && ostatus) ostatus[prob] = MPCQP_EINVAL;
+                return;
+            }
+        }
+        T *xs = sm + lp.off_xs;
+        notpd = model[L.mo_flag] != T(0);
+        const T *rowsrc = isc ? model + L.mo_M + cid * NV : model + L.mo_LinvT + (lane >= LB ? lane - LB : 0) * NV;
+        if (isc || lane >= LB) {
+            ld16(R, rowsrc);
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) R[k] = T(0);
+        }
+        if (lane < ka.nx) {
+            const T x = ((const T *)lp.states)[prob * ka.nx + lane];
+            xs[lane] = x;
+            if (lp.X) ((T *)lp.X)[prob * (int64_t)(lp.nperiods + 1) * ka.nx + lane] = x;
+        }
+        wave_sync();
+    } else if constexpr (MODE == MODE_MODEL) {
         // Shared model (gA): M, L^-T and the maps from the states are already factored;
         // this problem only differs by x0 / goal / targets.
         const T *model = gA;
@@ -505,7 +567,7 @@ __global__ void __launch_bounds__(64, 4)
     // with v_readlane (the LDS pipe is this kernel's bottleneck, the VALU is not); the
     // trailing update needs no sqrt: P[i][k] -= P[i][j] P[k][j] / piv.
     T myinv = T(1);  // lane j keeps 1 / L_jj
-    if constexpr (MODE != MODE_MODEL) {
+    if constexpr (!kFactored) {
     // Column j (one entry per lane) is broadcast through a double-buffered 16-entry LDS vector: column j+1
     // is brought up to date and written FIRST in step j, so its round trip overlaps the rest of step j's
     // updates. One write and <= 8 wavefront-uniform 16-byte reads per column replace 2 (15 - j) v_readlane.
@@ -555,12 +617,12 @@ __global__ void __launch_bounds__(64, 4)
     tick(2);
     int status = MPCQP_MAX_ITER, iters = 0;
     T xsol = T(0), lam_out = T(0);
-    if (notpd) {
+    if (!kLoop && notpd) {  // (MODE_LOOP: such a loop fails every period and its plant steps with a zero input, below)
         status = MPCQP_NOT_PD;
     } else {
         // Rows fetched only now (register pressure): lane 0 takes q, constraint lanes
         // their row of G, lanes 48.. the identity (-> rows of L^-T), all others zero.
-        if constexpr (MODE != MODE_MODEL) {
+        if constexpr (!kFactored) {
             const bool fetch = isc || lane == 0;
             const int row = isc ? cid : m;
             if (fetch) {
@@ -615,8 +677,77 @@ __global__ void __launch_bounds__(64, 4)
         }
         // rows of M for the row-p broadcasts: the LDS image, or the shared model itself
         // (4 KB read by every wavefront of the launch: it stays in L1/L2)
-        const T *Mbase = (MODE == MODE_MODEL) ? gA + L.mo_M : Ml;
-        const int mstride = (MODE == MODE_MODEL) ? NV : LDM;
+        const T *Mbase = kFactored ? gA + L.mo_M : Ml;
+        const int mstride = kFactored ? NV : LDM;
+        // MODE_LOOP: what a period that ended solved leaves to a warm one (the slot's row and occupancy, the row's slot, the
+        // set's size and mask), next to T in R and M_A in LDS. Copies: the solver's own variables are declared where they always
+        // were, further down -- declared up here, the other modes' register allocation changes (SOLVE: 9 -> 15 spilled VGPRs)
+        int k_myact = 0, k_pos = -1, k_nq = 0;
+        bool k_occ = false;
+        unsigned k_mask = 0;
+        // ... and, all wave-uniform: the period, its iterations before a cold restart, whether the last period ended solved,
+        // whether this one restarts cold / started warm, and the launch's counters
+        int period = 0, it_acc = 0, nfail = 0, nit = 0, ncold = 0;
+        bool prev_ok = false, force_cold = false, warmp = false;
+        // ... in a warm period: the kept set's multipliers are not settled yet / the slot the drop pass removes next
+        bool wphase = false;
+        int wdrop = -1;
+        for (;;) {  // one trip per control period (MODE_LOOP; every other mode leaves at the end of the first)
+        if constexpr (kLoop) {
+            // ---------------------------------------------------- this period's h and w = L^-1 q, from the state in LDS
+            const auto *kq = kernarg_now<KernelArgs>(kArgKa);
+            const auto *Lq = kernarg_now<Lay>(kArgLay);
+            const auto *lq = kernarg_now<LoopArgs>(kArgLoop);
+            int ln = lane;  // (and the lane's own addresses from a lane id the compiler cannot see through)
+            pin(ln);
+            const int lc = ln - CB;
+            const bool lisc = (ln >= CB) && (lc < kq->m);
+            const T *model = (const T *)kq->model;
+            const T *xq = sm + lq->off_xs;
+            const int nx = kq->nx, nT = kq->N * kq->nx, qfl = kq->flags;
+            const T *goal = (const T *)kq->goal.ptr, *tgt = (const T *)kq->targets.ptr;
+            if (goal) goal += prob * kq->goal.batch_stride + (int64_t)period * kq->goal.step_stride;
+            if (tgt) tgt += prob * kq->targets.batch_stride + (int64_t)period * kq->targets.step_stride;
+            status = MPCQP_MAX_ITER;
+            xsol = T(0);
+            lam_out = T(0);
+            T hh = INF;
+            invn_model = T(1);
+            if (lisc) {
+                invn_model = model[Lq->mo_invn + lc];  // 1 / |M_i| (read again per period: not held across the solve)
+                const T *Hx = model + Lq->mo_Hx + lc * nx;
+                hh = model[Lq->mo_e + lc];
+                for (int c = 0; c < nx; ++c) hh -= Hx[c] * xq[c];
+            }
+            wave_sync();
+            (sm + Lq->off_hv)[ln] = hh;
+            wave_sync();
+            if (ln < NV) {  // (lane k: component k)
+                T wk = T(0);
+                const T *Wx = model + Lq->mo_Wx + ln * nx;
+                for (int c = 0; c < nx; ++c) wk += Wx[c] * xq[c];
+                if ((qfl & MPCQP_Q_TERMINAL) && goal) {
+                    const T *Wg = model + Lq->mo_Wg + ln * nx;
+                    for (int c = 0; c < nx; ++c) wk -= Wg[c] * goal[c];
+                }
+                if ((qfl & MPCQP_Q_STAGE) && tgt) {
+                    const T *Wt = model + Lq->mo_Wt + ln * nT;
+                    for (int j2 = 0; j2 < nT; ++j2) wk -= Wt[j2] * tgt[j2];
+                }
+                (sm + Lq->off_hv + LB)[ln] = wk;  // y0v
+            }
+            // warm: only inside a launch, after a period that ended solved with rows active; else the empty set
+            warmp = lq->warm && prev_ok && !force_cold && k_nq > 0;
+            if (!warmp) {
+                if (low) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) R[k] = T(0);
+                }
+                T *MAq = sm + Lq->off_X;
+                for (int i = ln; i < (NV + 1) * NV; i += 64) MAq[i] = T(0);
+            }
+            wave_sync();
+        }
         const T hval = hv[lane];
         T s = hval + dot_reg_lds(R, y0v);  // h - M y0  (y0 = -L^-1 q)
         s = isc ? s : INF;
@@ -626,13 +757,13 @@ __global__ void __launch_bounds__(64, 4)
         // 10.8 iterations on average and 16 at most, against 12.3 / 26 when the
         // slack is only scaled by 1 + |h_i|, and it practically removes the drops.
         T invn = invn_model;
-        if constexpr (MODE != MODE_MODEL) {
+        if constexpr (!kFactored) {
             T nn = T(0);
 #pragma unroll
             for (int k = 0; k < NV; ++k) nn += R[k] * R[k];
             invn = (nn > T(0)) ? Cst<T>::rs(nn) : T(1);
         }
-        const bool selectable = isc && (hval < T(1e29));
+        const bool selectable = isc && (hval < T(1e29)) && !(kLoop && notpd);
         const T tol = (T)ka.tol;
         const T tolh = tol + tol * fabs(hval);  // row i is violated when s_i < -tol (1 + |h_i|)
         const int max_iter = ka.max_iter;
@@ -642,11 +773,66 @@ __global__ void __launch_bounds__(64, 4)
         bool occ = false;
         unsigned mask = 0;  // occupied slots (wave-uniform)
         bool fail = false;
+        if constexpr (kLoop) {
+            if (warmp) {
+                myact = k_myact;
+                pos = k_pos;
+                nq = k_nq;
+                occ = k_occ;
+                mask = k_mask;
+            }
+        }
+        if constexpr (kLoop) wphase = warmp;
         tick(4);
         for (int round = 0; round < 4 && !fail; ++round) {
             // ===================================================== active-set loop
             for (;;) {
-                const int p = argmin_coarse<T>(s * invn, selectable && pos < 0 && s < -tolh, lane);
+                if constexpr (kLoop) {
+                    if (wphase) {
+                        // multipliers of the equality-constrained problem on the kept set, at y_unc = -w: rho_a = h_a - M_a . y_unc,
+                        // lam_A = -T (T' rho_A) -- the refinement block's formulas started at lam = 0
+                        wave_sync();
+                        zv[vofs] = -y0v[l15];
+                        wave_sync();
+                        const T f0 = hv[lane] - dot_reg_lds(R, zv);
+                        T rho = __shfl(f0, myact);
+                        rho = occ ? rho : T(0);
+                        wave_sync();
+                        kAv[vofs] = rho;
+                        if (low) st16(Timg + lane * NV, R);
+                        wave_sync();
+                        const T uk = dot_vec_col<NV>(kAv, Timg + l15, T(0));
+                        rv[vofs] = low ? uk : T(0);
+                        wave_sync();
+                        const T lw = -dot_reg_lds(R, rv);
+                        lam = occ ? lw : T(0);
+                        const int l = argmin_row0<T>(lam, occ && lam < T(0), lane);
+                        if (l < 64) {
+                            // the most negative one leaves through the drop pass (one iteration; at most nq <= 16 of them)
+                            wdrop = l;
+                            ++iters;
+                            const int cl = lane_get(myact, l);
+                            wave_sync();
+                            if (lane == l) st16(kAv, R);
+                            if (lane == cl) pos = -1;
+                            wave_sync();
+                        } else {
+                            // settled: y = y_unc - M_A' lam, the slacks from scratch, and on with the active-set loop
+                            wphase = false;
+                            wave_sync();
+                            rv[vofs] = lam;
+                            wave_sync();
+                            T y = dot_vec_col<NV>(rv, MAl + l15, T(0));
+                            y = -y0v[l15] - y;
+                            wave_sync();
+                            zv[vofs] = y;
+                            wave_sync();
+                            const T fr = hv[lane] - dot_reg_lds(R, zv);
+                            s = isc ? ((pos >= 0) ? T(0) : fr) : INF;
+                        }
+                    }
+                }
+                const int p = (kLoop && wdrop >= 0) ? CB : argmin_coarse<T>(s * invn, selectable && pos < 0 && s < -tolh, lane);
                 if (p == 64) {
                     status = MPCQP_SOLVED;
                     break;
@@ -661,6 +847,12 @@ __global__ void __launch_bounds__(64, 4)
                 // a single modification site of R is what keeps R in registers.
                 bool dropping = false;
                 int ldrop = 0;
+                if constexpr (kLoop) {
+                    if (wdrop >= 0) {  // (a warm period's drop: straight into the drop pass, row p is not touched)
+                        dropping = true;
+                        ldrop = wdrop;
+                    }
+                }
                 while (!added) {
                     const T *vec;
                     T c, t = T(0), r = T(0);
@@ -767,6 +959,12 @@ __global__ void __launch_bounds__(64, 4)
                         mask &= ~(1u << ldrop);
                         --nq;
                         dropping = false;
+                        if constexpr (kLoop) {
+                            if (wdrop >= 0) {  // back to the multipliers of what is left
+                                wdrop = -1;
+                                added = true;
+                            }
+                        }
                     }
                     wave_sync();
                 }
@@ -826,6 +1024,70 @@ __global__ void __launch_bounds__(64, 4)
         if (status == MPCQP_SOLVED && olam) {
             const T lv = __shfl(lam, pos < 0 ? 0 : pos);
             lam_out = (pos >= 0) ? lv : T(0);
+        }
+        if constexpr (kLoop) {
+            // ---------------------------------------------------- the period's end: verdict, plant step, records
+            if (notpd) status = MPCQP_NOT_PD;
+            const bool okp = (status == MPCQP_SOLVED);
+            if (warmp && !okp) {
+                // a stale state costs a cold restart, never a wrong plan: whatever the verdict (the iteration limit, a failed
+                // verification, infeasible -- not believed from a drifted T), the period is solved again from the empty set
+                force_cold = true;
+                ++ncold;
+                it_acc += iters;
+                iters = 0;
+                continue;
+            }
+            iters += it_acc;
+            it_acc = 0;
+            force_cold = false;
+            prev_ok = okp;
+            k_myact = myact;
+            k_pos = pos;
+            k_nq = nq;
+            k_occ = occ;
+            k_mask = mask;
+            nfail += okp ? 0 : 1;
+            nit += iters;
+            const auto *kq = kernarg_now<KernelArgs>(kArgKa);
+            const auto *lq = kernarg_now<LoopArgs>(kArgLoop);
+            int ln = lane;
+            pin(ln);
+            const int nx = kq->nx, nu = kq->nu, nper = lq->nperiods;
+            T *xq = sm + lq->off_xs, *uq = xq + NV;
+            wave_sync();
+            if (ln >= LB) uq[ln - LB] = (okp && ln - LB < kq->n) ? xsol : T(0);  // lanes 48.. hold u_k; zero without a plan
+            wave_sync();
+            T xn = T(0);
+            if (ln < nx) {  // lane r: row r of the plant
+                const T *Ap = (const T *)lq->A.ptr + prob * lq->A.batch_stride + ln * nx;
+                const T *Bp = (const T *)lq->B.ptr + prob * lq->B.batch_stride + ln * nu;
+                for (int c = 0; c < nx; ++c) xn += Ap[c] * xq[c];
+                for (int j2 = 0; j2 < nu; ++j2) xn += Bp[j2] * uq[j2];
+                const T *dq = (const T *)lq->d.ptr;
+                if (dq) xn += dq[prob * lq->d.batch_stride + (int64_t)period * lq->d.step_stride + ln];
+            }
+            wave_sync();
+            T *Xq = (T *)lq->X, *U0q = (T *)lq->U0;
+            if (ln < nx) {
+                xq[ln] = xn;
+                if (Xq) Xq[(prob * (int64_t)(nper + 1) + period + 1) * nx + ln] = xn;
+            }
+            if (U0q && ln < nu) U0q[(prob * (int64_t)nper + period) * nu + ln] = uq[ln];
+            wave_sync();
+            if (++period < nper) {
+                iters = 0;
+                continue;
+            }
+            if (ln < nx) ((T *)lq->states)[prob * nx + ln] = xn;
+            long long *sq = lq->stats;
+            if (sq && ln == 0) {
+                sq[prob * 3 + 0] += nfail;
+                sq[prob * 3 + 1] += nit;
+                sq[prob * 3 + 2] += ncold;
+            }
+        }
+        break;
         }
     }
 
@@ -934,6 +1196,25 @@ int launch_w64(const KernelArgs &ka, int mode, int dtype, int64_t batch, hipStre
     }
     if (mode == MODE_MODEL) return launch_w64_t<double, MODE_MODEL, 4, 0>(ka, batch, st);
     return launch_w64_t<double, MODE_SOLVE, 4, 0>(ka, batch, st);
+}
+
+bool w64_loop_eligible(const KernelArgs &ka, int dtype)
+{
+    return dtype == MPCQP_F64 && ka.n <= NV && ka.m >= 1 && ka.m <= MMAX && ka.nx <= NV;
+}
+
+int launch_w64_loop(const KernelArgs &ka, const LoopArgs &loop, int64_t batch, hipStream_t st)
+{
+    Lay L = make_lay<double>(ka);
+    LoopArgs lp = loop;
+    lp.off_xs = L.total;  // the state and the applied input, behind the kernel's own carve
+    L.total += 2 * NV;
+    using T = double;
+    hipLaunchKernelGGL((mpcqp_w64_kernel<T, 4, MODE_LOOP, 0, LoopArgs>), dim3((unsigned)batch), dim3(64), (size_t)L.total * sizeof(T), st,
+                       (const T *)ka.model, (const T *)nullptr, (const T *)nullptr, (const T *)nullptr, (const T *)nullptr,
+                       (const T *)nullptr, (const T *)ka.goal.ptr, (const T *)ka.targets.ptr, (T *)ka.U, (T *)ka.lam, ka.status,
+                       ka.iters, ka, L, lp);
+    return (int)hipGetLastError();
 }
 
 }  // namespace mpcqp
