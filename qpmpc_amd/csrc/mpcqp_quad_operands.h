@@ -1,7 +1,7 @@
 // mpcqp_quad_operands.h -- the OPERAND LOADS of mpcqp_quad_kernel's build (mpcqp_quad.hip): a fragment of that kernel's body, included
 // once, right behind the two base pointers it needs (A, Cm) and in front of every other load of the build. It is no header in the
-// usual sense: it reads the kernel's locals (l, N, A, Cm, sA, sC, NAe, NEr) and fills op[][]. It sits in a file of its own so that the
-// kernel file keeps its line numbers (tests/dpp_instantiations.py names the launch lines of every instantiation).
+// usual sense: it reads the kernel's locals (l, N, A, Cm, sA, sC, NAe, NEr) and fills op[][]. It was split out while a test named lines
+// of the kernel file; none does now, so nothing but history keeps it in a file of its own.
 //
 // Lane e of the row keeps element e (and e + 16, ...) of [A_k | C_k] for every step k, straight from HBM; the chain fetches an operand
 // as a DPP row broadcast (lanes without an element load a valid address and are never read). The chain's first step waits for the first

@@ -2,8 +2,8 @@
 // top of its outer loop, in front of the general active-set loop. It is no header in the usual sense: it reads and writes the kernel's
 // local state (RT, RH, RM0, RM1, s0, s1, lam, myact, occ, e0, e1, mask, nq, iters, zn, cT, cH, done, status, p, up, needp; hd, kd0, kd1,
 // inv, t2, rd of the trip it leaves with) and defines `general`, false when every row finished here and the general loop has nothing to
-// do. It sits in a file of its own so that the kernel file keeps its line numbers (tests/dpp_instantiations.py names the launch lines
-// of every instantiation).
+// do. It was split out while a test named lines of the kernel file; none does now (tests/dpp_instantiations.py names the launcher
+// functions), so nothing but history keeps it in a file of its own.
 //
 // Nearly every trip is a plain one -- every row still in the loop selects a constraint and takes the full step, no multiplier
 // blocks (config 2: 10.75 iterations per problem, 10.75 rows active at the optimum). Those trips run here, in a loop of one

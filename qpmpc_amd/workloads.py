@@ -173,8 +173,7 @@ def tight_ltv(kind, rng, batch, tight):
     N = int(rng.integers(20, 41)); mk = int(rng.integers(4, 7))
     if kind == "widef":  # constraint matrices FIXED along the horizon, 4 / 8 / 12 / 16 rows per step: the wide kernel's layout in
         mk = 4 * int(rng.integers(1, 5))  # which the forward sweep forms the rows itself (config 5's)
-    w = random_ltv(rng, batch, nx, nu, N, mk, tight)  # (smaller: tighter rows, more of them active)
-    w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
+    w = tight_dynamics(random_ltv(rng, batch, nx, nu, N, mk, tight))  # (smaller: tighter rows, more of them active)
     if kind == "widef":
         w["C"], w["D"] = w["C"][:, :1].copy(), w["D"][:, :1].copy()
         for b in range(batch):  # bounds around the free response, as random_ltv makes them (with the fixed C)
@@ -182,6 +181,42 @@ def tight_ltv(kind, rng, batch, tight):
             for k in range(N):
                 w["e"][b, k] = w["C"][b, 0] @ x + tight * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
                 x = w["A"][b, k] @ x
+    return w
+
+
+def tight_dynamics(w):
+    """tight_ltv's dynamics on a random_ltv workload: A ten times closer to the identity (in place)"""
+    nx = w["A"].shape[-1]
+    w["A"] = np.eye(nx) + 0.1 * (w["A"] - np.eye(nx))
+    return w
+
+
+def mixed_family(rng, batch, nx, nu, N, mk, general):
+    """``batch`` random_ltv problems whose wavefronts of four mix the kinds of row: problem i is of kind i % 4 -- tight (0.05),
+    loose (3.0), inconsistent and tight (0.05), inconsistent (0.2) --, the kinds rotated within every four; A and C are those of the
+    first step, and the bounds run along that time-invariant system (consistent) or along the per-step one (inconsistent: the rows
+    no longer agree with e). ``general``: with D and a stage cost. The family of the four-per-wavefront kernel's bit fixtures
+    (tools/gen_golden_quad_*.py); the draws stay in this order."""
+    w = random_ltv(rng, batch, nx, nu, N, mk, 1.0)
+    tight = np.array([0.05, 3.0, 0.05, 0.2])[np.arange(batch) % 4]
+    broken = np.arange(batch) % 4 >= 2
+    shift = rng.integers(0, 4, batch // 4)  # (the kinds sit in another row of every wavefront)
+    for g in range(batch // 4):
+        sl = slice(4 * g, 4 * g + 4)
+        tight[sl], broken[sl] = np.roll(tight[sl], shift[g]), np.roll(broken[sl], shift[g])
+    A, Cm, e = w["A"], w["C"], w["e"]
+    for b in range(batch):
+        x = w["x0"][b].copy()
+        for k in range(N):
+            kk = k if broken[b] else 0
+            e[b, k] = Cm[b, kk] @ x + tight[b] * (0.05 + 0.5 * np.abs(rng.standard_normal(mk)))
+            x = A[b, kk] @ x
+    w["A"] = np.ascontiguousarray(A[:, :1])
+    w["C"] = np.ascontiguousarray(Cm[:, :1])
+    if general:
+        w["D"] = np.ascontiguousarray(w["D"][:, :1])
+    else:
+        w["wx"] = w["targets"] = w["D"] = None
     return w
 
 

@@ -4,7 +4,7 @@
 The wait states in front of a hand-written DPP instruction are kept by the source (dpp_ready), and what the register allocator puts
 between the two differs per template instantiation: an instantiation nobody launches is guarded by nothing. census() lists, from the
 gfx950 assembly of the five units, every kernel that holds such an instruction; MANIFEST maps each to the recipe that selects it --
-entry point, shape, rows, cost, flags, batch as a function of the device's SIMD count, and the source line that decides --;
+entry point, shape, rows, cost, flags, batch as a function of the device's SIMD count, and the launcher function that decides --;
 tests/test_dpp_instantiations_cpu.py holds the two to each other and the recipes' inputs to the conditions that make a green GPU case
 mean something; tests/test_gpu_dpp_instantiations.py runs one case per recipe.
 
@@ -94,7 +94,7 @@ def census() -> dict:
 # .launch(): matrices shared, bounds per problem); shape (nx, nu, N, mk); rows "c" / "d" / "cd" (state rows, an input box, both); stage:
 # with a stage cost; tight: the generator's tightness (those of tests/test_gpu_quad.py: 3.0, 0.2, 0.1, 0.05); flags: _capi.OPT_*
 # names; batch: SMALL problems, or a name of BATCHES -- a function of simds = 4 * compute units --; check: what the GPU case holds
-# (see tests/test_gpu_dpp_instantiations.py); line: the source line that selects the instantiation.
+# (see tests/test_gpu_dpp_instantiations.py); site: "<file of csrc/>:<launcher function>", the function that selects the instantiation.
 SMALL = 37  # a ragged last wavefront at four and at two problems per wavefront, ten / nineteen wavefronts
 BATCHES = {
     # more wavefronts than SIMDs (mpcqp_quad.hip: slim = waves > device_simds_now()), a ragged last wavefront
@@ -120,15 +120,28 @@ def oracle_subset(batch: int) -> np.ndarray:
     return np.concatenate([np.arange(ORACLE_HEAD), np.arange(batch - ORACLE_TAIL, batch)])
 
 
-def _r(entry, shape, rows, stage, tight, seed, line, check="oracle", flags=(), batch=SMALL):
-    return dict(entry=entry, shape=shape, rows=rows, stage=stage, tight=tight, seed=seed, line=line, check=check, flags=tuple(flags),
+def _r(entry, shape, rows, stage, tight, seed, site, check="oracle", flags=(), batch=SMALL):
+    return dict(entry=entry, shape=shape, rows=rows, stage=stage, tight=tight, seed=seed, site=site, check=check, flags=tuple(flags),
                 batch=batch)
 
 
-def _unreachable(line, why):
-    return dict(unreachable=True, line=line, why=why)
+def _unreachable(site, quote, why):
+    """site: the function that refuses the launch; quote: the source text of the rule, verbatim (once in that file)"""
+    return dict(unreachable=True, site=site, quote=quote, why=why)
 
 
+def function_text(source: str, function: str) -> list:
+    """the lines of the one definition of `function` in a source text, from its signature to the closing brace in column 0
+    (a declaration ends in a semicolon, a call is indented or names template arguments); [] if there is not exactly one"""
+    lines = source.split("\n")
+    starts = [i for i, s in enumerate(lines) if re.match(r"(?!//)\S.*\b" + function + r"\(", s) and not s.rstrip().endswith(";")]
+    if len(starts) != 1 or "}" not in lines[starts[0]:]:
+        return []
+    return lines[starts[0]: lines.index("}", starts[0]) + 1]
+
+
+QUAD_T, QUAD_MODEL, QUADG_T = "mpcqp_quad.hip:launch_quad_t", "mpcqp_quad.hip:launch_quad_model", "mpcqp_quadg.hip:launch_quadg_t"
+PAIR_T, PAIR_MODEL = "mpcqp_pair.hip:launch_pair_t", "mpcqp_pair.hip:launch_pair_model"
 FOUR, TWO = "OPT_FOUR_PER_WAVE", "OPT_TWO_PER_WAVE"
 # one shape per compiled size of the general build of mpcqp_quad.hip (nx = 7 .. 16 run the padded sizes 8, 12, 16)
 GENERAL = {2: ((2, 1, 16, 2), "d", False), 3: ((3, 1, 16, 2), "c", True), 4: ((4, 2, 8, 2), "cd", True), 5: ((5, 1, 16, 2), "cd", True),
@@ -149,47 +162,48 @@ def _manifest() -> dict:
     seed = iter(range(7000, 8000))
     # mpcqp_quad_kernel<NX, ORDER, 1, SLIM, MODEL, GEN> -- the general build, both LDS carves
     for nx, (shape, rows, stage) in GENERAL.items():
-        M[f"mpcqp_quad_kernel<{nx}, false, 1, false, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_quad.hip:1011")
-        M[f"mpcqp_quad_kernel<{nx}, false, 1, true, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_quad.hip:1009",
+        M[f"mpcqp_quad_kernel<{nx}, false, 1, false, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), QUAD_T)
+        M[f"mpcqp_quad_kernel<{nx}, false, 1, true, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), QUAD_T,
                                                                       check="slim", batch="slim")
     # ... the lean build: natural order / pairing order, roomy / slim carve
     for nx, shape in LEAN.items():
-        M[f"mpcqp_quad_kernel<{nx}, false, 1, false, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), "mpcqp_quad.hip:1021",
+        M[f"mpcqp_quad_kernel<{nx}, false, 1, false, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), QUAD_T,
                                                                         flags=[FOUR])
-        M[f"mpcqp_quad_kernel<{nx}, false, 1, true, false, false>"] = _r("solve", shape, "c", False, 0.05, next(seed), "mpcqp_quad.hip:1019",
+        M[f"mpcqp_quad_kernel<{nx}, false, 1, true, false, false>"] = _r("solve", shape, "c", False, 0.05, next(seed), QUAD_T,
                                                                        check="slim", batch="slim")
         if nx == 2:  # an order is refused unless the pair kernel could take the launch, and that kernel has nx = 3, 4 only
-            why = "MpcqpSolveOpts.order needs pair_eligible(MODE_FUSED), which asks for nx == 3 or 4 (mpcqp_pair.hip:1463): nx = 2 with an order is MPCQP_EUNSUPPORTED"
-            M["mpcqp_quad_kernel<2, true, 1, false, false, false>"] = _unreachable("mpcqp_capi.hip:794", why)
-            M["mpcqp_quad_kernel<2, true, 1, true, false, false>"] = _unreachable("mpcqp_capi.hip:794", why)
+            why = "MpcqpSolveOpts.order needs pair_eligible(MODE_FUSED), which asks for nx == 3 or 4 (pair_eligible of mpcqp_pair.hip): nx = 2 with an order is MPCQP_EUNSUPPORTED"
+            rule = "if (ka.order && (ka.warm_state || (fl & (MPCQP_OPT_FORCE_LDS | MPCQP_OPT_ONE_PER_WAVE | MPCQP_OPT_SEED_VIOLATED)) || !pairs())) return MPCQP_EUNSUPPORTED;"
+            M["mpcqp_quad_kernel<2, true, 1, false, false, false>"] = _unreachable("mpcqp_capi.hip:refusal", rule, why)
+            M["mpcqp_quad_kernel<2, true, 1, true, false, false>"] = _unreachable("mpcqp_capi.hip:refusal", rule, why)
             continue
-        M[f"mpcqp_quad_kernel<{nx}, true, 1, false, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), "mpcqp_quad.hip:1017",
+        M[f"mpcqp_quad_kernel<{nx}, true, 1, false, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), QUAD_T,
                                                                        check="order", flags=[FOUR])
-        M[f"mpcqp_quad_kernel<{nx}, true, 1, true, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), "mpcqp_quad.hip:1015",
+        M[f"mpcqp_quad_kernel<{nx}, true, 1, true, false, false>"] = _r("solve", shape, "c", False, 0.2, next(seed), QUAD_T,
                                                                       check="order", batch="slim")
     # ... the shared model (one instantiation for every nx)
     for order in (False, True):
         for slim in (False, True):
             M[f"mpcqp_quad_kernel<3, {_b(order)}, 1, {_b(slim)}, true, false>"] = _r(
-                "model", MODEL_SHAPE, "cd", True, 0.2, next(seed), f"mpcqp_quad.hip:{(1075, 1073, 1071, 1069)[2 * order + slim]}",
+                "model", MODEL_SHAPE, "cd", True, 0.2, next(seed), QUAD_MODEL,
                 check="order" if order else "slim" if slim else "oracle", flags=[FOUR], batch="slim" if slim else SMALL)
     # mpcqp_quadg_kernel<NX, 4, SLIM>: four rows per lane (more than 32 rows, or more than four per step)
     for nx, shape in FOUR_ROWS.items():
-        M[f"mpcqp_quadg_kernel<{nx}, 4, false>"] = _r("solve", shape, "cd", True, 0.2, next(seed), "mpcqp_quadg.hip:933")
-        M[f"mpcqp_quadg_kernel<{nx}, 4, true>"] = _r("solve", shape, "cd", True, 0.2, next(seed), "mpcqp_quadg.hip:933", check="slim", batch="slim4")
+        M[f"mpcqp_quadg_kernel<{nx}, 4, false>"] = _r("solve", shape, "cd", True, 0.2, next(seed), QUADG_T)
+        M[f"mpcqp_quadg_kernel<{nx}, 4, true>"] = _r("solve", shape, "cd", True, 0.2, next(seed), QUADG_T, check="slim", batch="slim4")
     # mpcqp_pair_kernel<NX, MK, MODEL, WARM, WPB, SEED, ORDER>
     for (nx, mk), (shape, rows, stage) in PAIR.items():
         k = f"mpcqp_pair_kernel<{nx}, {mk}, false, "
-        M[k + "false, 1, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_pair.hip:1504", flags=[TWO])
-        M[k + "false, 1, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_pair.hip:1500", check="order", flags=[TWO])
-        M[k + "false, 2, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_pair.hip:1502", check="two", flags=[TWO],
+        M[k + "false, 1, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), PAIR_T, flags=[TWO])
+        M[k + "false, 1, false, true>"] = _r("solve", shape, rows, stage, 0.2, next(seed), PAIR_T, check="order", flags=[TWO])
+        M[k + "false, 2, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), PAIR_T, check="two", flags=[TWO],
                                              batch="window")
-        M[k + "false, 1, true, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_pair.hip:1496", check="seeded")
-        M[k + "true, 1, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), "mpcqp_pair.hip:1498", check="warm")
+        M[k + "false, 1, true, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), PAIR_T, check="seeded")
+        M[k + "true, 1, false, false>"] = _r("solve", shape, rows, stage, 0.2, next(seed), PAIR_T, check="warm")
     k = "mpcqp_pair_kernel<3, 0, true, false, "
-    M[k + "1, false, false>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), "mpcqp_pair.hip:1526", flags=[TWO])
-    M[k + "1, false, true>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), "mpcqp_pair.hip:1522", check="order", flags=[TWO])
-    M[k + "2, false, false>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), "mpcqp_pair.hip:1524", check="two", flags=[TWO],
+    M[k + "1, false, false>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), PAIR_MODEL, flags=[TWO])
+    M[k + "1, false, true>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), PAIR_MODEL, check="order", flags=[TWO])
+    M[k + "2, false, false>"] = _r("model", MODEL_SHAPE, "cd", True, 0.2, next(seed), PAIR_MODEL, check="two", flags=[TWO],
                                   batch="window")
     return M
 

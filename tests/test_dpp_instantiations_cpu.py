@@ -28,25 +28,29 @@ def test_demangled_names_are_the_traces():
 
 def test_every_kernel_with_hand_written_dpp_has_a_recipe_and_no_recipe_lingers():
     """The manifest's keys are the census: the kernels of the five units that hold a v_fmac_f64_dpp. At most four of them may be
-    marked unreachable, each with the line that proves it; every other one has a recipe with a source line and a known check."""
+    marked unreachable, each with a verbatim quote of the rule that proves it (found once in its file, inside the function named);
+    every other one has a recipe with a known check and the launcher function that selects it, in whose text a line spells it."""
     census = DI.census()
     assert set(DI.MANIFEST) == set(census), (sorted(set(census) - set(DI.MANIFEST)), sorted(set(DI.MANIFEST) - set(census)))
     assert all(count > 0 for _, count in census.values())
     unreachable = [k for k, r in DI.MANIFEST.items() if r.get("unreachable")]
     assert len(unreachable) <= 4 and len(unreachable) + len(DI.REACHABLE) == len(census)
     for name, r in DI.MANIFEST.items():
-        src, _, line = r["line"].partition(":")
-        text = open(os.path.join(DI.ROOT, "qpmpc_amd", "csrc", src)).read().split("\n")
-        assert 0 < int(line) <= len(text), (name, r["line"])
+        src, _, function = r["site"].partition(":")
+        source = open(os.path.join(DI.ROOT, "qpmpc_amd", "csrc", src)).read()
+        text = DI.function_text(source, function)
+        assert text, (name, r["site"])  # the function is found in the file, once
         if r.get("unreachable"):
             assert r["why"]
+            assert source.count(r["quote"]) == 1 and "\n".join(text).count(r["quote"]) == 1, (name, r["site"])
             continue
         assert r["check"] in ("oracle", "slim", "order", "two", "seeded", "warm") and r["entry"] in ("solve", "model")
-        # the line that selects the instantiation names it: the kernel and the template arguments that differ from the defaults
+        # a line of the function names the instantiation: the kernel and its template arguments, of which trailing ones may be left
+        # to the templates' defaults (false; one wavefront per block)
         kernel, args = name.split("<")[0], name.split("<")[1].rstrip(">").split(", ")
         spelled = [[{"NX": args[0], "MK": args[1], "ROWS": args[1]}.get(a, a) for a in s.split(", ")]
-                   for s in re.findall(kernel + r"<([^>]*)>", text[int(line) - 1])]
-        assert any(s == args[: len(s)] for s in spelled), (name, r["line"], spelled)
+                   for line in text for s in re.findall(kernel + r"<([^>]*)>", line)]
+        assert any(s == args[: len(s)] and all(a in ("false", "1") for a in args[len(s):]) for s in spelled), (name, r["site"], spelled)
 
 
 @pytest.mark.parametrize("name", DI.REACHABLE)

@@ -2,7 +2,7 @@
 (tools/quad_trip_model.py) it was drawn with: no GPU, the stored arrays and the C oracle's condensing only.
 
 The fixture holds the four-per-wavefront kernel (csrc/mpcqp_quad.hip) to the bits of the build before its loops finished a non-plain
-trip once, dropped a slot inside the partial step's trip and went back to the steady loop (tests/test_gpu_quad_drops.py). It can only
+trip once, dropped a slot inside the partial step's trip and went back to the steady loop (tests/test_gpu_quad_parent_bits.py). It can only
 do that if its problems DO drop, in the arrangements those three changes treat differently: that is what is asserted here, on the
 model's trips of the stored operands -- and the model is held to the recording: for every solved problem of every set its iteration
 count is the one the kernel recorded."""
@@ -18,7 +18,7 @@ def _fixture():
     import tools.gen_golden_quad_drops as G
 
     if not _CACHE:
-        _CACHE["sets"], _CACHE["results"], _CACHE["max_iter"] = G.unpack(np.load(GOLDEN))
+        _, _CACHE["sets"], _CACHE["results"], _CACHE["max_iter"] = G.fixture()
         _CACHE["trips"] = G.model_trips(_CACHE["sets"])
     return G, _CACHE["sets"], _CACHE["results"], _CACHE["max_iter"], _CACHE["trips"]
 

@@ -2,12 +2,13 @@
 """Fixture generator (the recording needs a GPU; no reference code involved): tests/golden/quad_drops_parent.npz -- the operands of a
 few small problem sets in which rows DROP constraints, and what the four-per-wavefront kernel (csrc/mpcqp_quad.hip) computed for them,
 U, lam, status and iters, recorded from the build of the commit BEFORE the kernel finished a non-plain trip once, dropped inside the
-partial step's trip and returned to its steady loop. tests/test_gpu_quad_drops.py holds the kernel to these bits,
-tests/test_quad_drops_cpu.py holds the fixture to its conditions (no GPU). It follows tools/gen_golden_quad_steady.py.
+partial step's trip and returned to its steady loop. tests/test_gpu_quad_parent_bits.py holds the kernel to these bits,
+tests/test_quad_drops_cpu.py holds the fixture to its conditions (no GPU). What the four fixtures of this kind share is
+tools/quad_parent_bits.py.
 
-Sets (every launch forced through MPCQP_OPT_FOUR_PER_WAVE):
+Sets (launches(); every launch forced through MPCQP_OPT_FOUR_PER_WAVE):
   model        shared-model mode, the humanoid model, 64 initial states of twice the sweep's range
-  lean16       lean build, (nx, nu, N, mk) = (3, 1, 16, 2), 64 problems of the mixed family of tools/gen_golden_quad_steady.py
+  lean16       lean build, (nx, nu, N, mk) = (3, 1, 16, 2), 64 problems of the mixed family (qpmpc_amd/workloads.py: mixed_family)
   gen12        general build, (4, 1, 12) with state and input rows and a stage cost, 32 problems
   lean16_slim  lean16 tiled to 4100: more wavefronts than SIMDs, the slim LDS carve; every tile must give the same bits, 64 are stored
   lean16_mi    lean16 under the iteration limit `max_iter` (stored) that falls, for the most rows, on the trip right after a partial step
@@ -21,31 +22,32 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-import tools.gen_golden_quad_steady as S
+import tools.quad_parent_bits as H
 import tools.quad_trip_model as TM
 
 PATH = os.path.join(ROOT, "tests", "golden", "quad_drops_parent.npz")
-SLIM_BATCH = S.SLIM_BATCH
-OPERANDS, OUTPUTS = S.OPERANDS, S.OUTPUTS
-SETS = ("model", "lean16", "gen12", "lean16_slim", "lean16_mi")
+SLIM_BATCH = 4100
 OPERAND_SETS = ("model", "lean16", "gen12")
 
 
-def model_workload(x0):
-    from qpmpc_amd import workloads as W
+def launches(max_iter):
+    """the table of launches, lean16_mi under the fixture's iteration limit"""
+    return {
+        "model": H.Launch("model", model=True),
+        "lean16": H.Launch("lean16"),
+        "gen12": H.Launch("gen12"),
+        "lean16_slim": H.Launch("lean16", tile=SLIM_BATCH, stored=64),
+        "lean16_mi": H.Launch("lean16", max_iter=max_iter),
+    }
 
-    w = W.humanoid_batch(len(x0))
-    w["x0"] = x0
-    return w
 
-
-def workload(name, sets):
-    return model_workload(sets["model"]["x0"]) if name == "model" else sets[name]
+SETS = tuple(launches(None))
 
 
 def model_trips(sets, max_iter=None):
     """{set: [(iters, status, kinds)]} of the trip model on the stored operands"""
-    return {name: TM.trips_of_workload(workload(name, sets), max_iter=max_iter) for name in OPERAND_SETS}
+    table = launches(None)
+    return {name: TM.trips_of_workload(H.workload(table[name], sets), max_iter=max_iter) for name in OPERAND_SETS}
 
 
 def limit_after_partial(trips):
@@ -104,8 +106,8 @@ def draw(seed):
     rng = np.random.default_rng(20261020 + seed)
     return {
         "model": {"x0": 2.0 * W.humanoid_batch(64, seed=20261020 + seed)["x0"]},
-        "lean16": S.mixed_family(rng, 64, 3, 1, 16, 2, False),
-        "gen12": S.mixed_family(rng, 32, 4, 1, 12, 2, True),
+        "lean16": W.mixed_family(rng, 64, 3, 1, 16, 2, False),
+        "gen12": W.mixed_family(rng, 32, 4, 1, 12, 2, True),
     }
 
 
@@ -122,45 +124,11 @@ def search(limit=400, verbose=True):
     raise SystemExit("no seed satisfied the conditions")
 
 
-def run_set(name, sets, max_iter):
-    """what the kernel computes NOW for set `name` (lean16_slim: all SLIM_BATCH problems)"""
-    if name == "model":
-        return S.solve_model(sets["model"]["x0"])
-    if name == "lean16_slim":
-        return S.solve(S.tiled(sets["lean16"], SLIM_BATCH))
-    if name == "lean16_mi":
-        return S.solve(sets["lean16"], max_iter)
-    return S.solve(sets[name])
-
-
-def pack(sets, results, seed, max_iter):
-    out = {"seed": np.int64(seed), "max_iter": np.int64(max_iter)}
-    for name, w in sets.items():
-        for k in OPERANDS:
-            if isinstance(w.get(k), np.ndarray):
-                out[f"{name}__{k}"] = w[k]
-        for k in ("N", "wt", "wx", "wu"):
-            if k in w:
-                out[f"{name}__{k}"] = np.float64(-1.0 if w[k] is None else w[k])
-    for name, res in results.items():
-        for k, v in zip(OUTPUTS, res):
-            out[f"{name}__out_{k}"] = v
-    return out
-
-
-def unpack(z):
-    """(operand dictionaries by set, recorded outputs by set, the iteration limit of lean16_mi) of the loaded fixture"""
-    sets, results = {}, {}
-    for name in OPERAND_SETS:
-        w = {k: (z[f"{name}__{k}"] if f"{name}__{k}" in z.files else None) for k in OPERANDS}
-        for k in ("N", "wt", "wx", "wu"):
-            if f"{name}__{k}" in z.files:
-                v = float(z[f"{name}__{k}"])
-                w[k] = int(v) if k == "N" else (None if v < 0 else v)
-        sets[name] = w
-    for name in SETS:
-        results[name] = tuple(z[f"{name}__out_{k}"] for k in OUTPUTS)
-    return sets, results, int(z["max_iter"])
+def fixture():
+    """(launches, operand dictionaries by set, recorded outputs by launch, the iteration limit of lean16_mi) of the stored fixture"""
+    z = np.load(PATH)
+    max_iter = int(z["max_iter"])
+    return (launches(max_iter),) + H.unpack(z, OPERAND_SETS, SETS) + (max_iter,)
 
 
 def model_disagreements(sets, results, max_iter):
@@ -181,22 +149,12 @@ def main():
     print(f"seed {seed}; max_iter {max_iter} stops {rows} rows of lean16 right after a partial step")
     if "--search" in sys.argv:
         return
-    results = {name: run_set(name, sets, max_iter) for name in SETS}
-    again = {name: run_set(name, sets, max_iter) for name in SETS}  # (the kernel is deterministic: the bits of a second launch)
-    for name in SETS:
-        for a, b in zip(results[name], again[name]):
-            assert a.tobytes() == b.tobytes(), name
-    slim = results["lean16_slim"]
-    for v in slim:  # every tile of the slim launch: the same bits
-        ref = np.concatenate([v[:64]] * (SLIM_BATCH // 64 + 1))[:SLIM_BATCH]
-        assert ref.tobytes() == v.tobytes(), "slim tiles differ"
-    results["lean16_slim"] = tuple(v[:64] for v in slim)
-    for name in SETS:
-        st, it = results[name][2], results[name][3]
-        print(f"{name:12s} statuses {np.bincount(st, minlength=4)} iters mean {it.mean():.2f} max {it.max()}")
+    table = launches(max_iter)
+    results = H.stored(table, H.record(lambda name: H.run(table[name], sets), SETS))
+    H.report(results)
     bad = model_disagreements(sets, results, max_iter)
     assert not bad, bad
-    np.savez_compressed(PATH, **pack(sets, results, seed, max_iter))
+    np.savez_compressed(PATH, **H.pack(sets, results, seed=np.int64(seed), max_iter=np.int64(max_iter)))
     print("wrote", PATH, os.path.getsize(PATH), "bytes")
 
 

@@ -2,10 +2,10 @@
 """Fixture generator (the recording needs a GPU; no reference code involved): tests/golden/quad_prologue_parent.npz -- the operands of
 small problem sets that reach every path of the four-per-wavefront kernel's PROLOGUE (csrc/mpcqp_quad.hip: the operand loads and the
 chain of the build) and of its refinement / acceptance block, and what the kernel computed for them, U, lam, status and iters, recorded
-from the build of the commit BEFORE the operand loads went to the top of the kernel and the chain's sums were interleaved. tests/test_gpu_quad_prologue.py holds the kernel to these bits. It follows
-tools/gen_golden_quad_steady.py, whose mixed family it draws from.
+from the build of the commit BEFORE the operand loads went to the top of the kernel and the chain's sums were interleaved. tests/test_gpu_quad_parent_bits.py holds the kernel to these bits.
+What the four fixtures of this kind share is tools/quad_parent_bits.py; the mixed family is qpmpc_amd/workloads.py's mixed_family.
 
-Sets (every launch forced through MPCQP_OPT_FOUR_PER_WAVE; at most 32 problems each):
+Sets (LAUNCHES; every launch forced through MPCQP_OPT_FOUR_PER_WAVE; at most 32 problems each):
   shared16      lean build, (nx, nu, N, mk) = (3, 1, 16, 2), the triple integrator with every operand shared and time-invariant (all
                 strides 0: the loads read one address for every step)
   a_step16      lean, A per step and C time-invariant (tests/operand_layouts.py: make()), five problems
@@ -36,67 +36,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-import tools.gen_golden_quad_steady as S
+import tools.quad_parent_bits as H
 
 PATH = os.path.join(ROOT, "tests", "golden", "quad_prologue_parent.npz")
-OPERANDS, OUTPUTS = S.OPERANDS, S.OUTPUTS
-# set -> the set whose operands it runs on (itself when it has its own)
-SETS = {"shared16": "shared16", "a_step16": "a_step16", "c_step16": "c_step16", "tight16": "tight16", "tight16_pad": "tight16",
-        "tight16_cut5": "tight16", "tight16_cut7": "tight16", "lean1": "lean1", "lean2": "lean2", "lean15": "lean15", "nx2": "nx2",
-        "nx4": "nx4", "gen_mk1": "gen_mk1", "gen_mk3": "gen_mk3", "gen_mk4": "gen_mk4", "gen_nx5": "gen_nx5", "gen_nx6": "gen_nx6"}
-OPERAND_SETS = tuple(dict.fromkeys(SETS.values()))
 # elements past the packed batch stride, per operand (those of tests/operand_layouts.py)
 PADS = dict(A=2, B=3, C=7, e=5, x0=1, goal=6)
-_ATTR = dict(A="A", B="B", C="C", e="e", x0="initial_state", goal="goal_state")
 PAD_COUNT = 16
 SMALL = 8
 # the tight set's feasibility tolerance, far below the default (1e-12): at the default the acceptance test never failed in 200 draws of
 # 32 problems; at this one a row that is violated by rounding alone is taken up, and the acceptance test behind it can fail
 TIGHT_TOL = 1e-15
+LAUNCHES = {  # (every set but tight16's four runs on operands of its own, as it is)
+    **{name: H.Launch(name) for name in ("shared16", "a_step16", "c_step16")},
+    "tight16": H.Launch("tight16", feas_tol=TIGHT_TOL),
+    "tight16_pad": H.Launch("tight16", cut=PAD_COUNT, pads=PADS, feas_tol=TIGHT_TOL),
+    "tight16_cut5": H.Launch("tight16", cut=5, feas_tol=TIGHT_TOL),
+    "tight16_cut7": H.Launch("tight16", cut=7, feas_tol=TIGHT_TOL),
+    **{name: H.Launch(name) for name in ("lean1", "lean2", "lean15", "nx2", "nx4", "gen_mk1", "gen_mk3", "gen_mk4", "gen_nx5", "gen_nx6")},
+}
+SETS = tuple(LAUNCHES)
+OPERAND_SETS = tuple(dict.fromkeys(spec.on for spec in LAUNCHES.values()))
 
 
-def padded(bp, pads):
-    """the batch problem with every per-problem operand named in `pads` moved behind a wider batch stride (NaN in the padding)"""
-    import torch
-
-    for key, pad in pads.items():
-        t = getattr(bp, _ATTR[key])
-        if t is None or t.shape[0] == 1 or not pad:
-            continue
-        block = t[0].numel()
-        buf = torch.full((t.shape[0], block + pad), float("nan"), dtype=t.dtype, device=t.device)
-        buf[:, :block] = t.reshape(t.shape[0], block)
-        setattr(bp, _ATTR[key], buf[:, :block].view(t.shape))
-        assert getattr(bp, _ATTR[key]).stride(0) == block + pad
-    return bp
-
-
-def solve(w, pads=None, probe=False, feas_tol=None):
-    """(U, lam, status, iters) of the forced four-per-wavefront launch, as numpy arrays; with probe: and the [B, 16] probe record"""
-    import torch
-    from qpmpc_amd import _capi, solve_mpc_batch
-    from qpmpc_amd import workloads as W
-
-    bp = W.to_batch_problem(w)
-    if pads:
-        bp = padded(bp, pads)
-    kw = {}
-    if probe:
-        kw["probe"] = torch.zeros(bp.batch_size * 16, dtype=torch.int64, device=bp.device)
-    plan = solve_mpc_batch(bp, return_multipliers=True, feas_tol=feas_tol, flags=_capi.OPT_FOUR_PER_WAVE, **kw)
-    torch.cuda.synchronize()
-    out = tuple(t.cpu().numpy() for t in (plan.U, plan.multipliers, plan.status, plan.iters))
-    return out + (kw["probe"].view(-1, 16).cpu().numpy(),) if probe else out
-
-
-def run_set(name, sets):
-    """what the kernel computes NOW for set `name` of the operand dictionary `sets`"""
-    w = sets[SETS[name]]
-    if name == "tight16_pad":
-        return solve(S.cut(w, PAD_COUNT), pads=PADS, feas_tol=TIGHT_TOL)
-    if name in ("tight16_cut5", "tight16_cut7"):
-        return solve(S.cut(w, int(name[-1])), feas_tol=TIGHT_TOL)
-    return solve(w, feas_tol=TIGHT_TOL if name == "tight16" else None)
+def probed(sets):
+    """tight16's outputs and probe record"""
+    return H.solve(sets["tight16"], probe=True, feas_tol=TIGHT_TOL)
 
 
 def fails_of(probe):
@@ -117,60 +81,30 @@ def layout_case(per_step, seed):
     lay = dict(A="b1", B="bn", C="b1", D="bn", e="bn", goal="b", targets="b")
     lay[per_step] = "bn"
     w, _ = OL.make((3, 1, 16, 2), "c", False, lay, seed, 0.2)
-    return S.cut(w, 5)
+    return H.cut(w, 5)
 
 
 def draw(seed):
     from qpmpc_amd import workloads as W
 
     rng = np.random.default_rng(20261101 + seed)
-    sets = {"tight16": S.mixed_family(rng, 32, 3, 1, 16, 2, False)}
+    sets = {"tight16": W.mixed_family(rng, 32, 3, 1, 16, 2, False)}
     sets["shared16"] = W.triple_integrator_batch(SMALL, seed=20261101 + seed, heterogeneous=False)
     sets["shared16"]["x0"] = 2.0 * sets["shared16"]["x0"]  # (twice the benchmark's range: more rows bind)
     sets["a_step16"] = layout_case("A", 24100 + seed)
     sets["c_step16"] = layout_case("C", 24200 + seed)
     for N in (1, 2, 15):
-        sets[f"lean{N}"] = S.mixed_family(rng, SMALL, 3, 1, N, 2, False)
-    sets["nx2"] = S.mixed_family(rng, SMALL, 2, 1, 16, 2, False)
-    sets["nx4"] = S.mixed_family(rng, SMALL, 4, 1, 16, 2, False)
-    sets["gen_mk1"] = S.mixed_family(rng, SMALL, 3, 1, 16, 1, True)
-    sets["gen_mk3"] = S.mixed_family(rng, SMALL, 3, 1, 10, 3, True)
-    sets["gen_mk4"] = S.mixed_family(rng, SMALL, 3, 1, 8, 4, True)
-    sets["gen_nx5"] = S.mixed_family(rng, 4, 5, 1, 16, 2, True)
-    sets["gen_nx6"] = S.mixed_family(rng, 4, 6, 1, 16, 2, True)
+        sets[f"lean{N}"] = W.mixed_family(rng, SMALL, 3, 1, N, 2, False)
+    sets["nx2"] = W.mixed_family(rng, SMALL, 2, 1, 16, 2, False)
+    sets["nx4"] = W.mixed_family(rng, SMALL, 4, 1, 16, 2, False)
+    sets["gen_mk1"] = W.mixed_family(rng, SMALL, 3, 1, 16, 1, True)
+    sets["gen_mk3"] = W.mixed_family(rng, SMALL, 3, 1, 10, 3, True)
+    sets["gen_mk4"] = W.mixed_family(rng, SMALL, 3, 1, 8, 4, True)
+    sets["gen_nx5"] = W.mixed_family(rng, 4, 5, 1, 16, 2, True)
+    sets["gen_nx6"] = W.mixed_family(rng, 4, 6, 1, 16, 2, True)
     for name, w in sets.items():
         w.pop("name", None)
     return sets
-
-
-def pack(sets, results, seed, fails, refinements):
-    out = {"seed": np.int64(seed), "tight16__fails": fails, "refinements": np.int64(refinements)}
-    for name, w in sets.items():
-        for k in OPERANDS:
-            if isinstance(w.get(k), np.ndarray):
-                out[f"{name}__{k}"] = w[k]
-        for k in ("N", "wt", "wx", "wu"):
-            if k in w:
-                out[f"{name}__{k}"] = np.float64(-1.0 if w[k] is None else w[k])
-    for name, res in results.items():
-        for k, v in zip(OUTPUTS, res):
-            out[f"{name}__out_{k}"] = v
-    return out
-
-
-def unpack(z):
-    """(operand dictionaries by set, recorded outputs by set, failed acceptance tests per problem of tight16, problems of tight16
-    that took the refinement arm) of the loaded fixture"""
-    sets, results = {}, {}
-    for name in OPERAND_SETS:
-        w = {k: (z[f"{name}__{k}"] if f"{name}__{k}" in z.files else None) for k in OPERANDS}
-        for k in ("N", "wt", "wx", "wu"):
-            v = float(z[f"{name}__{k}"])
-            w[k] = int(v) if k == "N" else (None if v < 0 else v)
-        sets[name] = w
-    for name in SETS:
-        results[name] = tuple(z[f"{name}__out_{k}"] for k in OUTPUTS)
-    return sets, results, z["tight16__fails"], int(z["refinements"])
 
 
 def search(refinements):
@@ -178,7 +112,7 @@ def search(refinements):
     build that counts them (`refinements`), a problem that took the refinement arm"""
     for seed in range(400):
         sets = draw(seed)
-        res = solve(sets["tight16"], probe=True, feas_tol=TIGHT_TOL)
+        res = probed(sets)
         fails, took = fails_of(res[4]), refined_of(res[4])
         print("seed", seed, "statuses", np.bincount(res[2], minlength=4), "problems with a failed acceptance test", int((fails > 0).sum()),
               "with a refinement", int(took.sum()), flush=True)
@@ -187,36 +121,37 @@ def search(refinements):
     raise SystemExit("no seed gave a failed acceptance test" + (" and a refinement" if refinements else ""))
 
 
-def record(seed=None):
+def fixture():
+    """(launches, operand dictionaries by set, recorded outputs by launch, failed acceptance tests per problem of tight16, problems of
+    tight16 that took the refinement arm) of the stored fixture"""
+    z = np.load(PATH)
+    return (LAUNCHES,) + H.unpack(z, OPERAND_SETS, SETS) + (z["tight16__fails"], int(z["refinements"]))
+
+
+def main(seed=None):
     if seed is None:
         seed, sets, res = search(False)
     else:
         sets = draw(seed)
-        res = solve(sets["tight16"], probe=True, feas_tol=TIGHT_TOL)
+        res = probed(sets)
     fails = fails_of(res[4])
     assert (fails > 0).any()
-    assert tuple(a.tobytes() for a in res[:4]) == tuple(a.tobytes() for a in run_set("tight16", sets)), "the probe changes the outputs"
-    results = {name: run_set(name, sets) for name in SETS}
-    again = {name: run_set(name, sets) for name in SETS}  # (the kernel is deterministic: the bits of a second launch)
-    for name in SETS:
-        for a, b in zip(results[name], again[name]):
-            assert a.tobytes() == b.tobytes(), name
-    for name, count in (("tight16_pad", PAD_COUNT), ("tight16_cut5", 5), ("tight16_cut7", 7)):  # (a row's arithmetic: its own)
+    results = H.record(lambda name: H.run(LAUNCHES[name], sets), SETS)
+    assert tuple(a.tobytes() for a in res[:4]) == tuple(a.tobytes() for a in results["tight16"]), "the probe changes the outputs"
+    for name in ("tight16_pad", "tight16_cut5", "tight16_cut7"):  # (a row's arithmetic: its own)
         for a, b in zip(results[name], results["tight16"]):
-            assert a.tobytes() == b[:count].tobytes(), name
-    for name in SETS:
-        st, it = results[name][2], results[name][3]
-        print(f"{name:13s} statuses {np.bincount(st, minlength=4)} iters mean {it.mean():.2f} max {it.max()}")
-    np.savez_compressed(PATH, **pack(sets, results, seed, fails, -1))
+            assert a.tobytes() == b[:LAUNCHES[name].cut].tobytes(), name
+    H.report(results)
+    np.savez_compressed(PATH, **H.pack(sets, results, seed=np.int64(seed), tight16__fails=fails, refinements=np.int64(-1)))
     print("wrote", PATH, os.path.getsize(PATH), "bytes")
     assert os.path.getsize(PATH) < 200 * 1024
 
 
 def count_refinements():
     z = np.load(PATH)
-    sets, results, fails, _ = unpack(z)
-    res = solve(sets["tight16"], probe=True, feas_tol=TIGHT_TOL)
-    for k, a, b in zip(OUTPUTS, res, results["tight16"]):
+    _, sets, results, fails, _ = fixture()
+    res = probed(sets)
+    for k, a, b in zip(H.OUTPUTS, res, results["tight16"]):
         assert a.tobytes() == b.tobytes(), f"tight16: {k} is not the recorded one"
     assert np.array_equal(fails_of(res[4]), fails), "the probe's record of failed acceptance tests is not the recorded one"
     took = refined_of(res[4])
@@ -232,4 +167,4 @@ if __name__ == "__main__":
     elif "--refinements" in sys.argv:
         count_refinements()
     else:
-        record(int(sys.argv[sys.argv.index("--seed") + 1]) if "--seed" in sys.argv else None)
+        main(int(sys.argv[sys.argv.index("--seed") + 1]) if "--seed" in sys.argv else None)

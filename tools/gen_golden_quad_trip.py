@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fixture generator (needs a GPU; no reference code involved): tests/golden/quad_trip_parent.npz -- what the four-per-wavefront
 kernel (csrc/mpcqp_quad.hip) computed for a few small launches, U, lam, status and iters, recorded from the build of the commit
-BEFORE the steady loop's lane-mask arithmetic and its single trip counter. tests/test_gpu_quad_trip.py holds the kernel to these bits;
+BEFORE the steady loop's lane-mask arithmetic and its single trip counter. tests/test_gpu_quad_parent_bits.py holds the kernel to these
+bits (what the four fixtures of this kind share is tools/quad_parent_bits.py);
 tests/test_quad_trip_cpu.py holds the inputs to the conditions below with the oracle and tools/quad_trip_model.py alone.
 
 The inputs are drawn from fixed seeds (inputs(): nothing is stored but the outputs); every launch is forced through
@@ -25,18 +26,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
+import tools.quad_parent_bits as H
+
 PATH = os.path.join(ROOT, "tests", "golden", "quad_trip_parent.npz")
-OPERANDS = ("A", "B", "C", "D", "e", "x0", "goal", "targets")
-OUTPUTS = ("U", "lam", "status", "iters")
 LIMITS = (1, 2, 8)
-LAUNCHES = ("a",) + tuple(f"a_mi{k}" for k in LIMITS) + ("c", "d", "a_slim")
+LAUNCHES = {
+    "a": H.Launch("a"),
+    **{f"a_mi{k}": H.Launch("a", max_iter=k) for k in LIMITS},
+    "c": H.Launch("c"),
+    "d": H.Launch("d"),
+    "a_slim": H.Launch("a", tile=H.WAVE_PAST_SIMDS, stored=10),
+}
+SETS = tuple(LAUNCHES)
 SEED_A, SEED_C, SEED_D = 4, 2, 11
 TIGHT_A = (3.0, 0.6, 0.15, 0.04, 0.04)
 
 
-def _tight_dynamics(w):
-    w["A"] = np.eye(w["A"].shape[-1]) + 0.1 * (w["A"] - np.eye(w["A"].shape[-1]))  # (tight_ltv's)
-    return w
+def _draw(rng, batch, N, tight):
+    """random_ltv at (nx, nu, mk) = (3, 1, 2) with tight_ltv's dynamics"""
+    from qpmpc_amd.workloads import random_ltv, tight_dynamics
+
+    return tight_dynamics(random_ltv(rng, batch, 3, 1, N, 2, tight))
 
 
 def _lean(w):
@@ -46,10 +56,8 @@ def _lean(w):
 
 
 def set_a():
-    from qpmpc_amd.workloads import random_ltv
-
     rng = np.random.default_rng(SEED_A)
-    w = _tight_dynamics(random_ltv(rng, 10, 3, 1, 16, 2, 1.0))
+    w = _draw(rng, 10, 16, 1.0)
     tight = np.asarray(TIGHT_A)[np.arange(10) % len(TIGHT_A)]
     for b in range(10):  # bounds around the free response, as random_ltv makes them, at this problem's tightness
         x = w["x0"][b].copy()
@@ -60,17 +68,13 @@ def set_a():
 
 
 def set_c():
-    from qpmpc_amd.workloads import random_ltv
-
-    w = _tight_dynamics(random_ltv(np.random.default_rng(SEED_C), 10, 3, 1, 9, 2, 0.05))
+    w = _draw(np.random.default_rng(SEED_C), 10, 9, 0.05)
     w["wx"] = w["targets"] = None
     return w
 
 
 def set_d():
-    from qpmpc_amd.workloads import random_ltv
-
-    w = _lean(_tight_dynamics(random_ltv(np.random.default_rng(SEED_D), 8, 3, 1, 16, 2, 0.02)))
+    w = _lean(_draw(np.random.default_rng(SEED_D), 8, 16, 0.02))
     w["B"][0::2] *= 1e-3
     w["wt"] = -50.0
     return w
@@ -80,64 +84,22 @@ def inputs():
     return {"a": set_a(), "c": set_c(), "d": set_d()}
 
 
-def tiled(w, count):
-    out = dict(w)
-    for k in OPERANDS:
-        if isinstance(w.get(k), np.ndarray):
-            v = w[k]
-            out[k] = np.ascontiguousarray(np.concatenate([v] * (count // len(v) + 1))[:count])
-    return out
-
-
-def slim_batch():
-    """four problems per wavefront, one wavefront more than the device has SIMDs (four per compute unit)"""
-    import torch
-
-    return 4 * (4 * torch.cuda.get_device_properties(0).multi_processor_count + 1)
-
-
-def solve(w, max_iter=None):
-    """(U, lam, status, iters) of the forced four-per-wavefront launch, as numpy arrays"""
-    import torch
-    from qpmpc_amd import _capi, solve_mpc_batch
-    from qpmpc_amd import workloads as W
-
-    bp = W.to_batch_problem(w)
-    plan = solve_mpc_batch(bp, return_multipliers=True, max_iter=max_iter, flags=_capi.OPT_FOUR_PER_WAVE)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in (plan.U, plan.multipliers, plan.status, plan.iters))
-
-
-def run_launch(name, sets):
-    """what the kernel computes NOW for launch `name` (a_slim: all slim_batch() problems)"""
-    if name == "a_slim":
-        return solve(tiled(sets["a"], slim_batch()))
-    if name.startswith("a_mi"):
-        return solve(sets["a"], int(name[4:]))
-    return solve(sets[name])
-
-
 def load():
-    """{launch: (U, lam, status, iters)} of the stored fixture"""
-    z = np.load(PATH)
-    return {name: tuple(z[f"{name}__{k}"] for k in OUTPUTS) for name in LAUNCHES}
+    """{launch: (U, lam, status, iters)} of the stored fixture: outputs only, as {launch}__{output}"""
+    return H.unpack(np.load(PATH), (), LAUNCHES, out_prefix="")[1]
+
+
+def fixture():
+    """(launches, the inputs, the recorded outputs)"""
+    return LAUNCHES, inputs(), load()
 
 
 def main():
     sets = inputs()
-    results = {name: run_launch(name, sets) for name in LAUNCHES}
-    again = {name: run_launch(name, sets) for name in LAUNCHES}  # (the kernel is deterministic: the bits of a second launch)
-    for name in LAUNCHES:
-        for a, b in zip(results[name], again[name]):
-            assert a.tobytes() == b.tobytes(), name
-    slim, count = results["a_slim"], slim_batch()
-    for v in slim:  # every tile of the slim launch: the same bits
-        assert len(v) == count and np.concatenate([v[:10]] * (count // 10 + 1))[:count].tobytes() == v.tobytes(), "slim tiles differ"
-    results["a_slim"] = tuple(v[:10] for v in slim)
-    for name in LAUNCHES:
-        st, it = results[name][2], results[name][3]
+    results = H.stored(LAUNCHES, H.record(lambda name: H.run(LAUNCHES[name], sets), LAUNCHES))
+    for name, (_, _, st, it) in results.items():
         print(f"{name:8s} statuses {st.tolist()} iters {it.tolist()}")
-    np.savez_compressed(PATH, **{f"{name}__{k}": v for name, res in results.items() for k, v in zip(OUTPUTS, res)})
+    np.savez_compressed(PATH, **H.pack({}, results, out_prefix=""))
     print("wrote", PATH, os.path.getsize(PATH), "bytes")
 
 

@@ -61,7 +61,7 @@ def main(argv) -> int:
     for name, (unit, count) in sorted(census.items(), key=lambda kv: (kv[1][0], kv[0])):
         recipe = DI.MANIFEST.get(name, {})
         n = calls.get(name, 0)
-        note = "  unreachable: " + recipe["line"] if recipe.get("unreachable") else "  NO CALL" if n == 0 else ""
+        note = "  unreachable: " + recipe["site"] if recipe.get("unreachable") else "  NO CALL" if n == 0 else ""
         missing += n == 0 and not recipe.get("unreachable")
         print(f"{unit:16s} {name:58s} {count:5d} {n:6d}{note}")
     reach = sum(1 for k in census if not DI.MANIFEST.get(k, {}).get("unreachable"))
