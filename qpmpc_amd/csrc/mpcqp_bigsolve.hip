@@ -1213,8 +1213,72 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
             __syncthreads();
         };
         int reeval = 0;  // (mid-size kind) from-scratch evaluations of the slacks that found a violated row
+        // (dense kind) T = N* is only ever UPDATED: an admission scales what error it holds by |M_p| / |z|, about ten once nearly
+        // every slot is taken, and a degenerate vertex (rows through the optimum of n others) keeps the loop there for hundreds of
+        // add / drop pairs. |T M_A' - I| then grows from 1e-12 to 1 (float64, 160 x 512, within 300 iterations), the active rows
+        // leave their bounds and the loop ends INFEASIBLE with every slot taken on a solvable problem. The inner loop measures the
+        // inconsistency it can see for one reduction, z . M_p + |z|^2 = sum_a r_a (M_a . z), zero when T is exact; past 64 n eps
+        // |M_p|^2 (its own rounding is n eps) the state is rebuilt before the next row is selected: T from M_A by the admission
+        // update from an empty set, the multipliers from the active rows' equations, lam = T T' (M_A y0 - h_A), the slacks from
+        // scratch. Solves that do not linger there stay far below the threshold (a NumPy restatement of this loop saw at most 1.1 n eps on
+        // the sizes of tests/verdict_cases.py) and keep their path bit for bit.
+        bool stale = false;
         for (;;) {
             lap(-1);
+            if constexpr (!MFREE) {
+                if (stale && nq > 0) {
+                    stale = false;
+                    __syncthreads();
+                    for (int a = 0; a < nq; ++a) {
+                        const T *ma = MA + (int64_t)a * n;
+                        for (int b = tid >> 6; b < a; b += NWV) {
+                            T acc = T(0);
+                            for (int k = tid & 63; k < n; k += 64) acc += Tm[(int64_t)b * n + k] * ma[k];
+                            acc = wave_sum_shfl(acc);
+                            if ((tid & 63) == 0) rv[b] = acc;
+                        }
+                        __syncthreads();
+                        T zk = T(0);
+                        if (tid < n) {
+                            zk = -ma[tid];
+                            for (int b = 0; b < a; ++b) zk += rv[b] * MA[(int64_t)b * n + tid];
+                        }
+                        const T dd = block_sum<NWV>(zk * zk, red, tid);
+                        const T inv = dd > T(0) ? T(1) / dd : T(0);
+                        if (tid < n) {
+                            for (int b = 0; b < a; ++b) Tm[(int64_t)b * n + tid] += (rv[b] * inv) * zk;
+                            Tm[(int64_t)a * n + tid] = -zk * inv;
+                        }
+                        __syncthreads();
+                    }
+                    for (int a = tid >> 6; a < nq; a += NWV) {  // rho_a = M_a . y0 - h_a
+                        T acc = T(0);
+                        for (int k = tid & 63; k < n; k += 64) acc += MA[(int64_t)a * n + k] * y0[k];
+                        acc = wave_sum_shfl(acc);
+                        if ((tid & 63) == 0) rv[a] = acc - h[act[a]];
+                    }
+                    __syncthreads();
+                    if (tid < n) {  // t = T' rho
+                        T acc = T(0);
+                        for (int a = 0; a < nq; ++a) acc += Tm[(int64_t)a * n + tid] * rv[a];
+                        tmp[tid] = acc;
+                    }
+                    __syncthreads();
+                    for (int a = tid >> 6; a < nq; a += NWV) {  // lam_a = T_a . t
+                        T acc = T(0);
+                        for (int k = tid & 63; k < n; k += 64) acc += Tm[(int64_t)a * n + k] * tmp[k];
+                        acc = wave_sum_shfl(acc);
+                        if ((tid & 63) == 0) lam[a] = acc < T(0) ? T(0) : acc;
+                    }
+                    primal_point();
+                    for (int i = tid; i < m; i += BS) {
+                        T dot = T(0);
+                        for (int k = 0; k < n; ++k) dot += GT[(int64_t)k * m + i] * zx[k];
+                        sv[i] = (pos[i] >= 0) ? T(0) : h[i] - dot;
+                    }
+                    __syncthreads();
+                }
+            }
             // ---- select the violated row farthest from its hyperplane
             T best = INF;
             int bi = 0x7fffffff;
@@ -1354,6 +1418,11 @@ __global__ void __launch_bounds__(64 * NWV, (KIND == 2 && NWV == 4 && sizeof(T) 
                     zv[tid] = zk;
                 }
                 const T d2 = block_sum<NWV>(zk * zk, red, tid);
+                if constexpr (!MFREE) {
+                    const T chk = block_sum<NWV>((tid < n) ? zk * mp[tid] : T(0), red, tid);
+                    const T eps = sizeof(T) == 4 ? (T)1.1920929e-7 : (T)2.220446049250313e-16;
+                    stale |= (T)fabs(chk + d2) > T(64) * (T)n * eps * kpp;
+                }
                 // ratio test
                 T t1 = INF;
                 int l = 0x7fffffff;

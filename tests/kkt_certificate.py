@@ -62,14 +62,22 @@ def certify(w: Dict, b: int, U, lam, rollout: bool = False, active: Optional[np.
     ``lam=None``: only the primal half is certified (a launch that returns no multipliers); then ``active`` -- a boolean mask of
     the rows some other solve found active -- adds the check that those rows sit on their bounds. ``rollout``: the primal
     residual is also formed by the roll-out and the larger of the two is reported."""
-    LD = np.longdouble
     P, q, G, h = condensed(w, b)
+    other = row_residuals(w, b, np.asarray(U, dtype=np.float64)) if rollout else None
+    return certify_qp(P, q, G, h, U, lam, active=active, other_residual=other)
+
+
+def certify_qp(P, q, G, h, U, lam, active: Optional[np.ndarray] = None, other_residual=None) -> Certificate:
+    """certify() of a QP given as dense arrays (min 1/2 u'Pu + q'u s.t. G u <= h); ``other_residual``: G u - h formed some other
+    way, the larger of the two is reported."""
+    LD = np.longdouble
+    P, q, G, h = (np.asarray(a).astype(LD) for a in (P, q, G, h))
     u = np.asarray(U, dtype=np.float64).reshape(-1).astype(LD)
     r = G @ u - h  # G u - h
     rows = LD(1) + np.abs(h)
     primal = r / rows
-    if rollout:
-        primal = np.maximum(primal, row_residuals(w, b, np.asarray(U, dtype=np.float64)) / rows)
+    if other_residual is not None:
+        primal = np.maximum(primal, other_residual / rows)
     prim = float(primal.max()) if primal.size else 0.0
     if lam is None:
         on = 0.0
