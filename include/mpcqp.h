@@ -40,6 +40,7 @@
  *    `order` leaves out keeps its old outputs; the elements between two rows of a strided argument (u_stride) are not touched;
  *  - read-only arguments (everything declared const, the operands, the model of the solve_model exports) are never written;
  *  - mpcqp_model_vjp_batch / mpcqp_model_jvp_batch touch nothing outside the named extents and the model (mpcqp_model_bytes).
+ *    The same holds for mpcqp_model_periods_vjp_batch (tests/test_gpu_loop_diff.py).
  *
  * Stream contract (tests/test_gpu_streams.py holds every forward route, the stateful sequences and the Python layer to it)
  *  - every kernel of a call is enqueued on the stream the call is given, in order, and on no other: a call that launches several
@@ -813,6 +814,51 @@ int mpcqp_model_periods_batch(const MpcqpDims *dims, const void *model, const Mp
                               int64_t batch, int32_t nperiods, int32_t warm, const MpcqpSolveOpts *opts,
                               void *U, void *lam, int32_t *status, int32_t *iters, /* those of the LAST period */
                               const MpcqpLoopOut *out, void *stream);
+
+/* The vector-Jacobian product of those closed loops, one launch for all periods (an additive part of ABI 12:
+ * MPCQP_ABI_VERSION is unchanged): the reverse-time recursion through `nperiods` periods of every loop, each period the
+ * KKT adjoint of mpcqp_model_vjp_batch on the factored model with gU = [ubar; 0] and no gX. With the loop of
+ * mpcqp_model_periods_batch -- u0_t the plan's first input, zero when status[b][t] != 0, x_{t+1} = A x_t + B u0_t + d_t --
+ * and cotangents gX, gU0 of the records X, U0: a = gX_P, and for t = P-1 .. 0
+ *     g_d_t = a;   g_A += a x_t';   g_B += a u0_t';   ubar = gU0_t + B' a;   a_new = gX_t + A' a
+ *     status[b][t] == 0, A_t = {i : lam_i > 0}, S = M_A M_A':
+ *         tt = L^-1 [ubar; 0];   nu = S^-1 M_A tt;   w = tt - M_A' nu
+ *         a_new -= Wx' w + Hx_A' nu;   g_goal_t = Wg' w;   g_targets_t = Wt' w
+ *     a = a_new
+ * and g_x0 = a ("Closed-loop adjoint"). A period without a plan passes the costate through the plant
+ * only. The loops never interact: sixteen lanes per loop, four loops per wavefront, the period loop inside the kernel
+ * with the costate, the rows of g_A / g_B and the period sums in registers; no workspace, no allocation, no
+ * synchronisation. The reference has no counterpart: its closed loops are Python loops over NumPy plans
+ * (examples/wheeled_inverted_pendulum.py:99-118, examples/lipm_walking_controller.py:304-333) and carry no derivative.
+ * A gradient that is per loop and per period, or summed over the periods in the kernel (period_stride 0: one block per loop): */
+typedef struct MpcqpPeriodGrad {
+    void   *ptr;            /* NULL = not wanted */
+    int64_t batch_stride;   /* in elements, from loop to loop */
+    int64_t period_stride;  /* in elements, from period to period; 0 = the sum over the periods, one block per loop */
+} MpcqpPeriodGrad;
+
+/* Inputs, packed: lam [batch][nperiods][m] and status [batch][nperiods], EVERY period's multipliers and status (the fused loop
+ * keeps only the last period's: solve the recorded states again with mpcqp_solve_model_batch, batch * nperiods problems in
+ * one launch); X [batch][nperiods+1][nx] and U0 [batch][nperiods][nu], the loop's records, read only for g_A / g_B and
+ * nullable with them; gX [batch][nperiods+1][nx] and gU0 [batch][nperiods][nu], each nullable, NULL = zero. `plant`: A and B
+ * as mpcqp_model_periods_batch takes them (batch_stride 0 = shared); d is not read. `model` is only read.
+ * Outputs: g_x0 [batch][nx] (required); g_states [batch][nperiods+1][nx] (nullable), the costates a_0 .. a_P -- its rows
+ * 1 .. P are the gradient of the disturbance of periods 0 .. P-1, row 0 is g_x0 --; g_goal (blocks of nx) and g_targets (blocks
+ * of N nx), each a nullable MpcqpPeriodGrad; g_A [batch][nx][nx] and g_B [batch][nx][nu], per loop, summed over the periods,
+ * nullable; vjp_status [batch] (nullable): the NUMBER of periods of the loop whose S failed the pivot test of the other
+ * derivative exports or that had more active rows than variables -- such a period contributes its plant term only.
+ * A sum over the batch for operands the batch shares is the caller's, as in every derivative export. Terms follow
+ * dims->flags as in mpcqp_model_vjp_batch: a goal or targets that do not enter q get zeros, and Wg / Wt are not read.
+ * A model whose factorisation failed gives zeros everywhere and vjp_status = nperiods.
+ * Checks, before anything is launched: MPCQP_EDTYPE unless float64; MPCQP_EUNSUPPORTED outside n = N nu <= 16,
+ * 1 <= m = N mk <= 32, nx <= 16 (the envelope of mpcqp_model_periods_batch: whatever the fused loop ran can be
+ * differentiated); MPCQP_EINVAL for a NULL model, plant (or its A / B), lam, status or g_x0, nperiods < 1, batch < 0, a
+ * negative stride, or g_A / g_B without X / U0. */
+int mpcqp_model_periods_vjp_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant, int64_t batch,
+                                  int32_t nperiods, const void *lam, const int32_t *status, const void *X, const void *U0,
+                                  const void *gX, const void *gU0, void *g_x0, void *g_states,
+                                  const MpcqpPeriodGrad *g_goal, const MpcqpPeriodGrad *g_targets, void *g_A, void *g_B,
+                                  int32_t *vjp_status, void *stream);
 
 /* Bookkeeping of closed loops (the reference's loops count nothing; ours report failures and iterations):
  * stats[0] += number of problems with status != 0, stats[1] += sum of iters. stats: two int64 in DEVICE memory. */

@@ -71,6 +71,7 @@ EXPORTS = (
     "mpcqp_model_vjp_batch",
     "mpcqp_model_jvp_batch",
     "mpcqp_model_periods_batch",
+    "mpcqp_model_periods_vjp_batch",
 )
 
 
@@ -110,6 +111,10 @@ class LoopPlant(C.Structure):
 
 class LoopOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("X", "U0", "loop_stats")]
+
+
+class PeriodGrad(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("batch_stride", C.c_int64), ("period_stride", C.c_int64)]
 
 
 class SolveOpts(C.Structure):
@@ -261,6 +266,10 @@ def load():
     lib.mpcqp_model_periods_batch.argtypes = [C.POINTER(Dims), vp, C.POINTER(LoopPlant), vp, C.POINTER(Operand),
                                               C.POINTER(Operand), i64, C.c_int32, C.c_int32, C.POINTER(SolveOpts), vp, vp,
                                               vp, vp, C.POINTER(LoopOut), vp]
+    lib.mpcqp_model_periods_vjp_batch.restype = C.c_int
+    lib.mpcqp_model_periods_vjp_batch.argtypes = [C.POINTER(Dims), vp, C.POINTER(LoopPlant), i64, C.c_int32, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, C.POINTER(PeriodGrad), C.POINTER(PeriodGrad), vp, vp,
+                                                  vp, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

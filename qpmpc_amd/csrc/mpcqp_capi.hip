@@ -1758,6 +1758,52 @@ int mpcqp_model_periods_batch(const MpcqpDims *dims, const void *model, const Mp
     return run(r, ka, false, false, dims->dtype, batch, nullptr, (hipStream_t)stream, &lp);
 }
 
+int mpcqp_model_periods_vjp_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant, int64_t batch,
+                                  int32_t nperiods, const void *lam, const int32_t *status, const void *X, const void *U0,
+                                  const void *gX, const void *gU0, void *g_x0, void *g_states,
+                                  const MpcqpPeriodGrad *g_goal, const MpcqpPeriodGrad *g_targets, void *g_A, void *g_B,
+                                  int32_t *vjp_status, void *stream)
+{
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
+    const int64_t n = (int64_t)dims->N * dims->nu, m = (int64_t)dims->N * dims->mk;
+    if (n > 16 || m < 1 || m > 32 || dims->nx > 16) return MPCQP_EUNSUPPORTED;  // mpcqp_model_periods_batch's envelope
+    if (!model || !plant || !plant->A.ptr || !plant->B.ptr || !lam || !status || !g_x0 || nperiods < 1 || batch < 0)
+        return MPCQP_EINVAL;
+    if (plant->A.batch_stride < 0 || plant->B.batch_stride < 0) return MPCQP_EINVAL;
+    for (const MpcqpPeriodGrad *g : {g_goal, g_targets})
+        if (g && (g->batch_stride < 0 || g->period_stride < 0)) return MPCQP_EINVAL;
+    if ((g_A && !X) || (g_B && !U0)) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    LoopAdjointLaunch l{};
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.n = (int)n;
+    l.m = (int)m;
+    l.flags = dims->flags;
+    l.nperiods = nperiods;
+    l.batch = batch;
+    l.model = (const double *)model;
+    l.A = plant->A;
+    l.B = plant->B;
+    l.lam = (const double *)lam;
+    l.status = status;
+    l.X = (const double *)X;
+    l.U0 = (const double *)U0;
+    l.gX = (const double *)gX;
+    l.gU0 = (const double *)gU0;
+    l.g_x0 = (double *)g_x0;
+    l.g_states = (double *)g_states;
+    if (g_goal) l.g_goal = *g_goal;
+    if (g_targets) l.g_targets = *g_targets;
+    l.g_A = (double *)g_A;
+    l.g_B = (double *)g_B;
+    l.out_status = vjp_status;
+    return launch_loop_adjoint_small(l, (hipStream_t)stream);
+}
+
 int mpcqp_wip_advance_stats_batch(int32_t dtype, void *states, const void *U, int64_t u_stride, const int32_t *status,
                                   const int32_t *iters, int64_t *stats, int32_t N, double sampling_period,
                                   double target_vel, double length, double gravity, int32_t nsub, void *x0, void *goal,

@@ -379,6 +379,23 @@ bool model_diff_small_applies(int nx, int n, int m);
 int launch_model_diff_small(const ModelDiffLaunch &l, hipStream_t st);
 size_t model_diff_general_lds_bytes(int nx, int n);
 int launch_model_diff_general(const ModelDiffLaunch &l, hipStream_t st);
+// the adjoint of the closed loops of a shared model (mpcqp_model_periods_vjp_batch; mpcqp_model_adjoint.hip,
+// mpcqp_loop_adjoint_small_kernel: the small kernel's layout and envelope, the period loop inside); passed to the kernel as it is
+struct LoopAdjointLaunch {
+    int nx, nu, N, n, m, flags, nperiods;
+    int64_t batch;
+    const double *model;
+    MpcqpOperand A, B;                 // the plant (batch_stride 0: shared)
+    const double *lam;                 // [batch][nperiods][m]
+    const int32_t *status;             // [batch][nperiods]
+    const double *X, *U0;              // the records; read for g_A / g_B only (else null)
+    const double *gX, *gU0;            // nullable: zero
+    double *g_x0, *g_states;           // g_states nullable
+    MpcqpPeriodGrad g_goal, g_targets; // ptr nullable
+    double *g_A, *g_B;                 // nullable
+    int32_t *out_status;               // nullable
+};
+int launch_loop_adjoint_small(const LoopAdjointLaunch &l, hipStream_t st);
 
 }  // namespace mpcqp
 #endif

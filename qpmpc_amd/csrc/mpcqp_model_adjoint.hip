@@ -17,6 +17,10 @@
 //                                    workgroups striding over the batch;
 //   mpcqp_model_diff_general_kernel  every other model up to n = 64: one workgroup per problem, S and the vectors in LDS,
 //                                    the rows of M read in place from the model.
+// and the adjoint of closed loops of such a model, mpcqp_model_periods_vjp_batch:
+//   mpcqp_loop_adjoint_small_kernel  the small kernel's envelope and layout, sixteen lanes per LOOP; the reverse-time
+//                                    recursion over the periods inside, each period the VJP above with gU = [ubar; 0]
+//                                    ("Closed-loop adjoint").
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -314,6 +318,288 @@ __global__ void __launch_bounds__(kSmallThreads) mpcqp_model_diff_small_kernel(c
     }
 }
 
+// ------------------------------------------------------------------------------------------------ closed loops
+// The KKT block of one problem on its sixteen lanes, as mpcqp_model_diff_small_kernel has it inline, in a struct: the
+// active rows' ids (slot i takes the i-th set bit of lam > 0, two ballots), this slot's row `ma` of M_A, S = M_A M_A' with
+// row `l` on lane l, its in-place lower Cholesky factor, and the products and solves with them. `l` is the lane within the
+// row of sixteen, `g` the row within the wavefront; every loop over slots stops at kmax, the largest k of the wavefront's
+// four problems, so every member is called by the whole wavefront. (The kernel above keeps its own text: built on this
+// struct it compiled to 202 / 168 VGPRs, not the 204 / 169 of profiles/model_diff_kernel_resources.txt; DESIGN.md
+// section 9, "Closed-loop adjoint".)
+struct SmallKkt {
+    unsigned act;     // bit r: row r is active
+    int k, kmax, id;  // active rows; this slot's row (0 past the k-th: its products are masked)
+    double dinv;
+    double ma[16], S[16];
+
+    // -> false when more rows are active than there are variables (not a vertex's multipliers): k is then 0
+    __device__ __forceinline__ bool build(const double *Mm, const double *lam, bool live, int l, int g, int n, int m)
+    {
+        const bool a0 = live && l < m && lam[l] > 0.0, a1 = live && l + 16 < m && lam[l + 16] > 0.0;
+        const unsigned long long m0 = __ballot(a0), m1 = __ballot(a1);
+        act = (unsigned)((m0 >> (16 * g)) & 0xffffull) | ((unsigned)((m1 >> (16 * g)) & 0xffffull) << 16);
+        k = __popc(act);
+        const bool fits = k <= n;
+        if (!fits) k = 0;
+        id = 0;
+        {
+            unsigned x = act;
+            for (int s = 0; s < 15; ++s)
+                if (s < l) x &= x - 1;
+            if (l < k) id = __builtin_ctz(x);
+        }
+        kmax = max(max(lane_get(k, 0), lane_get(k, 16)), max(lane_get(k, 32), lane_get(k, 48)));
+#pragma unroll
+        for (int c = 0; c < 16; ++c) ma[c] = l < k ? Mm[id * 16 + c] : 0.0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            S[c] = 0.0;
+            if (c < kmax) {
+                const int idc = __shfl(id, c, 16);
+                const double *mc = Mm + idc * 16;
+                double acc = 0.0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc += ma[j] * mc[j];
+                S[c] = (c < k) ? acc : 0.0;
+            }
+        }
+        return fits;
+    }
+
+    // in-place lower Cholesky, the pivot test of chol_lower (mpcqp_adjoint_common.h) -> false when a pivot fails
+    __device__ __forceinline__ bool factor(int l)
+    {
+        bool bad = false;
+        dinv = 0.0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (j < kmax) {
+                const double d = __shfl(S[j], j, 16);
+                const bool in = j < k;
+                if (in && !(d > 0.0)) bad = true;
+                const bool ok = in && !bad;
+                const double sd = ok ? sqrt(d) : 1.0, inv = ok ? 1.0 / sd : 0.0;
+                if (l == j) dinv = inv;
+                const double lij = (l == j) ? sd : S[j] * inv;
+                S[j] = lij;
+#pragma unroll
+                for (int c = j + 1; c < 16; ++c) {
+                    if (c < kmax) {
+                        const double lcj = __shfl(lij, c, 16);
+                        S[c] -= lij * lcj;
+                    }
+                }
+            }
+        }
+        return !bad;
+    }
+
+    // x <- S^-1 x for the slot-distributed x
+    __device__ __forceinline__ double solve(double x, int l) const
+    {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (j < kmax) {
+                if (l == j) x *= dinv;
+                const double xj = __shfl(x, j, 16);
+                if (l > j) x -= S[j] * xj;
+            }
+        }
+#pragma unroll
+        for (int j = 15; j >= 0; --j) {
+            if (j < kmax) {
+                const double s = row_sum_dpp((l > j && l < k) ? S[j] * x : 0.0);
+                if (l == j) x = (x - s) * dinv;
+            }
+        }
+        return (l < k) ? x : 0.0;
+    }
+
+    // y_l = sum_i M[id_i][l] x_i for the slot-distributed x
+    __device__ __forceinline__ double rows_t(const double *Mm, double x, int l) const
+    {
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            if (i < kmax) {
+                const int idi = __shfl(id, i, 16);
+                const double xi = __shfl(x, i, 16);
+                acc += Mm[idi * 16 + l] * xi;
+            }
+        }
+        return acc;
+    }
+
+    // sum_c ma[c] v_c for the variable-distributed v
+    __device__ __forceinline__ double rows(double v) const
+    {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc += ma[c] * __shfl(v, c, 16);
+        return acc;
+    }
+};
+
+// mpcqp_model_periods_vjp_batch: the layout of the kernel above -- sixteen lanes per LOOP, four loops per wavefront, the LDS
+// image staged once per workgroup, workgroups striding over the batch -- with the period loop running backwards inside. Lane
+// l of a row carries component l of the costate `cs`, row l of g_A and g_B, component l of the period-summed g_goal and
+// components l, l + 16, ... of the period-summed g_targets, all in registers. A period without a plan, a loop past the end of
+// the batch or a failed model takes every wavefront-wide step with zeros: no lane leaves before the last one.
+__global__ void __launch_bounds__(kSmallThreads) mpcqp_loop_adjoint_small_kernel(const LoopAdjointLaunch a)
+{
+    extern __shared__ double lds_image[];
+    const int nx = a.nx, nu = a.nu, N = a.N, n = a.n, m = a.m, nT = N * nx, P = a.nperiods;
+    const ModelLayout ml = make_model_layout(nx, N, n, m);
+    const SmallImage im = make_small_image(nx, N, m);
+    const bool qt = (a.flags & MPCQP_Q_TERMINAL) != 0, qs = (a.flags & MPCQP_Q_STAGE) != 0;
+    {
+        const int tid = threadIdx.x;
+        for (int i = tid; i < m * 16; i += kSmallThreads) lds_image[im.M + i] = a.model[ml.off_M + i];
+        for (int i = tid; i < 256; i += kSmallThreads) lds_image[im.Lt + i] = a.model[ml.off_LinvT + i];
+        for (int i = tid; i < 16 * nx; i += kSmallThreads) {
+            lds_image[im.Wx + i] = a.model[ml.off_Wx + i];
+            if (qt) lds_image[im.Wg + i] = a.model[ml.off_Wg + i];
+        }
+        if (qs)
+            for (int i = tid; i < 16 * nT; i += kSmallThreads) lds_image[im.Wt + i] = a.model[ml.off_Wt + i];
+        for (int i = tid; i < m * nx; i += kSmallThreads) lds_image[im.Hx + i] = a.model[ml.off_Hx + i];
+    }
+    const bool model_bad = a.model[ml.total] != 0.0;
+    __syncthreads();
+    const double *Mm = lds_image + im.M, *Lt = lds_image + im.Lt, *Wx = lds_image + im.Wx, *Wg = lds_image + im.Wg;
+    const double *Wt = lds_image + im.Wt, *Hx = lds_image + im.Hx;
+    const int lane = threadIdx.x & 63, g = lane >> 4, l = lane & 15;
+    const int slot = (threadIdx.x >> 6) * 4 + g;  // this row's loop within the round
+    double *const gg_out = (double *)a.g_goal.ptr, *const gt_out = (double *)a.g_targets.ptr;
+    const bool gg_sum = a.g_goal.period_stride == 0, gt_sum = a.g_targets.period_stride == 0;
+
+    for (int64_t base = (int64_t)blockIdx.x * kSmallPerBlock; base < a.batch; base += (int64_t)gridDim.x * kSmallPerBlock) {
+        const bool valid = base + slot < a.batch;
+        const int64_t b = valid ? base + slot : 0;  // (a row past the end of the batch addresses loop 0 and touches nothing)
+        const bool on = valid && !model_bad;
+        const double *Ab = (const double *)a.A.ptr + b * a.A.batch_stride;
+        const double *Bb = (const double *)a.B.ptr + b * a.B.batch_stride;
+        const double *gXb = a.gX ? a.gX + b * (P + 1) * nx : nullptr;
+        double cs = (on && gXb && l < nx) ? gXb[P * nx + l] : 0.0;  // the costate a_P
+        if (a.g_states && valid && l < nx) a.g_states[(b * (P + 1) + P) * nx + l] = cs;
+        double gA[16], gB[16], gt[16], ggs = 0.0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) gA[c] = gB[c] = gt[c] = 0.0;
+        int fails = 0;
+
+        for (int t = P - 1; t >= 0; --t) {
+            const int64_t bt = b * P + t;
+            // the plant: g_A += a x_t', g_B += a u0_t', ubar = gU0_t + B' a, a_new = gX_t + A' a
+            if (a.g_A) {
+                const double xt = (on && l < nx) ? a.X[(b * (P + 1) + t) * nx + l] : 0.0;
+#pragma unroll
+                for (int c = 0; c < 16; ++c)
+                    if (c < nx) gA[c] += cs * __shfl(xt, c, 16);
+            }
+            if (a.g_B) {
+                const double ut = (on && l < nu) ? a.U0[bt * nu + l] : 0.0;
+#pragma unroll
+                for (int c = 0; c < 16; ++c)
+                    if (c < nu) gB[c] += cs * __shfl(ut, c, 16);
+            }
+            double accA = 0.0, accB = 0.0;
+            for (int c = 0; c < nx; ++c) {
+                const double pc = __shfl(cs, c, 16);
+                if (on && l < nx) accA += Ab[c * nx + l] * pc;
+                if (on && l < nu) accB += Bb[c * nu + l] * pc;
+            }
+            const double u = ((on && a.gU0 && l < nu) ? a.gU0[bt * nu + l] : 0.0) + accB;  // (zero from lane nu on)
+            double an = ((on && gXb && l < nx) ? gXb[t * nx + l] : 0.0) + accA;
+            // the period's plan on its active set
+            const bool live = on && a.status[bt] == 0;
+            SmallKkt q;
+            const bool fits = q.build(Mm, a.lam + bt * m, live, l, g, n, m);
+            const bool pd = q.factor(l);
+            const bool good = live && fits && pd;
+            if (live && !good) ++fails;
+            // tt = L^-1 [ubar; 0]
+            double tt = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                if (j < nu) {
+                    const double uj = __shfl(u, j, 16);
+                    if (j <= l) tt += Lt[j * 16 + l] * uj;
+                }
+            }
+            if (l >= n || !good) tt = 0.0;
+            const double nuv = q.solve(q.rows(tt), l);
+            const double w = (l < n) ? tt - q.rows_t(Mm, nuv, l) : 0.0;
+            // a_new -= Wx' w + Hx_A' nu, g_goal_t = Wg' w
+            double gx = an, gg = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const double wj = __shfl(w, j, 16);
+                if (l < nx) {
+                    gx -= Wx[j * nx + l] * wj;
+                    if (qt) gg += Wg[j * nx + l] * wj;
+                }
+                if (j < q.kmax) {
+                    const double nj = __shfl(nuv, j, 16);
+                    const int idj = __shfl(q.id, j, 16);
+                    if (l < nx) gx -= Hx[idj * nx + l] * nj;
+                }
+            }
+            if (good) an = gx;
+            if (!good) gg = 0.0;
+            if (gg_out) {
+                if (gg_sum)
+                    ggs += gg;
+                else if (valid && l < nx)
+                    gg_out[b * a.g_goal.batch_stride + t * a.g_goal.period_stride + l] = gg;
+            }
+            if (gt_out) {  // g_targets_t = Wt' w, sixteen components a pass
+#pragma unroll
+                for (int ci = 0; ci < 16; ++ci) {
+                    if (ci * 16 < nT) {
+                        const int c = ci * 16 + l;
+                        double acc = 0.0;
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const double wj = __shfl(w, j, 16);
+                            if (qs && c < nT) acc += Wt[j * nT + c] * wj;
+                        }
+                        if (!good) acc = 0.0;
+                        if (gt_sum)
+                            gt[ci] += acc;
+                        else if (valid && c < nT)
+                            gt_out[b * a.g_targets.batch_stride + t * a.g_targets.period_stride + c] = acc;
+                    }
+                }
+            }
+            cs = an;
+            if (a.g_states && valid && l < nx) a.g_states[(b * (P + 1) + t) * nx + l] = cs;
+        }
+
+        if (valid && l < nx) {
+            a.g_x0[b * nx + l] = cs;
+            if (gg_out && gg_sum) gg_out[b * a.g_goal.batch_stride + l] = ggs;
+            if (a.g_A) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c)
+                    if (c < nx) a.g_A[(b * nx + l) * nx + c] = gA[c];
+            }
+            if (a.g_B) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c)
+                    if (c < nu) a.g_B[(b * nx + l) * nu + c] = gB[c];
+            }
+        }
+        if (gt_out && gt_sum) {
+#pragma unroll
+            for (int ci = 0; ci < 16; ++ci) {
+                const int c = ci * 16 + l;
+                if (valid && c < nT) gt_out[b * a.g_targets.batch_stride + c] = gt[ci];
+            }
+        }
+        if (valid && l == 0 && a.out_status) a.out_status[b] = model_bad ? P : fails;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ general models
 // LDS carve of the general kernel, in doubles: S (n x ld), the vectors, two state vectors that roll along the horizon,
 // then the active rows' ids
@@ -537,6 +823,14 @@ int launch_model_diff_small(const ModelDiffLaunch &l, hipStream_t st)
     // (at most 47,104 bytes inside the envelope, at nx = 16, N = 16, m = 32: below the 48 KiB a launch gets unasked)
     auto kern = l.ntan > 0 ? mpcqp_model_diff_small_kernel<true> : mpcqp_model_diff_small_kernel<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)model_diff_small_grid(l.batch)), dim3(kSmallThreads), lds, st, l);
+    return (int)hipGetLastError();
+}
+
+int launch_loop_adjoint_small(const LoopAdjointLaunch &l, hipStream_t st)
+{
+    const size_t lds = (size_t)make_small_image(l.nx, l.N, l.m).total * sizeof(double);  // (the image of the kernel above)
+    hipLaunchKernelGGL(mpcqp_loop_adjoint_small_kernel, dim3((unsigned)model_diff_small_grid(l.batch)), dim3(kSmallThreads),
+                       lds, st, l);
     return (int)hipGetLastError();
 }
 
