@@ -538,6 +538,23 @@ int mpcqp_rollout_batch(const MpcqpDims *dims, const MpcqpOperand *A,
  * goal or targets that do not enter q get zero gradients.
  * Per problem: status[b] != 0 gives all-zero gradients and vjp_status[b] = status[b]; more active rows than variables or
  * a Gram matrix of the active rows that is not positive definite gives zeros and MPCQP_NOT_PD; else vjp_status[b] = 0.
+ * Dependent and weakly active rows -- the contract of the plan and shared-model derivative exports below
+ * (mpcqp_plan_vjp* / mpcqp_plan_jvp* / mpcqp_model_vjp_batch / mpcqp_model_jvp_batch; tests/test_gpu_degenerate_diff.py):
+ *  - "not positive definite" is decided relative to the rows: pivot j of the Gram matrix S = M_A M_A' of the whitened active
+ *    rows must exceed 4 (n + k + 1) 2^-53 S_jj, k the number of active rows (the rounding a Cholesky pivot of an exactly
+ *    row that is a multiple of one other active row can carry, whichever comes first; DESIGN.md section 9, "Dependent and
+ *    weakly active rows"). An active row that is a multiple of another active row -- a row stated twice, a row and a multiple
+ *    of it, both halves of an equality written as two inequalities, each with a positive multiplier -- is therefore
+ *    MPCQP_NOT_PD with zeros, whatever the sign of the rounding: never status 0 on a division by noise. The bound does not
+ *    cover a row that is a combination of several other active rows: there the verdict can still depend on rounding.
+ *    mpcqp_model_periods_vjp_batch is the exception: its factorisation keeps the plain test, pivot > 0.
+ *  - no forward route of this library returns such multipliers: the solvers keep an independent active set, so at a binding
+ *    pair one member carries the whole multiplier. The gradients with respect to x0, goal and targets, g_e off the pair and
+ *    g_e[i0] + f g_e[i1] on a pair with G_i1 = f G_i0 do not depend on which member that is, and equal the derivative of the
+ *    solution map (which is differentiable there); a lone g_e[i0] or g_e[i1] depends on the member, and a tangent of e gets
+ *    the unique response where it moves the pair together, de[i1] = f de[i0].
+ *  - a row that is tight with lam_i = 0 (a bound through the optimum) is inactive: one element of the generalized Jacobian, the
+ *    derivative of the problem without that row. With no positive multiplier at all that is the unconstrained derivative.
  * Envelope: float64 (MPCQP_EDTYPE otherwise), n <= 128 and whatever mpcqp_condense_batch condenses (MPCQP_EUNSUPPORTED
  * otherwise). The call runs mpcqp_condense_batch (Phi, Psi kept) into the workspace, then one adjoint launch. */
 int mpcqp_plan_vjp_workspace_bytes(const MpcqpDims *dims, int64_t batch, size_t *bytes);

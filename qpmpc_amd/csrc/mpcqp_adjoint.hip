@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_kernel(const AdjointLaunch a
                     for (int c = 0; c < n; ++c) acc += zi[c] * Z[c];
                     nu[i] = acc;
                 }
-                if (!chol_lower<BS>(S, k, ld, tid)) {
+                if (!chol_lower<BS, true>(S, k, ld, tid, gram_pivot_floor(n, k))) {
                     verdict = MPCQP_NOT_PD;
                 } else {
                     solve_lower<BS>(S, k, ld, nu, tid);
@@ -436,7 +436,7 @@ mpcqp_tangent_kernel(const typename std::conditional<kModel, TangentModelLaunch,
                     for (int c = 0; c < n; ++c) acc += zi[c] * zt[c];
                     mu[t * ld + i] = acc - mu[t * ld + i];
                 }
-                if (!chol_lower<BS>(S, k, ld, tid)) {
+                if (!chol_lower<BS, true>(S, k, ld, tid, gram_pivot_floor(n, k))) {
                     verdict = MPCQP_NOT_PD;
                 } else {
                     // mu_t = R^-T R^-1 (...), every tangent at once

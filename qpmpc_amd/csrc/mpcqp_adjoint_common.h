@@ -19,15 +19,35 @@ __device__ inline const double *op_step(const MpcqpOperand &o, int64_t b, int k)
 // problem b's part of a nullable output packed per problem
 __device__ inline double *out_at(void *p, int64_t off) { return p ? (double *)p + off : nullptr; }
 
+// The pivot test of the Gram matrix S = M_A M_A' of k whitened active rows of n entries: pivot j, the squared distance of
+// row j from the span of the rows before it, must exceed gram_pivot_floor(n, k) times S_jj as it was before elimination.
+// Where row j is a multiple f of an earlier row i the exact pivot is 0 and the computed one is rounding: the factor computed
+// is the exact factor of S + dS with |dS_ij| <= gamma_{k+1} sqrt(S_ii S_jj) (Higham, Accuracy and Stability, theorem 10.3),
+// on top of the gamma_n sqrt(S_ii S_jj) of the n-term sums that formed S (Cauchy-Schwarz), and the pivot moves by
+// dS_jj - 2 f dS_ji + f^2 dS_ii. With S_jj = f^2 S_ii the three terms are at most gamma S_jj, 2 |f| gamma sqrt(S_ii S_jj) =
+// 2 gamma S_jj and f^2 gamma S_ii = gamma S_jj: 4 (gamma_n + gamma_{k+1}) S_jj <= 4 (n + k + 1) 2^-53 S_jj for EVERY f, whichever
+// of the two rows comes first. So a row that is a multiple of ONE earlier active row (a row stated twice, a row and its
+// multiple, both halves of an equality) is MPCQP_NOT_PD whatever the sign of the rounding. A row that is a combination
+// sum_i x_i row_i of SEVERAL earlier rows is not covered by this bound: its pivot moves by up to
+// (sqrt(S_jj) + sum_i |x_i| sqrt(S_ii))^2 gamma, which grows with the conditioning of those rows, so there the verdict can
+// still depend on rounding. Rows that pass are at an angle of more than 1e-7 or so to the span of their predecessors. A
+// zero row (S_jj = 0) fails as before.
+__host__ __device__ inline double gram_pivot_floor(int n, int k) { return 4.0 * (double)(n + k + 1) * 0x1p-53; }
+
 // In-place lower Cholesky of the nn x nn matrix a (stride ld; only the lower triangle is read or written).
-// Uniform result: every thread reads the same pivot after a barrier.
-template <int BS>
-__device__ inline bool chol_lower(double *a, int nn, int ld, int tid)
+// Uniform result: every thread reads the same pivot after a barrier. kGram: the pivot test above, with rel =
+// gram_pivot_floor(n, k); the diagonal before elimination is kept in row 0 of the (otherwise unused) strict upper triangle.
+template <int BS, bool kGram = false>
+__device__ inline bool chol_lower(double *a, int nn, int ld, int tid, double rel = 0.0)
 {
+    if (kGram) {
+        __syncthreads();  // (the callers form S without a barrier behind it)
+        for (int j = 1 + tid; j < nn; j += BS) a[j] = a[j * ld + j];
+    }
     for (int j = 0; j < nn; ++j) {
         __syncthreads();
         const double d = a[j * ld + j];
-        if (!(d > 0.0)) return false;
+        if (!(d > (kGram ? rel * a[j] : 0.0))) return false;  // (j = 0: a[0] is d itself)
         const double sd = sqrt(d), inv = 1.0 / sd;
         __syncthreads();
         if (tid == 0) a[j * ld + j] = sd;

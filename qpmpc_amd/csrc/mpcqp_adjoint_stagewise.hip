@@ -386,7 +386,7 @@ __global__ void __launch_bounds__(BS) mpcqp_adjoint_stagewise_kernel(const Stage
         // 3b. the whitened active rows, 4. their Gram matrix and Y_A t
         whiten_rows(a.problem, b, rec, cv.rs, nx, nu, mk, n, idx, k, Y, sm + 2 * kMaxNx);
         gram_rows(Y, idx, k, mk, nu, n, S, cv.ldS, t, bv);
-        if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
+        if (!chol_lower<BS, true>(S, k, cv.ldS, tid, gram_pivot_floor(n, k))) verdict = MPCQP_NOT_PD;
     }
     if (verdict == 0) {
         solve_lower<BS>(S, k, cv.ldS, bv, tid);
@@ -551,7 +551,7 @@ mpcqp_tangent_stagewise_kernel(const typename std::conditional<kModel, Stagewise
     if (verdict == 0 && k > 0) {
         whiten_rows(a.problem, b, rec, cv.rs, nx, nu, mk, n, idx, k, Y, sm);
         gram_rows(Y, idx, k, mk, nu, n, S, cv.ldS, nullptr, nullptr);
-        if (!chol_lower<BS>(S, k, cv.ldS, tid)) verdict = MPCQP_NOT_PD;
+        if (!chol_lower<BS, true>(S, k, cv.ldS, tid, gram_pivot_floor(n, k))) verdict = MPCQP_NOT_PD;
     }
     if constexpr (kModel) {
         if (verdict == 0) {

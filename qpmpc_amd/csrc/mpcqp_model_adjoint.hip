@@ -130,13 +130,17 @@ __global__ void __launch_bounds__(kSmallThreads) mpcqp_model_diff_small_kernel(c
                 S[c] = (c < k) ? acc : 0.0;
             }
         }
-        // in-place lower Cholesky, the pivot test of chol_lower (mpcqp_adjoint_common.h)
+        // in-place lower Cholesky, the pivot test of chol_lower<BS, true> (mpcqp_adjoint_common.h): lane j holds pivot j and
+        // passes it on only where it exceeds the floor times its row's squared norm, the diagonal before elimination
         bool bad = false;
-        double dinv = 0.0;
+        double dinv = 0.0, dg = 0.0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) dg += ma[c] * ma[c];
+        dg *= gram_pivot_floor(16, 16);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             if (j < kmax) {
-                const double d = __shfl(S[j], j, 16);
+                const double d = __shfl(S[j] > dg ? S[j] : 0.0, j, 16);
                 const bool in = j < k;
                 if (in && !(d > 0.0)) bad = true;
                 const bool ok = in && !bad;
@@ -662,7 +666,7 @@ __global__ void __launch_bounds__(kGeneralThreads) mpcqp_model_diff_general_kern
                 S[i * ld + j] = acc;
             }
         }
-        if (!chol_lower<BS>(S, k, ld, tid)) verdict = MPCQP_NOT_PD;
+        if (!chol_lower<BS, true>(S, k, ld, tid, gram_pivot_floor(n, k))) verdict = MPCQP_NOT_PD;
     }
     // nu <- S^-1 (M_A v - sub) for v (n) in LDS; then out = v - M_A' nu. Called by the whole workgroup.
     auto kkt = [&](const double *v, const double *sub, double *out) {
