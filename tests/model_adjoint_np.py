@@ -20,6 +20,7 @@ from qpmpc_amd.workloads import problem_from_workload
 
 import adjoint_np as AN
 
+TOL = 1e-8  # what the shared-model derivative exports are held to against this restatement: TOL max(1, |ref|_inf)
 
 class NumpyModel:
     def __init__(self, w: dict):

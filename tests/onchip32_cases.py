@@ -32,6 +32,13 @@ SHAPES = (  # ((nx, nu, N, mk), family, why)
 )
 FAMILIES = tuple((shape, kind, tight, lti) for shape, kind, _ in SHAPES for tight in TIGHT for lti in (False, True))
 CLEAR = 1e-6
+VERDICT_SHAPES = ((3, 1, 24, 2), (4, 2, 16, 2))  # the shapes of the verdict tests of tests/test_gpu_onchip32.py
+# |lam - lam_ref| / (1 + max lam_ref) on the clear problems. Measured on an MI355X over the 54 families: 8.9e-9 for the default
+# route on these problems (the stage-wise kernels; worst on the time-invariant (3, 1, 32, 2) family at 0.05, whose condensed
+# Hessian is the worst conditioned) and 3.4e-10 for the flagged launch (the same family at 0.2). The bound is ten times the
+# default route's worst value (sums of up to 32 terms in another order, one refinement step), never below 1e-9:
+LAM_DEFAULT_ROUTE_WORST = 8.9e-9
+LAM_BOUND = max(1e-9, 10 * LAM_DEFAULT_ROUTE_WORST)
 
 
 @functools.lru_cache(maxsize=None)

@@ -29,6 +29,11 @@ SHAPES = (  # ((nx, nu, N, mk), why): each a place where the model prologue can 
 VARIANTS = tuple(range(len(OL.MODEL_VARIANTS)))
 PLAIN = (3, 1, 24, 2)
 VERDICT_SHAPES = ((3, 1, 24, 2), (4, 2, 16, 2))
+# what tests/golden/onchip32_model_default_parent.npz and onchip32_fused_parent.npz were captured on
+# (tools/gen_golden_onchip32_parent.py): the first variant that shares e (the export without bounds runs on it), and two
+# families of onchip32_cases
+DEFAULT_GOLDEN_VARIANT = 3
+FUSED_GOLDEN = (((3, 1, 24, 2), "lean", 0.05, False), ((4, 2, 16, 2), "general", 0.2, False))
 MANY = 61          # several wavefronts and an idle half
 MANY_SEED = 4100
 MANY_MARGIN = 0.2

@@ -3,7 +3,6 @@ recursion) against the condensed restatements (tests/adjoint_np.py, tests/adjoin
 C exports and Python surface of the feature."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
@@ -12,19 +11,12 @@ import pytest
 import adjoint_model_np as AM
 import adjoint_np as AN
 import adjoint_stagewise_np as AS
+from host_helpers import _dims, _header, _lib, _ltv
 from qpmpc_amd import _capi
 from qpmpc_amd import workloads as W
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 EXPORTS = ("mpcqp_plan_vjp_stagewise_workspace_bytes", "mpcqp_plan_vjp_stagewise_batch")
-
-
-def _ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _compare(w, rng, need, with_gX=True):
@@ -100,11 +92,6 @@ def test_zero_row_active_is_not_pd():
 
 # ---------------------------------------------------------------- public surface
 
-def _header() -> str:
-    with open(os.path.join(ROOT, "include", "mpcqp.h")) as f:
-        return f.read()
-
-
 def test_exports_declared_and_bound():
     declared = set(re.findall(r"(mpcqp_[a-z_]+)\(", _header()))
     for name in EXPORTS:
@@ -112,21 +99,6 @@ def test_exports_declared_and_bound():
         assert name in _capi.EXPORTS
     assert _capi.ABI_VERSION == 12
     assert "#define MPCQP_ABI_VERSION 12" in _header()
-
-
-def _lib():
-    from qpmpc_amd import build
-
-    if not os.path.exists(build.LIB_PATH):
-        pytest.fail("the library is not built (__graft_entry__.build())")
-    return _capi.load()
-
-
-def _dims(nx, nu, N, mk, dtype=_capi.F64):
-    d = _capi.Dims()
-    d.nx, d.nu, d.N, d.mk, d.dtype, d.flags = nx, nu, N, mk, dtype, 0
-    d.w_terminal, d.w_stage, d.w_input = 1.0, 0.0, 1e-3
-    return d
 
 
 def _query(dims, batch, max_active):

@@ -11,19 +11,12 @@ from qpmpc_amd import workloads as W
 from qpmpc_amd.workloads import problem_from_workload
 
 pytestmark = pytest.mark.gpu
+
+pytest.importorskip("torch")
+
+from guarded_launch import _random_ltv, _torch  # noqa: E402  (needs torch)
+
 KEYS = ("x0", "goal", "targets", "e")
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _gpu_vjp(w, gU, gX, **solve_kw):

@@ -11,20 +11,13 @@ import adjoint_np as AN
 from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
+
+pytest.importorskip("torch")
+
+from guarded_launch import _random_ltv, _torch  # noqa: E402  (needs torch)
+
 KEYS = ("x0", "goal", "targets", "e")
 MODEL = ("A", "B", "C", "D", "w")
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _check_path(w, seed, every=1, **solve_kw):

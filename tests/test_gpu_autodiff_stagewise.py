@@ -15,29 +15,14 @@ from golden_util import GOLDEN
 from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
+
+pytest.importorskip("torch")
+
+from guarded_launch import _random_ltv, _torch, _triple  # noqa: E402  (needs torch)
+
 KEYS = ("x0", "goal", "targets", "e")
 MODEL = ("A", "B", "C", "D")
 ALL = {"x0", "goal", "targets", "e", "A", "B", "C", "D", "wt", "wx", "wu"}
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
-
-
-def _triple(batch, N, seed=7):
-    A, B, Cm, e = W.triple_integrator_matrices(N)
-    rng = np.random.default_rng(seed)
-    x0 = np.stack([rng.uniform(-0.5, 0.5, batch), rng.uniform(-0.5, 0.5, batch), rng.uniform(-2.5, 2.5, batch)], 1)
-    goal = np.stack([rng.uniform(0.5, 1.5, batch), np.zeros(batch), np.zeros(batch)], 1)
-    return W._pack(A, B, Cm, None, e, N, 1.0, None, 1e-6, x0, goal, name=f"triple_integrator_N{N}")
 
 
 def _slack(w1, U):

@@ -8,7 +8,7 @@ same (tests/test_degenerate_cases_cpu.py shows on the C oracle that the inputs a
   duplicate  a row stated twice, and a row stated again at twice its scale, both binding. Reference: the oracle on the variant.
   band       a row and its exact negative with bounds e and -e: an equality written as two inequalities. Reference: the oracle.
 
-Launched as tests/test_gpu_verdicts.py launches its cases (Forward of tests/test_gpu_memory_discipline.py, the route's flags and
+Launched as tests/test_gpu_verdicts.py launches its cases (Forward of tests/guarded_launch.py, the route's flags and
 dtype, fill 0xFF), nine problems per launch. Per launch: return code 0, status 0 for all nine, iters written, no NaN; the plan
 within the route's bound (1e-7 float64, 1e-3 float32, scaled as against_oracle scales it) of the exact answer or the oracle's;
 on `free`, float64 routes whose rounding bound n 2^-53 sum_j |G_ij u0_j| / (1 + |h_i|) is at most 1e-13 on every row (a tenth of
@@ -25,7 +25,6 @@ The same assertions on the shared-model export (two and four per wavefront), the
 verdict_cases.DENSE_SIZES) and the on-chip 17 .. 32-variable kernel (csrc/mpcqp_duo.hip) in its three modes.
 
 With MPCQP_DEGENERATE_REPORT=<path> a complete run writes the table of profiles/degenerate_active_sets.txt."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -33,6 +32,7 @@ import pytest
 
 import degenerate_cases as DC
 import kkt_certificate as KC
+import onchip32_cases as OC
 import operand_layouts as OL
 import verdict_cases as VC
 
@@ -40,12 +40,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_memory_discipline as MD  # noqa: E402  (its arena launcher; needs torch)
-import test_gpu_onchip32 as T32  # noqa: E402  (_NoWorkspace: a forward launch without a workspace)
-import test_gpu_onchip32_model as TM  # noqa: E402  (ModelCase: a factored model and its per-problem operands in the arena)
-from test_gpu_memory_discipline import Forward, Launch  # noqa: E402
+import guarded_launch as GL  # noqa: E402  (the arena launchers; needs torch)
+from guarded_launch import Forward, ModelCase, QPs  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
 
-F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
+F, F64, F32, I32, U8 = GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 LD = np.longdouble
 ROUTES, VARIANTS = list(OL.ROUTES), list(DC.VARIANTS)
 FREE_ROUNDING = 1e-13  # a tenth of the default feas_tol of include/mpcqp.h
@@ -111,15 +110,6 @@ def _report():
                 s = SEEN[k]
                 fh.write(f"{k[0]:46s} {k[1]:9s} {s['status']:9s} {s['it_nom']:6d} {s['it_var']:>6s} {s['ratio']:>6s} {s['err']:8.1e} "
                          f"{s['cert']:>9s}{'' if k in PASSED else '  FAILED (xfail)' if k in XFAIL else '  FAILED'}\n")
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 def _rel(U, ref):
@@ -221,7 +211,7 @@ def test_route(route, name):
 # ---------------------------------------------------------------------------------------------- the shared-model export
 def _model_launch(flag):
     def launch(w):
-        return TM.ModelCase(DC.shared(w)).run(F, _flags([flag]))
+        return ModelCase(DC.shared(w)).run(F, _flags([flag]))
 
     return launch
 
@@ -240,28 +230,7 @@ def test_shared_model(shape, flag, name):
 
 # ---------------------------------------------------------------------------------------------- the dense-QP export
 def _dense_launch(P, q, G, h, f32, flags, workspace):
-    _capi, lib, stream = MD._api()
-    B, n = q.shape
-    m = h.shape[1]
-    dtype, code = (F32, _capi.F32) if f32 else (F64, _capi.F64)
-    nbytes = C.c_size_t(0)
-    if workspace:
-        assert lib.mpcqp_solve_workspace_bytes(n, m, code, B, C.byref(nbytes)) == 0
-    L = Launch()
-    for key, arr in (("P", P), ("q", q), ("G", G), ("h", h)):
-        L.add(key, "in", dtype, data=arr.reshape(B, -1))
-    L.add("U", "out", dtype, B * n)
-    L.add("lam", "out", dtype, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    o = _capi.SolveOpts()
-    o.flags = int(flags)
-    out = L.run(F, lambda: lib.mpcqp_solve_batch(n, m, code, L.ptr("P"), L.ptr("q"), L.ptr("G"), L.ptr("h"), B, C.byref(o), L.ptr("U"),
-                                                 L.ptr("lam"), L.ptr("status"), L.ptr("iters"), L.ptr("ws"), nbytes.value, stream()))
-    out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
-    return out
+    return QPs(P, q, G, h, dtype=F32 if f32 else F64, workspace=workspace).run(F, flags)
 
 
 def _dense_case(label, name, n, m, f32, tol, flags, workspace):
@@ -314,10 +283,10 @@ for _n, _m in DC.ONCHIP_QP_SIZES:
 def test_onchip_fused(shape, name):
     """MPCQP_OPT_ON_CHIP_32 through mpcqp_build_solve_batch, without a workspace, on the nine general problems of
     tests/test_gpu_onchip32.py::test_verdicts"""
-    assert tuple(T32.VERDICT_SHAPES) == tuple(DC.ONCHIP_SHAPES)
+    assert tuple(OC.VERDICT_SHAPES) == tuple(DC.ONCHIP_SHAPES)
 
     def launch(w):
-        return T32._NoWorkspace(w).run(F, _flags(["OPT_ON_CHIP_32"]))
+        return Forward(w, workspace=False).run(F, _flags(["OPT_ON_CHIP_32"]))
 
     _workload_case(f"on chip, fused {shape}", name, ("on chip", shape), DC.onchip_full(shape), None, False, launch, 1e-7)
 

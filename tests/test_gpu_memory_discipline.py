@@ -15,7 +15,8 @@ sizes, 512-byte aligned, 64 KiB of guard on either side. Each launch runs under 
       of tests/*_np.py at 1e-8 max(1, |ref|),
   (e) take workspace = NULL, workspace_bytes = 0 wherever the size query answers 0.
 
-The exports are called through ctypes directly. No launch ever gets a buffer smaller than the contract says."""
+The exports are called through ctypes directly, by the launchers of tests/guarded_launch.py (Launch, Forward, discipline, ModelCase,
+QPs, PlanVjp, PlanJvp). No launch ever gets a buffer smaller than the contract says."""
 import ctypes as C
 import os
 
@@ -23,263 +24,19 @@ import numpy as np
 import pytest
 
 import oracle
-from oracle import condense_np
 
 import adjoint_np as AN
-import adjoint_stagewise_np as AS
-import arena as AR
-from operand_layouts import f32_view, ltv  # noqa: F401  (ltv: the random workloads of this file, NumPy only)
-import tangent_model_np as TM
-import tangent_np as TN
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from guarded_launch import (F, F32, F64, I32, U8, Z, Forward, Launch, PlanJvp, PlanVjp, QPs, ModelCase, _api, _dense_qps,  # noqa: E402
+                            _rel, _tangents, add_problem, against_oracle, arena_problem, close, condense_refs, discipline,
+                            equal_outputs, f32_view, forward_on_cpu, holds, ltv, same_bits, same_plans)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
-
-Z, F = 0x00, 0xFF
-I32, U8, F64, F32 = torch.int32, torch.uint8, torch.float64, torch.float32
-OPS = (("A", "A"), ("B", "B"), ("C", "C"), ("D", "D"), ("e", "e"), ("x0", "initial_state"), ("goal", "goal_state"),
-       ("targets", "target_states"))
-
-
-def _api():
-    from qpmpc_amd import _capi
-    from qpmpc_amd.batch import _stream_ptr
-
-    return _capi, _capi.load(), _stream_ptr
-
-
-def _esz(dtype):
-    return torch.empty((), dtype=dtype).element_size()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def holds(a, byte):
-    return bool((bits(a) == byte).all())
-
-
-class Launch:
-    """The buffers of one call. Roles: "in" (read-only: snapshotted, must be unchanged), "out" and "scratch" (filled before every
-    run), "inout" (reloaded before every run, returned)."""
-
-    def __init__(self):
-        self.specs, self.arena = [], None
-
-    def add(self, name, role, dtype, count=None, data=None, stride=None):
-        rows = None
-        if data is not None:
-            data = torch.as_tensor(data).to("cuda", dtype).contiguous()
-            rows = data.reshape(data.shape[0], -1) if data.dim() > 1 else data.reshape(1, -1)
-            stride = int(stride or rows.shape[1])
-            count = (rows.shape[0] - 1) * stride + rows.shape[1]
-        self.specs.append(dict(name=name, role=role, dtype=dtype, count=int(count), rows=rows, stride=stride))
-
-    def build(self):
-        sizes = [s["count"] * _esz(s["dtype"]) for s in self.specs]
-        self.arena = AR.Arena(AR.capacity_for(sizes), "cuda")
-        for s, nb in zip(self.specs, sizes):
-            if nb:  # (a buffer of no bytes is passed as NULL)
-                self.arena.carve(s["name"], nb, s["dtype"])
-        return self
-
-    def has(self, name):
-        return name in self.arena.spans
-
-    def ptr(self, name):
-        return self.arena.ptr(name) if self.has(name) else None
-
-    def nbytes(self, name):
-        return self.arena.nbytes(name) if self.has(name) else 0
-
-    def run(self, byte, call, keep=()):
-        """One launch under fill `byte`; buffers named in `keep` stay as the launch before left them. Asserts (a) and the
-        read-only part of (c); returns every buffer that is not read-only as a NumPy array."""
-        a = self.arena
-        a.fill_guards(byte)
-        live = [s for s in self.specs if self.has(s["name"])]
-        for s in live:
-            if s["name"] in keep:
-                continue
-            a.fill([s["name"]], byte)
-            if s["rows"] is not None:
-                a.view(s["name"]).as_strided(tuple(s["rows"].shape), (s["stride"], 1)).copy_(s["rows"])
-        ro = [s["name"] for s in live if s["role"] == "in"]
-        a.snapshot(ro)
-        torch.cuda.synchronize()
-        rc = call()
-        torch.cuda.synchronize()
-        assert rc == 0, f"return code {rc}"
-        damaged = a.guards_intact()
-        assert damaged == [], f"fill {byte:#04x}: overrun (buffer, side, first, last, bytes) {damaged}"
-        changed = a.unchanged(ro)
-        assert changed == [], f"fill {byte:#04x}: read-only buffer written (buffer, first byte, bytes) {changed}"
-        return {s["name"]: a.view(s["name"]).clone().cpu().numpy() for s in live if s["role"] != "in"}
-
-
-def pad_of(pad, name):
-    """elements of batch-stride padding of operand `name`: `pad` is one int for every operand or a dict name -> elements"""
-    return int(pad.get(name, 0)) if isinstance(pad, dict) else int(pad)
-
-
-def add_problem(L, bp, pad=0, inout=()):
-    """the operands of `bp`, read-only but for those named in `inout` (a fused period writes the next problem over them)"""
-    for name, attr in OPS:
-        t = getattr(bp, attr)
-        if t is not None:
-            rows = t.reshape(t.shape[0], -1)
-            L.add("op_" + name, "inout" if name in inout else "in", bp.dtype, data=rows,
-                  stride=rows.shape[1] + (pad_of(pad, name) if rows.shape[0] > 1 else 0))
-
-
-def arena_problem(L, bp, pad=0):
-    """MpcqpProblem of `bp` with every operand pointing into the arena (batch strides `pad` elements past the packed ones; `pad`
-    as in pad_of)."""
-    _capi = _api()[0]
-    ops = []
-    for name, attr in OPS:
-        t = getattr(bp, attr)
-        if t is None:
-            ops.append(_capi.Operand(None, 0, 0))
-            continue
-        o = bp._operand(t)
-        bs = 0 if t.shape[0] == 1 else t.reshape(t.shape[0], -1).shape[1] + pad_of(pad, name)
-        ops.append(_capi.Operand(L.ptr("op_" + name), bs, o.step_stride))
-    return _capi.Problem(*ops)
-
-
-# ---------------------------------------------------------------------------------------------- workloads
-_ORACLE = {}
-
-
-def oracle_of(key, w):
-    if key not in _ORACLE:
-        Uo, lamo, sto, _ = oracle.solve_workload(w)
-        _ORACLE[key] = (Uo, lamo, sto)
-    return _ORACLE[key]
-
-
-# ---------------------------------------------------------------------------------------------- forward exports
-class Forward:
-    """mpcqp_build_solve_batch (or mpcqp_stagewise_solve_batch) of a workload with everything in an arena."""
-
-    def __init__(self, w, dtype=None, stagewise=False, max_active=0, query=None, pad=0, order=None, warm=False, inout=()):
-        from qpmpc_amd import workloads as W
-
-        _capi, lib, _ = _api()
-        self.bp = bp = W.to_batch_problem(w, dtype=dtype)
-        self.B, self.n, self.m = bp.batch_size, bp.nb_variables, bp.nb_constraints
-        self.dims, self.stagewise, self.max_active, self.pad = bp.dims(), stagewise, int(max_active), pad
-        nbytes = C.c_size_t(0)
-        if stagewise:
-            rc = lib.mpcqp_stagewise_workspace_bytes(C.byref(self.dims), self.B, int(max_active if query is None else query),
-                                                     C.byref(nbytes))
-        else:
-            rc = lib.mpcqp_workspace_bytes(C.byref(self.dims), self.B, 1, C.byref(nbytes))
-        assert rc == 0, rc
-        self.ws_bytes = nbytes.value
-        L = self.L = Launch()
-        add_problem(L, bp, pad, inout)  # (inout: operands a call rewrites itself, tests/test_gpu_streams.py)
-        L.add("U", "out", bp.dtype, self.B * self.n)
-        L.add("lam", "out", bp.dtype, self.B * self.m)
-        L.add("status", "out", I32, self.B)
-        L.add("iters", "out", I32, self.B)
-        L.add("ws", "scratch", U8, self.ws_bytes)
-        if order is not None:
-            L.add("order", "in", I32, data=torch.as_tensor(np.asarray(order, dtype=np.int32)))
-        if warm:
-            wb = C.c_size_t(0)
-            assert lib.mpcqp_warm_state_bytes(C.byref(self.dims), C.byref(wb)) == 0 and wb.value > 0
-            L.add("warm", "scratch", U8, self.B * wb.value)
-        L.build()
-        self.cp = arena_problem(L, bp, pad)
-        print(f"    batch {self.B} n {self.n} m {self.m}: workspace {self.ws_bytes} bytes")
-
-    def run(self, byte, flags=0, lam=True, iters=True, warm_start=0, keep=(), max_iter=0, factor_slot=0, warm_shift=0):
-        _capi, lib, stream = _api()
-        L = self.L
-        o = _capi.SolveOpts()
-        o.flags, o.max_iter, o.factor_slot = int(flags), int(max_iter), int(factor_slot)
-        if L.has("order"):
-            o.order = L.ptr("order")
-        if L.has("warm"):
-            o.warm_state, o.warm_state_bytes, o.warm_start = L.ptr("warm"), L.nbytes("warm"), int(warm_start)
-            o.warm_shift = int(warm_shift)
-        tail = (L.ptr("U"), L.ptr("lam") if lam else None, L.ptr("status"), L.ptr("iters") if iters else None, L.ptr("ws"),
-                self.ws_bytes, stream())
-
-        def call():
-            if self.stagewise:
-                return lib.mpcqp_stagewise_solve_batch(C.byref(self.dims), C.byref(self.cp), self.B, C.byref(o), self.max_active,
-                                                       *tail)
-            return lib.mpcqp_build_solve_batch(C.byref(self.dims), C.byref(self.cp), self.B, C.byref(o), *tail)
-
-        out = L.run(byte, call, keep)
-        out["U"] = out["U"].reshape(self.B, self.n)
-        out["lam"] = out["lam"].reshape(self.B, self.m)
-        return out
-
-
-def equal_outputs(a, b, what, items=None, lam=True, iters=True):
-    """(b): status and iters of every item (of `items`), U of every item (no plan: zeros), lam of the solved ones."""
-    sel = np.ones(len(a["status"]), dtype=bool) if items is None else items
-    assert np.array_equal(a["status"][sel], b["status"][sel]), (what, "status", a["status"], b["status"])
-    if iters:
-        assert np.array_equal(a["iters"][sel], b["iters"][sel]), (what, "iters", a["iters"], b["iters"])
-    bad = [i for i in np.flatnonzero(sel) if not same_bits(a["U"][i], b["U"][i])]
-    assert not bad, (what, "U differs for items", bad, a["status"][bad], a["U"][bad[0]], b["U"][bad[0]])
-    if lam:
-        ok = sel & (a["status"] == 0)
-        bad = [i for i in np.flatnonzero(ok) if not same_bits(a["lam"][i], b["lam"][i])]
-        assert not bad, (what, "lam differs for items", bad)
-
-
-def same_plans(a, b, what):
-    """two entry points that launch the same kernel (their slot counts may differ): statuses equal, plans equal to rounding"""
-    assert np.array_equal(a["status"], b["status"]), (what, a["status"], b["status"])
-    ok = a["status"] == 0
-    if ok.any():
-        ua, ub = a["U"][ok].astype(np.float64), b["U"][ok].astype(np.float64)
-        assert np.abs(ua - ub).max() <= 1e-9 * max(1.0, np.abs(ua).max()), what
-
-
-def against_oracle(key, w, out, tol, skip_status=()):
-    """(d) for a forward export; items whose status is in `skip_status` (MPCQP_SLOTS_FULL) have no counterpart in the oracle."""
-    Uo, lamo, sto = oracle_of(key, w)
-    st, U = out["status"], out["U"].astype(np.float64)
-    cmp = ~np.isin(st, skip_status)
-    assert cmp.sum() * 2 >= len(st), st
-    assert np.array_equal(st[cmp] == 0, sto[cmp] == 0), (st, sto)
-    ok = cmp & (sto == 0)
-    assert ok.sum() * 2 >= len(st), (st, sto)  # (at least half of the batch is compared)
-    scale = np.maximum(1.0, np.abs(Uo[ok]).max(axis=1, keepdims=True))
-    err = float((np.abs(U[ok] - Uo[ok]) / scale).max())
-    print(f"    {key}: {int(ok.sum())} of {len(st)} solved, max rel err vs oracle {err:.2e}")
-    assert err <= tol, err
-    assert not np.isnan(U).any() and (U[st != 0] == 0).all()  # (no plan: zeros, never NaN)
-    return ok
-
-
-def discipline(key, w, tol=1e-7, flags=0, skip_status=(), reference=None, **kw):
-    """(a) .. (e) of one forward launch: twice under fill Z, once under fill F, once with lam and iters NULL under fill F."""
-    case = Forward(w, **kw)
-    z1, z2, f = case.run(Z, flags), case.run(Z, flags), case.run(F, flags)
-    equal_outputs(z1, z2, key + ": run to run under fill Z")
-    equal_outputs(z1, f, key + ": fill Z against fill F")
-    nn = case.run(F, flags, lam=False, iters=False)
-    assert holds(nn["lam"], F) and holds(nn["iters"], F), key + ": a NULL output's neighbour was written"
-    equal_outputs(f, nn, key + ": lam and iters NULL", lam=False, iters=False)
-    against_oracle(key, reference if reference is not None else w, f, tol, skip_status)
-    return case, f
 
 
 def test_quad_lean_four_per_wavefront():
@@ -500,15 +257,6 @@ def test_stagewise_entry_point(shape):
 
 
 # ---------------------------------------------------------------------------------------------- condensing, dense solves
-def _rel(got, want):
-    return float(np.abs(got - want).max() / max(1.0, np.abs(want).max()))
-
-
-def condense_refs(w, count):
-    from qpmpc_amd.workloads import problem_from_workload
-
-    return [condense_np.condense(problem_from_workload(w, b)) for b in range(count)]
-
 
 @pytest.mark.parametrize("name", ["small", "large_f64", "large_f32"])
 def test_condense_and_its_phases(name):
@@ -574,18 +322,6 @@ def test_condense_and_its_phases(name):
         assert same_bits(outs[F][key], f[key]), (key, "the two phases are the whole call")
 
 
-def _dense_qps(rng, B, n, m):
-    """the dense QPs of tests/test_gpu_parity.py::_random_dense_qps: h > 0, so x = 0 is feasible and every problem has a solution"""
-    Ps, qs, Gs, hs = [], [], [], []
-    for _ in range(B):
-        M = rng.standard_normal((n, n))
-        Ps.append(M @ M.T / n + 0.1 * np.eye(n))
-        qs.append(rng.standard_normal(n))
-        Gs.append(rng.standard_normal((m, n)))
-        hs.append(np.abs(rng.standard_normal(m)) * 0.2 + 0.05)
-    return [np.stack(a) for a in (Ps, qs, Gs, hs)]
-
-
 @pytest.mark.parametrize("n,m,dtype,tol", [(10, 24, F64, 1e-7), (40, 90, F64, 1e-7), (96, 203, F32, 2e-3), (100, 300, F32, 2e-3),
                                            (160, 512, F64, 1e-8), (256, 1024, F32, 2e-3)])
 def test_dense_qp_solver(n, m, dtype, tol):
@@ -593,39 +329,14 @@ def test_dense_qp_solver(n, m, dtype, tol):
     kernel and the workspace-resident solver (every row of test_large_solver_dense_qps_vs_oracle, tolerances as there: the MFMA
     factor with m no multiple of 4, the scalar packed factor in float32 and float64, the blocked MFMA factor with 16-byte loads
     of G')."""
-    _capi, lib, stream = _api()
     B = 3
     P, q, G, h = _dense_qps(np.random.default_rng(n + m), B, n, m)
-    code = _capi.F64 if dtype == F64 else _capi.F32
-    nbytes = C.c_size_t(0)
-    assert lib.mpcqp_solve_workspace_bytes(n, m, code, B, C.byref(nbytes)) == 0
-    print(f"    dense QP n {n} m {m}: workspace {nbytes.value} bytes")
-    L = Launch()
-    for key, a in (("P", P), ("q", q), ("G", G), ("h", h)):
-        L.add(key, "in", dtype, data=a.reshape(B, -1))
-    L.add("U", "out", dtype, B * n)
-    L.add("lam", "out", dtype, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    o = _capi.SolveOpts()
-
-    def call(lam=True):
-        def go():
-            return lib.mpcqp_solve_batch(n, m, code, L.ptr("P"), L.ptr("q"), L.ptr("G"), L.ptr("h"), B, C.byref(o), L.ptr("U"),
-                                         L.ptr("lam") if lam else None, L.ptr("status"), L.ptr("iters") if lam else None,
-                                         L.ptr("ws"), nbytes.value, stream())
-        return go
-
-    def shaped(out):
-        out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
-        return out
-
-    z1, z2, f = shaped(L.run(Z, call())), shaped(L.run(Z, call())), shaped(L.run(F, call()))
+    c = QPs(P, q, G, h, dtype=dtype, workspace=True)
+    print(f"    dense QP n {n} m {m}: workspace {c.ws_bytes} bytes")
+    z1, z2, f = c.run(Z, 0), c.run(Z, 0), c.run(F, 0)
     equal_outputs(z1, z2, "run to run under fill Z")
     equal_outputs(z1, f, "fill Z against fill F")
-    nn = shaped(L.run(F, call(False)))
+    nn = c.run(F, 0, lam=False, iters=False)
     assert holds(nn["lam"], F) and holds(nn["iters"], F)
     equal_outputs(f, nn, "lam and iters NULL", lam=False, iters=False)
     ref = f32_view(dict(P=P, q=q, G=G, h=h)) if dtype == F32 else dict(P=P, q=q, G=G, h=h)
@@ -700,10 +411,9 @@ def test_update_vectors_and_rollout():
 def test_shared_model_factor_and_solves(family):
     """mpcqp_factor_model into a buffer of exactly mpcqp_model_bytes, then mpcqp_solve_model_batch (and _bounds_batch with bounds
     per problem) two and four per wavefront, 5 and 61 problems, against the oracle."""
-    from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
+    from qpmpc_amd import _capi
     from qpmpc_amd import workloads as W
 
-    _, lib, stream = _api()
     for batch in (5, 61):
         if family == "triple":
             w = W.triple_integrator_batch(batch, seed=batch, heterogeneous=False)
@@ -712,98 +422,24 @@ def test_shared_model_factor_and_solves(family):
             w["x0"][: batch // 2, 1] += 0.4
             ts = np.stack([w["pendulum"].target_states(x, 0.5) for x in w["x0"]])
             w["goal"], w["targets"] = ts[:, -4:], ts[:, :-4]
-        bp = W.to_batch_problem(w)
-        B, n, m, N, nx = bp.batch_size, bp.nb_variables, bp.nb_constraints, bp.nb_timesteps, bp.state_dim
-        # the pseudo-problems of include/mpcqp.h (x0 = goal = targets = 0, then unit vectors), condensed by the library
-        nb = 1 + 2 * nx + N * nx
-        x0, goal, tgt = torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, N * nx), dtype=F64)
-        x0[1:1 + nx], goal[1 + nx:1 + 2 * nx], tgt[1 + 2 * nx:] = torch.eye(nx), torch.eye(nx), torch.eye(N * nx)
-        pseudo = BatchMPCProblem(bp.A, bp.B, bp.C, bp.D, bp.e, N, bp.terminal_cost_weight, bp.stage_state_cost_weight,
-                                 bp.stage_input_cost_weight, x0, goal_state=goal, target_states=tgt)
-        mdims = pseudo.dims()
-        qp = BatchMPCQP(pseudo, keep_propagators=False)
-        torch.cuda.synchronize()
-        mbytes = C.c_size_t(0)
-        assert lib.mpcqp_model_bytes(C.byref(mdims), C.byref(mbytes)) == 0
-        print(f"    model {family} batch {batch}: model {mbytes.value} bytes")
-        L = Launch()
-        L.add("P", "in", F64, data=qp.P[0].reshape(1, -1))
-        L.add("G", "in", F64, data=qp.G[0].reshape(1, -1))
-        L.add("qb", "in", F64, data=qp.q.reshape(1, -1))
-        L.add("hb", "in", F64, data=qp.h.reshape(1, -1))
-        L.add("model", "scratch", U8, mbytes.value)
-        for key, attr in (("x0", "initial_state"), ("goal", "goal_state"), ("targets", "target_states")):
-            if getattr(bp, attr) is not None:
-                L.add(key, "in", F64, data=getattr(bp, attr))
-        e_rows = torch.as_tensor(np.broadcast_to(np.asarray(w["e"], dtype=float), (B, N, bp.ineq_dim)).copy())
-        L.add("e", "in", F64, data=e_rows.reshape(B, -1))
-        L.add("U", "out", F64, B * n)
-        L.add("lam", "out", F64, B * m)
-        L.add("status", "out", I32, B)
-        L.add("iters", "out", I32, B)
-        L.build()
-
-        def operand(key, attr):
-            t = getattr(bp, attr)
-            if t is None:
-                return _capi.Operand(None, 0, 0)
-            return _capi.Operand(L.ptr(key), 0 if t.shape[0] == 1 else t.shape[1], 0)
-
-        ops = [operand("x0", "initial_state"), operand("goal", "goal_state"), operand("targets", "target_states")]
-        e_op = _capi.Operand(L.ptr("e"), N * bp.ineq_dim, bp.ineq_dim)
-
-        def launch(flags, bounds, lam=True):
-            o = _capi.SolveOpts()
-            o.flags = flags
-
-            def go():
-                rc = lib.mpcqp_factor_model(C.byref(mdims), L.ptr("P"), L.ptr("G"), L.ptr("qb"), L.ptr("hb"), L.ptr("model"),
-                                            mbytes.value, stream())
-                if rc:
-                    return rc
-                tail = (C.byref(ops[0]), C.byref(ops[1]), C.byref(ops[2]), B, C.byref(o), L.ptr("U"),
-                        L.ptr("lam") if lam else None, L.ptr("status"), L.ptr("iters") if lam else None, stream())
-                if bounds:
-                    return lib.mpcqp_solve_model_bounds_batch(C.byref(mdims), L.ptr("model"), C.byref(e_op), *tail)
-                return lib.mpcqp_solve_model_batch(C.byref(mdims), L.ptr("model"), *tail)
-            return go
-
-        def shaped(out):
-            out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
-            return out
-
+        # the model's bounds are the workload's; every problem's own bounds are the same ones, stated per problem and per step
+        N, mk = int(w["N"]), np.asarray(w["e"]).shape[-1]
+        shared = dict(w, e_model=w["e"], e=np.broadcast_to(np.asarray(w["e"], dtype=float), (batch, N, mk)).copy())
+        case = ModelCase(shared, factor_in_arena=True)
+        print(f"    model {family} batch {batch}: model {case.model_bytes} bytes")
         for flags in (_capi.OPT_TWO_PER_WAVE, _capi.OPT_FOUR_PER_WAVE):
             for bounds in (False, True):
                 what = f"model {family} {batch} flags {flags} bounds {bounds}"
-                z1, z2, f = (shaped(L.run(byte, launch(flags, bounds))) for byte in (Z, Z, F))
+                z1, z2, f = (case.run(byte, flags, bounds) for byte in (Z, Z, F))
                 equal_outputs(z1, z2, what + ": run to run")
                 equal_outputs(z1, f, what + ": fill Z against fill F")
-                nn = shaped(L.run(F, launch(flags, bounds, lam=False)))
+                nn = case.run(F, flags, bounds, lam=False, iters=False)
                 assert holds(nn["lam"], F) and holds(nn["iters"], F)
                 equal_outputs(f, nn, what + ": lam and iters NULL", lam=False, iters=False)
                 against_oracle(f"model {family} {batch}", w, f, 1e-7)
 
 
 # ---------------------------------------------------------------------------------------------- derivative exports
-def forward_on_cpu(w, unsolved=()):
-    """U, lam, status of every problem by the C oracle (what a forward launch hands the derivative exports); the items of
-    `unsolved` are marked MPCQP_MAX_ITER."""
-    Uo, lamo, sto = oracle.solve_workload(w)[:3]
-    sto = np.asarray(sto, dtype=np.int32).copy()
-    for b in unsolved:
-        sto[b] = 1
-    return np.asarray(Uo, dtype=float), np.asarray(lamo, dtype=float), sto
-
-
-def max_active_of(lam, status, n):
-    return int(min(((lam > 0) & (status == 0)[:, None]).sum(axis=1).max(), n))
-
-
-def close(got, want, what):
-    err = float(np.abs(np.asarray(got).ravel() - np.asarray(want).ravel()).max()) if np.asarray(want).size else 0.0
-    assert err <= 1e-8 * max(1.0, float(np.abs(want).max()) if np.asarray(want).size else 0.0), (what, err)
-
-
 VJP_CASES = [("condensed", (3, 2, 8, 2), 5, ()), ("model", (3, 2, 8, 2), 5, ()), ("stagewise", (3, 2, 8, 2), 5, ()),
              ("condensed", (4, 2, 64, 2), 2, ()), ("model", (4, 2, 64, 2), 2, ()), ("stagewise", (3, 2, 70, 2), 3, (1,))]
 
@@ -812,77 +448,23 @@ VJP_CASES = [("condensed", (3, 2, 8, 2), 5, ()), ("model", (3, 2, 8, 2), 5, ()),
 def test_plan_vjp_exports(kind, shape, batch, unsolved):
     """mpcqp_plan_vjp_batch / _vjp_model_batch / _vjp_stagewise_batch with every gradient asked for, then with the nullable ones
     NULL; one item of the long stage-wise case is handed over as unsolved (zeros and its status)."""
-    from qpmpc_amd import autodiff
-    from qpmpc_amd import workloads as W
-
-    _capi, lib, stream = _api()
     nx, nu, N, mk = shape
     w = ltv(910 + N, batch, nx, nu, N, mk, 0.5)
-    bp = W.to_batch_problem(w)
-    B, n, m = batch, N * nu, N * mk
+    B = batch
     U, lam, status = forward_on_cpu(w, unsolved)
-    assert (status == 0).sum() * 2 >= B
-    rng = np.random.default_rng(3)
-    gU, gX = rng.standard_normal((B, n)), rng.standard_normal((B, (N + 1) * nx))
-    dims, nbytes = autodiff._vjp_dims(bp), C.c_size_t(0)
-    ka = max_active_of(lam, status, n)
-    if kind == "condensed":
-        rc = lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), B, C.byref(nbytes))
-    elif kind == "model":
-        rc = lib.mpcqp_plan_vjp_model_workspace_bytes(C.byref(dims), B, C.byref(nbytes))
-    else:
-        rc = lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), B, ka, C.byref(nbytes))
-    assert rc == 0
-    print(f"    vjp {kind} {shape} batch {B}: workspace {nbytes.value} bytes, max_active {ka}")
-    sizes = dict(x0=nx, goal=nx, targets=N * nx, e=m, A=N * nx * nx, B=N * nx * nu, C=N * mk * nx, D=N * mk * nu, w=3)
-    outs = list(sizes)[:4] if kind == "condensed" else list(sizes)
-    L = Launch()
-    add_problem(L, bp)
-    for key, a in (("lam", lam), ("U", U), ("gU", gU), ("gX", gX)):
-        L.add(key, "in", F64, data=a)
-    L.add("status", "in", I32, data=torch.as_tensor(status))
-    for key in outs:
-        L.add("g_" + key, "out", F64, B * sizes[key])
-    L.add("vjp_status", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    cp = arena_problem(L, bp)
-
-    def launch(full):
-        want = outs if full else ["x0"]
-        ptrs = [L.ptr("g_" + k) if k in want else None for k in sizes]
-        head = (C.byref(dims), C.byref(cp), B)
-        tail = (L.ptr("vjp_status"), L.ptr("ws"), nbytes.value, stream())
-        if kind == "condensed":
-            return lambda: lib.mpcqp_plan_vjp_batch(*head, L.ptr("lam"), L.ptr("status"), L.ptr("gU"), L.ptr("gX") if full else None,
-                                                    *ptrs[:4], *tail)
-        res = _capi.VjpModelOut(*ptrs)
-        if kind == "model":
-            return lambda: lib.mpcqp_plan_vjp_model_batch(*head, L.ptr("lam"), L.ptr("status"), L.ptr("U"), L.ptr("gU"),
-                                                          L.ptr("gX") if full else None, C.byref(res), *tail)
-        return lambda: lib.mpcqp_plan_vjp_stagewise_batch(*head, ka, L.ptr("lam"), L.ptr("status"), L.ptr("U"), L.ptr("gU"),
-                                                          L.ptr("gX") if full else None, C.byref(res), *tail)
-
-    z1, z2, f = L.run(Z, launch(True)), L.run(Z, launch(True)), L.run(F, launch(True))
+    p = PlanVjp(kind, shape, w, U, lam, status)
+    L, gU, gX = p.L, p.gU, p.gX
+    print(f"    vjp {kind} {shape} batch {B}: workspace {p.ws_bytes} bytes, max_active {p.ka}")
+    z1, z2, f = L.run(Z, p.call()), L.run(Z, p.call()), L.run(F, p.call())
     for key in z1:
         if key != "ws":
             assert same_bits(z1[key], z2[key]), (key, "run to run under fill Z")
             assert same_bits(z1[key], f[key]), (key, "fill Z against fill F")
-    vst = f["vjp_status"]
-    assert np.array_equal(vst[status != 0], status[status != 0]) and (vst[status == 0] == 0).all(), vst
-    for b in range(B):
-        got = {k: f["g_" + k].reshape(B, -1)[b] for k in outs}
-        if vst[b] != 0:
-            assert all((v == 0).all() for v in got.values()), (b, "an unsolved item's gradients are zeros")
-            continue
-        w1 = AN.single(w, b)
-        ref = AN.vjp(w1, lam[b], gU[b], gX[b]) if kind == "condensed" else AS.stagewise_vjp(w1, lam[b], gU[b], gX[b], U[b])
-        for k in outs:
-            close(got[k], ref[k], (kind, b, k))
+    _, vst = p.check(f, w, "packed")
     # the nullable pointers NULL (gX, every gradient but g_x0): their buffers keep the fill, g_x0 is that of gX = 0
     for byte in (Z, F):
-        part = L.run(byte, launch(False))
-        for k in outs[1:]:
+        part = L.run(byte, p.call(full=False))
+        for k in p.outs[1:]:
             assert holds(part["g_" + k], byte), (k, "was passed as NULL")
         assert np.array_equal(part["vjp_status"], vst)
         if byte == Z:
@@ -891,18 +473,6 @@ def test_plan_vjp_exports(kind, shape, batch, unsolved):
     for b in np.flatnonzero(vst == 0):
         w1 = AN.single(w, b)
         close(part["g_x0"].reshape(B, -1)[b], AN.vjp(w1, lam[b], gU[b], None)["x0"], (kind, b, "x0 without gX"))
-
-
-def _tangents(w, B, T, rng, model):
-    N = int(w["N"])
-    nx, nu, mk = np.asarray(w["x0"]).shape[-1], np.asarray(w["B"]).shape[-1], np.asarray(w["e"]).shape[-1]
-    tan = dict(x0=rng.standard_normal((B, T, nx)), goal=rng.standard_normal((B, T, nx)),
-               targets=rng.standard_normal((B, T, N * nx)), e=rng.standard_normal((B, T, N * mk)))
-    if model:
-        tan.update(A=rng.standard_normal((B, T, N, nx, nx)), B=rng.standard_normal((B, T, N, nx, nu)),
-                   C=rng.standard_normal((B, T, N, mk, nx)), D=rng.standard_normal((B, T, N, mk, nu)),
-                   w=rng.standard_normal((B, T, 3)))
-    return tan
 
 
 JVP_CASES = [(False, False, (3, 2, 8, 2), 5, 1), (False, False, (3, 2, 8, 2), 5, 86),
@@ -916,73 +486,21 @@ def test_plan_jvp_exports(model, stagewise, shape, batch, T):
     """mpcqp_plan_jvp_batch / _jvp_stagewise_batch / _jvp_model_batch / _jvp_model_stagewise_batch: one tangent, and a ragged count
     one past 256 / max(nx, nu) (85 side by side for nx = 3, 12 for nx = 20: two passes over the slots, the second with one
     tangent); max_active as autodiff._max_active counts it; dX and jvp_status NULL next to the full call."""
-    from qpmpc_amd import autodiff
-    from qpmpc_amd import workloads as W
-
-    _capi, lib, stream = _api()
     nx, nu, N, mk = shape
     w = ltv(930 + N, batch, nx, nu, N, mk, 0.5)
-    bp = W.to_batch_problem(w)
-    B, n, m = batch, N * nu, N * mk
+    B = batch
     unsolved = (1,) if N == 70 else ()
     U, lam, status = forward_on_cpu(w, unsolved)
-    assert (status == 0).sum() * 2 >= B
-    tan = _tangents(w, B, T, np.random.default_rng(4), model)
-    dims, nbytes = autodiff._vjp_dims(bp), C.c_size_t(0)
-    ka = max_active_of(lam, status, n)
-    query = {(False, False): lib.mpcqp_plan_jvp_workspace_bytes, (True, False): lib.mpcqp_plan_jvp_model_workspace_bytes,
-             (False, True): lib.mpcqp_plan_jvp_stagewise_workspace_bytes,
-             (True, True): lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes}[(model, stagewise)]
-    extra = (ka, T) if stagewise else (T,)
-    assert query(C.byref(dims), B, *extra, C.byref(nbytes)) == 0
-    print(f"    jvp model {model} stagewise {stagewise} {shape} batch {B} T {T}: workspace {nbytes.value} bytes, max_active {ka}")
-    L = Launch()
-    add_problem(L, bp)
-    L.add("lam", "in", F64, data=lam)
-    L.add("U", "in", F64, data=U)
-    L.add("status", "in", I32, data=torch.as_tensor(status))
-    for key, a in tan.items():
-        L.add("d" + key, "in", F64, data=a.reshape(B, -1))
-    L.add("dU", "out", F64, B * T * n)
-    L.add("dX", "out", F64, B * T * (N + 1) * nx)
-    L.add("jvp_status", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    cp = arena_problem(L, bp)
-    ctan = _capi.Tangents(*[L.ptr("d" + k) for k in ("x0", "goal", "targets", "e")],
-                          *[tan[k][0].size for k in ("x0", "goal", "targets", "e")])
-    mtan = _capi.ModelTangents(*[L.ptr("d" + k) for k in ("A", "B", "C", "D", "w")],
-                               *[tan[k][0].size for k in ("A", "B", "C", "D", "w")]) if model else None
-
-    def launch(full):
-        head = (C.byref(dims), C.byref(cp), B) + ((ka,) if stagewise else ()) + (T, L.ptr("lam"), L.ptr("status"))
-        tail = (L.ptr("dU"), L.ptr("dX") if full else None, L.ptr("jvp_status") if full else None, L.ptr("ws"), nbytes.value,
-                stream())
-        if model:
-            fn = lib.mpcqp_plan_jvp_model_stagewise_batch if stagewise else lib.mpcqp_plan_jvp_model_batch
-            return lambda: fn(*head, L.ptr("U"), C.byref(ctan), C.byref(mtan), *tail)
-        fn = lib.mpcqp_plan_jvp_stagewise_batch if stagewise else lib.mpcqp_plan_jvp_batch
-        return lambda: fn(*head, C.byref(ctan), *tail)
-
-    z1, z2, f = L.run(Z, launch(True)), L.run(Z, launch(True)), L.run(F, launch(True))
+    p = PlanJvp(model, stagewise, shape, w, U, lam, status, _tangents(w, B, T, np.random.default_rng(4), model))
+    L = p.L
+    print(f"    jvp model {model} stagewise {stagewise} {shape} batch {B} T {T}: workspace {p.ws_bytes} bytes, max_active {p.ka}")
+    z1, z2, f = L.run(Z, p.call()), L.run(Z, p.call()), L.run(F, p.call())
     for key in ("dU", "dX", "jvp_status"):
         assert same_bits(z1[key], z2[key]), (key, "run to run under fill Z")
         assert same_bits(z1[key], f[key]), (key, "fill Z against fill F")
-    vst = f["jvp_status"]
-    assert np.array_equal(vst[status != 0], status[status != 0]) and (vst[status == 0] == 0).all(), vst
-    dU, dX = f["dU"].reshape(B, T, -1), f["dX"].reshape(B, T, -1)
     which = range(T) if T <= 3 else (0, T // 2, T - 2, T - 1)  # (the last one is the second pass over the slots)
-    for b in range(B):
-        if vst[b] != 0:
-            assert (dU[b] == 0).all() and (dX[b] == 0).all(), (b, "an unsolved item's tangents are zeros")
-            continue
-        w1 = AN.single(w, b)
-        for t in which:
-            one = {k: v[b, t] for k, v in tan.items()}
-            ref = TM.jvp_model(w1, U[b], lam[b], one) if model else TN.jvp(w1, lam[b], one)
-            close(dU[b, t], ref["U"], (b, t, "dU"))
-            close(dX[b, t], ref["X"], (b, t, "dX"))
-    part = L.run(F, launch(False))
+    p.check(f, w, "packed", which)
+    part = L.run(F, p.call(full=False))
     assert holds(part["dX"], F) and holds(part["jvp_status"], F)
     assert same_bits(part["dU"], f["dU"]), "dX and jvp_status NULL"
 

@@ -17,15 +17,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-8
+
+pytest.importorskip("torch")
+
+from guarded_launch import _torch  # noqa: E402  (needs torch)
+
+TOL = MN.TOL
 NOT_PD = 3
 _REF = {}
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 def _max_grid():

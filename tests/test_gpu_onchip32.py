@@ -18,20 +18,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_memory_discipline as MD  # noqa: E402  (its arena launcher and comparisons; needs torch)
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, _flag  # noqa: E402
 
-# |lam - lam_ref| / (1 + max lam_ref) on the clear problems. Measured on an MI355X over the 54 families: 8.9e-9 for the default
-# route on these problems (the stage-wise kernels; worst on the time-invariant (3, 1, 32, 2) family at 0.05, whose condensed
-# Hessian is the worst conditioned) and 3.4e-10 for the flagged launch (the same family at 0.2). The bound is ten times the
-# default route's worst value (sums of up to 32 terms in another order, one refinement step), never below 1e-9:
-LAM_DEFAULT_ROUTE_WORST = 8.9e-9
-LAM_BOUND = max(1e-9, 10 * LAM_DEFAULT_ROUTE_WORST)
-
-
-def _flag():
-    from qpmpc_amd import _capi
-
-    return _capi.OPT_ON_CHIP_32
+LAM_BOUND, VERDICT_SHAPES = OC.LAM_BOUND, OC.VERDICT_SHAPES
 
 
 _PLANS = {}
@@ -39,13 +29,8 @@ _PLANS = {}
 
 def _solve(key, w, flags=None, **kw):
     """(U, lam, status, iters) of one launch as NumPy arrays, made once per key"""
-    from qpmpc_amd import solve_mpc_batch
-    from qpmpc_amd import workloads as W
-
     if key not in _PLANS:
-        plan = solve_mpc_batch(W.to_batch_problem(w), flags=_flag() if flags is None else flags, return_multipliers=True, **kw)
-        torch.cuda.synchronize()
-        _PLANS[key] = tuple(t.cpu().numpy() for t in (plan.U, plan.multipliers, plan.status, plan.iters))
+        _PLANS[key] = GL.solve_outputs(w, _flag() if flags is None else flags, **kw)
     return _PLANS[key]
 
 
@@ -62,7 +47,7 @@ def _take(w, idx):
 
 def _same_bits(a, b, items_a, items_b, what):
     for x, y, name in zip(a, b, ("U", "lam", "status", "iters")):
-        assert MD.same_bits(x[items_a], y[items_b]), (what, name)
+        assert GL.same_bits(x[items_a], y[items_b]), (what, name)
 
 
 # ---------------------------------------------------------------------------------------------- 1. oracle parity
@@ -97,7 +82,7 @@ def test_oracle_parity(shape, kind, why):
 # ---------------------------------------------------------------------------------------------- 2. multipliers
 def test_multipliers_and_active_sets_on_the_clear_problems():
     """On the clear problems of every family (onchip32_cases.clear: at least half of each per-step family, 34 of 61 at worst),
-    {lam > 0} is the oracle's active set and |lam - lam_ref| / (1 + max lam_ref) <= LAM_BOUND = 8.9e-8: ten times the 8.9e-9
+    {lam > 0} is the oracle's active set and |lam - lam_ref| / (1 + max lam_ref) <= onchip32_cases.LAM_BOUND = 8.9e-8: ten times the 8.9e-9
     measured for the default route on the same problems (the flagged launch measured 3.4e-10). The default route's figure is
     measured again and printed here; the bound is the constant."""
     worst, worst_default = 0.0, 0.0
@@ -139,9 +124,6 @@ def test_neighbour_and_batch_independence_bit_for_bit():
 
 
 # ---------------------------------------------------------------------------------------------- 4. verdicts
-VERDICT_SHAPES = ((3, 1, 24, 2), (4, 2, 16, 2))
-
-
 def _verdict_full(shape):
     return OL.make(shape, "cd", True, 0, OC.LAYOUT_SEED, OC.LAYOUT_MARGIN)[1]
 
@@ -171,45 +153,16 @@ def test_verdicts(shape):
 
 
 # ---------------------------------------------------------------------------------------------- 5. memory discipline
-class _NoWorkspace(MD.Forward):
-    """MD.Forward with the workspace pointer NULL whatever mpcqp_workspace_bytes says for the dimensions (its few lines restated:
-    the outputs in a guarded arena, no "ws" buffer)."""
-
-    def __init__(self, w, dtype=None, pad=0, warm=False, order=None):
-        from qpmpc_amd import workloads as W
-
-        _capi, lib, _ = MD._api()
-        self.bp = bp = W.to_batch_problem(w, dtype=dtype)
-        self.B, self.n, self.m = bp.batch_size, bp.nb_variables, bp.nb_constraints
-        self.dims, self.stagewise, self.max_active, self.pad = bp.dims(), False, 0, pad
-        self.ws_bytes = 0
-        L = self.L = MD.Launch()
-        MD.add_problem(L, bp, pad)
-        L.add("U", "out", bp.dtype, self.B * self.n)
-        L.add("lam", "out", bp.dtype, self.B * self.m)
-        L.add("status", "out", MD.I32, self.B)
-        L.add("iters", "out", MD.I32, self.B)
-        L.add("ws", "scratch", MD.U8, 0)
-        if order is not None:
-            L.add("order", "in", MD.I32, data=torch.as_tensor(np.asarray(order, dtype=np.int32)))
-        if warm:
-            wb = C.c_size_t(0)
-            assert lib.mpcqp_warm_state_bytes(C.byref(self.dims), C.byref(wb)) == 0 and wb.value > 0
-            L.add("warm", "scratch", MD.U8, self.B * wb.value)
-        L.build()
-        self.cp = MD.arena_problem(L, bp, pad)
-
-
 def _discipline(key, case, reference, tol=1e-7):
-    """(a) .. (e) of test_gpu_memory_discipline.discipline() for a case without a workspace"""
+    """(a) .. (e) of guarded_launch.discipline() for a case without a workspace"""
     flags = _flag()
     assert case.L.ptr("ws") is None
-    z1, z2, f = case.run(MD.Z, flags), case.run(MD.Z, flags), case.run(MD.F, flags)
-    MD.equal_outputs(z1, z2, key + ": run to run under fill Z")
-    MD.equal_outputs(z1, f, key + ": fill Z against fill F")
-    nn = case.run(MD.F, flags, lam=False, iters=False)
-    assert MD.holds(nn["lam"], MD.F) and MD.holds(nn["iters"], MD.F), key + ": a NULL output's neighbour was written"
-    MD.equal_outputs(f, nn, key + ": lam and iters NULL", lam=False, iters=False)
+    z1, z2, f = case.run(GL.Z, flags), case.run(GL.Z, flags), case.run(GL.F, flags)
+    GL.equal_outputs(z1, z2, key + ": run to run under fill Z")
+    GL.equal_outputs(z1, f, key + ": fill Z against fill F")
+    nn = case.run(GL.F, flags, lam=False, iters=False)
+    assert GL.holds(nn["lam"], GL.F) and GL.holds(nn["iters"], GL.F), key + ": a NULL output's neighbour was written"
+    GL.equal_outputs(f, nn, key + ": lam and iters NULL", lam=False, iters=False)
     Uo, lamo, sto = reference[:3]
     assert np.array_equal(f["status"] == 0, sto == 0), (f["status"], sto)
     ok = sto == 0
@@ -228,7 +181,7 @@ def test_memory_discipline_without_a_workspace(batch):
     shape, kind, tight = (3, 1, 24, 2), "lean", 0.2
     w = _take(OC.family(shape, kind, tight, False), np.arange(batch))
     ref = tuple(a[:batch] for a in OC.reference(shape, kind, tight, False))
-    _discipline(f"on chip 32, batch {batch}", _NoWorkspace(w), ref)
+    _discipline(f"on chip 32, batch {batch}", Forward(w, workspace=False), ref)
 
 
 # ---------------------------------------------------------------------------------------------- 6. operand layouts
@@ -237,13 +190,13 @@ def test_operand_layouts(layout):
     """Every layout of operand_layouts.LAYOUTS at (3, 1, 24, 2) with C and D rows and a stage cost -- mixed shared and per-step
     operands, the odd-numbered ones with padded batch strides --, in the arena, against the oracle on the materialised problems."""
     w, _ = OC.layout_case(layout)
-    _discipline(f"on chip 32, layout {layout}", _NoWorkspace(w, pad=OL.pads_of(layout)), OC.layout_reference(layout))
+    _discipline(f"on chip 32, layout {layout}", Forward(w, pad=OL.pads_of(layout), workspace=False), OC.layout_reference(layout))
 
 
 # ---------------------------------------------------------------------------------------------- 7. refusals, float32
 def _rc(case, flags, warm_start=0):
     """return code of one launch of a case; the arena's checks run as for any launch (a refused launch writes nothing)"""
-    _capi, lib, stream = MD._api()
+    _capi, lib, stream = GL._api()
     L = case.L
     o = _capi.SolveOpts()
     o.flags = int(flags)
@@ -258,7 +211,7 @@ def _rc(case, flags, warm_start=0):
                                                 L.ptr("status"), L.ptr("iters"), None, 0, stream())
         return 0
 
-    out = L.run(MD.F, call)
+    out = L.run(GL.F, call)
     return got["rc"], out
 
 
@@ -283,10 +236,10 @@ def test_refusals():
     EUNSUPPORTED = -6
     for kw, extra in ((dict(warm=True), 0), (dict(order=np.arange(5)), 0), (dict(), _capi.OPT_TWO_PER_WAVE), (dict(), _capi.OPT_FORCE_LDS),
                       (dict(), _capi.OPT_SEED_VIOLATED)):
-        rc, out = _rc(_NoWorkspace(w, **kw), _flag() | extra)
+        rc, out = _rc(Forward(w, workspace=False, **kw), _flag() | extra)
         assert rc == EUNSUPPORTED, (kw, extra, rc)
-        assert all(MD.holds(out[k], MD.F) for k in ("U", "lam", "status", "iters"))
-    rc, out = _rc(_NoWorkspace(w), _flag())  # (the same call without any of them runs)
+        assert all(GL.holds(out[k], GL.F) for k in ("U", "lam", "status", "iters"))
+    rc, out = _rc(Forward(w, workspace=False), _flag())  # (the same call without any of them runs)
     assert rc == 0 and (out["status"] == 0).all()
 
 

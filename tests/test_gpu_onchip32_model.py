@@ -4,15 +4,13 @@ and L^-T read from the factored model (the reference's build-once usage: MPCQP o
 update_constraint_vector per period, qpmpc/mpc_qp.py:129-163). The inputs are those of tests/onchip32_model_cases.py, held to
 their conditions on the C oracle by tests/test_onchip32_model_cpu.py.
 
-Every launch goes through ctypes with its buffers in the guarded arena of tests/arena.py, as
-tests/test_gpu_operand_layouts.py::test_shared_model_solves does (its few lines restated in ModelCase); the factored model is a
-read-only buffer there, so a solve that wrote into it is named.
+Every launch goes through ctypes with its buffers in the guarded arena of tests/arena.py (ModelCase of tests/guarded_launch.py,
+the model factored outside the arena): the factored model is a read-only buffer there, so a solve that wrote into it is named.
 
 Tolerances (float64): plans |u - u_ref|_inf <= 1e-7 max(1, |u_ref|_inf) against the C oracle on the materialised problems
-(test_gpu_memory_discipline.against_oracle); model against fused 1e-8 max(1, |u|_inf) (tests/test_gpu_quad.py holds its model mode
-to the same); multipliers test_gpu_onchip32.LAM_BOUND on the clear problems; the walking loop 1e-9 against the rebuilding loop and
-1e-7 against the oracle loop (tests/test_gpu_parity.py); gradients test_gpu_model_diff.TOL."""
-import ctypes as C
+(guarded_launch.against_oracle); model against fused 1e-8 max(1, |u|_inf) (tests/test_gpu_quad.py holds its model mode
+to the same); multipliers onchip32_cases.LAM_BOUND on the clear problems; the walking loop 1e-9 against the rebuilding loop and
+1e-7 against the oracle loop (tests/test_gpu_parity.py); gradients model_adjoint_np.TOL."""
 import os
 
 import numpy as np
@@ -27,106 +25,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_memory_discipline as MD  # noqa: E402  (its arena launcher and comparisons; needs torch)
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import ModelCase, _flag  # noqa: E402
 
-Z, F, F64, F32, I32, U8 = MD.Z, MD.F, MD.F64, MD.F32, MD.I32, MD.U8
-EUNSUPPORTED = -6
+Z, F, F64, F32, I32, U8 = GL.Z, GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-DEFAULT_GOLDEN_VARIANT = 3  # (the first variant that shares e: the export without bounds runs on it)
-FUSED_GOLDEN = (((3, 1, 24, 2), "lean", 0.05, False), ((4, 2, 16, 2), "general", 0.2, False))
-
-
-def _flag():
-    from qpmpc_amd import _capi
-
-    return _capi.OPT_ON_CHIP_32
-
-
-class ModelCase:
-    """A factored model and the per-problem operands of one shared-model workload `w` (A, B, C, D shared; x0, goal, targets, e
-    with 1 or B rows, `pad` elements past the packed batch stride) in a guarded arena. The model is factored once, outside the
-    arena, from the pseudo-problems of include/mpcqp.h (bounds: w["e_model"], else the first problem's) and copied in as a
-    read-only buffer. The operands named in `inout` are reloaded before every run and may be rewritten inside a call
-    (tests/test_gpu_streams.py)."""
-
-    def __init__(self, w, pad=None, dtype=F64, order=None, warm=False, wt=None, inout=()):
-        from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
-
-        _, lib, stream = MD._api()
-        pad = pad or {}
-        N = int(w["N"])
-        nx, nu, mk = w["A"].shape[-1], w["B"].shape[-1], w["e"].shape[-1]
-        self.B = B = max(w[k].shape[0] for k in ("x0", "goal", "targets", "e") if w.get(k) is not None)
-        self.n, self.m, self.dtype = N * nu, N * mk, dtype
-        nb = 1 + 2 * nx + N * nx
-        x0, goal, tgt = torch.zeros((nb, nx), dtype=dtype), torch.zeros((nb, nx), dtype=dtype), torch.zeros((nb, N * nx), dtype=dtype)
-        x0[1:1 + nx], goal[1 + nx:1 + 2 * nx], tgt[1 + 2 * nx:] = torch.eye(nx), torch.eye(nx), torch.eye(N * nx)
-        pseudo = BatchMPCProblem(w["A"], w["B"], w["C"], w["D"], w.get("e_model", w["e"][:1]), N, w["wt"] if wt is None else wt, w["wx"], w["wu"],
-                                 x0, goal_state=goal, target_states=tgt if w["wx"] is not None else None, dtype=dtype)
-        self.mdims = pseudo.dims()
-        qp = BatchMPCQP(pseudo, keep_propagators=False)
-        mbytes = C.c_size_t(0)
-        assert lib.mpcqp_model_bytes(C.byref(self.mdims), C.byref(mbytes)) == 0
-        model = torch.zeros((mbytes.value,), dtype=U8, device="cuda")
-        rc = lib.mpcqp_factor_model(C.byref(self.mdims), qp.P[0].data_ptr(), qp.G[0].data_ptr(), qp.q.data_ptr(), qp.h.data_ptr(),
-                                    model.data_ptr(), mbytes.value, stream())
-        assert rc == 0, rc
-        torch.cuda.synchronize()
-        L = self.L = MD.Launch()
-        L.add("model", "in", U8, data=model)
-        ops = {}
-        for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", self.m)):
-            if w.get(key) is None:
-                ops[key] = None
-                continue
-            rows = np.asarray(w[key]).reshape(w[key].shape[0], -1)
-            assert rows.shape[1] == width and rows.shape[0] in (1, B)
-            stride = width + int(pad.get(key, 0)) if rows.shape[0] > 1 else 0
-            L.add(key, "inout" if key in inout else "in", dtype, data=rows, stride=stride or None)
-            ops[key] = (stride, mk if key == "e" else 0)
-        L.add("U", "out", dtype, B * self.n)
-        L.add("lam", "out", dtype, B * self.m)
-        L.add("status", "out", I32, B)
-        L.add("iters", "out", I32, B)
-        if order is not None:
-            L.add("order", "in", I32, data=torch.as_tensor(np.asarray(order, dtype=np.int32)))
-        if warm:
-            L.add("warm", "scratch", U8, B * 4096)
-        L.build()
-        self.ops = {key: (_capi.Operand(None, 0, 0) if v is None else _capi.Operand(L.ptr(key), v[0], v[1])) for key, v in ops.items()}
-
-    def run(self, byte, flags=0, bounds=True, lam=True, iters=True, max_iter=0, expect=0):
-        """one launch under fill `byte`: the arena's checks (guards intact, read-only buffers -- the model among them -- unchanged)
-        and the return code `expect`; the outputs, U [B, n] and lam [B, m]"""
-        _capi, lib, stream = MD._api()
-        L = self.L
-        o = _capi.SolveOpts()
-        o.flags, o.max_iter = int(flags), int(max_iter)
-        if L.has("order"):
-            o.order = L.ptr("order")
-        if L.has("warm"):
-            o.warm_state, o.warm_state_bytes = L.ptr("warm"), L.nbytes("warm")
-        ops = self.ops
-        tail = (C.byref(ops["x0"]), C.byref(ops["goal"]), C.byref(ops["targets"]), self.B, C.byref(o), L.ptr("U"),
-                L.ptr("lam") if lam else None, L.ptr("status"), L.ptr("iters") if iters else None, stream())
-        got = {}
-
-        def call():
-            if bounds:
-                got["rc"] = lib.mpcqp_solve_model_bounds_batch(C.byref(self.mdims), L.ptr("model"), C.byref(ops["e"]), *tail)
-            else:
-                got["rc"] = lib.mpcqp_solve_model_batch(C.byref(self.mdims), L.ptr("model"), *tail)
-            return 0
-
-        out = L.run(byte, call)
-        assert got["rc"] == expect, (got["rc"], expect)
-        out["U"], out["lam"] = out["U"].reshape(self.B, self.n), out["lam"].reshape(self.B, self.m)
-        return out
-
-    def refused(self, flags=0, bounds=True):
-        """a launch that must return MPCQP_EUNSUPPORTED and write no output"""
-        out = self.run(F, flags, bounds, expect=EUNSUPPORTED)
-        assert all(MD.holds(out[k], F) for k in ("U", "lam", "status", "iters")), "a refused launch wrote an output"
+DEFAULT_GOLDEN_VARIANT, FUSED_GOLDEN = MC.DEFAULT_GOLDEN_VARIANT, MC.FUSED_GOLDEN
 
 
 _CASES = {}
@@ -146,7 +50,7 @@ def _many(count):
 
 def _same_bits(a, b, items_a, items_b, what):
     for name in ("U", "lam", "status", "iters"):
-        assert MD.same_bits(a[name][items_a], b[name][items_b]), (what, name)
+        assert GL.same_bits(a[name][items_a], b[name][items_b]), (what, name)
 
 
 def default_route_outputs():
@@ -157,12 +61,7 @@ def default_route_outputs():
 
 def fused_outputs(fam):
     """(U, lam, status, iters) of the flagged fused launch on a family of onchip32_cases"""
-    from qpmpc_amd import solve_mpc_batch
-    from qpmpc_amd import workloads as W
-
-    plan = solve_mpc_batch(W.to_batch_problem(OC.family(*fam)), flags=_flag(), return_multipliers=True)
-    torch.cuda.synchronize()
-    return tuple(t.cpu().numpy() for t in (plan.U, plan.multipliers, plan.status, plan.iters))
+    return GL.solve_outputs(OC.family(*fam), _flag())
 
 
 # ---------------------------------------------------------------------------------------------- 1. parity and layouts
@@ -181,7 +80,7 @@ def test_parity_and_layouts(shape, why):
             launches.append(("model bounds, flag", case.run(F, _flag(), bounds=False)))
         for what, out in launches:
             assert (out["status"] == 0).all(), (what, variant, out["status"])
-            ok = MD.against_oracle(f"model {shape} {variant}", full, out, 1e-7)
+            ok = GL.against_oracle(f"model {shape} {variant}", full, out, 1e-7)
             assert ok.all() and not np.isnan(out["U"]).any() and not np.isnan(out["lam"]).any()
         _same_bits(plain, flagged, slice(None), slice(None), f"variant {variant}: flag on the bounds export")
 
@@ -194,7 +93,7 @@ def test_default_route_without_bounds_did_not_move():
     gold = np.load(os.path.join(GOLDEN, "onchip32_model_default_parent.npz"))
     assert (out["status"] == 0).all()
     for name in ("U", "lam", "status", "iters"):
-        assert MD.same_bits(out[name], gold[name]), name
+        assert GL.same_bits(out[name], gold[name]), name
 
 
 # ---------------------------------------------------------------------------------------------- 2. memory discipline
@@ -205,11 +104,11 @@ def test_memory_discipline(batch):
     written next to lam and iters when they are NULL, plans within 1e-7 of the oracle."""
     case = _many(batch)
     z1, z2, f = case.run(Z), case.run(Z), case.run(F)
-    MD.equal_outputs(z1, z2, f"batch {batch}: run to run under fill Z")
-    MD.equal_outputs(z1, f, f"batch {batch}: fill Z against fill F")
+    GL.equal_outputs(z1, z2, f"batch {batch}: run to run under fill Z")
+    GL.equal_outputs(z1, f, f"batch {batch}: fill Z against fill F")
     nn = case.run(F, lam=False, iters=False)
-    assert MD.holds(nn["lam"], F) and MD.holds(nn["iters"], F), "a NULL output's neighbour was written"
-    MD.equal_outputs(f, nn, f"batch {batch}: lam and iters NULL", lam=False, iters=False)
+    assert GL.holds(nn["lam"], F) and GL.holds(nn["iters"], F), "a NULL output's neighbour was written"
+    GL.equal_outputs(f, nn, f"batch {batch}: lam and iters NULL", lam=False, iters=False)
     Uo, _, sto, _ = MC.many_reference(batch)
     assert (sto == 0).all() and (f["status"] == 0).all(), (f["status"], sto)
     err = float((np.abs(f["U"] - Uo) / np.maximum(1.0, np.abs(Uo).max(axis=1, keepdims=True))).max())
@@ -269,10 +168,9 @@ def test_verdicts(shape):
 def test_model_against_fused(shape):
     """Variant 0: the model launch and solve_mpc_batch(flags=OPT_ON_CHIP_32) on the materialised problems give equal statuses,
     plans within 1e-8 max(1, |u|_inf) and, on the clear problems (onchip32_cases.clear's rule), multipliers within
-    test_gpu_onchip32.LAM_BOUND of each other and of the oracle."""
+    onchip32_cases.LAM_BOUND of each other and of the oracle."""
     from qpmpc_amd import solve_mpc_batch
     from qpmpc_amd import workloads as W
-    from test_gpu_onchip32 import LAM_BOUND
 
     full = MC.case(shape, 0)[1]
     out = _case(shape, 0).run(F)
@@ -290,7 +188,7 @@ def test_model_against_fused(shape):
     print(f"    {shape}: model vs fused plan {err:.2e}; multipliers on {int(clear.sum())} clear items: vs fused {dev_f:.2e}, vs oracle {dev_o:.2e}")
     assert err <= 1e-8
     assert np.array_equal(out["lam"][clear] > 0, lamo[clear] > 0)
-    assert dev_f <= LAM_BOUND and dev_o <= LAM_BOUND
+    assert dev_f <= OC.LAM_BOUND and dev_o <= OC.LAM_BOUND
 
 
 # ---------------------------------------------------------------------------------------------- 6. the walking loop
@@ -336,7 +234,7 @@ def test_fused_mode_bit_for_bit_the_parent(fam):
     gold = np.load(os.path.join(GOLDEN, "onchip32_fused_parent.npz"))
     tag = "x".join(str(v) for v in fam[0])
     for name, got in zip(("U", "lam", "status", "iters"), fused_outputs(fam)):
-        assert MD.same_bits(got, gold[f"{name}_{tag}"]), (fam, name)
+        assert GL.same_bits(got, gold[f"{name}_{tag}"]), (fam, name)
 
 
 # ---------------------------------------------------------------------------------------------- 8. refusals
@@ -378,13 +276,13 @@ def test_refusals():
 # ---------------------------------------------------------------------------------------------- 9. derivatives, the Python layer
 def test_derivatives_and_the_python_layer():
     """SharedModel.solve_diff with bounds per problem at (3, 1, 24, 2), x0 and e requiring grad: the gradients of a fixed random
-    linear functional of (U, X) agree with solve_mpc_batch_diff's on the clear items within test_gpu_model_diff.TOL =
+    linear functional of (U, X) agree with solve_mpc_batch_diff's on the clear items within model_adjoint_np.TOL =
     1e-8 max(1, |ref|_inf); SharedModel.solve(..., ineq_vector=e) returns the plan of prepare(problem_for(..., e=e)), and
     flags=OPT_ON_CHIP_32 reaches the launch (a model without bounds per problem solved by the flagged route equals the ctypes
     launch bit for bit)."""
     from qpmpc_amd import SharedModel, solve_mpc_batch_diff
     from qpmpc_amd import workloads as W
-    from test_gpu_model_diff import TOL
+    from model_adjoint_np import TOL
 
     shape = MC.PLAIN
     nx, nu, N, mk = shape
@@ -428,7 +326,7 @@ def test_derivatives_and_the_python_layer():
     flagged = m3.solve(bp3.initial_state, bp3.goal_state, bp3.target_states, return_multipliers=True, flags=_flag())
     torch.cuda.synchronize()
     out = _case(shape, 3).run(F, _flag(), bounds=False)
-    assert MD.same_bits(flagged.U.cpu().numpy(), out["U"]) and np.array_equal(flagged.iters.cpu().numpy(), out["iters"])
+    assert GL.same_bits(flagged.U.cpu().numpy(), out["U"]) and np.array_equal(flagged.iters.cpu().numpy(), out["iters"])
     from qpmpc_amd import _capi
     from qpmpc_amd.exceptions import BackendError
 

@@ -2,7 +2,7 @@
 variables and 64 rows on chip, two problems per wavefront, no workspace (replacing qpsolvers.solve_problem at
 qpmpc/solve_mpc.py:43). The inputs are those of tests/onchip32_qp_cases.py, held to their conditions on the C oracle by
 tests/test_onchip32_qp_cpu.py. Every launch of the export goes through ctypes in the guarded arena of
-tests/test_gpu_memory_discipline.py, the workspace pointer NULL.
+tests/guarded_launch.py (QPs), the workspace pointer NULL.
 
 Tolerances (float64): |x - x_ref|_inf <= 1e-7 max(1, |x_ref|_inf) against the C oracle, the project's bound for float64 dense QPs
 (verdict_cases.DENSE_SIZES), and the same bound between two routes; multipliers on the clear items within 1e-7 (1 + max lam_ref)."""
@@ -18,74 +18,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_memory_discipline as MD  # noqa: E402  (its arena launcher and comparisons; needs torch)
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import EUNSUPPORTED, QPs, _flag  # noqa: E402
 
-EUNSUPPORTED = -6
 OUTS = ("U", "lam", "status", "iters")
-
-
-def _flag():
-    from qpmpc_amd import _capi
-
-    return _capi.OPT_ON_CHIP_32
-
-
-class QPs:
-    """The buffers of one mpcqp_solve_batch call in a guarded arena: P, q, G, h read-only (those named in `inout` reloaded before
-    every run and writable), x, lam, status, iters filled before every run, no workspace. m = 0: no G, h, lam."""
-
-    def __init__(self, P, q, G, h, dtype=MD.F64, inout=(), order=None, warm=False):
-        self.B, self.n = q.shape
-        self.m = 0 if G is None else G.shape[1]
-        self.dtype = dtype
-        L = self.L = MD.Launch()
-        for key, a in (("P", P), ("q", q), ("G", G), ("h", h)):
-            if a is not None and a.size:
-                L.add(key, "inout" if key in inout else "in", dtype, data=np.array(a).reshape(self.B, -1))  # (a writable copy)
-        L.add("U", "out", dtype, self.B * self.n)
-        L.add("lam", "out", dtype, self.B * self.m)
-        L.add("status", "out", MD.I32, self.B)
-        L.add("iters", "out", MD.I32, self.B)
-        if order is not None:
-            L.add("order", "in", MD.I32, data=torch.as_tensor(np.asarray(order, dtype=np.int32)))
-        if warm:
-            L.add("warm", "scratch", MD.U8, self.B * 4096)
-        L.build()
-
-    def c_call(self, flags, lam=True, iters=True, status=True, max_iter=0, stream=None):
-        """the C call on the arena's buffers; its return code"""
-        _capi, lib, cur = MD._api()
-        L = self.L
-        o = _capi.SolveOpts()
-        o.flags, o.max_iter = int(flags), int(max_iter)
-        if L.has("order"):
-            o.order = L.ptr("order")
-        if L.has("warm"):
-            o.warm_state, o.warm_state_bytes, o.warm_start = L.ptr("warm"), L.nbytes("warm"), 0
-        code = _capi.F64 if self.dtype == MD.F64 else _capi.F32
-        return lib.mpcqp_solve_batch(self.n, self.m, code, L.ptr("P"), L.ptr("q"), L.ptr("G"), L.ptr("h"), self.B, C.byref(o),
-                                     L.ptr("U"), L.ptr("lam") if lam else None, L.ptr("status") if status else None,
-                                     L.ptr("iters") if iters else None, None, 0, cur() if stream is None else stream)
-
-    def shaped(self, out):
-        out["U"] = out["U"].reshape(self.B, self.n)
-        if "lam" in out:
-            out["lam"] = out["lam"].reshape(self.B, self.m)
-        return out
-
-    def run(self, byte, flags, **kw):
-        return self.shaped(self.L.run(byte, lambda: self.c_call(flags, **kw)))
-
-    def rc(self, flags, **kw):
-        """(return code, outputs) of a launch that may be refused; the arena's checks run as for any launch"""
-        got = {}
-
-        def call():
-            got["rc"] = self.c_call(flags, **kw)
-            return 0
-
-        out = self.L.run(MD.F, call)
-        return got["rc"], out
 
 
 _CASES, _RUNS = {}, {}
@@ -100,7 +36,7 @@ def _case(n, m):
 def _flagged(n, m):
     """outputs of the flagged launch of a size under fill 0xFF, made once"""
     if (n, m) not in _RUNS:
-        _RUNS[(n, m)] = _case(n, m).run(MD.F, _flag())
+        _RUNS[(n, m)] = _case(n, m).run(GL.F, _flag())
     return _RUNS[(n, m)]
 
 
@@ -110,7 +46,7 @@ def _rel(x, ref):
 
 def _same_item(a, i, b, j, what):
     for k in OUTS:
-        assert MD.same_bits(a[k][i], b[k][j]), (what, k, i, j)
+        assert GL.same_bits(a[k][i], b[k][j]), (what, k, i, j)
 
 
 # ---------------------------------------------------------------------------------------------- 1. parity
@@ -121,9 +57,9 @@ def test_oracle_parity_and_memory_discipline(size, why):
     and status NULL the other outputs keep their bits and the NULL ones their fill; guards and operands intact (Launch.run)."""
     n, m = size
     c = _case(n, m)
-    z1, z2, f = c.run(MD.Z, _flag()), c.run(MD.Z, _flag()), _flagged(n, m)
-    MD.equal_outputs(z1, z2, f"{size}: run to run under fill Z")
-    MD.equal_outputs(z1, f, f"{size}: fill Z against fill F")
+    z1, z2, f = c.run(GL.Z, _flag()), c.run(GL.Z, _flag()), _flagged(n, m)
+    GL.equal_outputs(z1, z2, f"{size}: run to run under fill Z")
+    GL.equal_outputs(z1, f, f"{size}: fill Z against fill F")
     xo, lamo, sto, ito = QC.reference(n, m)
     assert np.array_equal(f["status"], VC.MIXED_STATUS), f["status"]
     ok = sto == 0
@@ -136,13 +72,13 @@ def test_oracle_parity_and_memory_discipline(size, why):
     assert err <= QC.TOL and dev <= QC.TOL, (err, dev)
     assert np.array_equal(f["lam"][clear] > 0, lamo[clear] > 0)
     assert (f["iters"] >= 0).all() and (f["iters"] <= 10 * (n + m) + 10).all()
-    nn = c.run(MD.F, _flag(), lam=False, iters=False, status=False)
-    assert MD.holds(nn["lam"], MD.F) and MD.holds(nn["iters"], MD.F) and MD.holds(nn["status"], MD.F)
-    bits_kept = [b for b in range(c.B) if not MD.same_bits(nn["U"][b], f["U"][b])]
+    nn = c.run(GL.F, _flag(), lam=False, iters=False, status=False)
+    assert GL.holds(nn["lam"], GL.F) and GL.holds(nn["iters"], GL.F) and GL.holds(nn["status"], GL.F)
+    bits_kept = [b for b in range(c.B) if not GL.same_bits(nn["U"][b], f["U"][b])]
     assert not bits_kept, (size, "x differs with lam, iters and status NULL", bits_kept)
-    only_lam = c.run(MD.F, _flag(), lam=False)
-    assert MD.holds(only_lam["lam"], MD.F)
-    MD.equal_outputs(f, only_lam, f"{size}: lam NULL", lam=False)
+    only_lam = c.run(GL.F, _flag(), lam=False)
+    assert GL.holds(only_lam["lam"], GL.F)
+    GL.equal_outputs(f, only_lam, f"{size}: lam NULL", lam=False)
 
 
 # ---------------------------------------------------------------------------------------------- 2. a problem's bits are its own
@@ -153,11 +89,11 @@ def test_a_problems_bits_are_its_own():
     ref = _flagged(n, m)
     P, q, G, h = QC.qps(n, m)
     B = len(q)
-    rev = QPs(P[::-1].copy(), q[::-1].copy(), G[::-1].copy(), h[::-1].copy()).run(MD.F, _flag())
+    rev = QPs(P[::-1].copy(), q[::-1].copy(), G[::-1].copy(), h[::-1].copy()).run(GL.F, _flag())
     for b in range(B):
         _same_item(ref, b, rev, B - 1 - b, "reversed")
     for b in range(B):
-        one = QPs(P[b:b + 1], q[b:b + 1], G[b:b + 1], h[b:b + 1]).run(MD.F, _flag())
+        one = QPs(P[b:b + 1], q[b:b + 1], G[b:b + 1], h[b:b + 1]).run(GL.F, _flag())
         _same_item(ref, b, one, 0, "alone")
 
 
@@ -166,7 +102,7 @@ def test_indefinite_item():
     """P[5][5] -= 50 on item 3 of (24, 48): status 3, iters 0, zeros (the oracle says (3, 0)); every other item keeps its bits"""
     n, m = 24, 48
     ref = _flagged(n, m)
-    out = QPs(*QC.indefinite(n, m)).run(MD.F, _flag())
+    out = QPs(*QC.indefinite(n, m)).run(GL.F, _flag())
     b = QC.INDEFINITE_ITEM
     assert out["status"][b] == 3 and out["iters"][b] == 0 and (out["U"][b] == 0).all() and (out["lam"][b] == 0).all()
     for i in range(len(ref["status"])):
@@ -183,7 +119,7 @@ def test_iteration_limit():
     lo, hi = np.flatnonzero(ref["iters"] <= k), np.flatnonzero(ref["iters"] > k)
     print(f"    iters {ref['iters'].tolist()}, limit {k}: {len(lo)} at or below, {len(hi)} above")
     assert k >= 1 and len(lo) >= 2 and len(hi) >= 2
-    lim = _case(n, m).run(MD.F, _flag(), max_iter=k)
+    lim = _case(n, m).run(GL.F, _flag(), max_iter=k)
     for i in lo:
         _same_item(ref, i, lim, i, "at or below the limit")
     assert (lim["status"][hi] == 1).all() and (lim["iters"][hi] == k).all(), (lim["status"], lim["iters"])
@@ -194,7 +130,7 @@ def test_iteration_limit():
 def _refused(case, flags, what):
     rc, out = case.rc(flags)
     assert rc == EUNSUPPORTED, (what, rc)
-    assert all(MD.holds(out[k], MD.F) for k in out), (what, "a refused launch wrote an output")
+    assert all(GL.holds(out[k], GL.F) for k in out), (what, "a refused launch wrote an output")
 
 
 def test_refusals_write_nothing():
@@ -204,11 +140,11 @@ def test_refusals_write_nothing():
 
     rng = np.random.default_rng(11)
     for n, m in ((33, 10), (10, 65)):
-        _refused(QPs(*MD._dense_qps(rng, 3, n, m)), _flag(), (n, m))
-    P, q, G, h = MD._dense_qps(rng, 3, 24, 48)
+        _refused(QPs(*GL._dense_qps(rng, 3, n, m)), _flag(), (n, m))
+    P, q, G, h = GL._dense_qps(rng, 3, 24, 48)
     _refused(QPs(P, q, None, None), _flag(), "m = 0")
     P, q, G, h = QC.qps(24, 48)
-    _refused(QPs(P, q, G, h, dtype=MD.F32), _flag(), "float32")
+    _refused(QPs(P, q, G, h, dtype=GL.F32), _flag(), "float32")
     _refused(QPs(P, q, G, h, order=np.arange(len(q))), _flag(), "order")
     _refused(QPs(P, q, G, h, warm=True), _flag(), "warm_state")
     c = _case(24, 48)
@@ -238,7 +174,7 @@ def test_flagged_and_default_route_agree(size):
     # ... and the Python layer's flagged call is the arena's launch
     xf, lamf, stf, itf = solve_qp_batch(P, q, G, h, return_multipliers=True, flags=_flag())
     torch.cuda.synchronize()
-    assert MD.same_bits(xf.cpu().numpy(), f["U"]) and np.array_equal(stf.cpu().numpy(), f["status"])
+    assert GL.same_bits(xf.cpu().numpy(), f["U"]) and np.array_equal(stf.cpu().numpy(), f["status"])
     assert np.array_equal(itf.cpu().numpy(), f["iters"])
 
 
@@ -277,11 +213,11 @@ def test_side_stream_capture_and_replay():
     s = torch.cuda.Stream()
     handle = C.c_void_p(s.cuda_stream)
     ref = _flagged(n, m)
-    side = c.run(MD.F, _flag(), stream=handle)
+    side = c.run(GL.F, _flag(), stream=handle)
     for k in OUTS:
-        assert MD.same_bits(side[k], ref[k]), ("side stream", k)
-    flipped = QPs(P, -q, G, h).run(MD.F, _flag())
-    assert not MD.same_bits(flipped["U"], ref["U"])
+        assert GL.same_bits(side[k], ref[k]), ("side stream", k)
+    flipped = QPs(P, -q, G, h).run(GL.F, _flag())
+    assert not GL.same_bits(flipped["U"], ref["U"])
     g, rcs = torch.cuda.CUDAGraph(), []
     torch.cuda.synchronize()
     with torch.cuda.graph(g, stream=s):
@@ -297,8 +233,8 @@ def test_side_stream_capture_and_replay():
         g.replay()
         return 0
 
-    first = c.shaped(c.L.run(MD.F, replay))
-    second = c.shaped(c.L.run(MD.F, negate_and_replay))
+    first = c.shaped(c.L.run(GL.F, replay))
+    second = c.shaped(c.L.run(GL.F, negate_and_replay))
     for k in OUTS:
-        assert MD.same_bits(first[k], ref[k]), ("first replay", k)
-        assert MD.same_bits(second[k], flipped[k]), ("second replay, q negated in place", k)
+        assert GL.same_bits(first[k], ref[k]), ("first replay", k)
+        assert GL.same_bits(second[k], flipped[k]), ("second replay, q negated in place", k)

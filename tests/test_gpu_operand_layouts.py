@@ -8,7 +8,7 @@ tests/operand_layouts.py holds the layouts (LAYOUTS: every operand in every form
 padded by a different amount per operand, PADS), the generator and the routes; tests/test_operand_layouts_cpu.py shows that
 every case has nine solvable problems of which at least six have a binding row, and that any two blocks of an operand differ.
 
-Each launch has its operands in the guarded arena of tests/test_gpu_memory_discipline.py in the STORED layout and runs once under
+Each launch has its operands in the guarded arena of tests/guarded_launch.py in the STORED layout and runs once under
 the all-0xFF fill: padding and guards hold NaN, so a read into the padding poisons the plan and an overrun is named. The
 reference always sees the MATERIALISED problems ([B, N, ...] operands), so the oracle's own stride handling is not what vouches
 for a kernel's. Bounds are those of tests/test_gpu_memory_discipline.py: 1e-7 relative for float64 plans, 1e-3 for float32 ones
@@ -30,34 +30,22 @@ import os
 import numpy as np
 import pytest
 
-import adjoint_np as AN
-import adjoint_stagewise_np as AS
 import operand_layouts as OL
-import tangent_model_np as TM
-import tangent_np as TN
-import test_gpu_memory_discipline as MD
-from test_gpu_memory_discipline import Forward, Launch, against_oracle, close
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, Launch, ModelCase, against_oracle, plan_jvp, plan_vjp  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
 
-F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
+F, F64, F32, I32, U8 = GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 ELAYOUT = -4
 NL = len(OL.LAYOUTS)
 
 # (route, layout) -> the code that refuses it. A skip is never silent, and no route may skip more than a third of the layouts.
 SKIPS = {}
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 # ---------------------------------------------------------------------------------------------- forward: route x layout
@@ -102,7 +90,7 @@ def test_forward_route_layout(route, layout):
     case = Forward(w, dtype=F32 if r["f32"] else None, stagewise=r["stagewise"], pad=OL.pads_of(layout))
     assert case.B == OL.BATCH
     out = case.run(F, _flags(r["flags"]))
-    Uo, _, sto = MD.oracle_of(repr(key), full)
+    Uo, _, sto = GL.oracle_of(repr(key), full)
     assert (sto == 0).all(), sto
     scale = np.maximum(1.0, np.abs(Uo).max(axis=1, keepdims=True))
     err = float((np.abs(out["U"].astype(np.float64) - Uo) / scale).max())
@@ -119,69 +107,24 @@ def test_forward_route_layout(route, layout):
 def test_shared_model_solves(shape, variant):
     """mpcqp_solve_model_batch and _bounds_batch, two and four per wavefront, 9 problems that share A, B, C, D (per step): x0, goal,
     targets and (for the bounds export) e per problem or shared, packed and padded, against the oracle on the materialised
-    problems at 1e-7. The export without bounds takes e from the model, so it runs where the variant shares e."""
-    from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
+    problems at 1e-7. The export without bounds takes e from the model, so it runs where the variant shares e. The model is
+    factored in the arena before every solve (ModelCase, factor_in_arena)."""
+    from qpmpc_amd import _capi
 
-    _, lib, stream = MD._api()
     v = OL.MODEL_VARIANTS[variant]
-    pad = OL.model_pads(variant)
     nx, nu, N, mk = shape
     w, full = OL.model_case(shape, variant)
-    B, n, m = OL.BATCH, N * nu, N * mk
-    # the pseudo-problems of include/mpcqp.h (x0 = goal = targets = 0, then unit vectors), condensed by the library
-    nb = 1 + 2 * nx + N * nx
-    x0, goal, tgt = torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, N * nx), dtype=F64)
-    x0[1:1 + nx], goal[1 + nx:1 + 2 * nx], tgt[1 + 2 * nx:] = torch.eye(nx), torch.eye(nx), torch.eye(N * nx)
-    pseudo = BatchMPCProblem(w["A"], w["B"], w["C"], w["D"], w["e"][:1], N, w["wt"], w["wx"], w["wu"], x0, goal_state=goal,
-                             target_states=tgt)
-    mdims = pseudo.dims()
-    qp = BatchMPCQP(pseudo, keep_propagators=False)
-    torch.cuda.synchronize()
-    mbytes = C.c_size_t(0)
-    assert lib.mpcqp_model_bytes(C.byref(mdims), C.byref(mbytes)) == 0
-    L = Launch()
-    L.add("P", "in", F64, data=qp.P[0].reshape(1, -1))
-    L.add("G", "in", F64, data=qp.G[0].reshape(1, -1))
-    L.add("qb", "in", F64, data=qp.q.reshape(1, -1))
-    L.add("hb", "in", F64, data=qp.h.reshape(1, -1))
-    L.add("model", "scratch", U8, mbytes.value)
-    ops = {}
-    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", m)):
-        rows = w[key].reshape(w[key].shape[0], -1)
-        assert rows.shape == (B if v[key] == "b" else 1, width)
-        stride = width + pad[key] if rows.shape[0] > 1 else 0
-        L.add(key, "in", F64, data=rows, stride=stride or None)
-        ops[key] = (stride, mk if key == "e" else 0)
-    L.add("U", "out", F64, B * n)
-    L.add("lam", "out", F64, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.build()
-    ops = {key: _capi.Operand(L.ptr(key), bs, ks) for key, (bs, ks) in ops.items()}
-
-    def launch(flags, bounds):
-        o = _capi.SolveOpts()
-        o.flags = flags
-
-        def go():
-            rc = lib.mpcqp_factor_model(C.byref(mdims), L.ptr("P"), L.ptr("G"), L.ptr("qb"), L.ptr("hb"), L.ptr("model"),
-                                        mbytes.value, stream())
-            if rc:
-                return rc
-            tail = (C.byref(ops["x0"]), C.byref(ops["goal"]), C.byref(ops["targets"]), B, C.byref(o), L.ptr("U"), L.ptr("lam"),
-                    L.ptr("status"), L.ptr("iters"), stream())
-            if bounds:
-                return lib.mpcqp_solve_model_bounds_batch(C.byref(mdims), L.ptr("model"), C.byref(ops["e"]), *tail)
-            return lib.mpcqp_solve_model_batch(C.byref(mdims), L.ptr("model"), *tail)
-        return go
-
+    B = OL.BATCH
+    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", N * mk)):
+        assert w[key].reshape(w[key].shape[0], -1).shape == (B if v[key] == "b" else 1, width)
+    case = ModelCase(w, OL.model_pads(variant), factor_in_arena=True)
+    assert case.B == B
     ran = 0
     for flags in (_capi.OPT_TWO_PER_WAVE, _capi.OPT_FOUR_PER_WAVE):
         for bounds in (True, False):
             if not bounds and v["e"] == "b":
                 continue  # (without the bounds operand every problem has the model's e)
-            out = L.run(F, launch(flags, bounds))
-            out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
+            out = case.run(F, flags, bounds)
             ok = against_oracle(f"model {shape} {variant}", full, out, 1e-7)
             assert ok.all() and (out["status"] == 0).all(), out["status"]
             ran += 1
@@ -192,10 +135,6 @@ def test_shared_model_solves(shape, variant):
 DIFF_LAYOUTS = OL.DIFF_LAYOUTS
 
 
-def SIZES(nx, nu, N, mk):
-    return dict(x0=nx, goal=nx, targets=N * nx, e=N * mk, A=N * nx * nx, B=N * nx * nu, C=N * mk * nx, D=N * mk * nu, w=3)
-
-
 _DIFF = {}
 
 
@@ -203,7 +142,7 @@ def _diff_case(shape, layout):
     """(w, full, U, lam, status) of a derivative case: the plan and multipliers are the CPU oracle's on the materialised problems"""
     if (shape, layout) not in _DIFF:
         w, full = OL.diff_case(shape, layout)
-        _DIFF[(shape, layout)] = (w, full) + MD.forward_on_cpu(full)
+        _DIFF[(shape, layout)] = (w, full) + GL.forward_on_cpu(full)
     return _DIFF[(shape, layout)]
 
 
@@ -219,72 +158,6 @@ def test_plan_vjp_layouts(kind, shape, layout):
     plan_vjp(kind, shape, _diff_case(shape, layout), OL.pads_of(layout), layout)
 
 
-def plan_vjp(kind, shape, case, pad, layout):
-    """the launch and the comparisons of test_plan_vjp_layouts on `case` = (w, full, U, lam, status) with batch-stride padding
-    `pad` (`layout` names the case in a failure); returns the gradients {operand: [B, size]} and the statuses
-    (tests/test_gpu_padded_rows.py runs its own cases through this)"""
-    from qpmpc_amd import _capi, autodiff
-    from qpmpc_amd import workloads as W
-
-    _, lib, stream = MD._api()
-    nx, nu, N, mk = shape
-    w, full, U, lam, status = case
-    bp = W.to_batch_problem(w)
-    B, n = OL.BATCH, N * nu
-    assert bp.batch_size == B and (status == 0).sum() * 2 >= B, status
-    rng = np.random.default_rng(3)
-    gU, gX = rng.standard_normal((B, n)), rng.standard_normal((B, (N + 1) * nx))
-    dims, nbytes = autodiff._vjp_dims(bp), C.c_size_t(0)
-    ka = MD.max_active_of(lam, status, n)
-    if kind == "condensed":
-        rc = lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), B, C.byref(nbytes))
-    elif kind == "model":
-        rc = lib.mpcqp_plan_vjp_model_workspace_bytes(C.byref(dims), B, C.byref(nbytes))
-    else:
-        rc = lib.mpcqp_plan_vjp_stagewise_workspace_bytes(C.byref(dims), B, ka, C.byref(nbytes))
-    assert rc == 0
-    sizes = SIZES(*shape)
-    outs = list(sizes)[:4] if kind == "condensed" else list(sizes)
-    L = Launch()
-    MD.add_problem(L, bp, pad)
-    for key, a in (("lam", lam), ("U", U), ("gU", gU), ("gX", gX)):
-        L.add(key, "in", F64, data=a)
-    L.add("status", "in", I32, data=torch.as_tensor(status))
-    for key in outs:
-        L.add("g_" + key, "out", F64, B * sizes[key])
-    L.add("vjp_status", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    cp = MD.arena_problem(L, bp, pad)
-    ptrs = [L.ptr("g_" + k) if k in outs else None for k in sizes]
-    head = (C.byref(dims), C.byref(cp), B)
-    tail = (L.ptr("vjp_status"), L.ptr("ws"), nbytes.value, stream())
-    res = _capi.VjpModelOut(*ptrs)
-
-    def call():
-        if kind == "condensed":
-            return lib.mpcqp_plan_vjp_batch(*head, L.ptr("lam"), L.ptr("status"), L.ptr("gU"), L.ptr("gX"), *ptrs[:4], *tail)
-        if kind == "model":
-            return lib.mpcqp_plan_vjp_model_batch(*head, L.ptr("lam"), L.ptr("status"), L.ptr("U"), L.ptr("gU"), L.ptr("gX"),
-                                                  C.byref(res), *tail)
-        return lib.mpcqp_plan_vjp_stagewise_batch(*head, ka, L.ptr("lam"), L.ptr("status"), L.ptr("U"), L.ptr("gU"), L.ptr("gX"),
-                                                  C.byref(res), *tail)
-
-    f = L.run(F, call)
-    vst = f["vjp_status"]
-    assert np.array_equal(vst[status != 0], status[status != 0]) and (vst[status == 0] == 0).all(), vst
-    for b in range(B):
-        got = {k: f["g_" + k].reshape(B, -1)[b] for k in outs}
-        if vst[b] != 0:
-            assert all((g == 0).all() for g in got.values()), (b, "an unsolved item's gradients are zeros")
-            continue
-        w1 = AN.single(full, b)
-        ref = AN.vjp(w1, lam[b], gU[b], gX[b]) if kind == "condensed" else AS.stagewise_vjp(w1, lam[b], gU[b], gX[b], U[b])
-        for k in outs:
-            close(got[k], ref[k], (kind, layout, b, k))
-    return {k: f["g_" + k].reshape(B, -1) for k in outs}, vst
-
-
 JVP = [(model, sw, shape, i) for i in DIFF_LAYOUTS for model, sw, shape in
        ((False, False, (3, 2, 8, 2)), (True, False, (3, 2, 8, 2)), (False, True, (3, 2, 8, 2)), (True, True, (3, 2, 8, 2)),
         (False, True, (3, 2, 70, 2)), (True, True, (3, 2, 70, 2)))]
@@ -298,71 +171,6 @@ def test_plan_jvp_layouts(model, stagewise, shape, layout):
     plan_jvp(model, stagewise, shape, _diff_case(shape, layout), OL.pads_of(layout), layout)
 
 
-def plan_jvp(model, stagewise, shape, case, pad, layout, tan=None):
-    """the launch and the comparisons of test_plan_jvp_layouts on `case` = (w, full, U, lam, status), with its three random
-    tangents or with `tan` ({operand: [B, 3, ...]}); returns dU, dX [B, 3, -1] and the statuses (tests/test_gpu_padded_rows.py
-    runs its own cases through this)"""
-    from qpmpc_amd import _capi, autodiff
-    from qpmpc_amd import workloads as W
-
-    _, lib, stream = MD._api()
-    nx, nu, N, mk = shape
-    w, full, U, lam, status = case
-    bp = W.to_batch_problem(w)
-    B, n, T = OL.BATCH, N * nu, 3
-    assert bp.batch_size == B and (status == 0).sum() * 2 >= B, status
-    tan = MD._tangents(full, B, T, np.random.default_rng(4), model) if tan is None else tan
-    dims, nbytes = autodiff._vjp_dims(bp), C.c_size_t(0)
-    ka = MD.max_active_of(lam, status, n)
-    query = {(False, False): lib.mpcqp_plan_jvp_workspace_bytes, (True, False): lib.mpcqp_plan_jvp_model_workspace_bytes,
-             (False, True): lib.mpcqp_plan_jvp_stagewise_workspace_bytes,
-             (True, True): lib.mpcqp_plan_jvp_model_stagewise_workspace_bytes}[(model, stagewise)]
-    extra = (ka, T) if stagewise else (T,)
-    assert query(C.byref(dims), B, *extra, C.byref(nbytes)) == 0
-    L = Launch()
-    MD.add_problem(L, bp, pad)
-    L.add("lam", "in", F64, data=lam)
-    L.add("U", "in", F64, data=U)
-    L.add("status", "in", I32, data=torch.as_tensor(status))
-    for key, a in tan.items():
-        L.add("d" + key, "in", F64, data=a.reshape(B, -1))
-    L.add("dU", "out", F64, B * T * n)
-    L.add("dX", "out", F64, B * T * (N + 1) * nx)
-    L.add("jvp_status", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    cp = MD.arena_problem(L, bp, pad)
-    ctan = _capi.Tangents(*[L.ptr("d" + k) for k in ("x0", "goal", "targets", "e")],
-                          *[tan[k][0].size for k in ("x0", "goal", "targets", "e")])
-    mtan = _capi.ModelTangents(*[L.ptr("d" + k) for k in ("A", "B", "C", "D", "w")],
-                               *[tan[k][0].size for k in ("A", "B", "C", "D", "w")]) if model else None
-    head = (C.byref(dims), C.byref(cp), B) + ((ka,) if stagewise else ()) + (T, L.ptr("lam"), L.ptr("status"))
-    tail = (L.ptr("dU"), L.ptr("dX"), L.ptr("jvp_status"), L.ptr("ws"), nbytes.value, stream())
-
-    def call():
-        if model:
-            fn = lib.mpcqp_plan_jvp_model_stagewise_batch if stagewise else lib.mpcqp_plan_jvp_model_batch
-            return fn(*head, L.ptr("U"), C.byref(ctan), C.byref(mtan), *tail)
-        fn = lib.mpcqp_plan_jvp_stagewise_batch if stagewise else lib.mpcqp_plan_jvp_batch
-        return fn(*head, C.byref(ctan), *tail)
-
-    f = L.run(F, call)
-    vst = f["jvp_status"]
-    assert np.array_equal(vst[status != 0], status[status != 0]) and (vst[status == 0] == 0).all(), vst
-    dU, dX = f["dU"].reshape(B, T, -1), f["dX"].reshape(B, T, -1)
-    for b in range(B):
-        if vst[b] != 0:
-            assert (dU[b] == 0).all() and (dX[b] == 0).all(), (b, "an unsolved item's tangents are zeros")
-            continue
-        w1 = AN.single(full, b)
-        for t in range(T):
-            one = {k: a[b, t] for k, a in tan.items()}
-            ref = TM.jvp_model(w1, U[b], lam[b], one) if model else TN.jvp(w1, lam[b], one)
-            close(dU[b, t], ref["U"], (layout, b, t, "dU"))
-            close(dX[b, t], ref["X"], (layout, b, t, "dX"))
-    return dU, dX, vst
-
-
 # ---------------------------------------------------------------------------------------------- condensing, vectors, roll-out
 @pytest.mark.parametrize("layout", DIFF_LAYOUTS)
 def test_condense_update_vectors_and_rollout_layouts(layout):
@@ -371,18 +179,18 @@ def test_condense_update_vectors_and_rollout_layouts(layout):
     test_condense_and_its_phases and test_update_vectors_and_rollout)."""
     from qpmpc_amd import workloads as W
 
-    _, lib, stream = MD._api()
+    _, lib, stream = GL._api()
     w, full = OL.condense_case(layout)
     bp = W.to_batch_problem(w)
     B, n, m, N, nx = bp.batch_size, bp.nb_variables, bp.nb_constraints, bp.nb_timesteps, bp.state_dim
     assert B == OL.BATCH
     dims, nbytes = bp.dims(), C.c_size_t(0)
     assert lib.mpcqp_workspace_bytes(C.byref(dims), B, 0, C.byref(nbytes)) == 0
-    refs = MD.condense_refs(full, B)
+    refs = GL.condense_refs(full, B)
     Uin = np.random.default_rng(5).standard_normal((B, n))
     pad = OL.pads_of(layout)
     L = Launch()
-    MD.add_problem(L, bp, pad)
+    GL.add_problem(L, bp, pad)
     sizes = dict(P=n * n, q=n, G=m * n, h=m, Phi=(N + 1) * nx * nx, Psi=(N + 1) * nx * n)
     for key, count in sizes.items():
         L.add(key, "out", F64, B * count)
@@ -394,7 +202,7 @@ def test_condense_update_vectors_and_rollout_layouts(layout):
     L.add("X", "out", F64, B * (N + 1) * nx)
     L.add("ws", "scratch", U8, nbytes.value)
     L.build()
-    cp = MD.arena_problem(L, bp, pad)
+    cp = GL.arena_problem(L, bp, pad)
 
     def condense():
         return lib.mpcqp_condense_batch(C.byref(dims), C.byref(cp), B, L.ptr("P"), L.ptr("q"), L.ptr("G"), L.ptr("h"), L.ptr("Phi"),
@@ -413,14 +221,14 @@ def test_condense_update_vectors_and_rollout_layouts(layout):
         for key, want in (("P", cq.P), ("q", cq.q), ("G", cq.G), ("h", cq.h), ("Phi", np.vstack([cq.Phi, cq.phi_last])),
                           ("Psi", np.vstack([cq.Psi, cq.psi_last]))):
             got = cond[key].reshape(B, -1)[b].reshape(want.shape)
-            assert MD._rel(got, want) <= 1e-12, (layout, b, key, MD._rel(got, want))
-        assert MD._rel(upd["q2"].reshape(B, n)[b], cq.q) <= 1e-12 and MD._rel(upd["h2"].reshape(B, m)[b], cq.h) <= 1e-12, (layout, b)
+            assert GL._rel(got, want) <= 1e-12, (layout, b, key, GL._rel(got, want))
+        assert GL._rel(upd["q2"].reshape(B, n)[b], cq.q) <= 1e-12 and GL._rel(upd["h2"].reshape(B, m)[b], cq.h) <= 1e-12, (layout, b)
         x = full["x0"][b]
         want = [x]
         for k in range(N):
             x = full["A"][b, k] @ x + full["B"][b, k] @ Uin[b].reshape(N, -1)[k]
             want.append(x)
-        assert MD._rel(roll["X"].reshape(B, -1)[b], np.concatenate(want)) <= 1e-12, (layout, b)
+        assert GL._rel(roll["X"].reshape(B, -1)[b], np.concatenate(want)) <= 1e-12, (layout, b)
 
 
 # ---------------------------------------------------------------------------------------------- MPCQP_ELAYOUT
@@ -436,7 +244,7 @@ def test_short_and_negative_batch_strides_are_refused(export):
     from qpmpc_amd import _capi, autodiff
     from qpmpc_amd import workloads as W
 
-    _, lib, stream = MD._api()
+    _, lib, stream = GL._api()
     shape = (3, 2, 8, 2)
     nx, nu, N, mk = shape
     everything = dict(A="bn", B="bn", C="bn", D="bn", e="bn", goal="b", targets="b")
@@ -444,11 +252,11 @@ def test_short_and_negative_batch_strides_are_refused(export):
     bp = W.to_batch_problem(w)
     B, n, m = OL.BATCH, N * nu, N * mk
     L = Launch()
-    MD.add_problem(L, bp)
+    GL.add_problem(L, bp)
     nbytes = C.c_size_t(0)
     o = _capi.SolveOpts()
     if export == "plan_vjp":
-        U, lam, status = MD.forward_on_cpu(full)
+        U, lam, status = GL.forward_on_cpu(full)
         dims = autodiff._vjp_dims(bp)
         assert lib.mpcqp_plan_vjp_workspace_bytes(C.byref(dims), B, C.byref(nbytes)) == 0
         L.add("lam", "in", F64, data=lam)
@@ -487,7 +295,7 @@ def test_short_and_negative_batch_strides_are_refused(export):
         if name in OL.MATS:
             bad.append(("step_stride", -(extent // N)))
         for field, value in bad:
-            cp = MD.arena_problem(L, bp)
+            cp = GL.arena_problem(L, bp)
             op = getattr(cp, name)
             assert op.ptr and op.batch_stride == extent
             setattr(op, field, value)
@@ -500,9 +308,9 @@ def test_short_and_negative_batch_strides_are_refused(export):
             out = L.run(F, refused)
             assert rcs == [ELAYOUT], (export, name, field, value, rcs)
             for key, buf in out.items():
-                assert MD.holds(buf, F), (export, name, field, value, key, "was written by a refused call")
+                assert GL.holds(buf, F), (export, name, field, value, key, "was written by a refused call")
             tried += 1
     assert tried == 8 * 2 + 5
-    good = L.run(F, lambda: call_with(MD.arena_problem(L, bp)))
-    assert not MD.holds(good["g_x0" if export == "plan_vjp" else "U"], F)
+    good = L.run(F, lambda: call_with(GL.arena_problem(L, bp)))
+    assert not GL.holds(good["g_x0" if export == "plan_vjp" else "U"], F)
     assert b"batch stride" in lib.mpcqp_error_string(ELAYOUT)

@@ -12,9 +12,8 @@ padding moves most plans by ten times the bound they are held to.
 The reference is always the STRIPPED problem (padded rows deleted from the condensed G and h, oracle.capi.gi_solve), never the
 padded one: statuses equal, U within the route's existing bound (1e-7 float64, 1e-3 float32, relative to max(1, |U|)), no NaN,
 lam == 0 on every padded row, and for an item padded whole iters == 0 and the plan within the bound of -P^-1 q. Every launch
-runs in the guarded arena of tests/test_gpu_memory_discipline.py under the all-0xFF fill. Multipliers on REAL rows are not
+runs in the guarded arena of tests/guarded_launch.py under the all-0xFF fill. Multipliers on REAL rows are not
 compared here (the verdict and parity tests hold statuses and plans; that is the existing contract)."""
-import ctypes as C
 import os
 from types import SimpleNamespace
 
@@ -24,29 +23,18 @@ import pytest
 import model_adjoint_np as MN
 import operand_layouts as OL
 import padded_rows as PR
-import test_gpu_memory_discipline as MD
-import test_gpu_operand_layouts as GL
 from golden_util import load_case
-from test_gpu_memory_discipline import Forward
-from test_gpu_onchip32 import _NoWorkspace
-from test_gpu_onchip32_model import ModelCase
-from test_gpu_onchip32_qp import QPs
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-F, F32 = MD.F, MD.F32
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, ModelCase, QPs  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
+
+F, F32 = GL.F, GL.F32
 B = PR.BATCH
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 def held(c, out, what):
@@ -123,7 +111,7 @@ def test_forward_route_placement(name, placement):
     r = PR.ROUTES[name]
     c = PR.case(name, placement)
     if name in PR.ON_CHIP_FUSED:
-        case = _NoWorkspace(c["w"])
+        case = Forward(c["w"], workspace=False)
     else:
         case = Forward(c["w"], dtype=F32 if r["f32"] else None, stagewise=r["stagewise"])
     assert case.B == B
@@ -138,7 +126,7 @@ def test_on_chip_qp_mode(name, placement):
     """mpcqp_solve_batch flagged MPCQP_OPT_ON_CHIP_32 (the QP mode of mpcqp_duo.hip) on the CONDENSED padded problems of the
     on-chip cases: zero rows of G with h = 1e30."""
     c = PR.case(name, placement)
-    refs = MD.condense_refs(c["full"], B)
+    refs = GL.condense_refs(c["full"], B)
     P, q, G, h = (np.stack([getattr(cq, k) for cq in refs]) for k in ("P", "q", "G", "h"))
     assert not G[c["mask"]].any() and (h[c["mask"]] == PR.PAD).all()
     out = QPs(P, q, G, h).run(F, _flags(["OPT_ON_CHIP_32"]))
@@ -192,7 +180,7 @@ def _reload(case, w):
     from qpmpc_amd import workloads as W
 
     bp = W.to_batch_problem(w)
-    for name, attr in MD.OPS:
+    for name, attr in GL.OPS:
         t = getattr(bp, attr)
         if t is not None:
             spec = next(s for s in case.L.specs if s["name"] == "op_" + name)
@@ -309,16 +297,16 @@ def test_pairing_order_on_a_mixed_batch():
     rounding for that. An order that moves whole wavefronts -- pairs (0, 1) <-> (2, 3), (4, 5) <-> (6, 7), the unconstrained
     problem 7 with them -- keeps every problem's half and partner: every output is bitwise the natural order's. The reversal
     keeps the halves (i and 8 - i have the same parity) and changes the partners: statuses and iteration counts equal, plans
-    equal to 1e-9 (tests/test_gpu_memory_discipline.py::same_plans)."""
+    equal to 1e-9 (guarded_launch.same_plans)."""
     c = PR.case("pair lean", "mixed")
     natural = Forward(c["w"]).run(F)
     held(c, natural, "pair lean, mixed, natural order")
     moved = Forward(c["w"], order=[2, 3, 0, 1, 6, 7, 4, 5, 8]).run(F)
     held(c, moved, "pair lean, mixed, wavefronts exchanged")
-    MD.equal_outputs(natural, moved, "a pairing order that moves whole wavefronts")
+    GL.equal_outputs(natural, moved, "a pairing order that moves whole wavefronts")
     reversed_ = Forward(c["w"], order=np.arange(B)[::-1].copy()).run(F)
     held(c, reversed_, "pair lean, mixed, reversed order")
-    MD.same_plans(natural, reversed_, "a pairing order that changes the partners")
+    GL.same_plans(natural, reversed_, "a pairing order that changes the partners")
     assert np.array_equal(natural["iters"], reversed_["iters"])
 
 
@@ -339,7 +327,7 @@ def _diff(shape):
 @pytest.mark.parametrize("kind,shape", [("condensed", (3, 2, 8, 2)), ("model", (3, 2, 8, 2)), ("stagewise", (3, 2, 70, 2))])
 def test_plan_vjp_on_a_tail_case(kind, shape):
     """mpcqp_plan_vjp_batch / _vjp_model_batch / _vjp_stagewise_batch: every gradient against the NumPy restatement on the
-    materialised (padded) problem at 1e-8 (test_gpu_operand_layouts.plan_vjp), and the gradients with respect to e, C and D
+    materialised (padded) problem at 1e-8 (guarded_launch.plan_vjp), and the gradients with respect to e, C and D
     exactly 0 on the padded rows."""
     nx, nu, N, mk = shape
     c, case = _diff(shape)
@@ -355,12 +343,12 @@ def test_plan_vjp_on_a_tail_case(kind, shape):
                                                   (False, True, (3, 2, 70, 2)), (True, True, (3, 2, 70, 2))])
 def test_plan_jvp_on_a_tail_case(model, stagewise, shape):
     """mpcqp_plan_jvp_batch / _jvp_model_batch / _jvp_stagewise_batch / _jvp_model_stagewise_batch: three random tangents
-    against the NumPy restatement at 1e-8 (test_gpu_operand_layouts.plan_jvp); then tangents that are non-zero only on padded
+    against the NumPy restatement at 1e-8 (guarded_launch.plan_jvp); then tangents that are non-zero only on padded
     rows of e (and of C and D): dU = dX = 0."""
     nx, nu, N, mk = shape
     c, case = _diff(shape)
     GL.plan_jvp(model, stagewise, shape, case, 0, "padded tail")
-    tan = MD._tangents(c["full"], B, 3, np.random.default_rng(6), model)
+    tan = GL._tangents(c["full"], B, 3, np.random.default_rng(6), model)
     for X in ("x0", "goal", "targets", "A", "B", "w"):
         if X in tan:
             tan[X][...] = 0.0
@@ -409,11 +397,11 @@ def test_shared_model_derivatives_with_padded_rows_in_the_model():
     for b in range(B):
         want = ref.vjp(lam[b], gU[b], gX[b])
         for key in ("x0", "goal", "targets", "e"):
-            MD.close(g[key][b], want[key], (b, key))
+            GL.close(g[key][b], want[key], (b, key))
         for t in range(3):
             rj = ref.jvp(lam[b], {k: v[b, t] for k, v in tan.items()})
-            MD.close(runs[0][0][b, t], rj["U"], (b, t, "dU"))
-            MD.close(runs[0][1][b, t], rj["X"], (b, t, "dX"))
+            GL.close(runs[0][0][b, t], rj["U"], (b, t, "dU"))
+            GL.close(runs[0][1][b, t], rj["X"], (b, t, "dX"))
     assert (g["e"][c["mask"]] == 0).all()
     assert np.abs(only["e"]).max() > 0 and (runs[1][0] == 0).all() and (runs[1][1] == 0).all()
 

@@ -138,7 +138,7 @@ def test_shared_model_solve_takes_the_order():
 ])
 def test_every_instantiation_of_the_kernel_takes_the_order(nx, nu, N, mk, with_c, with_d, wx):
     """Random LTV families of the small-problem kernel's other template instantiations, odd batch, reversed and sorted orders."""
-    from test_gpu_parity import _random_ltv_workload
+    from host_helpers import random_ltv_workload as _random_ltv_workload
 
     from qpmpc_amd import pairing_order, solve_mpc_batch
     from qpmpc_amd import workloads as W

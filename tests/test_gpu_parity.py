@@ -14,6 +14,7 @@ import pytest
 
 import oracle
 from golden_util import GOLDEN, all_cases, kkt_residuals, load_case
+from host_helpers import random_ltv_workload as _random_ltv_workload
 
 pytestmark = pytest.mark.gpu
 
@@ -550,23 +551,6 @@ def test_large_solve_f64_general_qp_in_workspace():
     for b in range(Bn):
         xo, lo, so, _ = oracle.gi_solve(Ps[b], qs[b], Gs[b], hs[b])
         assert so == 0 and _rel(x[b].cpu().numpy(), xo) <= 1e-7
-
-
-def _random_ltv_workload(rng, B, nx, nu, N, mk, with_c=True, with_d=True, wt=2.0, wx=0.5):
-    A = np.eye(nx) + 0.3 * rng.standard_normal((B, N, nx, nx))
-    Bm = rng.standard_normal((B, N, nx, nu))
-    Cm = rng.standard_normal((B, N, mk, nx)) if with_c else None
-    D = rng.standard_normal((B, N, mk, nu)) if with_d else None
-    x0 = 0.1 * rng.standard_normal((B, nx))
-    e = np.zeros((B, N, mk))
-    for b in range(B):
-        x = x0[b].copy()
-        for k in range(N):
-            base = Cm[b, k] @ x if with_c else 0.0
-            e[b, k] = base + 0.05 + 0.5 * np.abs(rng.standard_normal(mk))
-            x = A[b, k] @ x
-    return dict(A=A, B=Bm, C=Cm, D=D, e=e, N=N, wt=wt, wx=wx, wu=1e-2, x0=x0,
-                goal=rng.standard_normal((B, nx)), targets=None if wx is None else rng.standard_normal((B, N * nx)))
 
 
 @pytest.mark.parametrize("nx,nu,N,mk,with_c,with_d,wx", [

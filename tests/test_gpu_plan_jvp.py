@@ -11,26 +11,13 @@ import tangent_np as TN
 from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
+
+pytest.importorskip("torch")
+
+from guarded_launch import _random_ltv, _torch  # noqa: E402  (needs torch)
+from host_helpers import dims_of as _dims  # noqa: E402
+
 NAMES = dict(x0="initial_state", goal="goal_state", targets="target_states", e="ineq_vector")
-
-
-def _torch():
-    import torch
-
-    return torch
-
-
-def _random_ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
-
-
-def _dims(w):
-    N = int(w["N"])
-    nx, nu = np.asarray(w["x0"]).shape[1], np.asarray(w["B"]).shape[-1]
-    mk = 0 if w["e"] is None else np.asarray(w["e"]).shape[-1]
-    return N, nx, nu, mk
 
 
 def _tangents(w, B, T, rng):

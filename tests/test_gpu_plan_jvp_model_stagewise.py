@@ -2,24 +2,23 @@
 instantiation of mpcqp_tangent_stagewise_kernel in qpmpc_amd/csrc/mpcqp_adjoint_stagewise.hip) against the NumPy
 restatement of tests/tangent_model_np.py at 1e-8 max(1, |ref|) with every operand's tangent at once, beyond n = 128, on
 the config-5 shape (float32 storage too), beyond the wide forward kernel and without an active row; a tangent's
-independence of its slot, pass and T; and, through the helpers of tests/test_gpu_plan_jvp_model.py, the duality with
+independence of its slot, pass and T; and, through the checks of tests/plan_jvp_model_checks.py, the duality with
 mpcqp_plan_vjp_stagewise_batch, shared and time-invariant tangents, unsolved problems, the state-only call and the
 weight Jacobian."""
 
 import numpy as np
 import pytest
 
-import test_gpu_plan_jvp_model as M
 from qpmpc_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
+
+pytest.importorskip("torch")
+
+import plan_jvp_model_checks as M  # noqa: E402  (needs torch)
+from guarded_launch import _torch  # noqa: E402
+
 SW = dict(formulation="stagewise")
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 def test_n140_beyond_the_condensed_tangent():
@@ -91,4 +90,4 @@ def test_weight_jacobian_against_central_differences():
 
 
 def test_agrees_with_the_condensed_export():
-    M.test_the_two_formulations_agree()
+    M.check_the_two_formulations_agree()

@@ -12,7 +12,7 @@ stream runs ahead of the copy and returns A's plans; test_a_launch_on_the_wrong_
 (Two streams that share a hardware queue run in order whatever the handles say, so these tests take a side stream that the
 default stream is first shown to run ahead of: side_stream().)
 
-The arena machinery is that of tests/test_gpu_memory_discipline.py: Launch.run fills outputs and workspace with 0xFF before the
+The arena machinery is that of tests/guarded_launch.py: Launch.run fills outputs and workspace with 0xFF before the
 call and checks guards and read-only operands behind it, so a launch or a graph replay that did nothing leaves NaN plans.
 Bounds: 1e-7 relative for float64 plans, 1e-3 for float32 ones against the oracle on the float32-rounded operands (those of
 tests/test_gpu_operand_layouts.py); a launch on a side stream, a replay, a launch next to another stream's or another thread's
@@ -33,22 +33,14 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-import test_gpu_memory_discipline as MD  # noqa: E402  (its arena launcher and comparisons; needs torch)
-from test_gpu_memory_discipline import Forward, Launch, equal_outputs  # noqa: E402
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, Launch, ModelCase, equal_outputs  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
 
-F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
+F, F64, F32, I32, U8 = GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 OUTS = ("U", "lam", "status", "iters")
 ROUTES = list(SC.ROUTES_UNDER_TEST)
 DELAY_MS, MIN_DELAY_MS = 5.0, 1.0
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 def _handle(stream):
@@ -131,7 +123,7 @@ def two_streams():
 
 # ---------------------------------------------------------------------------------------------- a route in the arena
 class Case:
-    """One route of stream_cases.ROUTES_UNDER_TEST with everything in a guarded arena (MD.Forward, or the ModelCase of
+    """One route of stream_cases.ROUTES_UNDER_TEST with everything in a guarded arena (GL.Forward, or the ModelCase of
     tests/test_gpu_onchip32_model.py for the shared-model route), x0 as an "inout" buffer -- loaded with x0_A (`which` "B":
     x0_B) before every run, free to be rewritten inside call() --, and the route's raw C call on a stream handle."""
 
@@ -143,8 +135,6 @@ class Case:
         w = (SC.case_a(name) if which == "A" else SC.case_b(name))[0]
         self.dtype = F32 if r["f32"] else F64
         if self.model:
-            from test_gpu_onchip32_model import ModelCase
-
             self.case, x0 = ModelCase(w, OL.model_pads(r["variant"]), inout=("x0",)), "x0"
         else:
             self.case, x0 = Forward(w, dtype=self.dtype, stagewise=r["stagewise"], pad=OL.pads_of(SC.LAYOUT), inout=("x0",)), "op_x0"
@@ -160,7 +150,7 @@ class Case:
 
     def c_call(self, sp):
         """the route's C call with `sp` as its stream argument; the return code"""
-        _, lib, _ = MD._api()
+        _, lib, _ = GL._api()
         L, c = self.L, self.case
         if self.model:
             o = c.ops
@@ -273,7 +263,7 @@ def test_a_launch_on_the_wrong_stream_is_seen():
     out = c.run(call)
     delay.conclusive()
     equal_outputs(out, plain_A, "a launch that ran ahead of the copy returns A's plans")
-    assert not any(MD.same_bits(out["U"][i], plain_B["U"][i]) for i in range(OL.BATCH))
+    assert not any(GL.same_bits(out["U"][i], plain_B["U"][i]) for i in range(OL.BATCH))
     with pytest.raises(AssertionError):
         against_oracle(route, "B", out)
 
@@ -367,7 +357,7 @@ class Pair:
         from qpmpc_amd import _capi
         from qpmpc_amd import workloads as W
 
-        _, lib, _ = MD._api()
+        _, lib, _ = GL._api()
         self.w = OL.ltv(*seq["ltv"])
         bp = self.bp = W.to_batch_problem(self.w)
         self.B, self.n, self.m, self.dims = bp.batch_size, bp.nb_variables, bp.nb_constraints, bp.dims()
@@ -375,7 +365,7 @@ class Pair:
         assert lib.mpcqp_workspace_bytes(C.byref(self.dims), self.B, 1, C.byref(nbytes)) == 0
         self.ws_bytes = nbytes.value
         L = self.L = Launch()
-        MD.add_problem(L, bp)
+        GL.add_problem(L, bp)
         for i in (1, 2):
             L.add(f"U{i}", "out", F64, self.B * self.n)
             L.add(f"lam{i}", "out", F64, self.B * self.m)
@@ -388,7 +378,7 @@ class Pair:
             L.add("warm", "scratch", U8, self.B * wb.value)
         L.build()
         assert L.has(seq["carried"])  # (what the second launch reads of the first)
-        self.cp = MD.arena_problem(L, bp)
+        self.cp = GL.arena_problem(L, bp)
         self.opts = []
         for step in (seq["first"], seq["second"]):
             o = _capi.SolveOpts()
@@ -399,7 +389,7 @@ class Pair:
             self.opts.append(o)
 
     def c_call(self, i, sp):
-        _, lib, _ = MD._api()
+        _, lib, _ = GL._api()
         L = self.L
         return lib.mpcqp_build_solve_batch(C.byref(self.dims), C.byref(self.cp), self.B, C.byref(self.opts[i - 1]), L.ptr(f"U{i}"),
                                            L.ptr(f"lam{i}"), L.ptr(f"status{i}"), L.ptr(f"iters{i}"), L.ptr("ws"), self.ws_bytes, sp)
@@ -423,7 +413,7 @@ def test_captured_sequences(name):
 
     first = p.run(eager_pair)
     for i, out in enumerate(first):
-        MD.against_oracle(f"{name}, launch {i + 1}", p.w, out, 1e-7)
+        GL.against_oracle(f"{name}, launch {i + 1}", p.w, out, 1e-7)
     g, rcs = capture([lambda: p.c_call(1, _handle(s)), lambda: p.c_call(2, _handle(s))], s)
     assert rcs == [0, 0], f"the calls returned {rcs} while the stream was capturing"
 
@@ -461,11 +451,11 @@ def test_one_graph_holds_two_lds_sizes_of_one_instantiation():
     flag = _capi.OPT_FORCE_LDS
     twins = [case.run(F, flag) for case in (large, mid)]
     for shape, w, out in zip(shapes, (wl, wm), twins):
-        MD.against_oracle(f"workgroup kernel {shape}", w, out, 1e-7)
+        GL.against_oracle(f"workgroup kernel {shape}", w, out, 1e-7)
     s = torch.cuda.Stream()
     opts = _capi.SolveOpts()
     opts.flags = flag
-    _, lib, _ = MD._api()
+    _, lib, _ = GL._api()
 
     def c_call(case):
         L = case.L
@@ -474,7 +464,7 @@ def test_one_graph_holds_two_lds_sizes_of_one_instantiation():
 
     g, rcs = capture([lambda: c_call(large), lambda: c_call(mid)], s)
     assert rcs == [0, 0], f"the calls returned {rcs} while the stream was capturing"
-    MD.against_oracle(f"workgroup kernel {shapes[2]}", wsm, small.run(F, flag), 1e-7)
+    GL.against_oracle(f"workgroup kernel {shapes[2]}", wsm, small.run(F, flag), 1e-7)
     got = {}
 
     def replay():
@@ -489,7 +479,7 @@ def test_one_graph_holds_two_lds_sizes_of_one_instantiation():
     for key, case, twin, shape, w in (("large", large, twins[0], shapes[0], wl), ("mid", mid, twins[1], shapes[1], wm)):
         out = got[key]
         out["U"], out["lam"] = out["U"].reshape(case.B, case.n), out["lam"].reshape(case.B, case.m)
-        MD.against_oracle(f"workgroup kernel {shape}", w, out, 1e-7)
+        GL.against_oracle(f"workgroup kernel {shape}", w, out, 1e-7)
         equal_outputs(out, twin, f"workgroup kernel {shape}: replay against the eager launch")
 
 
@@ -555,7 +545,7 @@ def test_two_streams_in_flight(left, right):
 def test_order_by_count_on_two_streams():
     """mpcqp_order_by_count (three kernels per call) on two streams (shown to run side by side) with two count vectors, released together: each result a
     permutation, longest first, as tests/test_gpu_memory_discipline.py::test_order_by_count asks of it."""
-    _, lib, _ = MD._api()
+    _, lib, _ = GL._api()
     batch = 1025
     nbytes = int(lib.mpcqp_order_workspace_bytes(batch))
     streams = two_streams()
@@ -634,7 +624,7 @@ def test_two_host_threads():
 # ---------------------------------------------------------------------------------------------- 8. autograd on a side stream
 def _bits_equal(a, b, what):
     assert a.dtype == b.dtype and a.shape == b.shape, what
-    assert MD.same_bits(a.detach().cpu().numpy(), b.detach().cpu().numpy()), what
+    assert GL.same_bits(a.detach().cpu().numpy(), b.detach().cpu().numpy()), what
 
 
 def _diff_run(solve, operands, stream):

@@ -26,7 +26,6 @@ changes) and that the derivative laws hold on the restatements. The four true fl
 unit (UC.F32_SKIPS): their contract is an absolute bound in the caller's input units.
 
 With MPCQP_UNITS_REPORT=<path> a complete run writes the per-route table of profiles/unit_changes.txt."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -39,16 +38,18 @@ import kkt_certificate as KC
 import model_adjoint_np as MA
 import operand_layouts as OL
 import tangent_np as TN
-import test_gpu_memory_discipline as MD
 import unit_changes as UC
-from test_gpu_memory_discipline import Forward, Launch, close
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, ModelCase, close  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
 
-F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
+
+F, F64, F32, I32, U8 = GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 ROUTES, CHANGES = list(OL.ROUTES), list(UC.CHANGES)
 SOME = ("state-", "input+", "cost-", "mixed")  # the changes the shared-model and derivative tests run
 
@@ -80,15 +81,6 @@ def _report():
                     err, differ, held, base = SEEN[(r, c)]
                     cells.append(f"{err:.1e} {'=' if differ == 0 else differ} {held}/{base}")
                 fh.write(f"{r:40s}" + "".join(f" {c:>18s}" for c in cells) + "\n")
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 def _base_error(Uback, Uo):
@@ -138,7 +130,7 @@ def test_forward_route_change(route, change):
     r = OL.ROUTES[route]
     key, (_, full) = OL.route_case(route, 0)
     scaled, maps = UC.rescale(full, change, r["seed"])
-    Uo, _, sto = MD.oracle_of(repr(key), full)
+    Uo, _, sto = GL.oracle_of(repr(key), full)
     assert (sto == 0).all(), sto
     base, cert = _base_launch(route)
     out = _launch(route, scaled)
@@ -171,57 +163,12 @@ def test_forward_route_change(route, change):
 def _model_solves(shape, w):
     """mpcqp_factor_model + mpcqp_solve_model_bounds_batch of the shared-model workload `w` (A, B, C, D with a leading 1; x0, goal,
     targets, e per problem), two and four per wavefront, as tests/test_gpu_operand_layouts.py::test_shared_model_solves sets
-    them up (packed): {flags: out}"""
-    from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
-
-    _, lib, stream = MD._api()
+    them up (packed, the model factored in the arena): {flags: out}"""
     nx, nu, N, mk = shape
-    B, n, m = OL.BATCH, N * nu, N * mk
-    nb = 1 + 2 * nx + N * nx
-    x0, goal, tgt = torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, N * nx), dtype=F64)
-    x0[1:1 + nx], goal[1 + nx:1 + 2 * nx], tgt[1 + 2 * nx:] = torch.eye(nx), torch.eye(nx), torch.eye(N * nx)
-    pseudo = BatchMPCProblem(w["A"], w["B"], w["C"], w["D"], w["e"][:1], N, w["wt"], w["wx"], w["wu"], x0, goal_state=goal,
-                             target_states=tgt)
-    mdims = pseudo.dims()
-    qp = BatchMPCQP(pseudo, keep_propagators=False)
-    torch.cuda.synchronize()
-    mbytes = C.c_size_t(0)
-    assert lib.mpcqp_model_bytes(C.byref(mdims), C.byref(mbytes)) == 0
-    L = Launch()
-    L.add("P", "in", F64, data=qp.P[0].reshape(1, -1))
-    L.add("G", "in", F64, data=qp.G[0].reshape(1, -1))
-    L.add("qb", "in", F64, data=qp.q.reshape(1, -1))
-    L.add("hb", "in", F64, data=qp.h.reshape(1, -1))
-    L.add("model", "scratch", U8, mbytes.value)
-    ops = {}
-    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", m)):
-        rows = w[key].reshape(B, width)
-        L.add(key, "in", F64, data=rows)
-        ops[key] = (width, mk if key == "e" else 0)
-    L.add("U", "out", F64, B * n)
-    L.add("lam", "out", F64, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.build()
-    ops = {key: _capi.Operand(L.ptr(key), bs, ks) for key, (bs, ks) in ops.items()}
-    outs = {}
-    for flags in (_capi.OPT_TWO_PER_WAVE, _capi.OPT_FOUR_PER_WAVE):
-        o = _capi.SolveOpts()
-        o.flags = flags
-
-        def go():
-            rc = lib.mpcqp_factor_model(C.byref(mdims), L.ptr("P"), L.ptr("G"), L.ptr("qb"), L.ptr("hb"), L.ptr("model"),
-                                        mbytes.value, stream())
-            if rc:
-                return rc
-            return lib.mpcqp_solve_model_bounds_batch(C.byref(mdims), L.ptr("model"), C.byref(ops["e"]), C.byref(ops["x0"]),
-                                                      C.byref(ops["goal"]), C.byref(ops["targets"]), B, C.byref(o), L.ptr("U"),
-                                                      L.ptr("lam"), L.ptr("status"), L.ptr("iters"), stream())
-
-        out = L.run(F, go)
-        out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
-        outs[int(flags)] = out
-    return outs
+    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", N * mk)):
+        assert w[key].reshape(w[key].shape[0], -1).shape == (OL.BATCH, width)  # (every operand per problem)
+    case = ModelCase(w, factor_in_arena=True)
+    return {_flags([name]): case.run(F, _flags([name])) for name in ("OPT_TWO_PER_WAVE", "OPT_FOUR_PER_WAVE")}
 
 
 def _shared(full):
@@ -244,7 +191,7 @@ def test_shared_model_change(shape, change):
     _, full = OL.model_case(shape, 0)
     seed = 3000 + shape[0]
     scaled, maps = UC.rescale(full, change, seed, shared_rows=True)
-    Uo, _, sto = MD.oracle_of(f"model {shape} 0", full)
+    Uo, _, sto = GL.oracle_of(f"model {shape} 0", full)
     assert (sto == 0).all(), sto
     if shape not in _MODEL_BASE:
         _MODEL_BASE[shape] = _model_solves(shape, _shared(full))
@@ -274,7 +221,7 @@ def _diff_base(name):
     """(full, U, lam, status) of a derivative case in BASE units: the plan and multipliers are the C oracle's"""
     if name not in _DIFF:
         full = OL.model_case(OL.MODEL_SHAPES[0], 0)[1] if name == "model" else OL.diff_case(name, 0)[1]
-        _DIFF[name] = (full,) + MD.forward_on_cpu(full)
+        _DIFF[name] = (full,) + GL.forward_on_cpu(full)
     return _DIFF[name]
 
 
@@ -372,8 +319,7 @@ def test_jvp_change(formulation, shape, change):
     nx, nu, N, mk = shape
     B, T = OL.BATCH, 3
     rng = np.random.default_rng(4)
-    tan = dict(x0=rng.standard_normal((B, T, nx)), goal=rng.standard_normal((B, T, nx)),
-               targets=rng.standard_normal((B, T, N * nx)), e=rng.standard_normal((B, T, N * mk)))
+    tan = GL._tangents(full, B, T, rng, False)
     tans = UC.rescale_tangents(tan, maps)
     plan = solve_mpc_batch(bp, return_multipliers=True)
     t = {k: torch.as_tensor(v, device=dev) for k, v in tans.items()}
@@ -421,8 +367,7 @@ def test_shared_model_derivatives_change(change):
     assert ok.all() and (_np(plan.vjp_status) == 0).all()
     got = UC.back_gradients({k: _np(v.grad).reshape(B, -1) for k, v in leaves.items()}, maps)
     T = 3
-    tan = dict(x0=rng.standard_normal((B, T, nx)), goal=rng.standard_normal((B, T, nx)),
-               targets=rng.standard_normal((B, T, N * nx)), e=rng.standard_normal((B, T, N * mk)))
+    tan = GL._tangents(full, B, T, rng, False)
     t = {k: torch.as_tensor(v, device=dev) for k, v in UC.rescale_tangents(tan, maps).items()}
     dU, dX = sm.plan_jvp(plan, initial_state=t["x0"], goal_state=t["goal"], target_states=t["targets"],
                          ineq_vector=t["e"].reshape(B, T, N, mk), states=True)

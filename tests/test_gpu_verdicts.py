@@ -5,7 +5,7 @@ The other forward tests launch batches in which every problem is solvable and co
 held (MPCQP_MAX_ITER 1, MPCQP_INFEASIBLE 2, MPCQP_NOT_PD 3), on batches where the items that fail share a wavefront with items
 that run on, and the iteration limit is held to a bound that no kernel's own count enters. The inputs are those of
 tests/verdict_cases.py (tests/test_verdict_cases_cpu.py shows on the C oracle that they are what they claim to be), launched
-through Forward of tests/test_gpu_memory_discipline.py under the 0xFF fill: an output that was never written holds -1 or NaN.
+through Forward of tests/guarded_launch.py under the 0xFF fill: an output that was never written holds -1 or NaN.
 No kernel's multipliers are read: every expectation comes from the oracle or from the same kernel's unlimited launch.
 
   test_mixed_batch         items 1, 6 and 7 infeasible among six solvable ones: status exactly [0, 2, 0, 0, 0, 0, 2, 2, 0]
@@ -14,7 +14,6 @@ No kernel's multipliers are read: every expectation comes from the oracle or fro
   test_shared_model_mixed, test_dense_qp_mixed: the mixed batch through mpcqp_solve_model_bounds_batch and mpcqp_solve_batch
 
 With MPCQP_VERDICT_REPORT=<path> a complete run writes the per-route table of profiles/verdicts.txt."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -23,16 +22,18 @@ import pytest
 import oracle
 
 import operand_layouts as OL
-import test_gpu_memory_discipline as MD
 import verdict_cases as VC
-from test_gpu_memory_discipline import Forward, Launch, against_oracle, equal_outputs
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import guarded_launch as GL  # noqa: E402  (the arena launchers and comparisons; needs torch)
+from guarded_launch import Forward, ModelCase, QPs, against_oracle, equal_outputs  # noqa: E402
+from guarded_launch import flags as _flags  # noqa: E402
 
-F, F64, F32, I32, U8 = MD.F, MD.F64, MD.F32, MD.I32, MD.U8
+
+F, F64, F32, I32, U8 = GL.F, GL.F64, GL.F32, GL.I32, GL.U8
 MAX_ITER, INFEASIBLE, NOT_PD = 1, 2, 3
 NARROW = ("narrow stage-wise", "narrow stage-wise, stage-wise entry")  # (their code 1 and 2 items go to the wide kernel)
 ROUTES = list(OL.ROUTES)
@@ -61,15 +62,6 @@ def _report():
                 s = SEEN[r]
                 fh.write(f"{r:40s} {s['mixed']:20s} {s['not_pd']:7s} {s['k']:3d} {s['below']:>6s} {s['band']:>6s} {s['above']:>6s} "
                          f"{s['iters_k']:9d} {s['iters_1']:9d} {s['partial']:8d} {s['band2']:>6s} {s['interior']:9d}  {s['more']}\n")
-
-
-def _flags(names):
-    from qpmpc_amd import _capi
-
-    out = 0
-    for name in names:
-        out |= getattr(_capi, name)
-    return out
 
 
 def _case(route, w):
@@ -192,7 +184,7 @@ def test_iteration_limit(route):
     print(f"    {route}: unlimited counts {c.tolist()}")
     assert (unl["status"] == 0).all(), unl["status"]
     against_oracle(repr(key), full, unl, tol)
-    Uo, lamo, sto = MD.oracle_of(repr(key), full)
+    Uo, lamo, sto = GL.oracle_of(repr(key), full)
     a = VC.active_counts(lamo)
     assert (sto == 0).all()
     assert (c >= a).all(), (c, a)
@@ -240,55 +232,13 @@ def test_iteration_limit(route):
 def test_shared_model_mixed(shape, per_wave):
     """mpcqp_solve_model_bounds_batch, two and four per wavefront: the model is shared, so every problem has the band (row 1 of step
     N // 2 the negative of row 0); e of the six good items keeps u = 0 feasible, e of items 1, 6 and 7 is -1, -1
-    (verdict_cases.model_mixed). Set up as tests/test_gpu_operand_layouts.py::test_shared_model_solves."""
-    from qpmpc_amd import BatchMPCQP, BatchMPCProblem, _capi
-
-    _, lib, stream = MD._api()
+    (verdict_cases.model_mixed). Set up as tests/test_gpu_operand_layouts.py::test_shared_model_solves (ModelCase, the model
+    factored in the arena)."""
     nx, nu, N, mk = shape
     w, full, _ = VC.model_mixed(shape)
-    B, n, m = OL.BATCH, N * nu, N * mk
-    nb = 1 + 2 * nx + N * nx  # the pseudo-problems of include/mpcqp.h (x0 = goal = targets = 0, then unit vectors)
-    x0, goal, tgt = torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, nx), dtype=F64), torch.zeros((nb, N * nx), dtype=F64)
-    x0[1:1 + nx], goal[1 + nx:1 + 2 * nx], tgt[1 + 2 * nx:] = torch.eye(nx), torch.eye(nx), torch.eye(N * nx)
-    pseudo = BatchMPCProblem(w["A"], w["B"], w["C"], w["D"], w["e"][:1], N, w["wt"], w["wx"], w["wu"], x0, goal_state=goal,
-                             target_states=tgt)
-    mdims = pseudo.dims()
-    qp = BatchMPCQP(pseudo, keep_propagators=False)
-    torch.cuda.synchronize()
-    mbytes = C.c_size_t(0)
-    assert lib.mpcqp_model_bytes(C.byref(mdims), C.byref(mbytes)) == 0
-    L = Launch()
-    L.add("P", "in", F64, data=qp.P[0].reshape(1, -1))
-    L.add("G", "in", F64, data=qp.G[0].reshape(1, -1))
-    L.add("qb", "in", F64, data=qp.q.reshape(1, -1))
-    L.add("hb", "in", F64, data=qp.h.reshape(1, -1))
-    L.add("model", "scratch", U8, mbytes.value)
-    ops = {}
-    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", m)):
-        rows = w[key].reshape(w[key].shape[0], -1)
-        assert rows.shape == (B, width)
-        L.add(key, "in", F64, data=rows)
-        ops[key] = (width, mk if key == "e" else 0)
-    L.add("U", "out", F64, B * n)
-    L.add("lam", "out", F64, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.build()
-    ops = {key: _capi.Operand(L.ptr(key), bs, ks) for key, (bs, ks) in ops.items()}
-    o = _capi.SolveOpts()
-    o.flags = getattr(_capi, per_wave)
-
-    def go():
-        rc = lib.mpcqp_factor_model(C.byref(mdims), L.ptr("P"), L.ptr("G"), L.ptr("qb"), L.ptr("hb"), L.ptr("model"), mbytes.value,
-                                    stream())
-        if rc:
-            return rc
-        return lib.mpcqp_solve_model_bounds_batch(C.byref(mdims), L.ptr("model"), C.byref(ops["e"]), C.byref(ops["x0"]),
-                                                  C.byref(ops["goal"]), C.byref(ops["targets"]), B, C.byref(o), L.ptr("U"),
-                                                  L.ptr("lam"), L.ptr("status"), L.ptr("iters"), stream())
-
-    out = L.run(F, go)
-    out["U"], out["lam"] = out["U"].reshape(B, n), out["lam"].reshape(B, m)
+    for key, width in (("x0", nx), ("goal", nx), ("targets", N * nx), ("e", N * mk)):
+        assert w[key].reshape(w[key].shape[0], -1).shape == (OL.BATCH, width)
+    out = ModelCase(w, factor_in_arena=True).run(F, _flags([per_wave]))
     print(f"    model {shape} {per_wave}: status {out['status'].tolist()} iters {out['iters'].tolist()}")
     assert np.array_equal(out["status"], VC.MIXED_STATUS), out["status"]
     _no_plan(out, BAD, INFEASIBLE, f"model {shape}")
@@ -301,30 +251,13 @@ def test_shared_model_mixed(shape, per_wave):
 def test_dense_qp_mixed(n, m, f32, tol):
     """mpcqp_solve_batch at every size of tests/test_gpu_memory_discipline.py::test_dense_qp_solver (the small-problem kernel, the
     workgroup kernel and the workspace-resident solver), nine problems, the row pair written into G and h of items 1, 6 and 7."""
-    _capi, lib, stream = MD._api()
-    B = OL.BATCH
-    dtype = F32 if f32 else F64
     P, q, G, h = VC.dense_mixed(n, m)
-    nbytes = C.c_size_t(0)
-    assert lib.mpcqp_solve_workspace_bytes(n, m, _capi.F32 if f32 else _capi.F64, B, C.byref(nbytes)) == 0
-    L = Launch()
-    for key, arr in (("P", P), ("q", q), ("G", G), ("h", h)):
-        L.add(key, "in", dtype, data=arr.reshape(B, -1))
-    L.add("U", "out", dtype, B * n)
-    L.add("lam", "out", dtype, B * m)
-    L.add("status", "out", I32, B)
-    L.add("iters", "out", I32, B)
-    L.add("ws", "scratch", U8, nbytes.value)
-    L.build()
-    o = _capi.SolveOpts()
-    out = L.run(F, lambda: lib.mpcqp_solve_batch(n, m, _capi.F32 if f32 else _capi.F64, L.ptr("P"), L.ptr("q"), L.ptr("G"), L.ptr("h"),
-                                                 B, C.byref(o), L.ptr("U"), L.ptr("lam"), L.ptr("status"), L.ptr("iters"), L.ptr("ws"),
-                                                 nbytes.value, stream()))
-    out["U"] = out["U"].reshape(B, n)
+    assert len(q) == OL.BATCH
+    out = QPs(P, q, G, h, dtype=F32 if f32 else F64, workspace=True).run(F, 0)
     print(f"    dense QP n {n} m {m}: status {out['status'].tolist()} iters {out['iters'].tolist()}")
     assert np.array_equal(out["status"], VC.MIXED_STATUS), out["status"]
     _no_plan(out, BAD, INFEASIBLE, f"dense QP {n} {m}")
-    ref = MD.f32_view(dict(P=P, q=q, G=G, h=h)) if f32 else dict(P=P, q=q, G=G, h=h)
+    ref = GL.f32_view(dict(P=P, q=q, G=G, h=h)) if f32 else dict(P=P, q=q, G=G, h=h)
     for b in GOOD:
         xo, _, so, _ = oracle.gi_solve(ref["P"][b], ref["q"][b], ref["G"][b], ref["h"][b])
         assert so == 0

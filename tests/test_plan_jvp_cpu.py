@@ -3,7 +3,6 @@
 duality with the VJP restatement (tests/adjoint_np.py), the LQR gain on an unconstrained plan, and the C exports and
 Python surface of the feature."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -11,19 +10,12 @@ import pytest
 
 import adjoint_np as AN
 import tangent_np as TN
+from host_helpers import _dims, _header, _lib, _ltv
 from qpmpc_amd import _capi
 from qpmpc_amd import workloads as W
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 EXPORTS = ("mpcqp_plan_jvp_workspace_bytes", "mpcqp_plan_jvp_batch")
-
-
-def _ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _check_against_fd(w, rng, need):
@@ -95,11 +87,6 @@ def test_unconstrained_first_step_jacobian_is_the_lqr_gain():
 
 # ---------------------------------------------------------------- public surface
 
-def _header() -> str:
-    with open(os.path.join(ROOT, "include", "mpcqp.h")) as f:
-        return f.read()
-
-
 def test_exports_declared_and_bound():
     declared = set(re.findall(r"(mpcqp_[a-z_]+)\(", _header()))
     for name in EXPORTS:
@@ -112,21 +99,6 @@ def test_exports_declared_and_bound():
     lib = _lib()
     for name in EXPORTS:
         assert hasattr(lib, name)
-
-
-def _lib():
-    from qpmpc_amd import build
-
-    if not os.path.exists(build.LIB_PATH):
-        pytest.fail("the library is not built (__graft_entry__.build())")
-    return _capi.load()
-
-
-def _dims(nx, nu, N, mk, dtype=_capi.F64):
-    d = _capi.Dims()
-    d.nx, d.nu, d.N, d.mk, d.dtype, d.flags = nx, nu, N, mk, dtype, 0
-    d.w_terminal, d.w_stage, d.w_input = 1.0, 0.0, 1e-3
-    return d
 
 
 def _query(dims, batch, ntan):

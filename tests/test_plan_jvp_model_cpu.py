@@ -4,7 +4,6 @@ oracle's solve along a joint tangent of every operand, the stage-wise restatemen
 against it, and the C exports and Python surface of the feature."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
@@ -15,21 +14,14 @@ import adjoint_np as AN
 import tangent_model_np as TM
 import tangent_model_stagewise_np as TMS
 import tangent_np as TN
+from host_helpers import _dims, _header, _lib, _ltv
 from qpmpc_amd import _capi
 from qpmpc_amd import workloads as W
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 EXPORTS = ("mpcqp_plan_jvp_model_workspace_bytes", "mpcqp_plan_jvp_model_batch",
            "mpcqp_plan_jvp_model_stagewise_workspace_bytes", "mpcqp_plan_jvp_model_stagewise_batch")
 EINVAL, EDTYPE, EWORKSPACE, EUNSUPPORTED = -1, -3, _capi.EWORKSPACE, -6
-
-
-def _ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _p_only():
@@ -208,19 +200,6 @@ def test_stagewise_q_flag_combinations():
 
 # ---------------------------------------------------------------- public surface
 
-def _header() -> str:
-    with open(os.path.join(ROOT, "include", "mpcqp.h")) as f:
-        return f.read()
-
-
-def _lib():
-    from qpmpc_amd import build
-
-    if not os.path.exists(build.LIB_PATH):
-        pytest.fail("the library is not built (__graft_entry__.build())")
-    return _capi.load()
-
-
 def test_exports_declared_bound_and_built():
     declared = set(re.findall(r"(mpcqp_[a-z_]+)\(", _header()))
     lib = _lib()
@@ -235,13 +214,6 @@ def test_exports_declared_bound_and_built():
                                                        "dtargets_stride", "de_stride"]
     assert _capi.ABI_VERSION == 12 and lib.mpcqp_abi_version() == 12
     assert "#define MPCQP_ABI_VERSION 12" in _header()
-
-
-def _dims(nx, nu, N, mk, dtype=_capi.F64):
-    d = _capi.Dims()
-    d.nx, d.nu, d.N, d.mk, d.dtype, d.flags = nx, nu, N, mk, dtype, 0
-    d.w_terminal, d.w_stage, d.w_input = 1.0, 0.0, 1e-3
-    return d
 
 
 def _query(dims, batch, ntan):

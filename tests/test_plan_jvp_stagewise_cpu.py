@@ -4,7 +4,6 @@ adjoint's restatement, central differences of the C oracle beyond n = 128, the R
 surface of the feature."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
@@ -14,20 +13,13 @@ import adjoint_np as AN
 import adjoint_stagewise_np as AS
 import tangent_np as TN
 import tangent_stagewise_np as TS
+from host_helpers import _dims, _header, _lib, _ltv
 from qpmpc_amd import _capi
 from qpmpc_amd import workloads as W
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 EXPORTS = ("mpcqp_plan_jvp_stagewise_workspace_bytes", "mpcqp_plan_jvp_stagewise_batch")
 EINVAL, EDTYPE, EWORKSPACE, EUNSUPPORTED = -1, -3, _capi.EWORKSPACE, -6
-
-
-def _ltv(seed, B, nx, nu, N, mk, tight=1.0):
-    from qpmpc_amd.workloads import random_ltv
-
-    return random_ltv(np.random.default_rng(seed), B, nx, nu, N, mk, tight)
 
 
 def _tangents(w1, rng):
@@ -188,19 +180,6 @@ def test_no_active_row_first_step_jacobian_is_the_riccati_gain_n256():
 
 # ---------------------------------------------------------------- public surface
 
-def _header() -> str:
-    with open(os.path.join(ROOT, "include", "mpcqp.h")) as f:
-        return f.read()
-
-
-def _lib():
-    from qpmpc_amd import build
-
-    if not os.path.exists(build.LIB_PATH):
-        pytest.fail("the library is not built (__graft_entry__.build())")
-    return _capi.load()
-
-
 def test_exports_declared_bound_and_built():
     declared = set(re.findall(r"(mpcqp_[a-z_]+)\(", _header()))
     lib = _lib()
@@ -210,13 +189,6 @@ def test_exports_declared_bound_and_built():
         assert hasattr(lib, name)
     assert _capi.ABI_VERSION == 12 and lib.mpcqp_abi_version() == 12
     assert "#define MPCQP_ABI_VERSION 12" in _header()
-
-
-def _dims(nx, nu, N, mk, dtype=_capi.F64):
-    d = _capi.Dims()
-    d.nx, d.nu, d.N, d.mk, d.dtype, d.flags = nx, nu, N, mk, dtype, 0
-    d.w_terminal, d.w_stage, d.w_input = 1.0, 0.0, 1e-3
-    return d
 
 
 def _query(dims, batch, max_active, ntan):

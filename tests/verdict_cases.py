@@ -168,7 +168,7 @@ def model_mixed(shape):
 
 # ---------------------------------------------------------------------------------------------- the dense-QP export
 def dense_mixed(n, m):
-    """(P, q, G, h) of nine dense QPs drawn like tests/test_gpu_memory_discipline.py::_dense_qps (h > 0: x = 0 is feasible), rows 0 and 1
+    """(P, q, G, h) of nine dense QPs drawn like tests/guarded_launch.py::_dense_qps (h > 0: x = 0 is feasible), rows 0 and 1
     of items INFEASIBLE overwritten: G_1 = -G_0, h_0 = h_1 = -1"""
     rng = np.random.default_rng(n + m)
     Ps, qs, Gs, hs = [], [], [], []

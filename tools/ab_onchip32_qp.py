@@ -2,7 +2,7 @@
 """Dev: the QP-given mode of csrc/mpcqp_duo.hip (mpcqp_solve_batch with MPCQP_OPT_ON_CHIP_32: dense QPs of up to 32 variables and 64
 rows on chip, two problems per wavefront) against the same export without the flag -- the one-per-wavefront kernel up to sixteen
 variables, the workgroup kernel beyond --, in one process, on the same seeded problems. Dense QPs are drawn like
-tests/test_gpu_memory_discipline.py::_dense_qps (P = M M' / n + 0.1 I, G ~ N(0, 1), h > 0: x = 0 is feasible), on the device from a
+tests/guarded_launch.py::_dense_qps (P = M M' / n + 0.1 I, G ~ N(0, 1), h > 0: x = 0 is feasible), on the device from a
 seeded generator. MPC batches (random_ltv at tightness 0.3) are condensed by BatchMPCQP; the condense launch is timed apart
 (mpcqp_condense_batch on kept buffers), and solve_mpc_batch's own route for the same problems (PreparedSolve, one launch) is timed
 next to the two launches.
