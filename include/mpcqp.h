@@ -877,6 +877,60 @@ int mpcqp_model_periods_vjp_batch(const MpcqpDims *dims, const void *model, cons
                                   const MpcqpPeriodGrad *g_goal, const MpcqpPeriodGrad *g_targets, void *g_A, void *g_B,
                                   int32_t *vjp_status, void *stream);
 
+/* The Jacobian-vector products of those closed loops, one launch for all periods and all tangents (an additive part of ABI
+ * 12: MPCQP_ABI_VERSION is unchanged): the forward-time recursion through `nperiods` periods of every loop, each period the
+ * KKT tangent of mpcqp_model_jvp_batch on the factored model with dh = -Hx dx_t (the model's own bounds do not move). With
+ * the loop, the maps L, M, Wx, Wg, Wt, Hx and the active-set rule of mpcqp_model_periods_vjp_batch above, and tangents dx0,
+ * dgoal_t, dtargets_t, dd_t (the disturbance), dA and dB (the plant): dx_0 = dx0, and for t = 0 .. P-1
+ *     status[b][t] == 0, A_t = {i : lam_i > 0}, k = |A_t| <= n, S = M_A M_A' positive definite:
+ *         r = -(Wx dx_t - Wg dgoal_t - Wt dtargets_t);   mu = S^-1 (M_A r + Hx_A dx_t)
+ *         du0_t = the first nu entries of L^-T (r - M_A' mu)
+ *     otherwise du0_t = 0 (no plan: the tangent passes through the plant only; a failed S or k > n: likewise, and the
+ *     period is counted in jvp_status)
+ *     dx_{t+1} = A dx_t + B du0_t + dd_t + dA x_t + dB u0_t
+ * ("Closed-loop forward sensitivities"). It is the transpose of mpcqp_model_periods_vjp_batch on the
+ * same lam and status: <gX, dX> + <gU0, dU0> = <g, tangents>, and jvp_status equals vjp_status. S of a period is factored
+ * ONCE and every tangent reuses the factor: sixteen lanes per loop, four loops per wavefront, the period loop inside the
+ * kernel, lane l carrying component l of dx of up to sixteen tangents in registers (ntan > 16: the period loop runs again
+ * per chunk of sixteen); no workspace, no allocation, no synchronisation. The reference has no counterpart: its closed loops
+ * are Python loops over NumPy plans (examples/wheeled_inverted_pendulum.py:99-118,
+ * examples/lipm_walking_controller.py:304-333) and carry no derivative.
+ * A tangent of a reference or of the disturbance, per loop or shared, per period or constant in time: */
+typedef struct MpcqpPeriodTangent {   /* [B|1][ntan][P|1][w] */
+    const void *ptr;                  /* NULL = zero */
+    int64_t batch_stride;             /* elements from loop to loop; 0 = one set shared by the batch */
+    int64_t tangent_stride;           /* elements from tangent to tangent */
+    int64_t period_stride;            /* elements from period to period; 0 = the same in every period */
+} MpcqpPeriodTangent;
+
+typedef struct MpcqpLoopTangents {
+    const void *dx0; int64_t dx0_stride;     /* [B|1][ntan][nx], as MpcqpTangents */
+    MpcqpPeriodTangent dgoal, dtargets, dd;  /* w = nx, N nx, nx */
+    const void *dA;  int64_t dA_stride;      /* [B|1][ntan][nx][nx] */
+    const void *dB;  int64_t dB_stride;      /* [B|1][ntan][nx][nu] */
+} MpcqpLoopTangents;
+
+/* Inputs: lam [batch][nperiods][m] and status [batch][nperiods], EVERY period's, as for the VJP; X [batch][nperiods+1][nx]
+ * and U0 [batch][nperiods][nu], the loop's records, read only with dA / dB and nullable with them; `plant`: A and B as
+ * mpcqp_model_periods_batch takes them, d is not read; `tan`: every pointer nullable, NULL = zero (a stride of 0 shares one
+ * set with the batch). Terms follow dims->flags: a dgoal or dtargets whose operand does not enter q is not read.
+ * Outputs: dX [batch][ntan][nperiods+1][nx] (required), dx_0 .. dx_P of every tangent; dU0 [batch][ntan][nperiods][nu]
+ * (nullable); jvp_status [batch] (nullable): the NUMBER of periods with a plan whose S failed the pivot test (the plain
+ * one, pivot > 0, of mpcqp_model_periods_vjp_batch) or that had more active rows than variables.
+ * A model whose factorisation failed gives zeros everywhere and jvp_status = nperiods. batch == 0 launches nothing.
+ * Checks, before anything is launched, in this order: MPCQP_EDTYPE unless float64; MPCQP_EUNSUPPORTED outside
+ * n = N nu <= 16, 1 <= m = N mk <= 32, nx <= 16; MPCQP_EINVAL for a NULL model, plant (or its A / B), lam, status, tan or
+ * dX, nperiods < 1, batch < 0, ntan outside 1 .. 256, a negative stride, or dA / dB without X / U0. */
+int mpcqp_model_periods_jvp_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant,
+                                  int64_t batch, int32_t nperiods, int32_t ntan,
+                                  const void *lam, const int32_t *status,   /* every period's, as for the VJP */
+                                  const void *X, const void *U0,            /* records; read only with dA / dB */
+                                  const MpcqpLoopTangents *tan,
+                                  void *dX,                                  /* [batch][ntan][nperiods+1][nx], required */
+                                  void *dU0,                                 /* [batch][ntan][nperiods][nu], nullable */
+                                  int32_t *jvp_status,                       /* [batch], nullable: counted periods */
+                                  void *stream);
+
 /* Bookkeeping of closed loops (the reference's loops count nothing; ours report failures and iterations):
  * stats[0] += number of problems with status != 0, stats[1] += sum of iters. stats: two int64 in DEVICE memory. */
 int mpcqp_accumulate_stats(const int32_t *status, const int32_t *iters, int64_t batch, int64_t *stats, void *stream);

@@ -7,7 +7,8 @@ reason this package exists: ``BatchMPCProblem``, ``solve_mpc_batch``,
 carry gradients to x0, goal, targets and e, and ``plan_jvp`` / ``plan_jacobian``, their forward sensitivities, condensed
 (n <= 128) or, with ``formulation="stagewise"``, at any horizon, along tangents of the model matrices and the cost weights too
 (extensions: the reference has no gradients). ``closed_loop_diff`` carries gradients through whole closed loops of a
-``SharedModel`` (``ModelClosedLoop``), forward and backward one launch each.
+``SharedModel`` (``ModelClosedLoop``), forward and backward one launch each; ``closed_loop_jvp`` / ``closed_loop_jacobian`` are
+their forward sensitivities, every period and tangent in one launch.
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of
 ``include/mpcqp.h``; without the compiled library or without a GPU every
@@ -27,7 +28,7 @@ from .batch import (  # noqa: F401
     solve_qp_batch,
 )
 from .closed_loop import ModelClosedLoop  # noqa: F401
-from .loop_diff import closed_loop_diff  # noqa: F401
+from .loop_diff import closed_loop_diff, closed_loop_jacobian, closed_loop_jvp  # noqa: F401
 from .autodiff import plan_jacobian, plan_jvp, solve_mpc_batch_diff  # noqa: F401
 from .exceptions import (  # noqa: F401
     BackendError,
@@ -55,6 +56,8 @@ __all__ = [
     "PreparedModelSolve",
     "ModelClosedLoop",
     "closed_loop_diff",
+    "closed_loop_jvp",
+    "closed_loop_jacobian",
     "pairing_order",
     "solve_mpc_batch",
     "solve_qp_batch",

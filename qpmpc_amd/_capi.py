@@ -72,6 +72,7 @@ EXPORTS = (
     "mpcqp_model_jvp_batch",
     "mpcqp_model_periods_batch",
     "mpcqp_model_periods_vjp_batch",
+    "mpcqp_model_periods_jvp_batch",
 )
 
 
@@ -115,6 +116,16 @@ class LoopOut(C.Structure):
 
 class PeriodGrad(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("batch_stride", C.c_int64), ("period_stride", C.c_int64)]
+
+
+class PeriodTangent(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("batch_stride", C.c_int64), ("tangent_stride", C.c_int64), ("period_stride", C.c_int64)]
+
+
+class LoopTangents(C.Structure):
+    _fields_ = [("dx0", C.c_void_p), ("dx0_stride", C.c_int64), ("dgoal", PeriodTangent), ("dtargets", PeriodTangent),
+                ("dd", PeriodTangent), ("dA", C.c_void_p), ("dA_stride", C.c_int64), ("dB", C.c_void_p),
+                ("dB_stride", C.c_int64)]
 
 
 class SolveOpts(C.Structure):
@@ -270,6 +281,9 @@ def load():
     lib.mpcqp_model_periods_vjp_batch.argtypes = [C.POINTER(Dims), vp, C.POINTER(LoopPlant), i64, C.c_int32, vp, vp, vp, vp,
                                                   vp, vp, vp, vp, C.POINTER(PeriodGrad), C.POINTER(PeriodGrad), vp, vp,
                                                   vp, vp]
+    lib.mpcqp_model_periods_jvp_batch.restype = C.c_int
+    lib.mpcqp_model_periods_jvp_batch.argtypes = [C.POINTER(Dims), vp, C.POINTER(LoopPlant), i64, C.c_int32, C.c_int32, vp, vp,
+                                                  vp, vp, C.POINTER(LoopTangents), vp, vp, vp, vp]
     del i32p
     if lib.mpcqp_abi_version() != ABI_VERSION:
         raise BackendError(f"ABI mismatch: library {lib.mpcqp_abi_version()} != binding {ABI_VERSION}")

@@ -18,7 +18,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 _UNITS = ("mpcqp_lds.hip", "mpcqp_w64.hip", "mpcqp_pair.hip", "mpcqp_quad.hip", "mpcqp_quadw.hip", "mpcqp_quadg.hip", "mpcqp_quadgw.hip", "mpcqp_duo.hip", "mpcqp_big.hip", "mpcqp_bigsolve.hip",
           "mpcqp_model.hip", "mpcqp_stage.hip", "mpcqp_stagew.hip", "mpcqp_stageg.hip", "mpcqp_adjoint.hip", "mpcqp_adjoint_stagewise.hip",
-          "mpcqp_model_adjoint.hip", "mpcqp_capi.hip")
+          "mpcqp_model_adjoint.hip", "mpcqp_loop_tangent.hip", "mpcqp_capi.hip")
 SOURCES = [os.path.join(_PKG, "csrc", f) for f in _UNITS]
 # units that include another unit's source (mpcqp_quadw.hip compiles the wide instantiations of mpcqp_quad.hip): rebuilt with it
 _INCLUDES = {"mpcqp_quadw.hip": ("mpcqp_quad.hip",), "mpcqp_quadgw.hip": ("mpcqp_quadg.hip",)}

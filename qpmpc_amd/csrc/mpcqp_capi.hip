@@ -1804,6 +1804,49 @@ int mpcqp_model_periods_vjp_batch(const MpcqpDims *dims, const void *model, cons
     return launch_loop_adjoint_small(l, (hipStream_t)stream);
 }
 
+int mpcqp_model_periods_jvp_batch(const MpcqpDims *dims, const void *model, const MpcqpLoopPlant *plant, int64_t batch,
+                                  int32_t nperiods, int32_t ntan, const void *lam, const int32_t *status, const void *X,
+                                  const void *U0, const MpcqpLoopTangents *tan, void *dX, void *dU0, int32_t *jvp_status,
+                                  void *stream)
+{
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    if (dims->dtype != MPCQP_F64) return MPCQP_EDTYPE;
+    const int64_t n = (int64_t)dims->N * dims->nu, m = (int64_t)dims->N * dims->mk;
+    if (n > 16 || m < 1 || m > 32 || dims->nx > 16) return MPCQP_EUNSUPPORTED;  // mpcqp_model_periods_vjp_batch's envelope
+    if (!model || !plant || !plant->A.ptr || !plant->B.ptr || !lam || !status || !tan || !dX || nperiods < 1 || batch < 0 ||
+        ntan < 1 || ntan > 256)
+        return MPCQP_EINVAL;
+    if (plant->A.batch_stride < 0 || plant->B.batch_stride < 0) return MPCQP_EINVAL;
+    if (tan->dx0_stride < 0 || tan->dA_stride < 0 || tan->dB_stride < 0) return MPCQP_EINVAL;
+    for (const MpcqpPeriodTangent *p : {&tan->dgoal, &tan->dtargets, &tan->dd})
+        if (p->batch_stride < 0 || p->tangent_stride < 0 || p->period_stride < 0) return MPCQP_EINVAL;
+    if ((tan->dA && !X) || (tan->dB && !U0)) return MPCQP_EINVAL;
+    if (batch == 0) return 0;
+    LoopTangentLaunch l{};
+    l.nx = dims->nx;
+    l.nu = dims->nu;
+    l.N = dims->N;
+    l.n = (int)n;
+    l.m = (int)m;
+    l.flags = dims->flags;
+    l.nperiods = nperiods;
+    l.ntan = ntan;
+    l.batch = batch;
+    l.model = (const double *)model;
+    l.A = plant->A;
+    l.B = plant->B;
+    l.lam = (const double *)lam;
+    l.status = status;
+    l.X = (const double *)X;
+    l.U0 = (const double *)U0;
+    l.tan = *tan;
+    l.dX = (double *)dX;
+    l.dU0 = (double *)dU0;
+    l.out_status = jvp_status;
+    return launch_loop_tangent_small(l, (hipStream_t)stream);
+}
+
 int mpcqp_wip_advance_stats_batch(int32_t dtype, void *states, const void *U, int64_t u_stride, const int32_t *status,
                                   const int32_t *iters, int64_t *stats, int32_t N, double sampling_period,
                                   double target_vel, double length, double gravity, int32_t nsub, void *x0, void *goal,

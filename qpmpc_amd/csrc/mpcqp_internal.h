@@ -396,6 +396,21 @@ struct LoopAdjointLaunch {
     int32_t *out_status;               // nullable
 };
 int launch_loop_adjoint_small(const LoopAdjointLaunch &l, hipStream_t st);
+// the tangents of those closed loops (mpcqp_model_periods_jvp_batch; mpcqp_loop_tangent.hip, mpcqp_loop_tangent_small_kernel:
+// the same layout and envelope, the period loop running forwards inside); passed to the kernel as it is
+struct LoopTangentLaunch {
+    int nx, nu, N, n, m, flags, nperiods, ntan;
+    int64_t batch;
+    const double *model;
+    MpcqpOperand A, B;                 // the plant (batch_stride 0: shared)
+    const double *lam;                 // [batch][nperiods][m]
+    const int32_t *status;             // [batch][nperiods]
+    const double *X, *U0;              // the records; read with dA / dB only (else null)
+    MpcqpLoopTangents tan;             // every pointer nullable: zero
+    double *dX, *dU0;                  // dU0 nullable
+    int32_t *out_status;               // nullable
+};
+int launch_loop_tangent_small(const LoopTangentLaunch &l, hipStream_t st);
 
 }  // namespace mpcqp
 #endif

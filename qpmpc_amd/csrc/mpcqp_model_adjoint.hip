@@ -29,6 +29,7 @@
 #include "mpcqp_internal.h"
 #include "mpcqp_lane.h"
 #include "mpcqp_adjoint_common.h"
+#include "mpcqp_model_small.h"
 
 namespace mpcqp {
 
@@ -40,27 +41,7 @@ __device__ inline const double *tangent_of(const void *p, int64_t stride, int64_
 }
 
 // ------------------------------------------------------------------------------------------------ small models
-// LDS image of the shared matrices, in doubles: M [m][16], L^-T [16][16], Wx [16][nx], Wg [16][nx], Wt [16][N nx],
-// Hx [m][nx]
-struct SmallImage {
-    int M, Lt, Wx, Wg, Wt, Hx, total;
-};
-__host__ __device__ inline SmallImage make_small_image(int nx, int N, int m)
-{
-    SmallImage s{};
-    s.M = 0;
-    s.Lt = s.M + m * 16;
-    s.Wx = s.Lt + 256;
-    s.Wg = s.Wx + 16 * nx;
-    s.Wt = s.Wg + 16 * nx;
-    s.Hx = s.Wt + 16 * N * nx;
-    s.total = s.Hx + m * nx;
-    return s;
-}
-
-constexpr int kSmallThreads = 256;                       // four wavefronts,
-constexpr int kSmallPerBlock = kSmallThreads / 16;       // sixteen problems per round of a workgroup
-
+// (the LDS image, the workgroup shape, SmallKkt and the grid: mpcqp_model_small.h)
 // Sixteen lanes per problem: lane l of a row is variable l (t, w~, r, dU), active slot l (its row of S, nu, mu), state
 // component l (costate, rollout, the nx-wide outputs) and inequality rows l and l + 16. A problem that is not solved, or
 // a row past the end of the batch, takes every wavefront-wide step with zeros: there is no return before the last one.
@@ -323,127 +304,7 @@ __global__ void __launch_bounds__(kSmallThreads) mpcqp_model_diff_small_kernel(c
 }
 
 // ------------------------------------------------------------------------------------------------ closed loops
-// The KKT block of one problem on its sixteen lanes, as mpcqp_model_diff_small_kernel has it inline, in a struct: the
-// active rows' ids (slot i takes the i-th set bit of lam > 0, two ballots), this slot's row `ma` of M_A, S = M_A M_A' with
-// row `l` on lane l, its in-place lower Cholesky factor, and the products and solves with them. `l` is the lane within the
-// row of sixteen, `g` the row within the wavefront; every loop over slots stops at kmax, the largest k of the wavefront's
-// four problems, so every member is called by the whole wavefront. (The kernel above keeps its own text: built on this
-// struct it compiled to 202 / 168 VGPRs, not the 204 / 169 of profiles/model_diff_kernel_resources.txt; DESIGN.md
-// section 9, "Closed-loop adjoint".)
-struct SmallKkt {
-    unsigned act;     // bit r: row r is active
-    int k, kmax, id;  // active rows; this slot's row (0 past the k-th: its products are masked)
-    double dinv;
-    double ma[16], S[16];
-
-    // -> false when more rows are active than there are variables (not a vertex's multipliers): k is then 0
-    __device__ __forceinline__ bool build(const double *Mm, const double *lam, bool live, int l, int g, int n, int m)
-    {
-        const bool a0 = live && l < m && lam[l] > 0.0, a1 = live && l + 16 < m && lam[l + 16] > 0.0;
-        const unsigned long long m0 = __ballot(a0), m1 = __ballot(a1);
-        act = (unsigned)((m0 >> (16 * g)) & 0xffffull) | ((unsigned)((m1 >> (16 * g)) & 0xffffull) << 16);
-        k = __popc(act);
-        const bool fits = k <= n;
-        if (!fits) k = 0;
-        id = 0;
-        {
-            unsigned x = act;
-            for (int s = 0; s < 15; ++s)
-                if (s < l) x &= x - 1;
-            if (l < k) id = __builtin_ctz(x);
-        }
-        kmax = max(max(lane_get(k, 0), lane_get(k, 16)), max(lane_get(k, 32), lane_get(k, 48)));
-#pragma unroll
-        for (int c = 0; c < 16; ++c) ma[c] = l < k ? Mm[id * 16 + c] : 0.0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            S[c] = 0.0;
-            if (c < kmax) {
-                const int idc = __shfl(id, c, 16);
-                const double *mc = Mm + idc * 16;
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) acc += ma[j] * mc[j];
-                S[c] = (c < k) ? acc : 0.0;
-            }
-        }
-        return fits;
-    }
-
-    // in-place lower Cholesky, the pivot test of chol_lower (mpcqp_adjoint_common.h) -> false when a pivot fails
-    __device__ __forceinline__ bool factor(int l)
-    {
-        bool bad = false;
-        dinv = 0.0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (j < kmax) {
-                const double d = __shfl(S[j], j, 16);
-                const bool in = j < k;
-                if (in && !(d > 0.0)) bad = true;
-                const bool ok = in && !bad;
-                const double sd = ok ? sqrt(d) : 1.0, inv = ok ? 1.0 / sd : 0.0;
-                if (l == j) dinv = inv;
-                const double lij = (l == j) ? sd : S[j] * inv;
-                S[j] = lij;
-#pragma unroll
-                for (int c = j + 1; c < 16; ++c) {
-                    if (c < kmax) {
-                        const double lcj = __shfl(lij, c, 16);
-                        S[c] -= lij * lcj;
-                    }
-                }
-            }
-        }
-        return !bad;
-    }
-
-    // x <- S^-1 x for the slot-distributed x
-    __device__ __forceinline__ double solve(double x, int l) const
-    {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (j < kmax) {
-                if (l == j) x *= dinv;
-                const double xj = __shfl(x, j, 16);
-                if (l > j) x -= S[j] * xj;
-            }
-        }
-#pragma unroll
-        for (int j = 15; j >= 0; --j) {
-            if (j < kmax) {
-                const double s = row_sum_dpp((l > j && l < k) ? S[j] * x : 0.0);
-                if (l == j) x = (x - s) * dinv;
-            }
-        }
-        return (l < k) ? x : 0.0;
-    }
-
-    // y_l = sum_i M[id_i][l] x_i for the slot-distributed x
-    __device__ __forceinline__ double rows_t(const double *Mm, double x, int l) const
-    {
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            if (i < kmax) {
-                const int idi = __shfl(id, i, 16);
-                const double xi = __shfl(x, i, 16);
-                acc += Mm[idi * 16 + l] * xi;
-            }
-        }
-        return acc;
-    }
-
-    // sum_c ma[c] v_c for the variable-distributed v
-    __device__ __forceinline__ double rows(double v) const
-    {
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) acc += ma[c] * __shfl(v, c, 16);
-        return acc;
-    }
-};
-
+// (SmallKkt, the KKT block of one problem on its sixteen lanes: mpcqp_model_small.h)
 // mpcqp_model_periods_vjp_batch: the layout of the kernel above -- sixteen lanes per LOOP, four loops per wavefront, the LDS
 // image staged once per workgroup, workgroups striding over the batch -- with the period loop running backwards inside. Lane
 // l of a row carries component l of the costate `cs`, row l of g_A and g_B, component l of the period-summed g_goal and
@@ -814,12 +675,6 @@ __global__ void __launch_bounds__(kGeneralThreads) mpcqp_model_diff_general_kern
 }  // namespace
 
 bool model_diff_small_applies(int nx, int n, int m) { return n <= 16 && m <= 32 && nx <= 16; }
-
-static int model_diff_small_grid(int64_t batch)
-{
-    const int64_t blocks = (batch + kSmallPerBlock - 1) / kSmallPerBlock;
-    return (int)(blocks < kModelDiffMaxGrid ? blocks : kModelDiffMaxGrid);
-}
 
 int launch_model_diff_small(const ModelDiffLaunch &l, hipStream_t st)
 {

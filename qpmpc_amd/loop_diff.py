@@ -8,6 +8,11 @@ The fused forward keeps only the last period's multipliers, so the recorded stat
 ``mpcqp_solve_model_batch`` launch over all ``B * P`` (loop, period) pairs, fully parallel -- and that replay's multipliers
 and statuses feed the backward.
 
+Forward mode is ``closed_loop_jvp`` / ``closed_loop_jacobian``: the same forward and replay, then one
+``mpcqp_model_periods_jvp_batch`` launch -- the forward-time recursion through the periods for every tangent, each period's
+active rows factored once (qpmpc_amd/csrc/mpcqp_loop_tangent.hip, ``mpcqp_loop_tangent_small_kernel``; DESIGN.md section 9,
+"Closed-loop forward sensitivities"). ``closed_loop_diff`` serves ``torch.autograd.forward_ad`` duals through it.
+
 The reference has no counterpart: its closed loops are Python loops over NumPy plans.
 """
 from __future__ import annotations
@@ -15,9 +20,9 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _capi
-from .autodiff import _detached, _ptr, _reduce
+from .autodiff import MAX_TANGENTS, _detached, _is_dual, _ptr, _reduce
 from .batch import _stream_ptr
-from .exceptions import BackendError
+from .exceptions import BackendError, ProblemDefinitionError
 
 OPERANDS = ("x0", "goal", "targets", "disturbance", "Ap", "Bp")
 
@@ -38,12 +43,14 @@ class LoopDiffInfo:
     ``vjp_status``    int32 ``[B]`` after a backward, None before: per loop the number of periods with a plan whose active
                       rows' Gram matrix failed the pivot test or that had more active rows than variables (such a period
                       contributes its plant term only)
+    ``jvp_status``    int32 ``[B]`` after a forward-mode pass (``closed_loop_jvp``, ``closed_loop_jacobian``, a ``forward_ad``
+                      dual), None otherwise: the same count as ``vjp_status``, by ``mpcqp_model_periods_jvp_batch``
     ``replay_error``  0-d float64, ``max |U0_replay - U0| / max(1, |U0|)``: how far the replayed solves' first inputs are
                       from the recorded ones (None when nothing was replayed)
     ``loop``          the ``ModelClosedLoop`` that ran the forward (``fused=True``)"""
 
     def __init__(self):
-        self.status = self.failed = self.vjp_status = self.replay_error = self.loop = None
+        self.status = self.failed = self.vjp_status = self.jvp_status = self.replay_error = self.loop = None
         self._plans = None
 
     def _by_hand_vjp_status(self):
@@ -137,6 +144,75 @@ def loop_vjp(model, loop, lam, status, X, U0, gX, gU0, want):
     return out, vjp_status
 
 
+TANGENTS = ("d_x0", "d_goal", "d_targets", "d_disturbance", "d_Ap", "d_Bp")
+
+
+def _loop_tangents(tangents, B, P, nx, nu, N, device):
+    """The six tangents (the order of TANGENTS, None = zero) as contiguous float64 tensors -> (list, T). A tangent is
+    ``[B|1, T, *tail]``; one of a reference may carry a period axis, ``[B|1, T, P' >= P, w]``, or none (constant in time)."""
+    torch = _torch()
+    tails = ((nx,), (nx,), (N * nx,), (nx,), (nx, nx), (nx, nu))
+    out, Ts = [], set()
+    for name, v, tail in zip(TANGENTS, tangents, tails):
+        if v is None:
+            out.append(None)
+            continue
+        v = torch.as_tensor(v, device=device).to(torch.float64)
+        periodic = name in ("d_goal", "d_targets", "d_disturbance") and v.dim() == 4
+        want = 2 + len(tail) + int(periodic)
+        if (v.dim() != want or tuple(v.shape[-len(tail):]) != tail or v.shape[0] not in (1, B) or v.shape[1] < 1
+                or (periodic and v.shape[2] < P)):
+            shape = ", ".join(str(d) for d in tail)
+            raise ProblemDefinitionError(
+                f"{name}: tangent of shape {tuple(v.shape)} is not [{B}|1, T, {shape}]"
+                + (f" or [{B}|1, T, P >= {P}, {shape}]" if len(tail) == 1 and name != "d_x0" else ""))
+        Ts.add(v.shape[1])
+        out.append(v.contiguous())
+    if not Ts:
+        raise ProblemDefinitionError("closed_loop_jvp: no tangent given")
+    if len(Ts) > 1:
+        raise ProblemDefinitionError(f"closed_loop_jvp: the tangents disagree on T: {sorted(Ts)}")
+    T = Ts.pop()
+    if T > MAX_TANGENTS:
+        raise ProblemDefinitionError(f"closed_loop_jvp: T = {T} tangents, at most {MAX_TANGENTS} per call")
+    return out, T
+
+
+def loop_jvp(model, loop, lam, status, X, U0, tangents):
+    """One ``mpcqp_model_periods_jvp_batch`` launch. ``tangents``: what ``_loop_tangents`` returned.
+    -> (dX [B, T, P+1, nx], dU0 [B, T, P, nu], jvp_status [B]), float64."""
+    torch = _torch()
+    lib = _capi.load()
+    tans, T = tangents
+    B, P, nx, nu = loop.batch, U0.shape[1], loop.nx, loop.nu
+    f64 = dict(dtype=torch.float64, device=X.device)
+    dX, dU0 = torch.empty((B, T, P + 1, nx), **f64), torch.empty((B, T, P, nu), **f64)
+    jvp_status = torch.empty((B,), dtype=torch.int32, device=X.device)
+    shared = lambda v: v.shape[0] == 1 and B > 1  # noqa: E731
+
+    def flat(v):
+        return (None, 0) if v is None else (v.data_ptr(), 0 if shared(v) else v[0].numel())
+
+    def periodic(v):
+        if v is None:
+            return _capi.PeriodTangent(None, 0, 0, 0)
+        return _capi.PeriodTangent(v.data_ptr(), 0 if shared(v) else v[0].numel(), v[0, 0].numel(),
+                                   v.shape[-1] if v.dim() == 4 else 0)
+
+    d_x0, d_goal, d_targets, d_dist, d_Ap, d_Bp = tans
+    tan = _capi.LoopTangents(*flat(d_x0), periodic(d_goal), periodic(d_targets), periodic(d_dist), *flat(d_Ap), *flat(d_Bp))
+    plant = _capi.LoopPlant(_capi.Operand(loop._Ap.data_ptr(), nx * nx if loop._Ap.ndim == 3 else 0, 0),
+                            _capi.Operand(loop._Bp.data_ptr(), nx * nu if loop._Bp.ndim == 3 else 0, 0),
+                            _capi.Operand(None, 0, 0))
+    rc = lib.mpcqp_model_periods_jvp_batch(
+        C.byref(model.dims), model.model.data_ptr(), C.byref(plant), B, P, T, lam.data_ptr(), status.data_ptr(),
+        X.data_ptr() if d_Ap is not None else None, U0.data_ptr() if d_Bp is not None else None, C.byref(tan),
+        dX.data_ptr(), dU0.data_ptr(), jvp_status.data_ptr(), _stream_ptr())
+    _capi.check(rc, "mpcqp_model_periods_jvp_batch")
+    loop._jvp_keep = (tans, lam, status, X, U0, plant, tan)  # alive until the stream has consumed them
+    return dX, dU0, jvp_status
+
+
 def _canon(name, v, loop):
     """The shape ``autodiff._reduce`` takes as the operand's canonical one: a size of 1 where the operand broadcasts."""
     if name == "x0":
@@ -176,6 +252,25 @@ def _make_function():
             out = [_reduce(grads[nm], like, canon) if nd and grads[nm] is not None else None
                    for nm, nd, like, canon in zip(OPERANDS, need, ctx.inputs, ctx.canon)]
             return (None, None, None, None, *out)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            loop = ctx.loop
+            lam, status, X, U0, _ = ctx.keep
+            args = []
+            for nm, v, canon in zip(OPERANDS, tangents[4:], ctx.canon):
+                if v is None:
+                    args.append(None)
+                    continue
+                v = v.reshape(canon).unsqueeze(1)  # T = 1
+                if nm in ("goal", "targets", "disturbance") and canon[1] == 1:
+                    v = v[:, :, 0]  # constant in time
+                args.append(v)
+            if all(v is None for v in args):
+                return torch.zeros_like(X), torch.zeros_like(U0)
+            tans = _loop_tangents(args, loop.batch, U0.shape[1], loop.nx, loop.nu, loop.N, X.device)
+            dX, dU0, ctx.info.jvp_status = loop_jvp(ctx.model, loop, lam, status, X, U0, tans)
+            return dX[:, 0].to(X.dtype), dU0[:, 0].to(U0.dtype)
 
     return _ClosedLoopFunction
 
@@ -226,7 +321,8 @@ def closed_loop_diff(model, x0, nb_periods, goal=None, targets=None, plant=None,
     where the batch shares it, over the periods (inside the kernel) where it is constant in time. The model matrices,
     the weights and the model's ``e`` are NOT differentiated here -- they change the factorisation; ``solve_mpc_batch_diff``
     differentiates single plans with respect to them. The active set of a period is ``{i : lam_i > 0}``, as in every
-    derivative export.
+    derivative export. ``torch.autograd.forward_ad`` duals on the same six operands are served too (``fused=True``): the
+    forward, the replay and one ``mpcqp_model_periods_jvp_batch`` launch with one tangent per call, as :func:`closed_loop_jvp`.
 
     ``fused=True``: the forward is ONE ``mpcqp_model_periods_batch`` launch with records (``warm`` is passed through) and
     the backward ONE ``mpcqp_model_periods_vjp_batch`` launch. When a gradient is needed the recorded states are solved
@@ -269,7 +365,8 @@ def closed_loop_diff(model, x0, nb_periods, goal=None, targets=None, plant=None,
     loop._check_periods(P)
     info.loop, info.failed = loop, loop._loopstats[:, 0].sum()
     tens = [v if isinstance(v, torch.Tensor) else None for v in passed]
-    if not (torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in tens)):
+    dual = any(_is_dual(v) for v in tens)
+    if not dual and not (torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in tens)):
         loop.step(P)
         info.failed = loop.failed
         return loop.X, loop.U0, info
@@ -278,3 +375,121 @@ def closed_loop_diff(model, x0, nb_periods, goal=None, targets=None, plant=None,
     X, U0 = _FUNCTION.apply(model, loop, P, info, *tens)
     info.failed = loop.failed
     return X, U0, info
+
+
+def _jvp_by_hand(model, x0, P, goal, targets, plant, disturbance, tangents, feas_tol, max_iter, info):
+    """The loop and its tangents composed in torch: ``SharedModel.solve`` and ``SharedModel.plan_jvp`` per period, then the
+    plant step of both."""
+    torch = _torch()
+    t = model.template
+    as_t = lambda v: None if v is None else torch.as_tensor(v, dtype=t.dtype, device=t.device)  # noqa: E731
+    x, goal, targets, dist = as_t(_detached(x0)), as_t(_detached(goal)), as_t(_detached(targets)), as_t(_detached(disturbance))
+    Ap, Bp = (t.A[0, 0], t.B[0, 0]) if plant is None else (as_t(_detached(plant[0])), as_t(_detached(plant[1])))
+    for ref, what in ((goal, "goal"), (targets, "targets"), (dist, "disturbance")):
+        if ref is not None and ref.ndim == 3 and ref.shape[1] < P:
+            raise ValueError(f"{what} is laid out for {ref.shape[1]} periods; {P} were asked for")
+    B = x.shape[0]
+    (d_x0, d_goal, d_targets, d_dist, d_Ap, d_Bp), T = _loop_tangents(tangents, B, P, t.state_dim, t.input_dim,
+                                                                       t.nb_timesteps, t.device)
+    at = lambda r, k: None if r is None else (r[:, k] if r.ndim == 3 else r)  # noqa: E731
+    tat = lambda r, k: None if r is None else (r[:, :, k] if r.ndim == 4 else r)  # noqa: E731
+    zero = torch.zeros((), dtype=t.dtype, device=t.device)
+    zero64 = torch.zeros((), dtype=torch.float64, device=t.device)
+    step = lambda M, v: torch.matmul(v, M.transpose(-1, -2))  # noqa: E731  ([B, T, w] by a shared or a per-loop matrix)
+    dx = torch.zeros((B, T, t.state_dim), dtype=torch.float64, device=t.device) if d_x0 is None else d_x0.expand(B, -1, -1)
+    X, U0, dX, dU0, plans = [x], [], [dx], [], []
+    for k in range(P):
+        plan = model.solve(x, at(goal, k), at(targets, k), return_multipliers=True, feas_tol=feas_tol, max_iter=max_iter)
+        dU, _ = model.plan_jvp(plan, initial_state=dx.contiguous(), goal_state=tat(d_goal, k),
+                               target_states=tat(d_targets, k))
+        ok = (plan.status == 0)[:, None]
+        u0 = torch.where(ok, plan.U.view(B, t.nb_timesteps, t.input_dim)[:, 0, :], zero)
+        du0 = torch.where(ok[:, None], dU[:, :, 0, :].to(torch.float64), zero64)
+        dxn = step(Ap.to(torch.float64), dx) + step(Bp.to(torch.float64), du0)
+        if d_dist is not None:
+            dxn = dxn + tat(d_dist, k)
+        if d_Ap is not None:
+            dxn = dxn + torch.matmul(d_Ap, x.to(torch.float64)[:, None, :, None])[..., 0]
+        if d_Bp is not None:
+            dxn = dxn + torch.matmul(d_Bp, u0.to(torch.float64)[:, None, :, None])[..., 0]
+        xa = torch.bmm(Ap, x[:, :, None])[:, :, 0] if Ap.ndim == 3 else x @ Ap.T
+        xb = torch.bmm(Bp, u0[:, :, None])[:, :, 0] if Bp.ndim == 3 else u0 @ Bp.T
+        x = xa + xb if dist is None else xa + xb + at(dist, k)
+        dx = dxn
+        X.append(x)
+        U0.append(u0)
+        dX.append(dx)
+        dU0.append(du0)
+        plans.append(plan)
+    info._plans = plans
+    info.status = torch.stack([p.status for p in plans], dim=1)
+    info.failed = (info.status != 0).sum()
+    info.jvp_status = torch.stack([p.jvp_status != p.status for p in plans], 1).sum(1).to(torch.int32)
+    return torch.stack(X, dim=1), torch.stack(U0, dim=1), torch.stack(dX, dim=2), torch.stack(dU0, dim=2)
+
+
+def closed_loop_jvp(model, x0, nb_periods, goal=None, targets=None, plant=None, disturbance=None, *, d_x0=None, d_goal=None,
+                    d_targets=None, d_disturbance=None, d_Ap=None, d_Bp=None, warm: bool = False, feas_tol: float = 1e-9,
+                    max_iter=None, fused: bool = True):
+    """Run ``B`` closed loops of a :class:`SharedModel` for ``nb_periods`` periods, as :func:`closed_loop_diff` does, and push
+    ``T`` tangents through them: ``(X [B, P+1, nx], U0 [B, P, nu], dX [B, T, P+1, nx], dU0 [B, T, P, nu], info)`` --
+    how the whole trajectory moves with ``x0``, the references, the disturbance and the plant. ``dX`` and ``dU0`` are float64.
+
+    A tangent has its operand's shape with a ``T`` axis behind the batch axis: ``d_x0`` ``[B|1, T, nx]``; ``d_goal``,
+    ``d_targets`` and ``d_disturbance`` ``[B|1, T, w]`` (constant in time) or ``[B|1, T, P, w]``; ``d_Ap`` ``[B|1, T, nx, nx]``
+    and ``d_Bp`` ``[B|1, T, nx, nu]``. A leading 1 shares one set with the batch; None is zero; ``T <= 256`` and every tangent
+    given agrees on it. The recursion is that of ``mpcqp_model_periods_jvp_batch`` (include/mpcqp.h): a period with a plan
+    contributes the KKT tangent of the plan on its active set ``{i : lam_i > 0}`` with the model's own bounds fixed, a
+    period without one passes the tangent through the plant only. The model matrices, the weights and the model's ``e`` are
+    not perturbed here (they change the factorisation).
+
+    ``fused=True``: the forward launch with records, the replay of :func:`closed_loop_diff` (``info.replay_error``) and ONE
+    ``mpcqp_model_periods_jvp_batch`` launch for all periods and tangents, which factors every period's active rows once.
+    Envelope: ``check_envelope`` -- ``BackendError`` outside it, before anything is launched. ``info.jvp_status`` counts, per
+    loop, the periods with a plan whose active rows failed (they contribute their plant term only).
+
+    ``fused=False``: the loop composed in torch from ``SharedModel.solve`` and ``SharedModel.plan_jvp`` per period plus the
+    plant step; it serves whatever ``plan_jvp`` serves and is the baseline the fused path is measured against
+    (profiles/loop_jvp.md). ``warm`` is ignored there."""
+    P = int(nb_periods)
+    if P < 1:
+        raise ValueError("nb_periods must be at least 1")
+    info = LoopDiffInfo()
+    tangents = (d_x0, d_goal, d_targets, d_disturbance, d_Ap, d_Bp)
+    if not fused:
+        X, U0, dX, dU0 = _jvp_by_hand(model, x0, P, goal, targets, plant, disturbance, tangents, feas_tol, max_iter, info)
+        return X, U0, dX, dU0, info
+    from .closed_loop import ModelClosedLoop
+
+    check_envelope(model)
+    loop = ModelClosedLoop(model, _detached(x0), goal=_detached(goal), targets=_detached(targets),
+                           plant=None if plant is None else (_detached(plant[0]), _detached(plant[1])),
+                           disturbance=_detached(disturbance), warm=warm, feas_tol=feas_tol, max_iter=max_iter)
+    loop._check_periods(P)
+    tans = _loop_tangents(tangents, loop.batch, P, loop.nx, loop.nu, loop.N, loop._dev)
+    loop.step(P)
+    X, U0 = loop.X, loop.U0
+    lam, status, info.replay_error, _ = _replay(model, loop, X, U0, P)
+    dX, dU0, info.jvp_status = loop_jvp(model, loop, lam, status, X, U0, tans)
+    info.loop, info.status, info.failed = loop, status, loop.failed
+    return X, U0, dX, dU0, info
+
+
+JACOBIAN_WRT = ("x0", "goal")
+
+
+def closed_loop_jacobian(model, x0, nb_periods, goal=None, targets=None, plant=None, disturbance=None, *, wrt: str = "x0",
+                         warm: bool = False, feas_tol: float = 1e-9, max_iter=None, fused: bool = True):
+    """``(J_X [B, P+1, nx, nx], J_U0 [B, P, nu, nx], info)``: the Jacobians of the states and of the applied inputs of every
+    loop with respect to its initial state (``wrt="x0"``) or to a goal that is constant over the periods (``wrt="goal"``) --
+    :func:`closed_loop_jvp` with one identity shared by the batch, ``T = nx``, one pass of the tangent kernel.
+    ``J_X[:, P]`` with ``wrt="x0"`` is the linearised return map of the loop."""
+    torch = _torch()
+    if wrt not in JACOBIAN_WRT:
+        raise ProblemDefinitionError(f"wrt: expected one of {JACOBIAN_WRT}, got {wrt!r}")
+    t = model.template
+    eye = torch.eye(t.state_dim, dtype=torch.float64, device=t.device)[None]
+    _, _, dX, dU0, info = closed_loop_jvp(model, x0, nb_periods, goal, targets, plant, disturbance, warm=warm,
+                                          feas_tol=feas_tol, max_iter=max_iter, fused=fused,
+                                          **{"d_x0" if wrt == "x0" else "d_goal": eye})
+    return dX.permute(0, 2, 3, 1), dU0.permute(0, 2, 3, 1), info
